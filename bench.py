@@ -23,6 +23,11 @@ Rank 0 prints ONE JSON line.  Besides the driver's fields it carries
   rccl          N > 1: the path's only collective, the flat fp32 all-reduce of process_feature's gradient, in microseconds
 --train-step replaces the step by one training step of the aggregator (BASELINE configs[4]): VolumeGenerator forward, scalar
 loss, backward (1x1 conv + un-projection backward) and that all-reduce; shapes come from --grid/--channels/--batch.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32: `volume` for the forward step;
+`volume`, `grad_features` and `grad_<parameter>` for --train-step.  An output of more than DUMP_SAMPLE values is written as a
+fixed sample of its flattened values (positions from DUMP_SEED, sorted), so at most 64 MB in all.  The inputs depend only on the
+arguments: two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import ctypes
@@ -39,6 +44,9 @@ sys.path.insert(0, ROOT)
 from multiviewhmr_amd import _capi, multiview  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_SAMPLE = 1 << 22     # --dump-outputs: values kept of a larger output (16 MB as float32; a train step writes three such)
+DUMP_SEED = 0
+DUMP_LIMIT = 64 << 20
 
 
 def parse():
@@ -66,7 +74,29 @@ def parse():
     ap.add_argument("--rccl-selftest", action="store_true",
                     help="one rank, one GPU: initialise the 'nccl' (= RCCL) backend with world size 1 and run the path's collective on the device "
                          "(proves init_process_group, the IPC-mode pin and the flat-buffer all-reduce load and run on this pool; no scaling number)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; a fixed sample of a large output)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: each tensor as d/<name>.npy in float32, whole when it has at most DUMP_SAMPLE values, else the values at
+    DUMP_SAMPLE positions of its flattened form drawn with DUMP_SEED (deduplicated, sorted): the same positions for the same
+    shape in every run."""
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        arr = t.float().cpu().numpy()
+        total += arr.nbytes
+        assert total <= DUMP_LIMIT, "--dump-outputs: more than 64 MB"
+        np.save(os.path.join(d, name + ".npy"), arr)
 
 
 def rccl_selftest(a):
@@ -246,19 +276,25 @@ def train_step_bench(a, rank, world, dev, use_rccl):
         if record:
             torch.cuda.synchronize(); t.append(time.perf_counter())
             parts[:] += np.diff(t)
+        return vol
 
     for _ in range(a.warmup):
         step()
     sync()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for _ in range(a.steps - 1):
         step()
+    vol = step()                   # the last timed step: what --dump-outputs writes
     sync()
     elapsed = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], device=dev if use_rccl else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict([("volume", vol), ("grad_features", feats.grad)] +
+                                          [("grad_" + n.replace(".", "_"), p.grad) for n, p in gen.named_parameters()]))
+    del vol
     for _ in range(2):
         step(record=True)                                          # untimed: where the step goes (synchronising)
     ms = elapsed / a.steps * 1e3
@@ -383,6 +419,8 @@ def main():
         t = torch.tensor([elapsed], device=dev if use_rccl else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"volume": out})
     ms_step = elapsed / a.steps * 1e3
     k_layout = float(np.mean([ev[3 * i].elapsed_time(ev[3 * i + 1]) for i in range(a.steps)]))
     k_all = [ev[3 * i + 1].elapsed_time(ev[3 * i + 2]) for i in range(a.steps)]
