@@ -32,7 +32,8 @@ extern "C" {
 
 #define MVHMR_ABI_VERSION 4   /* 2: MVHMR_LAYOUT_QUAD became column-major (B,V,C/4,Wf,Hf,4).  3: QUAD + AUTO is geometry-gated and needs its
                                  workspace; explicit GATHER with QUAD input is served; MVHMR_BF16 out_dtype; mvhmr_unproject_backward_supported,
-                                 mvhmr_triangulate_dlt.  4: MVHMR_LAYOUT_QUAD_LOG2E (ABI history) */
+                                 mvhmr_triangulate_dlt.  4: MVHMR_LAYOUT_QUAD_LOG2E (ABI history); additive within 4:
+                                 mvhmr_unproject_backward_geometry[_workspace_bytes] */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -151,8 +152,8 @@ int mvhmr_unproject_forward(const mvhmr_unproject_desc *desc, const void *featur
 
 /*
  * Backward w.r.t. features: replaces autograd through the reference graph (CopySlices, softmax/mul/sum,
- * masked fill, grid_sampler_2d_backward per (b, v)); proj and coords never need gradients
- * (they are built from numpy / arange, aggregation.py:132-187).
+ * masked fill, grid_sampler_2d_backward per (b, v)).  The gradients w.r.t. proj and coords, which the reference's graph
+ * also has (a caller that refines cameras or predicts where the volume sits), are mvhmr_unproject_backward_geometry below.
  *   grad_out       (B,C,X,Y,Z) desc->out_dtype                                          [read]
  *   grad_features  same shape/layout/dtype as features, every element is written        [write]
  * Scatter-adds use fp32 float atomics, so low-order bits can differ from run to run.  The brick variant sums a
@@ -169,6 +170,26 @@ int mvhmr_unproject_forward(const mvhmr_unproject_desc *desc, const void *featur
 int mvhmr_unproject_backward(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
                              const float *proj, const float *coords, void *grad_features, void *workspace,
                              size_t workspace_bytes, void *hip_stream);
+
+/*
+ * Backward w.r.t. the geometry: the gradients autograd through the reference graph gives proj_matricies and coord_volumes
+ * (grid_sampler_2d_backward's grid gradient, back through the normalisation, the perspective divide and the projection).
+ *   grad_out     (B,C,X,Y,Z) desc->out_dtype                                                  [read]
+ *   features     as for mvhmr_unproject_backward: BVCHW, BVHWC or QUAD (C % 4 == 0);
+ *                MVHMR_LAYOUT_QUAD_LOG2E is MVHMR_ERR_UNSUPPORTED (forward only)                [read]
+ *   grad_proj    (B,V,3,4) fp32 or NULL, every element written                                [write]
+ *   grad_coords  (B,X,Y,Z,3) fp32 or NULL, every element written                              [write]
+ * At least one output must be non-null (both NULL: MVHMR_ERR_INVALID_ARGUMENT).  Any storage pairing check_desc admits, 1 ... 16
+ * views, any C and volume extents.  desc->variant is ignored: one kernel family serves every shape.  A view with depth <= 0 takes no
+ * part (its gradients are 0); the taps are grid_sampler_2d_backward's, floor() on exact cell boundaries, ix == -1 included.
+ * No float atomics: grad_coords is written once per voxel, grad_proj is summed per (sample, view) from fixed-order fp32 partials in
+ * float64 -- both are bitwise reproducible from run to run.  The workspace (mvhmr_unproject_backward_geometry_workspace_bytes) holds
+ * a channels-last copy of the features (none for MVHMR_LAYOUT_BVHWC) and the partials of grad_proj.
+ */
+size_t mvhmr_unproject_backward_geometry_workspace_bytes(const mvhmr_unproject_desc *desc);
+int mvhmr_unproject_backward_geometry(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                      const float *coords, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes,
+                                      void *hip_stream);
 
 /*
  * The same two calls for the volumes VolumeGenerator.forward builds (models/aggregation.py:138-187): instead of reading a

@@ -25,6 +25,7 @@ EXPORTS = (
     "mvhmr_conv1x1_to_quad", "mvhmr_conv1x1_to_quad_supported", "mvhmr_conv1x1_planar", "mvhmr_conv1x1_planar_supported", "mvhmr_conv1x1_wgrad", "mvhmr_conv1x1_wgrad_supported", "mvhmr_unproject_query_variant_cuboid",
     "mvhmr_unproject_backward_supported", "mvhmr_triangulate_dlt", "mvhmr_triangulate_dlt_weighted",
     "mvhmr_unproject_forward_kernel_name",
+    "mvhmr_unproject_backward_geometry_workspace_bytes", "mvhmr_unproject_backward_geometry",
 )
 
 
@@ -69,6 +70,10 @@ def lib():
     L.mvhmr_unproject_forward.argtypes = [dp, vp, vp, vp, vp, vp, sz, vp]
     L.mvhmr_unproject_backward.restype = ctypes.c_int
     L.mvhmr_unproject_backward.argtypes = [dp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.mvhmr_unproject_backward_geometry_workspace_bytes.restype = sz
+    L.mvhmr_unproject_backward_geometry_workspace_bytes.argtypes = [dp]
+    L.mvhmr_unproject_backward_geometry.restype = ctypes.c_int
+    L.mvhmr_unproject_backward_geometry.argtypes = [dp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     d3 = ctypes.POINTER(ctypes.c_double)
     L.mvhmr_unproject_forward_cuboid.restype = ctypes.c_int
     L.mvhmr_unproject_forward_cuboid.argtypes = [dp, vp, vp, vp, vp, d3, d3, vp, vp, sz, vp]

@@ -7,8 +7,9 @@
 Same names, argument meaning, return shapes/dtypes, state-dict keys and quirks (SURVEY.md section 8a,
 Q1-Q6).  What differs is HOW: the b x v Python loop with ~20 ATen launches per iteration and the
 (V,C,X,Y,Z) intermediates is one fused HIP kernel launch behind the C ABI of include/mvhmr_unproject.h
-(forward), and one more for the gradient w.r.t. `features` (backward), exposed as torch.library custom ops
-(mvhmr::unprojection / mvhmr::unprojection_cuboid + their _backward ops, with fake / meta shape functions and a
+(forward), one more for the gradient w.r.t. `features` and one for the gradients w.r.t. `proj_matricies` / `coord_volumes` when those
+require grad (backward), exposed as torch.library custom ops (mvhmr::unprojection / mvhmr::unprojection_cuboid + their _backward ops
+and mvhmr::unprojection_backward_geometry, with fake / meta shape functions and a
 registered autograd formula) whose host side runs in the PyTorch-ROCm C++ extension csrc_ext/mvhmr_torch_ext.cpp
 (or, without it, through the ctypes binding of the same C ABI).  There is no CPU / eager fallback: the call raises
 if the tensors are not on a HIP device or the library is not built.
@@ -143,7 +144,7 @@ def _op_forward(features, proj, coords, method, out_dtype, variant):
 
 
 def _op_backward(grad_out, features, proj, coords, method, out_dtype, variant):
-    """gradient w.r.t. features only: proj_matricies and coord_volumes come from numpy / arange in the caller and never require grad"""
+    """gradient w.r.t. features (the geometry's is _op_backward_geometry)"""
     L = _capi.lib()
     features, layout, like = _feature_layout(features, coords, method, _DTYPES[out_dtype], variant)
     grad_out = grad_out.contiguous()
@@ -160,12 +161,43 @@ def _op_backward(grad_out, features, proj, coords, method, out_dtype, variant):
     return grad_features
 
 
+def _op_backward_geometry(grad_out, features, proj, coords, method, out_dtype, variant, want_proj=True, want_coords=True):
+    """gradients w.r.t. proj_matricies (B,V,3,4) and coord_volumes (B,X,Y,Z,3), fp32 (mvhmr_unproject_backward_geometry); an output
+    not asked for comes back empty.  Planar features go through the library's channels-last pass, channels-last ones are read as
+    they are; `variant` plays no part."""
+    L = _capi.lib()
+    if _is_channels_last5(features) and features.shape[2] % 4 == 0:
+        layout = _capi.LAYOUT_BVHWC
+    else:
+        features, layout = features.contiguous(), _capi.LAYOUT_BVCHW
+    grad_out = grad_out.contiguous()
+    if _NATIVE:
+        a = _native_args(features, layout, features, coords, method, out_dtype, variant)
+        return tuple(torch.ops.mvhmr_native.unprojection_backward_geometry(grad_out, a[0], proj, *a[2:], want_proj, want_coords))
+    desc = _make_desc(features, coords, method, _DTYPES[out_dtype], layout, variant)
+    dev = features.device
+    with torch.cuda.device(dev):
+        gp = torch.empty(proj.shape if want_proj else (0,), dtype=torch.float32, device=dev)
+        gc = torch.empty(coords.shape if want_coords else (0,), dtype=torch.float32, device=dev)
+        ws, wsp = _workspace(L.mvhmr_unproject_backward_geometry_workspace_bytes(ctypes.byref(desc)), dev)
+        _capi.check(L.mvhmr_unproject_backward_geometry(ctypes.byref(desc), _ptr(grad_out), _ptr(features), _ptr(proj), _ptr(coords),
+                                                        _ptr(gp) if want_proj else ctypes.c_void_p(0),
+                                                        _ptr(gc) if want_coords else ctypes.c_void_p(0),
+                                                        wsp, 0 if ws is None else ws.numel(), _stream(dev)))
+    return gp, gc
+
+
 def _fake_forward(features, proj, coords, method, out_dtype, variant):
     return features.new_empty((features.shape[0], features.shape[2]) + tuple(coords.shape[1:4]), dtype=_DTYPES[out_dtype])
 
 
 def _fake_backward(grad_out, features, proj, coords, method, out_dtype, variant):
     return torch.empty_like(features)
+
+
+def _fake_backward_geometry(grad_out, features, proj, coords, method, out_dtype, variant, want_proj=True, want_coords=True):
+    return (proj.new_empty(proj.shape if want_proj else (0,), dtype=torch.float32),
+            coords.new_empty(coords.shape if want_coords else (0,), dtype=torch.float32))
 
 
 def _autograd_setup(ctx, inputs, output):
@@ -177,7 +209,11 @@ def _autograd_setup(ctx, inputs, output):
 def _autograd_backward(ctx, grad_out):
     features, proj, coords = ctx.saved_tensors
     g = torch.ops.mvhmr.unprojection_backward(grad_out, features, proj, coords, *ctx.args) if ctx.needs_input_grad[0] else None
-    return g, None, None, None, None, None
+    g_proj = g_coords = None
+    want_proj, want_coords = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+    if want_proj or want_coords:                       # a features-only backward launches nothing more
+        g_proj, g_coords = torch.ops.mvhmr.unprojection_backward_geometry(grad_out, features, proj, coords, *ctx.args, want_proj, want_coords)
+    return g, (g_proj if want_proj else None), (g_coords if want_coords else None), None, None, None
 
 
 def _op_defined(name):
@@ -199,6 +235,10 @@ def _register_ops():
     torch.library.impl("mvhmr::unprojection_backward", "CUDA")(_op_backward)
     torch.library.register_fake("mvhmr::unprojection")(_fake_forward)
     torch.library.register_fake("mvhmr::unprojection_backward")(_fake_backward)
+    torch.library.define("mvhmr::unprojection_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
+                         + ", bool want_proj=True, bool want_coords=True) -> (Tensor, Tensor)")
+    torch.library.impl("mvhmr::unprojection_backward_geometry", "CUDA")(_op_backward_geometry)
+    torch.library.register_fake("mvhmr::unprojection_backward_geometry")(_fake_backward_geometry)
     torch.library.register_autograd("mvhmr::unprojection", _autograd_backward, setup_context=_autograd_setup)
 
 
@@ -246,8 +286,9 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
         # empty batch / empty volume: the reference's loops do not run and its zero-initialised volume comes back
         # (aggregation.py:25-28); nothing to launch
         return torch.zeros((B, features.shape[2]) + tuple(coord_volumes.shape[1:4]), dtype=out_dtype, device=features.device)
-    proj = proj_matricies.detach().to(torch.float32).contiguous()
-    coords = coord_volumes.detach().to(torch.float32).contiguous()
+    # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
+    proj = proj_matricies.to(torch.float32).contiguous()
+    coords = coord_volumes.to(torch.float32).contiguous()
     return torch.ops.mvhmr.unprojection(features, proj, coords, _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
 
 

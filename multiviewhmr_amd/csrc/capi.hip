@@ -533,6 +533,45 @@ int mvhmr_unproject_backward_cuboid(const mvhmr_unproject_desc *desc, const void
     return backward_impl(desc, p, grad_out, features, proj, cs, grad_features, workspace, workspace_bytes, hip_stream);
 }
 
+// Gradient w.r.t. proj and coords: the channels-last feature copy k_bwd_geom reads (none for channels-last input), then the fp32
+// partials of grad_proj.  desc->variant plays no part.
+size_t mvhmr_unproject_backward_geometry_workspace_bytes(const mvhmr_unproject_desc *desc)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
+    return (desc->feat_layout == MVHMR_LAYOUT_BVHWC ? 0 : featT_bytes(p)) + align_up(geom_partial_bytes(p));
+}
+
+int mvhmr_unproject_backward_geometry(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                      const float *coords, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes,
+                                      void *hip_stream)
+{
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    if (!grad_out || !features || !proj || !coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / coords must be non-null");
+    if (!grad_proj && !grad_coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj and grad_coords are both null: nothing to compute");
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p))
+        return fail(MVHMR_ERR_UNSUPPORTED, "quad-planar features of this shape cannot be converted to channels-last (C %% 4 == 0, C <= 4092, B * V <= 65535)");
+    rc = check_ws(workspace, workspace_bytes, mvhmr_unproject_backward_geometry_workspace_bytes(desc));
+    if (rc != MVHMR_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    const void *featT = features;
+    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) {
+        rc = launched(desc->feat_layout == MVHMR_LAYOUT_QUAD ? launch_quad_to_channels_last(features, ws, p, s) : launch_to_channels_last(features, ws, p, s),
+                      "layout pass");
+        if (rc != MVHMR_OK) return rc;
+        featT = ws;
+        ws += featT_bytes(p);
+    }
+    return launched(launch_bwd_geom(grad_out, featT, proj, coords_from_tensor(coords, p), grad_proj ? reinterpret_cast<float *>(ws) : nullptr,
+                                    grad_proj, grad_coords, p, s),
+                    "geometry backward");
+}
+
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)
 {
     Problem p;

@@ -3,14 +3,15 @@
 a register spill is a vector-memory operation, is counted in vmcnt, and silently breaks the count.
 Reads hipcc's -Rpass-analysis=kernel-resource-usage output.
 
-k_fwd_brick is held to zero scratch here.  k_fwd_brick_groups and k_bwd_brick keep a cold noinline slow path whose call frame is
+k_fwd_brick is held to zero scratch here, and so is k_bwd_geom: it holds 3 V values per channel of a lane in registers (the
+channels per lane shrink with V to keep that at <= 48), and a spill inside its channel loop would cost a scratch round trip per tap.  k_fwd_brick_groups and k_bwd_brick keep a cold noinline slow path whose call frame is
 scratch OUTSIDE their hot loops; their loops are checked on the device assembly instead (check_loops.py).  k_bwd_brick's one
 counted wait, wait_vmcnt(n_at) after the flush atomics, relies on vmcnt retiring in issue order: an extra vector-memory operation
 the compiler adds among the wave's youngest could only make that wait cover more, never less."""
 import re
 import sys
 
-NO_SCRATCH = ("k_fwd_brick",)
+NO_SCRATCH = ("k_fwd_brick", "k_bwd_geom")
 EXEMPT = re.compile(r"k_fwd_brick_groups")      # (k_fwd_ws: cold noinline slow path + prologue spills outside its loops; check_loops.py holds the loops)
 text = open(sys.argv[1]).read()
 bad = []

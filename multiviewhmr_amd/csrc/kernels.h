@@ -104,6 +104,12 @@ hipError_t launch_conv1x1_quad(const float *x, const float *w, const float *bias
 hipError_t launch_triangulate_dlt(const float *proj, const float *points, const float *conf, float *out, int B, int V, int points_per_sample,
                                   int conf_per_sample, hipStream_t s);
 
+// gradient w.r.t. proj and coords (unproject_geom_bwd.hip): featT channels-last (B,V,HW,C4) in the feature dtype; `part` holds
+// geom_partial_bytes(p) of fp32 partials of grad_proj (needed when grad_proj is non-null); either output may be null
+size_t geom_partial_bytes(const Problem &p);
+hipError_t launch_bwd_geom(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
+                           float *grad_coords, const Problem &p, hipStream_t s);
+
 hipError_t launch_build_coords(float *coords_out, const float *rot, const float *center, int B, int S,
                                const double pos[3], const double sides[3], hipStream_t s);
 

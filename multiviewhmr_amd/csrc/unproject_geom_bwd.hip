@@ -1,0 +1,403 @@
+// Gradient of the un-projection w.r.t. the GEOMETRY: proj_matricies and coord_volumes (models/aggregation.py:20-87 differentiates
+// with respect to all three of its tensors; mvhmr_unproject_backward covers the features).
+//
+// Per sample b, voxel n at X, view v:  h = P_v [X, 1] = (a, b, z), u = a / z, w = b / z, and with quirk Q1 and align_corners=True
+//     ix = u (Wf - 1) / Hf,   iy = w (Hf - 1) / Wf          (computed in the forward's fp32 rounding order, device_common.h)
+// The bilinear sample s = sum of the four taps at floor(ix), floor(iy); a tap outside the map has the VALUE 0 (zero padding), so
+//     ds/dix = (1 - ty)(f01 - f00) + ty (f11 - f10),   ds/diy = (1 - tx)(f10 - f00) + tx (f11 - f01)
+// with tx, ty the fractions -- the taps grid_sampler_2d_backward uses, also on the boundary ix == -1 / iy == -1, where the forward
+// (make_taps) has no taps at all but the grid gradient is not zero: this file builds its own tap record.  With
+// ds_vc = aggregate_grad (device_common.h) and G_v = sum_c ds_vc ds_vc/dix (Gx) resp. /diy (Gy):
+//     dL/du = Gx (Wf - 1) / Hf,   dL/dw = Gy (Hf - 1) / Wf,   dh_v = (dL/du / z, dL/dw / z, -(dL/du u + dL/dw w) / z)
+//     grad_coords[b, n] = sum_v P_v[:, :3]^T dh_v            grad_proj[b, v] = sum_n dh_v (X0, X1, X2, 1)^T
+// A view with z <= 0 (or NaN) takes no part (the reference masks the sample): all its geometric gradients are 0.
+//
+// Mapping (the gather family's, unproject_gather.hip):
+//   block   = 32 consecutive voxels of one sample x EVERY channel (256 threads, 4 waves): the sum over C ends on chip
+//   phase 1 = one thread per (voxel, view): project, tap record -> LDS
+//   phase 2 = per 256-channel group: the grad_out tile turned through LDS (loads along voxels); one wave per voxel, channels across
+//             lanes, channels-last feature rows read as wave-uniform coalesced rows; all V views' s, ds/dix, ds/diy are held in
+//             registers until aggregate_grad gives ds -- 3 V values per channel, so a lane takes 4 / 2 / 1 channels for V <= 4 / <= 8
+//             / <= 16; then one DPP reduction of Gx and Gy per (voxel, view) into LDS (each voxel belongs to one wave: no atomics)
+//   phase 3 = one thread per (voxel, view): dh_v; grad_coords written once per voxel by plain stores; 12 fp32 partials of grad_proj
+//             per (block, view) into the workspace, summed per (b, v) by k_geom_reduce in float64 in a fixed order.
+// No float atomics anywhere: both outputs are bitwise reproducible from run to run.
+#include "device_common.h"
+#include "kernels.h"
+
+namespace mvhmr {
+
+namespace {
+
+constexpr int kGeoTile = 32;                 // voxels per block
+constexpr int kGeoGroup = 256;               // channels of the grad_out tile per pass
+constexpr int kGeoLd = kGeoGroup + 4;        // tile row stride (floats): rows stay 16-B aligned, consecutive voxels 4 banks apart
+
+// One voxel seen by one camera, with the taps of grid_sampler_2d_backward
+struct alignas(16) GeoRec {
+    int o00, o01, o10, o11;      // element offsets of the taps (y0,x0) (y0,x1) (y1,x0) (y1,x1) in a channels-last map, clamped into it
+    float w00, w01, w10, w11;    // the forward's bilinear weights, 0 for a tap outside the map
+    float tx, ty;                // ix - floor(ix), iy - floor(iy)
+    int mask;                    // bit k: tap k lies inside the map (its value is read); bit 4: the view takes part
+    int pad;
+};
+
+__device__ __forceinline__ GeoRec make_geo_rec(const float *__restrict__ P, float X0, float X1, float X2, int H, int W, int C4)
+{
+    GeoRec r;
+    r.o00 = r.o01 = r.o10 = r.o11 = 0;
+    r.w00 = r.w01 = r.w10 = r.w11 = 0.f;
+    r.tx = r.ty = 0.f;
+    r.mask = 0;
+    r.pad = 0;
+    // projection, divides and Q1 exactly as make_taps (the forward's rounding order)
+    const float a = __fmaf_rn(P[3], 1.f, __fmaf_rn(P[2], X2, __fmaf_rn(P[1], X1, __fmul_rn(P[0], X0))));
+    const float b = __fmaf_rn(P[7], 1.f, __fmaf_rn(P[6], X2, __fmaf_rn(P[5], X1, __fmul_rn(P[4], X0))));
+    const float z = __fmaf_rn(P[11], 1.f, __fmaf_rn(P[10], X2, __fmaf_rn(P[9], X1, __fmul_rn(P[8], X0))));
+    if (!(z > 0.f)) return r;
+    const float u = __fdiv_rn(a, z), v = __fdiv_rn(b, z);
+    const float gx = __fmul_rn(2.f, __fsub_rn(__fdiv_rn(u, (float)H), 0.5f));
+    const float gy = __fmul_rn(2.f, __fsub_rn(__fdiv_rn(v, (float)W), 0.5f));
+    const float ix = __fmul_rn(__fmul_rn(__fadd_rn(gx, 1.f), 0.5f), (float)(W - 1));
+    const float iy = __fmul_rn(__fmul_rn(__fadd_rn(gy, 1.f), 0.5f), (float)(H - 1));
+    // every tap outside (or NaN): value and gradient 0.  ix == -1 is KEPT: the tap at x = 0 has weight 0 but a gradient
+    if (!(ix >= -1.f && ix < (float)W && iy >= -1.f && iy < (float)H)) return r;
+    const float fx0 = floorf(ix), fy0 = floorf(iy);
+    const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
+    const float wx1 = __fsub_rn(ix, fx0), wx0 = __fsub_rn(__fadd_rn(fx0, 1.f), ix);
+    const float wy1 = __fsub_rn(iy, fy0), wy0 = __fsub_rn(__fadd_rn(fy0, 1.f), iy);
+    const bool xin0 = x0 >= 0, xin1 = x1 <= W - 1, yin0 = y0 >= 0, yin1 = y1 <= H - 1;
+    r.w00 = (xin0 && yin0) ? __fmul_rn(wx0, wy0) : 0.f;
+    r.w01 = (xin1 && yin0) ? __fmul_rn(wx1, wy0) : 0.f;
+    r.w10 = (xin0 && yin1) ? __fmul_rn(wx0, wy1) : 0.f;
+    r.w11 = (xin1 && yin1) ? __fmul_rn(wx1, wy1) : 0.f;
+    const int xc0 = xin0 ? x0 : 0, xc1 = xin1 ? x1 : W - 1, yc0 = yin0 ? y0 : 0, yc1 = yin1 ? y1 : H - 1;
+    r.o00 = (yc0 * W + xc0) * C4;
+    r.o01 = (yc0 * W + xc1) * C4;
+    r.o10 = (yc1 * W + xc0) * C4;
+    r.o11 = (yc1 * W + xc1) * C4;
+    r.tx = wx1;
+    r.ty = wy1;
+    r.mask = (xin0 && yin0 ? 1 : 0) | (xin1 && yin0 ? 2 : 0) | (xin0 && yin1 ? 4 : 0) | (xin1 && yin1 ? 8 : 0) | 16;
+    return r;
+}
+
+__device__ __forceinline__ GeoRec uniform_geo(const GeoRec &r)
+{
+    GeoRec u;
+    u.o00 = uniform(r.o00); u.o01 = uniform(r.o01); u.o10 = uniform(r.o10); u.o11 = uniform(r.o11);
+    u.w00 = uniform(r.w00); u.w01 = uniform(r.w01); u.w10 = uniform(r.w10); u.w11 = uniform(r.w11);
+    u.tx = uniform(r.tx); u.ty = uniform(r.ty);
+    u.mask = uniform(r.mask);
+    u.pad = 0;
+    return u;
+}
+
+// CPL consecutive channels of one channels-last row (CPL * sizeof(T)-byte aligned)
+template <typename T, int CPL> struct Row;
+template <typename T> struct Row<T, 4> {
+    static __device__ __forceinline__ void load(const T *p, float (&o)[4])
+    {
+        const f32x4 a = Vec4<T>::load(p);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = a.v[i];
+    }
+};
+template <> struct Row<float, 2> {
+    static __device__ __forceinline__ void load(const float *p, float (&o)[2])
+    {
+        const float2 a = *reinterpret_cast<const float2 *>(p);
+        o[0] = a.x; o[1] = a.y;
+    }
+};
+template <> struct Row<__half, 2> {
+    static __device__ __forceinline__ void load(const __half *p, float (&o)[2])
+    {
+        const float2 a = __half22float2(*reinterpret_cast<const __half2 *>(p));
+        o[0] = a.x; o[1] = a.y;
+    }
+};
+template <typename T> struct Row<T, 1> {
+    static __device__ __forceinline__ void load(const T *p, float (&o)[1]) { o[0] = to_f32<T>(*p); }
+};
+
+// sum over the wave, in a fixed order (DPP inside each row of 16 lanes, then the four row sums): the same bits every run
+__device__ __forceinline__ float wave_sum(float x)
+{
+    auto dpp = [](float y, auto ctrl) __attribute__((always_inline)) {
+        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, y), decltype(ctrl)::value, 0xF, 0xF, false));
+    };
+    x += dpp(x, std::integral_constant<int, 0xB1>());     // quad_perm [1,0,3,2]
+    x += dpp(x, std::integral_constant<int, 0x4E>());     // quad_perm [2,3,0,1]
+    x += dpp(x, std::integral_constant<int, 0x124>());    // row_ror:4
+    x += dpp(x, std::integral_constant<int, 0x128>());    // row_ror:8
+    const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 0));
+    const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 16));
+    const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 32));
+    const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), 48));
+    return (r0 + r1) + (r2 + r3);
+}
+
+constexpr int geo_cpl(int V) { return V <= 4 ? 4 : V <= 8 ? 2 : 1; }
+
+size_t geo_lds_bytes(int V)
+{
+    return sizeof(GeoRec) * kGeoTile * V + sizeof(float2) * kGeoTile * V + sizeof(float) * kGeoTile * 4 + sizeof(float) * kGeoTile * kGeoLd;
+}
+
+}  // namespace
+
+template <typename TF, typename TO, int METHOD, int VT>
+__global__ void __launch_bounds__(256)
+k_bwd_geom(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj, const Coords coords,
+           float *__restrict__ part, float *__restrict__ grad_coords, int C, int C4, int H, int W, long long N)
+{
+    constexpr int CPL = geo_cpl(VT);
+    constexpr int kPass = kGeoGroup / (64 * CPL);
+    extern __shared__ __align__(16) unsigned char smem[];
+    GeoRec *recs = reinterpret_cast<GeoRec *>(smem);                                      // [kGeoTile * VT], (voxel, view)
+    float2 *acc = reinterpret_cast<float2 *>(smem + sizeof(GeoRec) * kGeoTile * VT);      // (Gx, Gy) per (voxel, view)
+    float *xyz = reinterpret_cast<float *>(acc + kGeoTile * VT);                          // [kGeoTile][3] (+ padding to 16 B)
+    float *gtile = xyz + kGeoTile * 4;                                                    // [kGeoTile][kGeoLd]; phase 3: dh [kGeoTile * VT][3]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y;
+    const long long n0 = (long long)blockIdx.x * kGeoTile;
+    const long long mapsz = (long long)H * W * C4;
+
+    for (int idx = tid; idx < kGeoTile * VT; idx += blockDim.x) {
+        const int j = idx / VT, v = idx - j * VT;
+        long long n = n0 + j;
+        n = n < N ? n : N - 1;                          // tail voxels are computed and dropped
+        float X0, X1, X2;
+        voxel_xyz(coords, b, N, n, X0, X1, X2);
+        recs[idx] = make_geo_rec(proj + ((long long)b * VT + v) * 12, X0, X1, X2, H, W, C4);
+        acc[idx] = make_float2(0.f, 0.f);
+        if (v == 0) { xyz[j * 3 + 0] = X0; xyz[j * 3 + 1] = X1; xyz[j * 3 + 2] = X2; }
+    }
+
+    const TF *fb = featT + (long long)b * VT * mapsz;
+    for (int c0 = 0; c0 < C4; c0 += kGeoGroup) {
+        __syncthreads();                                // records ready / the previous group's tile consumed
+        {   // grad_out tile, coalesced along voxels: the two half-waves load alternate channels
+            const int vl = lane & (kGeoTile - 1), half = lane / kGeoTile;
+            const long long n = n0 + vl;
+            for (int r = wave * 64 + half; r < wave * 64 + 64; r += 64 / kGeoTile) {
+                const int c = c0 + r;
+                float g = 0.f;
+                if (c < C && n < N) g = to_f32<TO>(grad_out[((long long)b * C + c) * N + n]);
+                gtile[vl * kGeoLd + r] = g;
+            }
+        }
+        __syncthreads();
+
+        for (int jj = 0; jj < kGeoTile / 4; ++jj) {
+            const int j = wave * (kGeoTile / 4) + jj;
+            if (n0 + j >= N) break;                     // wave-uniform
+            float gx[VT], gy[VT];
+#pragma unroll
+            for (int v = 0; v < VT; ++v) gx[v] = gy[v] = 0.f;
+            for (int ps = 0; ps < kPass; ++ps) {
+                const int lc0 = ps * 64 * CPL;
+                if (c0 + lc0 >= C4) break;              // wave-uniform: the group's last channels lie past the row
+                const int lc = lc0 + lane * CPL, c = c0 + lc;
+                const bool act = c < C4;                // C4 % CPL == 0: a lane's channels are all in or all out
+                const int cc = act ? c : 0;             // idle lanes read a valid row and contribute nothing
+                float g[CPL];
+#pragma unroll
+                for (int i = 0; i < CPL; ++i) g[i] = gtile[j * kGeoLd + lc + i];
+                float s[CPL][VT], dx[CPL][VT], dy[CPL][VT];
+#pragma unroll
+                for (int v = 0; v < VT; ++v) {
+                    const GeoRec u = uniform_geo(recs[j * VT + v]);
+                    if (!(u.mask & 16)) {               // the view takes no part: s = 0 and no gradient (wave-uniform)
+#pragma unroll
+                        for (int i = 0; i < CPL; ++i) s[i][v] = dx[i][v] = dy[i][v] = 0.f;
+                        continue;
+                    }
+                    const TF *fv = fb + v * mapsz + cc;
+                    float f00[CPL], f01[CPL], f10[CPL], f11[CPL];
+                    Row<TF, CPL>::load(fv + u.o00, f00);
+                    Row<TF, CPL>::load(fv + u.o01, f01);
+                    Row<TF, CPL>::load(fv + u.o10, f10);
+                    Row<TF, CPL>::load(fv + u.o11, f11);
+                    const float wx0 = 1.f - u.tx, wy0 = 1.f - u.ty;   // exact: the fractions lie in [0, 1)
+#pragma unroll
+                    for (int i = 0; i < CPL; ++i) {
+                        // a tap outside the map has the value 0 (zero padding), not just the weight 0
+                        const float a00 = (u.mask & 1) ? f00[i] : 0.f, a01 = (u.mask & 2) ? f01[i] : 0.f;
+                        const float a10 = (u.mask & 4) ? f10[i] : 0.f, a11 = (u.mask & 8) ? f11[i] : 0.f;
+                        s[i][v] = bilerp(a00, a01, a10, a11, u.w00, u.w01, u.w10, u.w11);
+                        dx[i][v] = fmaf(wy0, a01 - a00, u.ty * (a11 - a10));
+                        dy[i][v] = fmaf(wx0, a10 - a00, u.tx * (a11 - a01));
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < CPL; ++i) {
+                    float ds[VT];
+                    aggregate_grad<METHOD, VT>(s[i], g[i], ds);
+#pragma unroll
+                    for (int v = 0; v < VT; ++v) {
+                        gx[v] = act ? fmaf(ds[v], dx[i][v], gx[v]) : gx[v];
+                        gy[v] = act ? fmaf(ds[v], dy[i][v], gy[v]) : gy[v];
+                    }
+                }
+            }
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                const float sx = wave_sum(gx[v]), sy = wave_sum(gy[v]);
+                if (lane == 0) {
+                    float2 a = acc[j * VT + v];
+                    a.x += sx;
+                    a.y += sy;
+                    acc[j * VT + v] = a;
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // phase 3: dh per (voxel, view); the grad_out tile is dead, its space holds dh
+    float *dh = gtile;
+    const float kx = __fdiv_rn((float)(W - 1), (float)H), ky = __fdiv_rn((float)(H - 1), (float)W);   // dix/du, diy/dw (Q1)
+    for (int idx = tid; idx < kGeoTile * VT; idx += blockDim.x) {
+        const int j = idx / VT, v = idx - j * VT;
+        float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+        if (n0 + j < N && (recs[idx].mask & 16)) {
+            const float *P = proj + ((long long)b * VT + v) * 12;
+            const float X0 = xyz[j * 3 + 0], X1 = xyz[j * 3 + 1], X2 = xyz[j * 3 + 2];
+            const float a = __fmaf_rn(P[3], 1.f, __fmaf_rn(P[2], X2, __fmaf_rn(P[1], X1, __fmul_rn(P[0], X0))));
+            const float bb = __fmaf_rn(P[7], 1.f, __fmaf_rn(P[6], X2, __fmaf_rn(P[5], X1, __fmul_rn(P[4], X0))));
+            const float z = __fmaf_rn(P[11], 1.f, __fmaf_rn(P[10], X2, __fmaf_rn(P[9], X1, __fmul_rn(P[8], X0))));
+            const float u = __fdiv_rn(a, z), w = __fdiv_rn(bb, z);
+            const float2 G = acc[idx];
+            const float du = G.x * kx, dw = G.y * ky;
+            d0 = __fdiv_rn(du, z);
+            d1 = __fdiv_rn(dw, z);
+            d2 = -__fdiv_rn(fmaf(du, u, dw * w), z);
+        }
+        dh[idx * 3 + 0] = d0;
+        dh[idx * 3 + 1] = d1;
+        dh[idx * 3 + 2] = d2;
+    }
+    __syncthreads();
+    if (grad_coords && tid < kGeoTile && n0 + tid < N) {
+        // grad_coords[b, n] = sum_v P_v[:, :3]^T dh_v, views in order; one plain store per coordinate
+        const int j = tid;
+        float g0 = 0.f, g1 = 0.f, g2 = 0.f;
+#pragma unroll
+        for (int v = 0; v < VT; ++v) {
+            const float *P = proj + ((long long)b * VT + v) * 12;
+            const float e0 = dh[(j * VT + v) * 3 + 0], e1 = dh[(j * VT + v) * 3 + 1], e2 = dh[(j * VT + v) * 3 + 2];
+            g0 = fmaf(P[8], e2, fmaf(P[4], e1, fmaf(P[0], e0, g0)));
+            g1 = fmaf(P[9], e2, fmaf(P[5], e1, fmaf(P[1], e0, g1)));
+            g2 = fmaf(P[10], e2, fmaf(P[6], e1, fmaf(P[2], e0, g2)));
+        }
+        float *o = grad_coords + ((long long)b * N + n0 + j) * 3;
+        o[0] = g0; o[1] = g1; o[2] = g2;
+    }
+    if (part && tid < VT * 12) {
+        // this block's share of grad_proj[b, v][r][k] = sum_n dh_v[r] (X, 1)[k], voxels in order (tail voxels have dh = 0)
+        const int v = tid / 12, r = (tid % 12) / 4, k = tid % 4;
+        float sum = 0.f;
+        for (int j = 0; j < kGeoTile; ++j) {
+            const float d = dh[(j * VT + v) * 3 + r];
+            sum = d != 0.f ? fmaf(d, k < 3 ? xyz[j * 3 + k] : 1.f, sum) : sum;
+        }
+        part[(((long long)b * gridDim.x + blockIdx.x) * VT + v) * 12 + tid % 12] = sum;
+    }
+}
+
+// grad_proj[b, v] = sum over the blocks of sample b of their 12 partials: float64, each thread a fixed stride of blocks, then a fixed
+// tree over the threads -- the same bits every run
+__global__ void __launch_bounds__(256) k_geom_reduce(const float *__restrict__ part, float *__restrict__ grad_proj, int V, int tiles)
+{
+    __shared__ double red[12][256];
+    const int tid = threadIdx.x, bv = blockIdx.x, b = bv / V, v = bv - b * V;
+    double s[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) s[k] = 0.0;
+    for (int t = tid; t < tiles; t += 256) {
+        const float *p = part + (((long long)b * tiles + t) * V + v) * 12;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) s[k] += (double)p[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) red[k][tid] = s[k];
+    for (int w = 128; w > 0; w >>= 1) {
+        __syncthreads();
+        if (tid < w) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) red[k][tid] += red[k][tid + w];
+        }
+    }
+    __syncthreads();
+    if (tid < 12) grad_proj[(long long)bv * 12 + tid] = (float)red[tid][0];
+}
+
+// ------------------------------------------------------------------------------------------ launchers
+static unsigned geom_tiles(const Problem &p) { return (unsigned)((p.N + kGeoTile - 1) / kGeoTile); }
+
+size_t geom_partial_bytes(const Problem &p) { return (size_t)p.B * geom_tiles(p) * p.V * 12 * sizeof(float); }
+
+template <typename TF, typename TO, int METHOD>
+static hipError_t geom_dispatch_v(const TO *go_, const TF *featT, const float *proj, const Coords &coords, float *part, float *grad_coords,
+                                  const Problem &p, hipStream_t s)
+{
+    const size_t lds = geo_lds_bytes(p.V);
+    const dim3 grid(geom_tiles(p), (unsigned)p.B);
+    auto go = [&](auto kern) -> hipError_t {
+        hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, part, grad_coords, p.C, p.C4, p.H, p.W, p.N);
+        return hipGetLastError();
+    };
+    switch (p.V) {
+    case 1: return go(k_bwd_geom<TF, TO, METHOD, 1>);
+    case 2: return go(k_bwd_geom<TF, TO, METHOD, 2>);
+    case 3: return go(k_bwd_geom<TF, TO, METHOD, 3>);
+    case 4: return go(k_bwd_geom<TF, TO, METHOD, 4>);
+    case 5: return go(k_bwd_geom<TF, TO, METHOD, 5>);
+    case 6: return go(k_bwd_geom<TF, TO, METHOD, 6>);
+    case 7: return go(k_bwd_geom<TF, TO, METHOD, 7>);
+    case 8: return go(k_bwd_geom<TF, TO, METHOD, 8>);
+    case 9: return go(k_bwd_geom<TF, TO, METHOD, 9>);
+    case 10: return go(k_bwd_geom<TF, TO, METHOD, 10>);
+    case 11: return go(k_bwd_geom<TF, TO, METHOD, 11>);
+    case 12: return go(k_bwd_geom<TF, TO, METHOD, 12>);
+    case 13: return go(k_bwd_geom<TF, TO, METHOD, 13>);
+    case 14: return go(k_bwd_geom<TF, TO, METHOD, 14>);
+    case 15: return go(k_bwd_geom<TF, TO, METHOD, 15>);
+    case 16: return go(k_bwd_geom<TF, TO, METHOD, 16>);
+    }
+    return hipErrorNotSupported;
+}
+
+template <typename TF, typename TO>
+static hipError_t geom_dispatch_m(const TO *go_, const TF *featT, const float *proj, const Coords &coords, float *part, float *grad_coords,
+                                  const Problem &p, hipStream_t s)
+{
+    switch (p.method) {
+    case AGG_SOFTMAX: return geom_dispatch_v<TF, TO, AGG_SOFTMAX>(go_, featT, proj, coords, part, grad_coords, p, s);
+    case AGG_SUM: return geom_dispatch_v<TF, TO, AGG_SUM>(go_, featT, proj, coords, part, grad_coords, p, s);
+    case AGG_MEAN: return geom_dispatch_v<TF, TO, AGG_MEAN>(go_, featT, proj, coords, part, grad_coords, p, s);
+    case AGG_MAX: return geom_dispatch_v<TF, TO, AGG_MAX>(go_, featT, proj, coords, part, grad_coords, p, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_bwd_geom(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
+                           float *grad_coords, const Problem &p, hipStream_t s)
+{
+    if (p.V < 1 || p.V > kMaxViews || (grad_proj && !part)) return hipErrorInvalidValue;
+    hipError_t e;
+    if (p.out_bf16) e = p.feat_f16 ? hipErrorNotSupported : geom_dispatch_m((const bf16_t *)grad_out, (const float *)featT, proj, coords, part, grad_coords, p, s);
+    else if (!p.feat_f16 && !p.out_f16) e = geom_dispatch_m((const float *)grad_out, (const float *)featT, proj, coords, part, grad_coords, p, s);
+    else if (p.feat_f16 && p.out_f16) e = geom_dispatch_m((const __half *)grad_out, (const __half *)featT, proj, coords, part, grad_coords, p, s);
+    else if (p.feat_f16 && !p.out_f16) e = geom_dispatch_m((const float *)grad_out, (const __half *)featT, proj, coords, part, grad_coords, p, s);
+    else e = hipErrorNotSupported;
+    if (e != hipSuccess || !grad_proj) return e;
+    hipLaunchKernelGGL(k_geom_reduce, dim3((unsigned)(p.B * p.V)), dim3(256), 0, s, (const float *)part, grad_proj, p.V, (int)geom_tiles(p));
+    return hipGetLastError();
+}
+
+}  // namespace mvhmr

@@ -1,5 +1,5 @@
 // PyTorch-ROCm C++ extension over the C ABI (include/mvhmr_unproject.h): the native implementation of the custom ops
-// mvhmr::unprojection_native / mvhmr::unprojection_backward_native, which multiviewhmr_amd/aggregation.py dispatches to from its
+// mvhmr_native::unprojection / unprojection_backward / unprojection_backward_geometry, which multiviewhmr_amd/aggregation.py dispatches to from its
 // torch.library ops mvhmr::unprojection / _backward (reference boundary: unprojection(), models/aggregation.py:20-87, and the autograd
 // graph through it).  What runs here per call: descriptor, output / gradient tensor and workspace from the caching allocator, the
 // current HIP stream, one C-ABI call -- no Python, no ctypes marshalling.  Host code only: the kernels live in libmvhmr_unproject.so.
@@ -90,6 +90,31 @@ at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Te
     return layout == MVHMR_LAYOUT_BVHWC ? grad.permute({0, 1, 4, 2, 3}) : grad;
 }
 
+// gradients w.r.t. proj (B,V,3,4) and coords (B,X,Y,Z,3), both fp32; an output not asked for comes back as an empty tensor
+std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
+                                                                          const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H,
+                                                                          int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
+                                                                          int64_t variant, bool want_proj, bool want_coords)
+{
+    TORCH_CHECK(grad_out.is_cuda() && features.is_cuda() && proj.is_cuda() && coords.is_cuda(), "unprojection runs only on a HIP device");
+    TORCH_CHECK(grad_out.is_contiguous() && features.is_contiguous() && proj.is_contiguous() && coords.is_contiguous(), "contiguous tensors expected");
+    TORCH_CHECK(want_proj || want_coords, "mvhmr_unproject: neither gradient was asked for");
+    check_sizes(features, proj, coords, B, V, C, H, W, feat_dtype, layout);
+    TORCH_CHECK(grad_out.scalar_type() == scalar_of(out_dtype) && grad_out.numel() == B * C * coords.size(1) * coords.size(2) * coords.size(3),
+                "mvhmr_unproject: grad_out must be (B, C, X, Y, Z) in the volume's dtype");
+    c10::DeviceGuard guard(features.device());
+    const mvhmr_unproject_desc d = make_desc(B, V, C, H, W, coords, method, feat_dtype, out_dtype, layout, variant);
+    const auto opts = features.options().dtype(at::kFloat);
+    at::Tensor gp = want_proj ? at::empty({B, V, 3, 4}, opts) : at::empty({0}, opts);
+    at::Tensor gc = want_coords ? at::empty(coords.sizes(), opts) : at::empty({0}, opts);
+    const size_t need = mvhmr_unproject_backward_geometry_workspace_bytes(&d);
+    at::Tensor ws = at::empty({(int64_t)need}, features.options().dtype(at::kByte));
+    check(mvhmr_unproject_backward_geometry(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
+                                            want_proj ? gp.data_ptr<float>() : nullptr, want_coords ? gc.data_ptr<float>() : nullptr,
+                                            need ? ws.data_ptr() : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream()));
+    return {gp, gc};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(mvhmr_native, m)
@@ -98,6 +123,8 @@ TORCH_LIBRARY(mvhmr_native, m)
           "int layout, int variant) -> Tensor");
     m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, int B, int V, int C, int H, int W, int method, "
           "int feat_dtype, int out_dtype, int layout, int variant) -> Tensor");
+    m.def("unprojection_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, int B, int V, int C, int H, int W, "
+          "int method, int feat_dtype, int out_dtype, int layout, int variant, bool want_proj, bool want_coords) -> (Tensor, Tensor)");
     m.def("abi_version() -> int");
 }
 
@@ -105,6 +132,7 @@ TORCH_LIBRARY_IMPL(mvhmr_native, CUDA, m)
 {
     m.impl("unprojection", &unprojection_native);
     m.impl("unprojection_backward", &unprojection_backward_native);
+    m.impl("unprojection_backward_geometry", &unprojection_backward_geometry_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)
