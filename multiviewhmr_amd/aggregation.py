@@ -10,9 +10,9 @@ Q1-Q6).  What differs is HOW: the b x v Python loop with ~20 ATen launches per i
 (forward), one more for the gradient w.r.t. `features` and one for the gradients w.r.t. `proj_matricies` / `coord_volumes` when those
 require grad (backward), exposed as torch.library custom ops (mvhmr::unprojection / mvhmr::unprojection_cuboid + their _backward ops
 and mvhmr::unprojection_backward_geometry, with fake / meta shape functions and a
-registered autograd formula) whose host side runs in the PyTorch-ROCm C++ extension csrc_ext/mvhmr_torch_ext.cpp
-(or, without it, through the ctypes binding of the same C ABI).  There is no CPU / eager fallback: the call raises
-if the tensors are not on a HIP device or the library is not built.
+registered autograd formula) whose host side runs in the PyTorch-ROCm C++ extension csrc_ext/mvhmr_torch_ext.cpp -- the one
+route of every un-projection launch, VolumeGenerator's fused conv + un-projection included.  There is no CPU / eager fallback: the
+call raises if the tensors are not on a HIP device or the library or the extension is not built.
 """
 import ctypes
 import os
@@ -34,13 +34,6 @@ def _ptr(t):
 
 def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _workspace(nbytes, device):
-    if nbytes == 0:
-        return None, ctypes.c_void_p(0)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)   # caching allocator: 512-B aligned, stream-ordered
-    return ws, _ptr(ws)
 
 
 def _is_channels_last5(features):
@@ -98,93 +91,61 @@ def _make_desc(features, coord_volumes, method, out_dtype, layout, variant):
     return d
 
 
-# The op is registered with torch.library (mvhmr::unprojection / mvhmr::unprojection_backward): eager calls dispatch to the C ABI,
+# The op is registered with torch.library (mvhmr::unprojection / mvhmr::unprojection_backward): eager calls dispatch to the C++ extension,
 # FakeTensor / meta calls to the shape functions, autograd to the registered formula -- so torch.compile and AOT autograd see one
 # opaque node with a known output shape and a known backward instead of a Python autograd.Function they cannot trace into.
 _DTYPES = {_capi.F32: torch.float32, _capi.F16: torch.float16, _capi.BF16: torch.bfloat16}
+_ext = None
 
 
-def _load_native():
-    """The PyTorch-ROCm C++ extension over the C ABI (csrc_ext/mvhmr_torch_ext.cpp, built in-tree by multiviewhmr_amd.build.build_ext):
-    the per-call host work -- descriptor, output and workspace from the caching allocator, current stream, the C-ABI call -- in C++.
-    Without it (not built, or MVHMR_NO_NATIVE_EXT=1) the same C-ABI calls are made through ctypes: both are the HIP path."""
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib_ext", "mvhmr_torch_ext.so")
-    if os.environ.get("MVHMR_NO_NATIVE_EXT") == "1" or not os.path.exists(path) or not os.path.exists(_capi.LIB_PATH):
-        return False
-    torch.ops.load_library(path)
-    if torch.ops.mvhmr_native.abi_version() != _capi.ABI_VERSION:
-        raise RuntimeError("mvhmr_torch_ext.so speaks ABI %d, this package %d: rebuild (python -m multiviewhmr_amd.build)"
-                           % (torch.ops.mvhmr_native.abi_version(), _capi.ABI_VERSION))
-    return True
+def _native():
+    """torch.ops.mvhmr_native: the C++ extension that does the host work of every launch (csrc_ext/mvhmr_torch_ext.cpp, built by
+    multiviewhmr_amd.build.build_ext).  Loaded on first use like _capi.lib(), so importing the package does not need it."""
+    global _ext
+    if _ext is None:
+        from . import build as _build                    # not at import: `python -m multiviewhmr_amd.build` runs that module as __main__
+        if not os.path.exists(_build.EXT):
+            raise RuntimeError("mvhmr_torch_ext.so is not built (%s). Build it with `python -m multiviewhmr_amd.build`." % _build.EXT)
+        _capi.lib()                                      # the extension links libmvhmr_unproject.so: same error when that is missing
+        torch.ops.load_library(_build.EXT)
+        if torch.ops.mvhmr_native.abi_version() != _capi.ABI_VERSION:
+            raise RuntimeError("mvhmr_torch_ext.so speaks ABI %d, this package %d: rebuild (python -m multiviewhmr_amd.build)"
+                               % (torch.ops.mvhmr_native.abi_version(), _capi.ABI_VERSION))
+        _ext = torch.ops.mvhmr_native
+    return _ext
 
 
-_NATIVE = _load_native()
-
-
-def _native_args(features, layout, like, coords, method, out_dtype, variant):
+def _native_args(features, vol, method, out_dtype, variant, layout=None):
+    """_feature_layout's decision (or `layout`) as the extension's ops take it: the view the library reads, the descriptor's fields"""
+    like = features
+    if layout is None:
+        features, layout, like = _feature_layout(features, vol, method, _DTYPES[out_dtype], variant)
     B, V, C, Hf, Wf = like.shape
-    read = features.permute(0, 1, 3, 4, 2) if layout == _capi.LAYOUT_BVHWC else features     # the contiguous view the library reads
-    return (read, None, coords, B, V, C, Hf, Wf, method, _dtype_code(like.dtype), out_dtype, layout, variant)
+    read = features.permute(0, 1, 3, 4, 2) if layout == _capi.LAYOUT_BVHWC else features
+    return read, (B, V, C, Hf, Wf, method, _dtype_code(like.dtype), out_dtype, layout, variant)
 
 
 def _op_forward(features, proj, coords, method, out_dtype, variant):
-    L = _capi.lib()
-    features, layout, like = _feature_layout(features, coords, method, _DTYPES[out_dtype], variant)
-    if _NATIVE:
-        a = _native_args(features, layout, like, coords, method, out_dtype, variant)
-        return torch.ops.mvhmr_native.unprojection(a[0], proj, *a[2:])
-    desc = _make_desc(like, coords, method, _DTYPES[out_dtype], layout, variant)
-    B, C = like.shape[0], like.shape[2]
-    with torch.cuda.device(features.device):
-        out = torch.empty((B, C) + tuple(coords.shape[1:4]), dtype=_DTYPES[out_dtype], device=features.device)
-        ws, wsp = _workspace(L.mvhmr_unproject_forward_workspace_bytes(ctypes.byref(desc)), features.device)
-        _capi.check(L.mvhmr_unproject_forward(ctypes.byref(desc), _ptr(features), _ptr(proj), _ptr(coords), _ptr(out),
-                                              wsp, 0 if ws is None else ws.numel(), _stream(features.device)))
-    return out
+    read, desc = _native_args(features, coords, method, out_dtype, variant)
+    return _native().unprojection(read, proj, coords, *desc)
 
 
 def _op_backward(grad_out, features, proj, coords, method, out_dtype, variant):
     """gradient w.r.t. features (the geometry's is _op_backward_geometry)"""
-    L = _capi.lib()
-    features, layout, like = _feature_layout(features, coords, method, _DTYPES[out_dtype], variant)
-    grad_out = grad_out.contiguous()
-    if _NATIVE:
-        a = _native_args(features, layout, like, coords, method, out_dtype, variant)
-        return torch.ops.mvhmr_native.unprojection_backward(grad_out, a[0], proj, *a[2:])
-    desc = _make_desc(like, coords, method, _DTYPES[out_dtype], layout, variant)
-    with torch.cuda.device(features.device):
-        # same strides as what the library read -- except quad-planar features, whose gradient comes back planar
-        grad_features = torch.empty(like.shape, dtype=like.dtype, device=like.device) if layout == _capi.LAYOUT_QUAD else torch.empty_like(features)
-        ws, wsp = _workspace(L.mvhmr_unproject_backward_workspace_bytes(ctypes.byref(desc)), features.device)
-        _capi.check(L.mvhmr_unproject_backward(ctypes.byref(desc), _ptr(grad_out), _ptr(features), _ptr(proj), _ptr(coords),
-                                               _ptr(grad_features), wsp, 0 if ws is None else ws.numel(), _stream(features.device)))
-    return grad_features
+    read, desc = _native_args(features, coords, method, out_dtype, variant)
+    return _native().unprojection_backward(grad_out.contiguous(), read, proj, coords, *desc)
 
 
 def _op_backward_geometry(grad_out, features, proj, coords, method, out_dtype, variant, want_proj=True, want_coords=True):
     """gradients w.r.t. proj_matricies (B,V,3,4) and coord_volumes (B,X,Y,Z,3), fp32 (mvhmr_unproject_backward_geometry); an output
     not asked for comes back empty.  Planar features go through the library's channels-last pass, channels-last ones are read as
     they are; `variant` plays no part."""
-    L = _capi.lib()
     if _is_channels_last5(features) and features.shape[2] % 4 == 0:
         layout = _capi.LAYOUT_BVHWC
     else:
         features, layout = features.contiguous(), _capi.LAYOUT_BVCHW
-    grad_out = grad_out.contiguous()
-    if _NATIVE:
-        a = _native_args(features, layout, features, coords, method, out_dtype, variant)
-        return tuple(torch.ops.mvhmr_native.unprojection_backward_geometry(grad_out, a[0], proj, *a[2:], want_proj, want_coords))
-    desc = _make_desc(features, coords, method, _DTYPES[out_dtype], layout, variant)
-    dev = features.device
-    with torch.cuda.device(dev):
-        gp = torch.empty(proj.shape if want_proj else (0,), dtype=torch.float32, device=dev)
-        gc = torch.empty(coords.shape if want_coords else (0,), dtype=torch.float32, device=dev)
-        ws, wsp = _workspace(L.mvhmr_unproject_backward_geometry_workspace_bytes(ctypes.byref(desc)), dev)
-        _capi.check(L.mvhmr_unproject_backward_geometry(ctypes.byref(desc), _ptr(grad_out), _ptr(features), _ptr(proj), _ptr(coords),
-                                                        _ptr(gp) if want_proj else ctypes.c_void_p(0),
-                                                        _ptr(gc) if want_coords else ctypes.c_void_p(0),
-                                                        wsp, 0 if ws is None else ws.numel(), _stream(dev)))
-    return gp, gc
+    read, desc = _native_args(features, coords, method, out_dtype, variant, layout)
+    return tuple(_native().unprojection_backward_geometry(grad_out.contiguous(), read, proj, coords, *desc, want_proj, want_coords))
 
 
 def _fake_forward(features, proj, coords, method, out_dtype, variant):
@@ -245,6 +206,37 @@ def _register_ops():
 _register_ops()
 
 
+def _check_call(features, proj_matricies, volume, volume_shape, aggregation_method, variant, out_dtype, same_device):
+    """The argument checks unprojection() and unprojection_cuboid() share.  volume: the tensors that place the volume; volume_shape(B)
+    raises when they do not fit, else returns (X, Y, Z); same_device: refuse proj_matricies / volume on another device than features.
+    -> (out_dtype with its default applied, (X, Y, Z), the zero volume when there is nothing to launch or None)"""
+    for t in (features, proj_matricies) + volume:
+        if not torch.is_tensor(t):
+            raise TypeError(_TYPE_MSG)                       # utils/multiview.py:110
+    if aggregation_method not in _METHODS:
+        raise ValueError("Unknown aggregation_method: {}".format(aggregation_method))
+    if variant not in _capi.VARIANT:
+        raise ValueError("Unknown kernel variant: {}".format(variant))
+    if features.dim() != 5:
+        raise RuntimeError("unprojection: features must be (B, V, C, Hf, Wf), got %s" % (tuple(features.shape),))
+    B, V = features.shape[:2]
+    if tuple(proj_matricies.shape) != (B, V, 3, 4):
+        raise RuntimeError("unprojection: proj_matricies must be (%d, %d, 3, 4), got %s" % (B, V, tuple(proj_matricies.shape)))
+    vol = volume_shape(B)
+    if not features.is_cuda:
+        raise RuntimeError("unprojection: features live on %s; this implementation runs only on a HIP device "
+                           "(MI355X) and has no CPU path" % features.device)
+    if same_device and any(t.device != features.device for t in (proj_matricies,) + volume):
+        raise RuntimeError("unprojection: expected all tensors on %s, got proj_matricies on %s and coord_volumes on %s"
+                           % ((features.device, proj_matricies.device) + tuple(t.device for t in volume)))
+    if out_dtype is None:
+        out_dtype = torch.float16 if features.dtype == torch.float16 else torch.float32
+    if features.numel() == 0 or 0 in vol:
+        # empty batch / empty volume: the reference's zero-initialised volume comes back (aggregation.py:25-28), nothing to launch
+        return out_dtype, vol, torch.zeros((B, features.shape[2]) + vol, dtype=out_dtype, device=features.device)
+    return out_dtype, vol, None
+
+
 def unprojection(features, proj_matricies, coord_volumes, aggregation_method='softmax', *, out_dtype=None,
                  variant='auto'):
     """Fused project -> bilinear-sample -> cross-view aggregate (reference: models/aggregation.py:20-87).
@@ -260,32 +252,15 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
 
     `out_dtype` and `variant` ('auto' | 'gather' | 'brick') are keyword-only extensions.
     """
-    for t in (features, proj_matricies, coord_volumes):
-        if not torch.is_tensor(t):
-            raise TypeError(_TYPE_MSG)                       # utils/multiview.py:110
-    if aggregation_method not in _METHODS:
-        raise ValueError("Unknown aggregation_method: {}".format(aggregation_method))
-    if variant not in _capi.VARIANT:
-        raise ValueError("Unknown kernel variant: {}".format(variant))
-    if features.dim() != 5:
-        raise RuntimeError("unprojection: features must be (B, V, C, Hf, Wf), got %s" % (tuple(features.shape),))
-    B, V = features.shape[:2]
-    if tuple(proj_matricies.shape) != (B, V, 3, 4):
-        raise RuntimeError("unprojection: proj_matricies must be (%d, %d, 3, 4), got %s" % (B, V, tuple(proj_matricies.shape)))
-    if coord_volumes.dim() != 5 or coord_volumes.shape[0] != B or coord_volumes.shape[4] != 3:
-        raise RuntimeError("unprojection: coord_volumes must be (%d, X, Y, Z, 3), got %s" % (B, tuple(coord_volumes.shape)))
-    if not features.is_cuda:
-        raise RuntimeError("unprojection: features live on %s; this implementation runs only on a HIP device "
-                           "(MI355X) and has no CPU path" % features.device)
-    if proj_matricies.device != features.device or coord_volumes.device != features.device:
-        raise RuntimeError("unprojection: expected all tensors on %s, got proj_matricies on %s and coord_volumes on %s"
-                           % (features.device, proj_matricies.device, coord_volumes.device))
-    if out_dtype is None:
-        out_dtype = torch.float16 if features.dtype == torch.float16 else torch.float32
-    if features.numel() == 0 or coord_volumes.numel() == 0:
-        # empty batch / empty volume: the reference's loops do not run and its zero-initialised volume comes back
-        # (aggregation.py:25-28); nothing to launch
-        return torch.zeros((B, features.shape[2]) + tuple(coord_volumes.shape[1:4]), dtype=out_dtype, device=features.device)
+    def volume_shape(B):
+        if coord_volumes.dim() != 5 or coord_volumes.shape[0] != B or coord_volumes.shape[4] != 3:
+            raise RuntimeError("unprojection: coord_volumes must be (%d, X, Y, Z, 3), got %s" % (B, tuple(coord_volumes.shape)))
+        return tuple(coord_volumes.shape[1:4])
+
+    out_dtype, _, empty = _check_call(features, proj_matricies, (coord_volumes,), volume_shape, aggregation_method, variant, out_dtype,
+                                      same_device=True)
+    if empty is not None:
+        return empty
     # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
     proj = proj_matricies.to(torch.float32).contiguous()
     coords = coord_volumes.to(torch.float32).contiguous()
@@ -294,35 +269,14 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
 
 # The same kernels fed by the cuboid recipe instead of a coordinate tensor (mvhmr_unproject_*_cuboid), registered the same way
 # (mvhmr::unprojection_cuboid / mvhmr::unprojection_cuboid_backward).
-def _d3(values):
-    return (ctypes.c_double * 3)(*[float(x) for x in values])
-
-
 def _opc_forward(features, proj, rot, center, position, sides, vol, method, out_dtype, variant):
-    L = _capi.lib()
-    features, layout, like = _feature_layout(features, vol, method, _DTYPES[out_dtype], variant)
-    desc = _make_desc(like, vol, method, _DTYPES[out_dtype], layout, variant)
-    B, C = like.shape[0], like.shape[2]
-    with torch.cuda.device(features.device):
-        out = torch.empty((B, C) + tuple(vol), dtype=_DTYPES[out_dtype], device=features.device)
-        ws, wsp = _workspace(L.mvhmr_unproject_forward_workspace_bytes(ctypes.byref(desc)), features.device)
-        _capi.check(L.mvhmr_unproject_forward_cuboid(ctypes.byref(desc), _ptr(features), _ptr(proj), _ptr(rot), _ptr(center), _d3(position),
-                                                     _d3(sides), _ptr(out), wsp, 0 if ws is None else ws.numel(), _stream(features.device)))
-    return out
+    read, desc = _native_args(features, vol, method, out_dtype, variant)
+    return _native().unprojection_cuboid(read, proj, rot, center, position, sides, vol, *desc)
 
 
 def _opc_backward(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant):
-    L = _capi.lib()
-    features, layout, like = _feature_layout(features, vol, method, _DTYPES[out_dtype], variant)
-    desc = _make_desc(like, vol, method, _DTYPES[out_dtype], layout, variant)
-    grad_out = grad_out.contiguous()
-    with torch.cuda.device(features.device):
-        grad_features = torch.empty(like.shape, dtype=like.dtype, device=like.device) if layout == _capi.LAYOUT_QUAD else torch.empty_like(features)
-        ws, wsp = _workspace(L.mvhmr_unproject_backward_workspace_bytes(ctypes.byref(desc)), features.device)
-        _capi.check(L.mvhmr_unproject_backward_cuboid(ctypes.byref(desc), _ptr(grad_out), _ptr(features), _ptr(proj), _ptr(rot), _ptr(center),
-                                                      _d3(position), _d3(sides), _ptr(grad_features), wsp, 0 if ws is None else ws.numel(),
-                                                      _stream(features.device)))
-    return grad_features
+    read, desc = _native_args(features, vol, method, out_dtype, variant)
+    return _native().unprojection_cuboid_backward(grad_out.contiguous(), read, proj, rot, center, position, sides, vol, *desc)
 
 
 def _opc_setup(ctx, inputs, output):
@@ -363,30 +317,17 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
 
     rotations (B,3,3) and centers (B,3): float32 tensors on features.device; position, sides: 3 numbers each (cuboid corner and
     edge lengths); volume_shape: (X, Y, Z)."""
-    for t in (features, proj_matricies, rotations, centers):
-        if not torch.is_tensor(t):
-            raise TypeError(_TYPE_MSG)
-    if aggregation_method not in _METHODS:
-        raise ValueError("Unknown aggregation_method: {}".format(aggregation_method))
-    if variant not in _capi.VARIANT:
-        raise ValueError("Unknown kernel variant: {}".format(variant))
-    if features.dim() != 5:
-        raise RuntimeError("unprojection: features must be (B, V, C, Hf, Wf), got %s" % (tuple(features.shape),))
-    B, V = features.shape[:2]
-    if tuple(proj_matricies.shape) != (B, V, 3, 4):
-        raise RuntimeError("unprojection: proj_matricies must be (%d, %d, 3, 4), got %s" % (B, V, tuple(proj_matricies.shape)))
-    if tuple(rotations.shape) != (B, 3, 3) or tuple(centers.shape) != (B, 3):
-        raise RuntimeError("unprojection: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
-                           % (B, B, tuple(rotations.shape), tuple(centers.shape)))
-    if not features.is_cuda:
-        raise RuntimeError("unprojection: features live on %s; this implementation runs only on a HIP device "
-                           "(MI355X) and has no CPU path" % features.device)
-    vol = tuple(int(v) for v in volume_shape)
-    if out_dtype is None:
-        out_dtype = torch.float16 if features.dtype == torch.float16 else torch.float32
-    if features.numel() == 0 or min(vol) == 0:
-        return torch.zeros((B, features.shape[2]) + vol, dtype=out_dtype, device=features.device)
-    dev = features.device
+    def checked_shape(B):
+        if tuple(rotations.shape) != (B, 3, 3) or tuple(centers.shape) != (B, 3):
+            raise RuntimeError("unprojection: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
+                               % (B, B, tuple(rotations.shape), tuple(centers.shape)))
+        return tuple(int(v) for v in volume_shape)
+
+    out_dtype, vol, empty = _check_call(features, proj_matricies, (rotations, centers), checked_shape, aggregation_method, variant,
+                                        out_dtype, same_device=False)
+    if empty is not None:
+        return empty
+    dev = features.device                               # the cuboid's few numbers move to the features' device
     proj = proj_matricies.detach().to(device=dev, dtype=torch.float32).contiguous()
     rot = rotations.detach().to(device=dev, dtype=torch.float32).contiguous()
     cen = centers.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -438,35 +379,26 @@ class _FusedAggregate(torch.autograd.Function):
         dev = x.device
         x = x.contiguous()
         w2 = weight.reshape(Cout, Cin).contiguous()
-        pos = (ctypes.c_double * 3)(*[float(v) for v in position])
-        sid = (ctypes.c_double * 3)(*[float(v) for v in sides])
         with torch.cuda.device(dev):
             quad = torch.empty(B * V * Cout * Hf * Wf, dtype=torch.float32, device=dev)
             _capi.check(L.mvhmr_conv1x1_to_quad(_ptr(x), _ptr(w2), _ptr(bias) if bias is not None else ctypes.c_void_p(0), _ptr(quad),
                                                 B * V, Cin, Cout, Hf, Wf, _stream(dev)))
-            desc = _make_desc(torch.empty((B, V, Cout, Hf, Wf), dtype=torch.float32, device="meta"), vol, method, out_dtype, _capi.LAYOUT_QUAD, _capi.VARIANT["auto"])
-            out = torch.empty((B, Cout) + tuple(vol), dtype=out_dtype, device=dev)
-            ws, wsp = _workspace(L.mvhmr_unproject_forward_workspace_bytes(ctypes.byref(desc)), dev)
-            _capi.check(L.mvhmr_unproject_forward_cuboid(ctypes.byref(desc), _ptr(quad), _ptr(proj), _ptr(rot), _ptr(center), pos, sid,
-                                                         _ptr(out), wsp, 0 if ws is None else ws.numel(), _stream(dev)))
+        geometry = ([float(v) for v in position], [float(v) for v in sides], [int(v) for v in vol])
+        desc = (B, V, Cout, Hf, Wf, method, _capi.F32, _dtype_code(out_dtype), _capi.LAYOUT_QUAD, _capi.VARIANT["auto"])
+        out = _native().unprojection_cuboid(quad, proj, rot, center, *geometry, *desc)
         ctx.save_for_backward(x, w2, quad, proj, rot, center)
-        ctx.desc, ctx.pos, ctx.sid, ctx.has_bias, ctx.wshape = desc, pos, sid, bias is not None, tuple(weight.shape)
+        ctx.geometry, ctx.desc, ctx.has_bias, ctx.wshape = geometry, desc, bias is not None, tuple(weight.shape)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         x, w2, quad, proj, rot, center = ctx.saved_tensors
         L = _capi.lib()
-        desc = ctx.desc
         B, V, Cin, Hf, Wf = x.shape
         Cout = w2.shape[0]
         dev = x.device
-        grad_out = grad_out.contiguous()
-        with torch.cuda.device(dev):
-            gy = torch.empty((B * V, Cout, Hf * Wf), dtype=torch.float32, device=dev)           # gradient w.r.t. the conv output, planar
-            ws, wsp = _workspace(L.mvhmr_unproject_backward_workspace_bytes(ctypes.byref(desc)), dev)
-            _capi.check(L.mvhmr_unproject_backward_cuboid(ctypes.byref(desc), _ptr(grad_out), _ptr(quad), _ptr(proj), _ptr(rot), _ptr(center),
-                                                          ctx.pos, ctx.sid, _ptr(gy), wsp, 0 if ws is None else ws.numel(), _stream(dev)))
+        gy = _native().unprojection_cuboid_backward(grad_out.contiguous(), quad, proj, rot, center, *ctx.geometry, *ctx.desc).view(
+            B * V, Cout, Hf * Wf)                                                                # gradient w.r.t. the conv output, planar
         xf = x.view(B * V, Cin, Hf * Wf)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:

@@ -1,8 +1,7 @@
-// PyTorch-ROCm C++ extension over the C ABI (include/mvhmr_unproject.h): the native implementation of the custom ops
-// mvhmr_native::unprojection / unprojection_backward / unprojection_backward_geometry, which multiviewhmr_amd/aggregation.py dispatches to from its
-// torch.library ops mvhmr::unprojection / _backward (reference boundary: unprojection(), models/aggregation.py:20-87, and the autograd
-// graph through it).  What runs here per call: descriptor, output / gradient tensor and workspace from the caching allocator, the
-// current HIP stream, one C-ABI call -- no Python, no ctypes marshalling.  Host code only: the kernels live in libmvhmr_unproject.so.
+// PyTorch-ROCm C++ extension over the C ABI (include/mvhmr_unproject.h): the host side of every un-projection launch, as the ops
+// mvhmr_native::unprojection[_backward[_geometry]] / unprojection_cuboid[_backward] that multiviewhmr_amd/aggregation.py calls from its
+// torch.library ops and from _FusedAggregate.  Per call: tensor checks, descriptor, output and workspace from the caching allocator, the
+// current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <c10/core/DeviceGuard.h>
@@ -12,17 +11,31 @@
 
 namespace {
 
-mvhmr_unproject_desc make_desc(int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, const at::Tensor &coords, int64_t method,
+// B..W: the logical feature shape; X..Z: the volume
+mvhmr_unproject_desc make_desc(int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t X, int64_t Y, int64_t Z, int64_t method,
                                int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
 {
-    TORCH_CHECK(coords.dim() == 5 && coords.size(4) == 3, "coord_volumes must be (B, X, Y, Z, 3)");
     mvhmr_unproject_desc d;
     d.abi_version = MVHMR_ABI_VERSION;
     d.batch = (int32_t)B; d.views = (int32_t)V; d.channels = (int32_t)C; d.feat_h = (int32_t)H; d.feat_w = (int32_t)W;
-    d.vol_x = (int32_t)coords.size(1); d.vol_y = (int32_t)coords.size(2); d.vol_z = (int32_t)coords.size(3);
+    d.vol_x = (int32_t)X; d.vol_y = (int32_t)Y; d.vol_z = (int32_t)Z;
     d.method = (int32_t)method; d.feat_dtype = (int32_t)feat_dtype; d.out_dtype = (int32_t)out_dtype;
     d.feat_layout = (int32_t)layout; d.variant = (int32_t)variant;
     return d;
+}
+
+mvhmr_unproject_desc coords_desc(const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
+                                 int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    TORCH_CHECK(coords.dim() == 5 && coords.size(0) == B && coords.size(4) == 3, "mvhmr_unproject: coord_volumes must be fp32 (B, X, Y, Z, 3)");
+    return make_desc(B, V, C, H, W, coords.size(1), coords.size(2), coords.size(3), method, feat_dtype, out_dtype, layout, variant);
+}
+
+mvhmr_unproject_desc cuboid_desc(at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C,
+                                 int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    TORCH_CHECK(position.size() == 3 && sides.size() == 3 && vol.size() == 3, "mvhmr_unproject: position, sides and vol take 3 values each");
+    return make_desc(B, V, C, H, W, vol[0], vol[1], vol[2], method, feat_dtype, out_dtype, layout, variant);
 }
 
 at::ScalarType scalar_of(int64_t code)
@@ -30,64 +43,87 @@ at::ScalarType scalar_of(int64_t code)
     return code == MVHMR_F16 ? at::kHalf : code == MVHMR_BF16 ? at::kBFloat16 : at::kFloat;
 }
 
-void check(int status)
+// a tensor the library reads through a plain pointer: contiguous on the features' device, `dtype` with `numel` elements
+void check_tensor(const at::Tensor &t, const at::Tensor &features, const char *name, at::ScalarType dtype, int64_t numel)
 {
+    TORCH_CHECK(t.is_cuda() && t.device() == features.device() && t.is_contiguous(), "mvhmr_unproject: ", name,
+                " must be a contiguous tensor on ", features.device(), ", got one on ", t.device());
+    TORCH_CHECK(t.scalar_type() == dtype && t.numel() == numel, "mvhmr_unproject: ", name, " must be ", dtype, " with ", numel,
+                " elements, got ", t.scalar_type(), " with ", t.numel());
+}
+
+// The C ABI trusts its descriptor (plain pointers carry no sizes): every tensor is checked against it HERE, before anything is launched.
+// coords (tensor ops) or rot + center (cuboid ops) describe the volume; grad_out is undefined for a forward.
+void check_inputs(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *coords,
+                  const at::Tensor *rot, const at::Tensor *center, const at::Tensor *grad_out)
+{
+    const int64_t B = d.batch, V = d.views, C = d.channels, H = d.feat_h, W = d.feat_w;
+    TORCH_CHECK(features.is_cuda() && features.is_contiguous(), "mvhmr_unproject: features must be a contiguous tensor on a HIP device");
+    TORCH_CHECK(B >= 1 && V >= 1 && C >= 1 && H >= 1 && W >= 1, "mvhmr_unproject: every dimension must be >= 1");
+    TORCH_CHECK(d.feat_dtype == MVHMR_F32 || d.feat_dtype == MVHMR_F16, "mvhmr_unproject: features are fp32 or fp16");
+    const bool quad = d.feat_layout == MVHMR_LAYOUT_QUAD || d.feat_layout == MVHMR_LAYOUT_QUAD_LOG2E;
+    const int64_t need = B * V * ((C + 3) / 4 * 4) * H * W * (quad ? 4 : d.feat_dtype == MVHMR_F16 ? 2 : 4);
+    const int64_t have = features.numel() * (int64_t)features.element_size();
+    TORCH_CHECK(quad || d.feat_layout == MVHMR_LAYOUT_BVHWC ? have >= need : have == B * V * C * H * W * (int64_t)features.element_size(),
+                "mvhmr_unproject: features hold ", have, " bytes, the descriptor (", B, ", ", V, ", ", C, ", ", H, ", ", W, ") needs ", need);
+    TORCH_CHECK(quad || features.element_size() == (d.feat_dtype == MVHMR_F16 ? 2 : 4), "mvhmr_unproject: feature dtype and descriptor disagree");
+    check_tensor(proj, features, "proj_matricies (B, V, 3, 4)", at::kFloat, B * V * 12);
+    if (coords)
+        check_tensor(*coords, features, "coord_volumes (B, X, Y, Z, 3)", at::kFloat, B * d.vol_x * d.vol_y * d.vol_z * 3);
+    if (rot)
+        check_tensor(*rot, features, "rot (B, 3, 3)", at::kFloat, B * 9);
+    if (center)
+        check_tensor(*center, features, "center (B, 3)", at::kFloat, B * 3);
+    if (grad_out)
+        check_tensor(*grad_out, features, "grad_out (B, C, X, Y, Z)", scalar_of(d.out_dtype), B * C * d.vol_x * d.vol_y * d.vol_z);
+}
+
+// the common tail: workspace from the caching allocator, the features' device, the current HIP stream, one C-ABI call
+template <typename Launch>
+void run(const mvhmr_unproject_desc &d, const at::Tensor &features, size_t (*workspace_bytes)(const mvhmr_unproject_desc *), Launch launch)
+{
+    c10::DeviceGuard guard(features.device());
+    const size_t need = workspace_bytes(&d);
+    at::Tensor ws = at::empty({(int64_t)need}, features.options().dtype(at::kByte));
+    const int status = launch(need ? ws.data_ptr() : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream());
     TORCH_CHECK(status == MVHMR_OK, "mvhmr_unproject: ", mvhmr_last_error());
 }
 
-// The C ABI trusts its descriptor (plain pointers carry no sizes): every tensor is checked against it HERE, before anything is launched
-void check_sizes(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H,
-                 int64_t W, int64_t feat_dtype, int64_t layout)
+// gradient w.r.t. the features in their dtype: channels-last strides for channels-last features (the permuted view's data_ptr() is
+// its storage's), planar otherwise, quad-planar features included
+at::Tensor new_feature_grad(const mvhmr_unproject_desc &d, const at::Tensor &features)
 {
-    TORCH_CHECK(B >= 1 && V >= 1 && C >= 1 && H >= 1 && W >= 1, "mvhmr_unproject: every dimension must be >= 1");
-    TORCH_CHECK(feat_dtype == MVHMR_F32 || feat_dtype == MVHMR_F16, "mvhmr_unproject: features are fp32 or fp16");
-    const int64_t quad = layout == MVHMR_LAYOUT_QUAD || layout == MVHMR_LAYOUT_QUAD_LOG2E;
-    const int64_t need = B * V * ((C + 3) / 4 * 4) * H * W * (quad ? 4 : feat_dtype == MVHMR_F16 ? 2 : 4);
-    const int64_t have = features.numel() * (int64_t)features.element_size();
-    TORCH_CHECK(quad || layout == MVHMR_LAYOUT_BVHWC ? have >= need : have == B * V * C * H * W * (int64_t)features.element_size(),
-                "mvhmr_unproject: features hold ", have, " bytes, the descriptor (", B, ", ", V, ", ", C, ", ", H, ", ", W, ") needs ", need);
-    TORCH_CHECK(quad || features.element_size() == (feat_dtype == MVHMR_F16 ? 2 : 4), "mvhmr_unproject: feature dtype and descriptor disagree");
-    TORCH_CHECK(proj.scalar_type() == at::kFloat && proj.numel() == B * V * 12, "mvhmr_unproject: proj_matricies must be fp32 (B, V, 3, 4)");
-    TORCH_CHECK(coords.scalar_type() == at::kFloat && coords.dim() == 5 && coords.size(0) == B && coords.size(4) == 3,
-                "mvhmr_unproject: coord_volumes must be fp32 (B, X, Y, Z, 3)");
+    const auto opts = features.options().dtype(scalar_of(d.feat_dtype));
+    if (d.feat_layout == MVHMR_LAYOUT_BVHWC)
+        return at::empty({d.batch, d.views, d.feat_h, d.feat_w, d.channels}, opts).permute({0, 1, 4, 2, 3});
+    return at::empty({d.batch, d.views, d.channels, d.feat_h, d.feat_w}, opts);
 }
 
 // features: the tensor the library reads (planar, channels-last or the quad-planar byte buffer); B..W: the logical feature shape
 at::Tensor unprojection_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C,
                                int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
 {
-    TORCH_CHECK(features.is_cuda() && proj.is_cuda() && coords.is_cuda(), "unprojection runs only on a HIP device");
-    TORCH_CHECK(features.is_contiguous() && proj.is_contiguous() && coords.is_contiguous(), "contiguous tensors expected");
-    check_sizes(features, proj, coords, B, V, C, H, W, feat_dtype, layout);
-    c10::DeviceGuard guard(features.device());
-    const mvhmr_unproject_desc d = make_desc(B, V, C, H, W, coords, method, feat_dtype, out_dtype, layout, variant);
-    at::Tensor out = at::empty({B, C, coords.size(1), coords.size(2), coords.size(3)}, features.options().dtype(scalar_of(out_dtype)));
-    const size_t need = mvhmr_unproject_forward_workspace_bytes(&d);
-    at::Tensor ws = at::empty({(int64_t)need}, features.options().dtype(at::kByte));
-    check(mvhmr_unproject_forward(&d, features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(), out.data_ptr(),
-                                  need ? ws.data_ptr() : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream()));
+    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, &coords, nullptr, nullptr, nullptr);
+    at::Tensor out = at::empty({B, C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(out_dtype)));
+    run(d, features, mvhmr_unproject_forward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_forward(&d, features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(), out.data_ptr(), ws, n, s);
+    });
     return out;
 }
 
-// gradient w.r.t. the features, in the feature dtype; planar (B,V,C,H,W) -- or channels-last strides when layout is BVHWC
 at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
                                         int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
                                         int64_t out_dtype, int64_t layout, int64_t variant)
 {
-    TORCH_CHECK(grad_out.is_cuda() && features.is_cuda(), "unprojection runs only on a HIP device");
-    TORCH_CHECK(grad_out.is_contiguous() && features.is_contiguous(), "contiguous tensors expected");
-    check_sizes(features, proj, coords, B, V, C, H, W, feat_dtype, layout);
-    TORCH_CHECK(grad_out.scalar_type() == scalar_of(out_dtype) && grad_out.numel() == B * C * coords.size(1) * coords.size(2) * coords.size(3),
-                "mvhmr_unproject: grad_out must be (B, C, X, Y, Z) in the volume's dtype");
-    c10::DeviceGuard guard(features.device());
-    const mvhmr_unproject_desc d = make_desc(B, V, C, H, W, coords, method, feat_dtype, out_dtype, layout, variant);
-    const auto opts = features.options().dtype(scalar_of(feat_dtype));
-    at::Tensor grad = layout == MVHMR_LAYOUT_BVHWC ? at::empty({B, V, H, W, C}, opts) : at::empty({B, V, C, H, W}, opts);
-    const size_t need = mvhmr_unproject_backward_workspace_bytes(&d);
-    at::Tensor ws = at::empty({(int64_t)need}, features.options().dtype(at::kByte));
-    check(mvhmr_unproject_backward(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(), grad.data_ptr(),
-                                   need ? ws.data_ptr() : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream()));
-    return layout == MVHMR_LAYOUT_BVHWC ? grad.permute({0, 1, 4, 2, 3}) : grad;
+    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
+    at::Tensor grad = new_feature_grad(d, features);
+    run(d, features, mvhmr_unproject_backward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_backward(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
+                                        grad.data_ptr(), ws, n, s);
+    });
+    return grad;
 }
 
 // gradients w.r.t. proj (B,V,3,4) and coords (B,X,Y,Z,3), both fp32; an output not asked for comes back as an empty tensor
@@ -96,35 +132,64 @@ std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const a
                                                                           int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
                                                                           int64_t variant, bool want_proj, bool want_coords)
 {
-    TORCH_CHECK(grad_out.is_cuda() && features.is_cuda() && proj.is_cuda() && coords.is_cuda(), "unprojection runs only on a HIP device");
-    TORCH_CHECK(grad_out.is_contiguous() && features.is_contiguous() && proj.is_contiguous() && coords.is_contiguous(), "contiguous tensors expected");
     TORCH_CHECK(want_proj || want_coords, "mvhmr_unproject: neither gradient was asked for");
-    check_sizes(features, proj, coords, B, V, C, H, W, feat_dtype, layout);
-    TORCH_CHECK(grad_out.scalar_type() == scalar_of(out_dtype) && grad_out.numel() == B * C * coords.size(1) * coords.size(2) * coords.size(3),
-                "mvhmr_unproject: grad_out must be (B, C, X, Y, Z) in the volume's dtype");
-    c10::DeviceGuard guard(features.device());
-    const mvhmr_unproject_desc d = make_desc(B, V, C, H, W, coords, method, feat_dtype, out_dtype, layout, variant);
+    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
     const auto opts = features.options().dtype(at::kFloat);
     at::Tensor gp = want_proj ? at::empty({B, V, 3, 4}, opts) : at::empty({0}, opts);
     at::Tensor gc = want_coords ? at::empty(coords.sizes(), opts) : at::empty({0}, opts);
-    const size_t need = mvhmr_unproject_backward_geometry_workspace_bytes(&d);
-    at::Tensor ws = at::empty({(int64_t)need}, features.options().dtype(at::kByte));
-    check(mvhmr_unproject_backward_geometry(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
-                                            want_proj ? gp.data_ptr<float>() : nullptr, want_coords ? gc.data_ptr<float>() : nullptr,
-                                            need ? ws.data_ptr() : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream()));
+    run(d, features, mvhmr_unproject_backward_geometry_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_backward_geometry(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
+                                                 want_proj ? gp.data_ptr<float>() : nullptr, want_coords ? gc.data_ptr<float>() : nullptr, ws, n, s);
+    });
     return {gp, gc};
+}
+
+// the same two launches for the cuboid recipe (mvhmr_unproject_*_cuboid): rot (B,3,3) and center (B,3) on the device, position / sides / vol
+// 3 values each
+at::Tensor unprojection_cuboid_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
+                                      at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C,
+                                      int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, nullptr, &rot, &center, nullptr);
+    at::Tensor out = at::empty({B, C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(out_dtype)));
+    run(d, features, mvhmr_unproject_forward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_forward_cuboid(&d, features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(),
+                                              position.data(), sides.data(), out.data_ptr(), ws, n, s);
+    });
+    return out;
+}
+
+at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
+                                               const at::Tensor &center, at::ArrayRef<double> position, at::ArrayRef<double> sides,
+                                               at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
+                                               int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
+    at::Tensor grad = new_feature_grad(d, features);
+    run(d, features, mvhmr_unproject_backward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_backward_cuboid(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(),
+                                               center.data_ptr<float>(), position.data(), sides.data(), grad.data_ptr(), ws, n, s);
+    });
+    return grad;
 }
 
 }  // namespace
 
+// the descriptor's fields after an op's tensors, and the cuboid ops' arguments
+#define MVHMR_DESC_ARGS "int B, int V, int C, int H, int W, int method, int feat_dtype, int out_dtype, int layout, int variant"
+#define MVHMR_CUBOID_ARGS "Tensor proj, Tensor rot, Tensor center, float[] position, float[] sides, int[] vol, " MVHMR_DESC_ARGS
+
 TORCH_LIBRARY(mvhmr_native, m)
 {
-    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, int B, int V, int C, int H, int W, int method, int feat_dtype, int out_dtype, "
-          "int layout, int variant) -> Tensor");
-    m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, int B, int V, int C, int H, int W, int method, "
-          "int feat_dtype, int out_dtype, int layout, int variant) -> Tensor");
-    m.def("unprojection_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, int B, int V, int C, int H, int W, "
-          "int method, int feat_dtype, int out_dtype, int layout, int variant, bool want_proj, bool want_coords) -> (Tensor, Tensor)");
+    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS ") -> Tensor");
+    m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS ") -> Tensor");
+    m.def("unprojection_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS
+          ", bool want_proj, bool want_coords) -> (Tensor, Tensor)");
+    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS ") -> Tensor");
+    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS ") -> Tensor");
     m.def("abi_version() -> int");
 }
 
@@ -133,6 +198,8 @@ TORCH_LIBRARY_IMPL(mvhmr_native, CUDA, m)
     m.impl("unprojection", &unprojection_native);
     m.impl("unprojection_backward", &unprojection_backward_native);
     m.impl("unprojection_backward_geometry", &unprojection_backward_geometry_native);
+    m.impl("unprojection_cuboid", &unprojection_cuboid_native);
+    m.impl("unprojection_cuboid_backward", &unprojection_cuboid_backward_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)

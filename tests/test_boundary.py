@@ -114,5 +114,16 @@ def test_torch_extension_builds_and_speaks_the_abi():
     assert os.path.exists(ext)
     torch.ops.load_library(ext)
     assert torch.ops.mvhmr_native.abi_version() == _capi.ABI_VERSION
-    for name in ("unprojection", "unprojection_backward"):
+    for name in ("unprojection", "unprojection_backward", "unprojection_cuboid", "unprojection_cuboid_backward"):
         assert hasattr(torch.ops.mvhmr_native, name)
+
+
+def test_missing_torch_extension_fails_on_first_call_not_on_import(monkeypatch, tmp_path):
+    """the extension is loaded on first use: the package imports without it (CPU hosts, FakeTensor tracing), a launch raises"""
+    import importlib
+    from multiviewhmr_amd import aggregation, build
+    monkeypatch.setattr(build, "EXT", str(tmp_path / "nope.so"))
+    importlib.reload(aggregation)
+    assert aggregation._ext is None
+    with pytest.raises(RuntimeError, match=re.escape("python -m multiviewhmr_amd.build")):
+        aggregation._native()

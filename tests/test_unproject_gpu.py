@@ -1902,26 +1902,43 @@ def test_mean_over_absent_views_is_one_division_by_the_real_views(views, gpu):
     record_err("mean V%d brick bwd" % views, _err(fb.grad.cpu().numpy(), gref), _bound(gref))
 
 
-def test_native_extension_is_the_route_and_equals_the_ctypes_route(gpu, monkeypatch):
+def _capi_route(f, p, c, go):
+    """forward + feature backward as direct C-ABI calls through _capi (as bench.py makes them): the layout decision and the
+    descriptor the custom op uses, outputs and workspaces allocated here"""
+    L, vp = _capi.lib(), ctypes.c_void_p
+    stream = vp(torch.cuda.current_stream(f.device).cuda_stream)
+    method, auto = _capi.AGG["softmax"], _capi.VARIANT["auto"]
+    feats, layout, like = aggregation._feature_layout(f, c, method, torch.float32, auto)
+    desc = ctypes.byref(aggregation._make_desc(like, c, method, torch.float32, layout, auto))
+    out = torch.empty((like.shape[0], like.shape[2]) + tuple(c.shape[1:4]), device=f.device)
+    grad = torch.empty(like.shape, device=f.device) if layout == _capi.LAYOUT_QUAD else torch.empty_like(feats)
+    ws = torch.empty(L.mvhmr_unproject_forward_workspace_bytes(desc), dtype=torch.uint8, device=f.device)
+    _capi.check(L.mvhmr_unproject_forward(desc, vp(feats.data_ptr()), vp(p.data_ptr()), vp(c.data_ptr()), vp(out.data_ptr()),
+                                          vp(ws.data_ptr() if ws.numel() else 0), ws.numel(), stream))
+    ws = torch.empty(L.mvhmr_unproject_backward_workspace_bytes(desc), dtype=torch.uint8, device=f.device)
+    _capi.check(L.mvhmr_unproject_backward(desc, vp(go.data_ptr()), vp(feats.data_ptr()), vp(p.data_ptr()), vp(c.data_ptr()),
+                                           vp(grad.data_ptr()), vp(ws.data_ptr() if ws.numel() else 0), ws.numel(), stream))
+    return out, grad
+
+
+def test_native_extension_is_the_route_and_equals_direct_c_abi_calls(gpu):
     """north_star: "drop-in ... via a PyTorch-ROCm C++/HIP extension".  The custom ops' host work runs in lib_ext/mvhmr_torch_ext.so
-    (csrc_ext/mvhmr_torch_ext.cpp over the C ABI); the ctypes route makes the same C-ABI calls: bit-equal forward, and backward up
-    to the float atomics' order"""
-    assert aggregation._NATIVE, "the C++ extension was not built / not found beside the package"
+    (csrc_ext/mvhmr_torch_ext.cpp over the C ABI); the same C-ABI calls made directly through the ctypes binding give a bit-equal
+    forward, and a backward equal up to the float atomics' order"""
     d = load_golden("unproj", "bricks_v4c8")
     p, c, go = _dev(d, "proj", gpu), _dev(d, "coords", gpu), _dev(d, "grad_out", gpu)
     outs, grads = [], []
-    for native in (True, False):
-        monkeypatch.setattr(aggregation, "_NATIVE", native)
-        for feats in (_dev(d, "features", gpu), _dev(d, "features", gpu).permute(0, 1, 3, 4, 2).contiguous().permute(0, 1, 4, 2, 3)):
-            f = feats.detach().requires_grad_(True)
-            out = aggregation.unprojection(f, p, c)
-            out.backward(go)
-            outs.append(out.detach()); grads.append(f.grad)
-    assert torch.equal(outs[0], outs[2]) and torch.equal(outs[1], outs[3])                  # planar, channels-last
-    record_err("native vs ctypes route, planar bwd", float((grads[0] - grads[2]).abs().max()), 1e-5)
-    record_err("native vs ctypes route, channels-last bwd", float((grads[1] - grads[3]).abs().max()), 1e-5)
-    assert grads[1].stride() == grads[3].stride()                                            # channels-last gradient for channels-last features
-    record_err("native route vs golden", _err(outs[0].cpu().numpy(), d["out_softmax"]), TOL)
+    for feats in (_dev(d, "features", gpu), _dev(d, "features", gpu).permute(0, 1, 3, 4, 2).contiguous().permute(0, 1, 4, 2, 3)):
+        f = feats.detach().requires_grad_(True)
+        out = aggregation.unprojection(f, p, c)
+        out.backward(go)
+        ref_out, ref_grad = _capi_route(feats, p, c, go)
+        outs.append((out.detach(), ref_out)); grads.append((f.grad, ref_grad))
+    assert torch.equal(*outs[0]) and torch.equal(*outs[1])                                   # planar, channels-last
+    record_err("extension vs C ABI, planar bwd", float((grads[0][0] - grads[0][1]).abs().max()), 1e-5)
+    record_err("extension vs C ABI, channels-last bwd", float((grads[1][0] - grads[1][1]).abs().max()), 1e-5)
+    assert grads[1][0].stride() == grads[1][1].stride()                                      # channels-last gradient for channels-last features
+    record_err("extension route vs golden", _err(outs[0][0].cpu().numpy(), d["out_softmax"]), TOL)
     # the C ABI trusts its descriptor: the extension checks every tensor against it BEFORE anything is launched
     fe = _dev(d, "features", gpu)
     B, V, C, H, W = fe.shape
@@ -1931,3 +1948,11 @@ def test_native_extension_is_the_route_and_equals_the_ctypes_route(gpu, monkeypa
         torch.ops.mvhmr_native.unprojection(fe, p[:, :1].contiguous(), c, B, V, C, H, W, 0, 0, 0, 0, 2)
     with pytest.raises(RuntimeError, match="mvhmr_unproject"):                               # library errors surface as RuntimeError
         torch.ops.mvhmr_native.unprojection(fe, p, c, B, V, C, H, W, 7, 0, 0, 0, 2)         # unknown aggregate
+    # a host tensor is refused, not handed to a kernel as a device pointer
+    with pytest.raises(RuntimeError, match="proj_matricies .* contiguous tensor on"):
+        torch.ops.mvhmr_native.unprojection(fe, p.cpu(), c, B, V, C, H, W, 0, 0, 0, 0, 2)
+    with pytest.raises(RuntimeError, match="proj_matricies .* contiguous tensor on"):
+        torch.ops.mvhmr_native.unprojection_backward(go, fe, p.cpu(), c, B, V, C, H, W, 0, 0, 0, 0, 2)
+    rot, cen = torch.eye(3).expand(B, 3, 3).contiguous(), torch.zeros(B, 3, device=gpu)
+    with pytest.raises(RuntimeError, match="rot .* contiguous tensor on"):
+        torch.ops.mvhmr_native.unprojection_cuboid(fe, p, rot, cen, [0.0] * 3, [1.0] * 3, [4, 4, 4], B, V, C, H, W, 0, 0, 0, 0, 2)
