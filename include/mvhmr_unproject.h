@@ -33,7 +33,8 @@ extern "C" {
 #define MVHMR_ABI_VERSION 4   /* 2: MVHMR_LAYOUT_QUAD became column-major (B,V,C/4,Wf,Hf,4).  3: QUAD + AUTO is geometry-gated and needs its
                                  workspace; explicit GATHER with QUAD input is served; MVHMR_BF16 out_dtype; mvhmr_unproject_backward_supported,
                                  mvhmr_triangulate_dlt.  4: MVHMR_LAYOUT_QUAD_LOG2E (ABI history); additive within 4:
-                                 mvhmr_unproject_backward_geometry[_workspace_bytes] */
+                                 mvhmr_unproject_backward_geometry[_workspace_bytes], mvhmr_unproject_backward_geometry_cuboid[_workspace_bytes],
+                                 mvhmr_triangulate_dlt_backward */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -211,6 +212,23 @@ int mvhmr_unproject_backward_cuboid(const mvhmr_unproject_desc *desc, const void
                                     void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
+ * Backward w.r.t. the geometry of the cuboid recipe: grad_proj as mvhmr_unproject_backward_geometry gives it (the same partials, the
+ * same bits as that call on the coordinates mvhmr_build_coord_volumes builds), and the gradients w.r.t. the pose the recipe takes,
+ *   grad_rot     (B,3,3) fp32 or NULL    grad_rot[b][r][k] = sum_n gX_n[r] d_n[k],   d_n = fl(grid_n - center[b])          [write]
+ *   grad_center  (B,3) fp32 or NULL      grad_center[b] = sum_n gX_n - rot[b]^T sum_n gX_n                                   [write]
+ * with gX_n the gradient w.r.t. the centre of voxel n (dX/dcenter = I - rot).  rot = I gives grad_center == 0 exactly.  Validation,
+ * layouts and storage pairings as mvhmr_unproject_backward_geometry; at least one output non-null.  Per-block fp32 partials summed
+ * per sample in float64 in a fixed order, no float atomics: bitwise reproducible.  The workspace
+ * (mvhmr_unproject_backward_geometry_cuboid_workspace_bytes) holds the channels-last copy when one is needed and the partials of
+ * grad_proj and of the pose.
+ */
+size_t mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(const mvhmr_unproject_desc *desc);
+int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                             const float *rot, const float *center, const double position[3], const double sides[3],
+                                             float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
+                                             void *hip_stream);
+
+/*
  * Layout pass on its own: features (B,V,C,Hf,Wf) -> dst in `dst_layout` (MVHMR_LAYOUT_BVHWC with the channel
  * count rounded up to a multiple of 4 and zero padded, or MVHMR_LAYOUT_QUAD), desc->feat_dtype.
  * desc->feat_layout names the SOURCE: MVHMR_LAYOUT_BVCHW (also assumed for MVHMR_LAYOUT_QUAD descriptors, as before), or
@@ -276,6 +294,20 @@ int mvhmr_triangulate_dlt(const float *proj, const float *points, float *out, in
  * view v are multiplied by c_v before the decomposition): confidences (V) fp32 shared by the samples (confidences_per_sample = 0) or (B,V) */
 int mvhmr_triangulate_dlt_weighted(const float *proj, const float *points, const float *confidences, float *out, int32_t batch, int32_t views,
                                    int32_t points_per_sample, int32_t confidences_per_sample, void *hip_stream);
+/*
+ * Backward of the DLT: the gradient torch.svd's backward gives through the reference's -vh[:, 3] (sign-invariant), from the eigenpairs
+ * of the same normal matrix, float64, one thread per sample.
+ *   confidences  (V) / (B,V) fp32 as for mvhmr_triangulate_dlt_weighted, or NULL (every weight 1)
+ *   grad_out     (B,3) fp32                                                                          [read]
+ *   grad_proj    (B,V,3,4) fp32 or NULL; grad_points (B,V,2) fp32 or NULL; grad_conf (B,V) fp32 or NULL   [write]
+ * grad_points and grad_conf are always per sample, also when points / confidences are shared: the caller sums them over the batch.
+ * At least one output must be non-null.  views >= 1: a sample with fewer than 2 views, or whose normal matrix has a repeated smallest
+ * eigenvalue (|l_k - l_min| <= 1e-12 l_max for some other eigenvalue l_k), has no gradient -- every output of that sample is NaN (the
+ * reference's SVD backward is non-finite there, or fails outright at V = 1).
+ */
+int mvhmr_triangulate_dlt_backward(const float *proj, const float *points, const float *confidences, const float *grad_out, float *grad_proj,
+                                   float *grad_points, float *grad_conf, int32_t batch, int32_t views, int32_t points_per_sample,
+                                   int32_t confidences_per_sample, void *hip_stream);
 
 /*
  * Caller-side helper of VolumeGenerator.forward (models/aggregation.py:138-187): fills

@@ -26,6 +26,7 @@ EXPORTS = (
     "mvhmr_unproject_backward_supported", "mvhmr_triangulate_dlt", "mvhmr_triangulate_dlt_weighted",
     "mvhmr_unproject_forward_kernel_name",
     "mvhmr_unproject_backward_geometry_workspace_bytes", "mvhmr_unproject_backward_geometry",
+    "mvhmr_unproject_backward_geometry_cuboid_workspace_bytes", "mvhmr_unproject_backward_geometry_cuboid", "mvhmr_triangulate_dlt_backward",
 )
 
 
@@ -79,6 +80,10 @@ def lib():
     L.mvhmr_unproject_forward_cuboid.argtypes = [dp, vp, vp, vp, vp, d3, d3, vp, vp, sz, vp]
     L.mvhmr_unproject_backward_cuboid.restype = ctypes.c_int
     L.mvhmr_unproject_backward_cuboid.argtypes = [dp, vp, vp, vp, vp, vp, d3, d3, vp, vp, sz, vp]
+    L.mvhmr_unproject_backward_geometry_cuboid_workspace_bytes.restype = sz
+    L.mvhmr_unproject_backward_geometry_cuboid_workspace_bytes.argtypes = [dp]
+    L.mvhmr_unproject_backward_geometry_cuboid.restype = ctypes.c_int
+    L.mvhmr_unproject_backward_geometry_cuboid.argtypes = [dp, vp, vp, vp, vp, vp, d3, d3, vp, vp, vp, vp, sz, vp]
     L.mvhmr_conv1x1_to_quad.restype = ctypes.c_int
     L.mvhmr_conv1x1_to_quad.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     L.mvhmr_conv1x1_to_quad_supported.restype = ctypes.c_int
@@ -105,6 +110,8 @@ def lib():
     L.mvhmr_triangulate_dlt.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     L.mvhmr_triangulate_dlt_weighted.restype = ctypes.c_int
     L.mvhmr_triangulate_dlt_weighted.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
+    L.mvhmr_triangulate_dlt_backward.restype = ctypes.c_int
+    L.mvhmr_triangulate_dlt_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.mvhmr_build_coord_volumes.restype = ctypes.c_int
     L.mvhmr_build_coord_volumes.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), vp]

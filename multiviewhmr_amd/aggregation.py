@@ -8,8 +8,9 @@ Same names, argument meaning, return shapes/dtypes, state-dict keys and quirks (
 Q1-Q6).  What differs is HOW: the b x v Python loop with ~20 ATen launches per iteration and the
 (V,C,X,Y,Z) intermediates is one fused HIP kernel launch behind the C ABI of include/mvhmr_unproject.h
 (forward), one more for the gradient w.r.t. `features` and one for the gradients w.r.t. `proj_matricies` / `coord_volumes` when those
-require grad (backward), exposed as torch.library custom ops (mvhmr::unprojection / mvhmr::unprojection_cuboid + their _backward ops
-and mvhmr::unprojection_backward_geometry, with fake / meta shape functions and a
+require grad (backward), exposed as torch.library custom ops (mvhmr::unprojection / mvhmr::unprojection_cuboid + their _backward ops,
+mvhmr::unprojection_backward_geometry / mvhmr::unprojection_cuboid_backward_geometry -- the latter also w.r.t. the cuboid's rotations and
+centers -- and mvhmr::triangulate_dlt[_backward] for the pivot VolumeGenerator triangulates, with fake / meta shape functions and a
 registered autograd formula) whose host side runs in the PyTorch-ROCm C++ extension csrc_ext/mvhmr_torch_ext.cpp -- the one
 route of every un-projection launch, VolumeGenerator's fused conv + un-projection included.  There is no CPU / eager fallback: the
 call raises if the tensors are not on a HIP device or the library or the extension is not built.
@@ -140,10 +141,7 @@ def _op_backward_geometry(grad_out, features, proj, coords, method, out_dtype, v
     """gradients w.r.t. proj_matricies (B,V,3,4) and coord_volumes (B,X,Y,Z,3), fp32 (mvhmr_unproject_backward_geometry); an output
     not asked for comes back empty.  Planar features go through the library's channels-last pass, channels-last ones are read as
     they are; `variant` plays no part."""
-    if _is_channels_last5(features) and features.shape[2] % 4 == 0:
-        layout = _capi.LAYOUT_BVHWC
-    else:
-        features, layout = features.contiguous(), _capi.LAYOUT_BVCHW
+    features, layout = _geometry_read_layout(features)
     read, desc = _native_args(features, coords, method, out_dtype, variant, layout)
     return tuple(_native().unprojection_backward_geometry(grad_out.contiguous(), read, proj, coords, *desc, want_proj, want_coords))
 
@@ -279,6 +277,28 @@ def _opc_backward(grad_out, features, proj, rot, center, position, sides, vol, m
     return _native().unprojection_cuboid_backward(grad_out.contiguous(), read, proj, rot, center, position, sides, vol, *desc)
 
 
+def _geometry_read_layout(features):
+    """the features as the geometry backward reads them: channels-last as they are (C % 4 == 0), else a planar contiguous copy"""
+    if _is_channels_last5(features) and features.shape[2] % 4 == 0:
+        return features, _capi.LAYOUT_BVHWC
+    return features.contiguous(), _capi.LAYOUT_BVCHW
+
+
+def _opc_backward_geometry(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant, want_proj=True,
+                           want_rot=True, want_center=True):
+    """gradients w.r.t. proj_matricies (B,V,3,4), rotations (B,3,3) and centers (B,3), fp32 (mvhmr_unproject_backward_geometry_cuboid);
+    an output not asked for comes back empty.  Layouts as _op_backward_geometry."""
+    features, layout = _geometry_read_layout(features)
+    read, desc = _native_args(features, vol, method, out_dtype, variant, layout)
+    return tuple(_native().unprojection_cuboid_backward_geometry(grad_out.contiguous(), read, proj, rot, center, position, sides, vol, *desc,
+                                                                 want_proj, want_rot, want_center))
+
+
+def _fake_backward_geometry_cuboid(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant, want_proj=True,
+                                   want_rot=True, want_center=True):
+    return tuple(t.new_empty(t.shape if want else (0,), dtype=torch.float32) for t, want in ((proj, want_proj), (rot, want_rot), (center, want_center)))
+
+
 def _opc_setup(ctx, inputs, output):
     ctx.save_for_backward(*inputs[:4])
     ctx.args = tuple(inputs[4:])
@@ -287,7 +307,11 @@ def _opc_setup(ctx, inputs, output):
 def _opc_autograd(ctx, grad_out):
     features, proj, rot, center = ctx.saved_tensors
     g = torch.ops.mvhmr.unprojection_cuboid_backward(grad_out, features, proj, rot, center, *ctx.args) if ctx.needs_input_grad[0] else None
-    return (g,) + (None,) * 9
+    want = tuple(ctx.needs_input_grad[1:4])
+    geo = (None, None, None)
+    if any(want):                                      # a features-only backward launches nothing more
+        geo = torch.ops.mvhmr.unprojection_cuboid_backward_geometry(grad_out, features, proj, rot, center, *ctx.args, *want)
+    return (g,) + tuple(t if w else None for t, w in zip(geo, want)) + (None,) * 6
 
 
 def _register_cuboid_ops():
@@ -303,10 +327,61 @@ def _register_cuboid_ops():
         features.new_empty((features.shape[0], features.shape[2]) + tuple(vol), dtype=_DTYPES[out_dtype]))
     torch.library.register_fake("mvhmr::unprojection_cuboid_backward")(
         lambda grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant: torch.empty_like(features))
+    torch.library.define("mvhmr::unprojection_cuboid_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
+                         + ", bool want_proj=True, bool want_rot=True, bool want_center=True) -> (Tensor, Tensor, Tensor)")
+    torch.library.impl("mvhmr::unprojection_cuboid_backward_geometry", "CUDA")(_opc_backward_geometry)
+    torch.library.register_fake("mvhmr::unprojection_cuboid_backward_geometry")(_fake_backward_geometry_cuboid)
     torch.library.register_autograd("mvhmr::unprojection_cuboid", _opc_autograd, setup_context=_opc_setup)
 
 
 _register_cuboid_ops()
+
+
+# DLT triangulation (mvhmr_triangulate_dlt[_weighted] and mvhmr_triangulate_dlt_backward) as mvhmr::triangulate_dlt[_backward]: proj (B,V,3,4),
+# points (V,2) shared or (B,V,2), confidences None, (V,) shared or (B,V), all fp32 on one HIP device -> (B,3)
+def _dlt_forward(proj, points, confidences):
+    return _native().triangulate_dlt(proj, points, confidences)
+
+
+def _dlt_backward(grad_out, proj, points, confidences):
+    """per-sample gradients w.r.t. proj (B,V,3,4), points (B,V,2) and confidences (B,V); NaN where the gradient does not exist"""
+    return tuple(_native().triangulate_dlt_backward(grad_out.contiguous(), proj, points, confidences))
+
+
+def _fake_dlt_backward(grad_out, proj, points, confidences):
+    B, V = proj.shape[:2]
+    return proj.new_empty((B, V, 3, 4)), proj.new_empty((B, V, 2)), proj.new_empty((B, V))
+
+
+def _dlt_setup(ctx, inputs, output):
+    proj, points, confidences = inputs
+    ctx.save_for_backward(proj, points, confidences)
+
+
+def _dlt_autograd(ctx, grad_out):
+    proj, points, confidences = ctx.saved_tensors
+    gp, gu, gc = torch.ops.mvhmr.triangulate_dlt_backward(grad_out, proj, points, confidences)
+    if points.dim() == 2:                              # per-sample gradients of shared inputs: summed over the batch
+        gu = gu.sum(0)
+    if confidences is not None and confidences.dim() == 1:
+        gc = gc.sum(0)
+    return (gp if ctx.needs_input_grad[0] else None, gu if ctx.needs_input_grad[1] else None,
+            gc if confidences is not None and ctx.needs_input_grad[2] else None)
+
+
+def _register_dlt_op():
+    if _op_defined("triangulate_dlt"):
+        return
+    torch.library.define("mvhmr::triangulate_dlt", "(Tensor proj, Tensor points, Tensor? confidences) -> Tensor")
+    torch.library.impl("mvhmr::triangulate_dlt", "CUDA")(_dlt_forward)
+    torch.library.register_fake("mvhmr::triangulate_dlt")(lambda proj, points, confidences: proj.new_empty((proj.shape[0], 3)))
+    torch.library.define("mvhmr::triangulate_dlt_backward", "(Tensor grad_out, Tensor proj, Tensor points, Tensor? confidences) -> (Tensor, Tensor, Tensor)")
+    torch.library.impl("mvhmr::triangulate_dlt_backward", "CUDA")(_dlt_backward)
+    torch.library.register_fake("mvhmr::triangulate_dlt_backward")(_fake_dlt_backward)
+    torch.library.register_autograd("mvhmr::triangulate_dlt", _dlt_autograd, setup_context=_dlt_setup)
+
+
+_register_dlt_op()
 
 
 def unprojection_cuboid(features, proj_matricies, rotations, centers, position, sides, volume_shape,
@@ -316,7 +391,7 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     mvhmr_build_coord_volumes followed by `unprojection`).
 
     rotations (B,3,3) and centers (B,3): float32 tensors on features.device; position, sides: 3 numbers each (cuboid corner and
-    edge lengths); volume_shape: (X, Y, Z)."""
+    edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers."""
     def checked_shape(B):
         if tuple(rotations.shape) != (B, 3, 3) or tuple(centers.shape) != (B, 3):
             raise RuntimeError("unprojection: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
@@ -328,9 +403,10 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     if empty is not None:
         return empty
     dev = features.device                               # the cuboid's few numbers move to the features' device
-    proj = proj_matricies.detach().to(device=dev, dtype=torch.float32).contiguous()
-    rot = rotations.detach().to(device=dev, dtype=torch.float32).contiguous()
-    cen = centers.detach().to(device=dev, dtype=torch.float32).contiguous()
+    # no detach: the op differentiates w.r.t. proj, rot and center too (the casts carry the gradients back to the caller's device and dtype)
+    proj = proj_matricies.to(device=dev, dtype=torch.float32).contiguous()
+    rot = rotations.to(device=dev, dtype=torch.float32).contiguous()
+    cen = centers.to(device=dev, dtype=torch.float32).contiguous()
     return torch.ops.mvhmr.unprojection_cuboid(features, proj, rot, cen, [float(x) for x in position], [float(x) for x in sides], list(vol),
                                                _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
 
@@ -369,7 +445,8 @@ class _FusedAggregate(torch.autograd.Function):
     geometry gate decides brick / gather on the device for THIS call's cameras and pose (the gather side converts the copy to
     channels-last first), forward and backward each for their own bricks -- no cached decision, no host synchronisation.
     Backward: the un-projection backward gives the gradient w.r.t. the conv output in the planar layout; weight / bias / input
-    gradients are three GEMMs on it."""
+    gradients are three GEMMs on it.  proj / rot / center gradients, when asked for, come from the cuboid geometry backward on the
+    saved quad-planar copy (which the library converts to channels-last for it)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, proj, rot, center, position, sides, vol, method, out_dtype=torch.float32):
@@ -397,10 +474,18 @@ class _FusedAggregate(torch.autograd.Function):
         B, V, Cin, Hf, Wf = x.shape
         Cout = w2.shape[0]
         dev = x.device
+        g_geo = (None, None, None)
+        want_geo = tuple(ctx.needs_input_grad[3:6])
+        if any(want_geo):
+            g_geo = _native().unprojection_cuboid_backward_geometry(grad_out.contiguous(), quad, proj, rot, center, *ctx.geometry, *ctx.desc,
+                                                                    *want_geo)
+            g_geo = tuple(t if w else None for t, w in zip(g_geo, want_geo))
+        gx = gw = gb = None
+        if not any(ctx.needs_input_grad[:3]):
+            return (None, None, None) + g_geo + (None,) * 5
         gy = _native().unprojection_cuboid_backward(grad_out.contiguous(), quad, proj, rot, center, *ctx.geometry, *ctx.desc).view(
             B * V, Cout, Hf * Wf)                                                                # gradient w.r.t. the conv output, planar
         xf = x.view(B * V, Cin, Hf * Wf)
-        gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             if L.mvhmr_conv1x1_planar_supported(Cout, Cin, Hf * Wf):                           # (Cin, Cout) @ (BV, Cout, HW) on the MFMA GEMM
                 gx = torch.empty((B, V, Cin, Hf, Wf), dtype=torch.float32, device=dev)
@@ -421,7 +506,7 @@ class _FusedAggregate(torch.autograd.Function):
                 gw = torch.einsum("nop,nip->oi", gy, xf).view(ctx.wshape)
             if want_b:
                 gb = gy.sum(dim=(0, 2))
-        return gx, gw, gb, None, None, None, None, None, None, None, None
+        return (gx, gw, gb) + g_geo + (None,) * 5
 
 
 def pack_cameras(cameras, device):
@@ -491,7 +576,8 @@ class VolumeGenerator(nn.Module):
 
         Training draws theta ~ U(0, 2 pi) from the GLOBAL numpy stream, one draw per sample in order
         (quirk Q6); eval uses theta = 0.  The pivot is keypoints_3d[b][6, :3], or the DLT-triangulated
-        image centre when use_triangulation is set."""
+        image centre when use_triangulation is set -- a function of proj_matricies_org that carries its gradient (the reference
+        triangulates from the caller's proj_matricies with torch.svd)."""
         batch_size = proj_matricies_org.shape[0]
         axis = self.rotation_axis()
         if self.training:
@@ -511,7 +597,7 @@ class VolumeGenerator(nn.Module):
             # one batched DLT on the device, no per-sample .cpu(); stays a device tensor
             n_views = proj_matricies_org.shape[1]
             images_center = (torch.tensor(images_shape, dtype=torch.float32) / 2).expand(n_views, 2)
-            centers = multiview.triangulate_points_from_multiple_views_linear_batch(proj_matricies_org.detach(), images_center)
+            centers = multiview.triangulate_points_from_multiple_views_linear_batch(proj_matricies_org, images_center)   # differentiable
         else:
             kp = batch['keypoints_3d']
             if torch.is_tensor(kp):                                          # already a (B, 17, 3|4) tensor (any device)

@@ -572,6 +572,49 @@ int mvhmr_unproject_backward_geometry(const mvhmr_unproject_desc *desc, const vo
                     "geometry backward");
 }
 
+size_t mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(const mvhmr_unproject_desc *desc)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
+    return (desc->feat_layout == MVHMR_LAYOUT_BVHWC ? 0 : featT_bytes(p)) + align_up(geom_partial_bytes(p)) + align_up(pose_partial_bytes(p));
+}
+
+int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                             const float *rot, const float *center, const double position[3], const double sides[3],
+                                             float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
+                                             void *hip_stream)
+{
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    if (!grad_out || !features || !proj) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj must be non-null");
+    Coords cs;
+    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
+    if (rc != MVHMR_OK) return rc;
+    if (!grad_proj && !grad_rot && !grad_center)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj, grad_rot and grad_center are all null: nothing to compute");
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p))
+        return fail(MVHMR_ERR_UNSUPPORTED, "quad-planar features of this shape cannot be converted to channels-last (C %% 4 == 0, C <= 4092, B * V <= 65535)");
+    rc = check_ws(workspace, workspace_bytes, mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(desc));
+    if (rc != MVHMR_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    const void *featT = features;
+    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) {
+        rc = launched(desc->feat_layout == MVHMR_LAYOUT_QUAD ? launch_quad_to_channels_last(features, ws, p, s) : launch_to_channels_last(features, ws, p, s),
+                      "layout pass");
+        if (rc != MVHMR_OK) return rc;
+        featT = ws;
+        ws += featT_bytes(p);
+    }
+    float *part = reinterpret_cast<float *>(ws), *pose_part = reinterpret_cast<float *>(ws + align_up(geom_partial_bytes(p)));
+    return launched(launch_bwd_geom_cuboid(grad_out, featT, proj, cs, grad_proj ? part : nullptr, grad_proj, (grad_rot || grad_center) ? pose_part : nullptr,
+                                           grad_rot, grad_center, p, s),
+                    "cuboid geometry backward");
+}
+
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)
 {
     Problem p;
@@ -709,6 +752,18 @@ int mvhmr_triangulate_dlt_weighted(const float *proj, const float *points, const
     if (batch < 1 || views < 2) return fail(MVHMR_ERR_INVALID_ARGUMENT, "batch must be >= 1 and views >= 2 (got %d, %d)", batch, views);
     return launched(launch_triangulate_dlt(proj, points, confidences, out, batch, views, points_per_sample ? 1 : 0, confidences_per_sample ? 1 : 0,
                                            static_cast<hipStream_t>(hip_stream)), "weighted DLT triangulation");
+}
+
+int mvhmr_triangulate_dlt_backward(const float *proj, const float *points, const float *confidences, const float *grad_out, float *grad_proj,
+                                   float *grad_points, float *grad_conf, int32_t batch, int32_t views, int32_t points_per_sample,
+                                   int32_t confidences_per_sample, void *hip_stream)
+{
+    if (!proj || !points || !grad_out) return fail(MVHMR_ERR_INVALID_ARGUMENT, "proj / points / grad_out must be non-null");
+    if (!grad_proj && !grad_points && !grad_conf) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj, grad_points and grad_conf are all null: nothing to compute");
+    if (batch < 1 || views < 1) return fail(MVHMR_ERR_INVALID_ARGUMENT, "batch and views must be >= 1 (got %d, %d)", batch, views);
+    return launched(launch_triangulate_dlt_bwd(proj, points, confidences, grad_out, grad_proj, grad_points, grad_conf, batch, views, points_per_sample ? 1 : 0,
+                                               confidences && confidences_per_sample ? 1 : 0, static_cast<hipStream_t>(hip_stream)),
+                    "DLT triangulation backward");
 }
 
 int mvhmr_build_coord_volumes(float *coords, const float *rot, const float *center, int32_t batch, int32_t volume_size,

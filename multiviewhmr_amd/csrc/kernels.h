@@ -103,12 +103,21 @@ hipError_t launch_conv1x1_quad(const float *x, const float *w, const float *bias
 // DLT triangulation of one point per sample (fp32 in / out, float64 inside); points (V,2) shared or (B,V,2) per sample
 hipError_t launch_triangulate_dlt(const float *proj, const float *points, const float *conf, float *out, int B, int V, int points_per_sample,
                                   int conf_per_sample, hipStream_t s);
+// its backward: grad_out (B,3) -> grad_proj (B,V,3,4), grad_points (B,V,2), grad_conf (B,V), each per sample and each optional;
+// NaN where the gradient does not exist (V < 2, a degenerate eigenvalue)
+hipError_t launch_triangulate_dlt_bwd(const float *proj, const float *points, const float *conf, const float *grad_out, float *grad_proj,
+                                      float *grad_points, float *grad_conf, int B, int V, int points_per_sample, int conf_per_sample, hipStream_t s);
 
 // gradient w.r.t. proj and coords (unproject_geom_bwd.hip): featT channels-last (B,V,HW,C4) in the feature dtype; `part` holds
 // geom_partial_bytes(p) of fp32 partials of grad_proj (needed when grad_proj is non-null); either output may be null
 size_t geom_partial_bytes(const Problem &p);
 hipError_t launch_bwd_geom(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
                            float *grad_coords, const Problem &p, hipStream_t s);
+// the same for the cuboid recipe (coords.ptr == null): grad_proj as above, and the gradients w.r.t. the pose, grad_rot (B,3,3) and
+// grad_center (B,3), from pose_part (pose_partial_bytes(p) of fp32 partials, needed when either is non-null); grad_coords is not written
+size_t pose_partial_bytes(const Problem &p);
+hipError_t launch_bwd_geom_cuboid(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
+                                  float *pose_part, float *grad_rot, float *grad_center, const Problem &p, hipStream_t s);
 
 hipError_t launch_build_coords(float *coords_out, const float *rot, const float *center, int B, int S,
                                const double pos[3], const double sides[3], hipStream_t s);

@@ -568,16 +568,12 @@ hipError_t launch_grad_cast(const float *srcT, void *dst, const Problem &p, hipS
 // constraint would change and with it the answer.  One thread per sample, float64 throughout: the smallest eigenvector of the 4 x 4
 // normal matrix A^T A by cyclic Jacobi rotations -- no SVD, no host round trip.  cond(A) is ~10^1..10^4 for pixel-scale projection
 // matrices, its square far inside float64 (agreement with numpy's float64 SVD: tests/test_unproject_gpu.py).
-__global__ void __launch_bounds__(64)
-k_triangulate_dlt(const float *__restrict__ proj, const float *__restrict__ points, const float *__restrict__ conf, float *__restrict__ out, int B, int V,
-                  int points_per_sample, int conf_per_sample)
+// The normal matrix M = A^T A of sample b (rows of view v times c_v) and its eigen-decomposition by cyclic Jacobi rotations: on return
+// M's diagonal holds the eigenvalues, E's columns the eigenvectors.  Shared by the DLT and its backward (the same bits in both).
+__device__ __forceinline__ void dlt_eigen(const float *P, const float *uv, const float *cf, int V, double (&M)[4][4], double (&E)[4][4])
 {
-    const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= B) return;
-    const float *P = proj + (long long)b * V * 12;
-    const float *uv = points + (points_per_sample ? (long long)b * V * 2 : 0);
-    double M[4][4] = {{0}}, E[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    const float *cf = conf ? conf + (conf_per_sample ? (long long)b * V : 0) : nullptr;    // A *= confidences (utils/multiview.py:156-161): rows of view v times c_v
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) { M[i][j] = 0.0; E[i][j] = i == j ? 1.0 : 0.0; }
     for (int v = 0; v < V; ++v)
         for (int r = 0; r < 2; ++r) {
             double a[4];
@@ -609,6 +605,19 @@ k_triangulate_dlt(const float *__restrict__ proj, const float *__restrict__ poin
                 }
             }
     }
+}
+
+__global__ void __launch_bounds__(64)
+k_triangulate_dlt(const float *__restrict__ proj, const float *__restrict__ points, const float *__restrict__ conf, float *__restrict__ out, int B, int V,
+                  int points_per_sample, int conf_per_sample)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const float *P = proj + (long long)b * V * 12;
+    const float *uv = points + (points_per_sample ? (long long)b * V * 2 : 0);
+    const float *cf = conf ? conf + (conf_per_sample ? (long long)b * V : 0) : nullptr;    // A *= confidences (utils/multiview.py:156-161): rows of view v times c_v
+    double M[4][4], E[4][4];
+    dlt_eigen(P, uv, cf, V, M, E);
     int m = 0;
     for (int k = 1; k < 4; ++k) m = M[k][k] < M[m][m] ? k : m;
     const double h0 = E[0][m], h1 = E[1][m], h2 = E[2][m], h3 = E[3][m];
@@ -619,6 +628,79 @@ hipError_t launch_triangulate_dlt(const float *proj, const float *points, const 
                                   int conf_per_sample, hipStream_t s)
 {
     hipLaunchKernelGGL(k_triangulate_dlt, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, proj, points, conf, out, B, V, points_per_sample, conf_per_sample);
+    return hipGetLastError();
+}
+
+// Backward of the DLT, one thread per sample, float64.  With the eigenpairs (l_k, e_k) of M, h = e_m (smallest l_m), x = h[:3] / h3:
+//     gh = (gx / h3, -(gx . h[:3]) / h3^2)                                         (x is invariant to the sign of h: so is all below)
+//     G  = sum_{k != m} ((e_k^T gh) / (l_m - l_k)) e_k h^T,  Gs = (G + G^T) / 2     (first-order eigenvector perturbation)
+//     g a_r = 2 Gs a_r  for every row a_r = c_v (uv_{v,r} P_v[2] - P_v[r])          (dM = sum_r da_r a_r^T + a_r da_r^T)
+// then the chain rule into P_v, uv_v and c_v: the gradient torch.svd's backward gives through the reference's -vh[:, 3].  It does not
+// exist for V < 2 (M has rank <= 2) or a degenerate eigenvalue (|l_k - l_m| <= 1e-12 l_max for some k != m): NaN is written there.
+// grad_points / grad_conf are per sample; any output may be null.
+__global__ void __launch_bounds__(64)
+k_triangulate_dlt_bwd(const float *__restrict__ proj, const float *__restrict__ points, const float *__restrict__ conf, const float *__restrict__ grad_out,
+                      float *__restrict__ grad_proj, float *__restrict__ grad_points, float *__restrict__ grad_conf, int B, int V, int points_per_sample,
+                      int conf_per_sample)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const float *P = proj + (long long)b * V * 12;
+    const float *uv = points + (points_per_sample ? (long long)b * V * 2 : 0);
+    const float *cf = conf ? conf + (conf_per_sample ? (long long)b * V : 0) : nullptr;
+    double Gs[4][4];
+    bool ok = V >= 2;
+    if (ok) {
+        double M[4][4], E[4][4];
+        dlt_eigen(P, uv, cf, V, M, E);
+        int m = 0;
+        double lmax = M[0][0];
+        for (int k = 1; k < 4; ++k) { m = M[k][k] < M[m][m] ? k : m; lmax = fmax(lmax, M[k][k]); }
+        const double h[4] = {E[0][m], E[1][m], E[2][m], E[3][m]};
+        const double gx0 = grad_out[3 * b + 0], gx1 = grad_out[3 * b + 1], gx2 = grad_out[3 * b + 2];
+        const double gh[4] = {gx0 / h[3], gx1 / h[3], gx2 / h[3], -(gx0 * h[0] + gx1 * h[1] + gx2 * h[2]) / (h[3] * h[3])};
+        double G[4][4] = {{0}};
+        for (int k = 0; k < 4; ++k) {
+            if (k == m) continue;
+            const double gap = M[m][m] - M[k][k];
+            if (!(fabs(gap) > 1e-12 * lmax)) ok = false;
+            const double ck = (E[0][k] * gh[0] + E[1][k] * gh[1] + E[2][k] * gh[2] + E[3][k] * gh[3]) / gap;
+            for (int i = 0; i < 4; ++i)
+                for (int j = 0; j < 4; ++j) G[i][j] += ck * E[i][k] * h[j];
+        }
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j) Gs[i][j] = 0.5 * (G[i][j] + G[j][i]);
+    }
+    const float nan = __builtin_nanf("");
+    for (int v = 0; v < V; ++v) {
+        const double w = cf ? (double)cf[v] : 1.0;
+        double gP[3][4] = {{0}}, gc = 0.0;
+        for (int r = 0; r < 2; ++r) {
+            double a0[4], ga[4];                                 // a0: the row before the confidence weight
+            const double u = uv[2 * v + r];
+            for (int k = 0; k < 4; ++k) a0[k] = u * (double)P[v * 12 + 8 + k] - (double)P[v * 12 + 4 * r + k];
+            double gu = 0.0;
+            for (int i = 0; i < 4; ++i) {
+                ga[i] = 0.0;
+                for (int k = 0; k < 4; ++k) ga[i] += 2.0 * (ok ? Gs[i][k] : 0.0) * (w * a0[k]);
+                gc += a0[i] * ga[i];
+                gP[2][i] += w * u * ga[i];
+                gP[r][i] -= w * ga[i];
+                gu += w * (double)P[v * 12 + 8 + i] * ga[i];
+            }
+            if (grad_points) grad_points[((long long)b * V + v) * 2 + r] = ok ? (float)gu : nan;
+        }
+        if (grad_conf) grad_conf[(long long)b * V + v] = ok ? (float)gc : nan;
+        if (grad_proj)
+            for (int i = 0; i < 12; ++i) grad_proj[((long long)b * V + v) * 12 + i] = ok ? (float)gP[i / 4][i % 4] : nan;
+    }
+}
+
+hipError_t launch_triangulate_dlt_bwd(const float *proj, const float *points, const float *conf, const float *grad_out, float *grad_proj,
+                                      float *grad_points, float *grad_conf, int B, int V, int points_per_sample, int conf_per_sample, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_triangulate_dlt_bwd, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, proj, points, conf, grad_out, grad_proj, grad_points,
+                       grad_conf, B, V, points_per_sample, conf_per_sample);
     return hipGetLastError();
 }
 

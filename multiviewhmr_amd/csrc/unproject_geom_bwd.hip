@@ -22,6 +22,13 @@
 //   phase 3 = one thread per (voxel, view): dh_v; grad_coords written once per voxel by plain stores; 12 fp32 partials of grad_proj
 //             per (block, view) into the workspace, summed per (b, v) by k_geom_reduce in float64 in a fixed order.
 // No float atomics anywhere: both outputs are bitwise reproducible from run to run.
+//
+// Cuboid route (POSE instances): the voxel centre is X = R d + c with d = fl(g - c), g = position + step (i,j,k) (voxel_xyz).  With
+// gX_n = sum_v P_v[:, :3]^T dh_v (what grad_coords would hold)
+//     grad_rot[b][r][k] = sum_n gX_n[r] d_n[k]          grad_center[b] = sum_n gX_n - R^T sum_n gX_n     (dX/dc = I - R)
+// phase 3 gains an epilogue: gX and d (recomputed from (i,j,k) in voxel_xyz's rounding) per voxel into LDS, then 12 fp32 partials per
+// block (9 of sum gX (x) d, 3 of sum gX), voxels in order; k_pose_reduce sums them per sample in float64 in a fixed order and applies
+// R^T in float64 (R = I gives grad_center == 0 exactly).  grad_coords is not written on this route.
 #include "device_common.h"
 #include "kernels.h"
 
@@ -147,10 +154,10 @@ size_t geo_lds_bytes(int V)
 
 }  // namespace
 
-template <typename TF, typename TO, int METHOD, int VT>
+template <typename TF, typename TO, int METHOD, int VT, bool POSE>
 __global__ void __launch_bounds__(256)
 k_bwd_geom(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj, const Coords coords,
-           float *__restrict__ part, float *__restrict__ grad_coords, int C, int C4, int H, int W, long long N)
+           float *__restrict__ part, float *__restrict__ grad_coords, int C, int C4, int H, int W, long long N, float *__restrict__ pose_part)
 {
     constexpr int CPL = geo_cpl(VT);
     constexpr int kPass = kGeoGroup / (64 * CPL);
@@ -280,7 +287,7 @@ k_bwd_geom(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const 
         dh[idx * 3 + 2] = d2;
     }
     __syncthreads();
-    if (grad_coords && tid < kGeoTile && n0 + tid < N) {
+    if (!POSE && grad_coords && tid < kGeoTile && n0 + tid < N) {
         // grad_coords[b, n] = sum_v P_v[:, :3]^T dh_v, views in order; one plain store per coordinate
         const int j = tid;
         float g0 = 0.f, g1 = 0.f, g2 = 0.f;
@@ -304,6 +311,34 @@ k_bwd_geom(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const 
             sum = d != 0.f ? fmaf(d, k < 3 ? xyz[j * 3 + k] : 1.f, sum) : sum;
         }
         part[(((long long)b * gridDim.x + blockIdx.x) * VT + v) * 12 + tid % 12] = sum;
+    }
+    if constexpr (POSE) {
+        // epilogue of the cuboid route: gX and d per voxel (0 for tail voxels) behind dh, then this block's 12 pose partials
+        float *gxd = dh + kGeoTile * VT * 3;            // [kGeoTile][6]: gX, d
+        if (tid < kGeoTile) {
+            const int j = tid;
+            float g0 = 0.f, g1 = 0.f, g2 = 0.f, e0 = 0.f, e1 = 0.f, e2 = 0.f;
+            if (n0 + j < N) {
+#pragma unroll 1
+                for (int v = 0; v < VT; ++v) {                  // (not unrolled: keeps the 16-view instances at the tensor route's registers)
+                    const float *P = proj + ((long long)b * VT + v) * 12;
+                    const float h0 = dh[(j * VT + v) * 3 + 0], h1 = dh[(j * VT + v) * 3 + 1], h2 = dh[(j * VT + v) * 3 + 2];
+                    g0 = fmaf(P[8], h2, fmaf(P[4], h1, fmaf(P[0], h0, g0)));
+                    g1 = fmaf(P[9], h2, fmaf(P[5], h1, fmaf(P[1], h0, g1)));
+                    g2 = fmaf(P[10], h2, fmaf(P[6], h1, fmaf(P[2], h0, g2)));
+                }
+                cuboid_offset(coords, b, n0 + j, e0, e1, e2);
+            }
+            gxd[j * 6 + 0] = g0; gxd[j * 6 + 1] = g1; gxd[j * 6 + 2] = g2;
+            gxd[j * 6 + 3] = e0; gxd[j * 6 + 4] = e1; gxd[j * 6 + 5] = e2;
+        }
+        __syncthreads();
+        if (tid >= 256 - 12) {                          // threads the grad_proj partials leave idle (VT * 12 <= 192)
+            const int t = tid - (256 - 12), r = t < 9 ? t / 3 : t - 9, k = t % 3;
+            float sum = 0.f;
+            for (int j = 0; j < kGeoTile; ++j) sum = t < 9 ? fmaf(gxd[j * 6 + r], gxd[j * 6 + 3 + k], sum) : sum + gxd[j * 6 + r];
+            pose_part[((long long)b * gridDim.x + blockIdx.x) * 12 + t] = sum;
+        }
     }
 }
 
@@ -334,70 +369,136 @@ __global__ void __launch_bounds__(256) k_geom_reduce(const float *__restrict__ p
     if (tid < 12) grad_proj[(long long)bv * 12 + tid] = (float)red[tid][0];
 }
 
+// grad_rot[b] = S_gd, grad_center[b] = S_g - R^T S_g from the pose partials of sample b (sum over blocks as k_geom_reduce: float64,
+// fixed order); either output may be null
+__global__ void __launch_bounds__(256) k_pose_reduce(const float *__restrict__ pose_part, const float *__restrict__ rot, float *__restrict__ grad_rot,
+                                                     float *__restrict__ grad_center, int tiles)
+{
+    __shared__ double red[12][256];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    double s[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) s[k] = 0.0;
+    for (int t = tid; t < tiles; t += 256) {
+        const float *p = pose_part + ((long long)b * tiles + t) * 12;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) s[k] += (double)p[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) red[k][tid] = s[k];
+    for (int w = 128; w > 0; w >>= 1) {
+        __syncthreads();
+        if (tid < w) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) red[k][tid] += red[k][tid + w];
+        }
+    }
+    __syncthreads();
+    if (grad_rot && tid < 9) grad_rot[(long long)b * 9 + tid] = (float)red[tid][0];
+    if (grad_center && tid < 3) {
+        const float *R = rot + (long long)b * 9;
+        const double rt = (double)R[tid] * red[9][0] + (double)R[3 + tid] * red[10][0] + (double)R[6 + tid] * red[11][0];   // (R^T S_g)[tid]
+        grad_center[(long long)b * 3 + tid] = (float)(red[9 + tid][0] - rt);
+    }
+}
+
 // ------------------------------------------------------------------------------------------ launchers
 static unsigned geom_tiles(const Problem &p) { return (unsigned)((p.N + kGeoTile - 1) / kGeoTile); }
 
 size_t geom_partial_bytes(const Problem &p) { return (size_t)p.B * geom_tiles(p) * p.V * 12 * sizeof(float); }
+size_t pose_partial_bytes(const Problem &p) { return (size_t)p.B * geom_tiles(p) * 12 * sizeof(float); }
 
-template <typename TF, typename TO, int METHOD>
+template <typename TF, typename TO, int METHOD, bool POSE>
 static hipError_t geom_dispatch_v(const TO *go_, const TF *featT, const float *proj, const Coords &coords, float *part, float *grad_coords,
-                                  const Problem &p, hipStream_t s)
+                                  float *pose_part, const Problem &p, hipStream_t s)
 {
     const size_t lds = geo_lds_bytes(p.V);
     const dim3 grid(geom_tiles(p), (unsigned)p.B);
     auto go = [&](auto kern) -> hipError_t {
         hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, part, grad_coords, p.C, p.C4, p.H, p.W, p.N);
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, part, grad_coords, p.C, p.C4, p.H, p.W, p.N, pose_part);
         return hipGetLastError();
     };
     switch (p.V) {
-    case 1: return go(k_bwd_geom<TF, TO, METHOD, 1>);
-    case 2: return go(k_bwd_geom<TF, TO, METHOD, 2>);
-    case 3: return go(k_bwd_geom<TF, TO, METHOD, 3>);
-    case 4: return go(k_bwd_geom<TF, TO, METHOD, 4>);
-    case 5: return go(k_bwd_geom<TF, TO, METHOD, 5>);
-    case 6: return go(k_bwd_geom<TF, TO, METHOD, 6>);
-    case 7: return go(k_bwd_geom<TF, TO, METHOD, 7>);
-    case 8: return go(k_bwd_geom<TF, TO, METHOD, 8>);
-    case 9: return go(k_bwd_geom<TF, TO, METHOD, 9>);
-    case 10: return go(k_bwd_geom<TF, TO, METHOD, 10>);
-    case 11: return go(k_bwd_geom<TF, TO, METHOD, 11>);
-    case 12: return go(k_bwd_geom<TF, TO, METHOD, 12>);
-    case 13: return go(k_bwd_geom<TF, TO, METHOD, 13>);
-    case 14: return go(k_bwd_geom<TF, TO, METHOD, 14>);
-    case 15: return go(k_bwd_geom<TF, TO, METHOD, 15>);
-    case 16: return go(k_bwd_geom<TF, TO, METHOD, 16>);
+    case 1: return go(k_bwd_geom<TF, TO, METHOD, 1, POSE>);
+    case 2: return go(k_bwd_geom<TF, TO, METHOD, 2, POSE>);
+    case 3: return go(k_bwd_geom<TF, TO, METHOD, 3, POSE>);
+    case 4: return go(k_bwd_geom<TF, TO, METHOD, 4, POSE>);
+    case 5: return go(k_bwd_geom<TF, TO, METHOD, 5, POSE>);
+    case 6: return go(k_bwd_geom<TF, TO, METHOD, 6, POSE>);
+    case 7: return go(k_bwd_geom<TF, TO, METHOD, 7, POSE>);
+    case 8: return go(k_bwd_geom<TF, TO, METHOD, 8, POSE>);
+    case 9: return go(k_bwd_geom<TF, TO, METHOD, 9, POSE>);
+    case 10: return go(k_bwd_geom<TF, TO, METHOD, 10, POSE>);
+    case 11: return go(k_bwd_geom<TF, TO, METHOD, 11, POSE>);
+    case 12: return go(k_bwd_geom<TF, TO, METHOD, 12, POSE>);
+    case 13: return go(k_bwd_geom<TF, TO, METHOD, 13, POSE>);
+    case 14: return go(k_bwd_geom<TF, TO, METHOD, 14, POSE>);
+    case 15: return go(k_bwd_geom<TF, TO, METHOD, 15, POSE>);
+    case 16: return go(k_bwd_geom<TF, TO, METHOD, 16, POSE>);
     }
     return hipErrorNotSupported;
 }
 
-template <typename TF, typename TO>
+template <typename TF, typename TO, bool POSE>
 static hipError_t geom_dispatch_m(const TO *go_, const TF *featT, const float *proj, const Coords &coords, float *part, float *grad_coords,
-                                  const Problem &p, hipStream_t s)
+                                  float *pose_part, const Problem &p, hipStream_t s)
 {
     switch (p.method) {
-    case AGG_SOFTMAX: return geom_dispatch_v<TF, TO, AGG_SOFTMAX>(go_, featT, proj, coords, part, grad_coords, p, s);
-    case AGG_SUM: return geom_dispatch_v<TF, TO, AGG_SUM>(go_, featT, proj, coords, part, grad_coords, p, s);
-    case AGG_MEAN: return geom_dispatch_v<TF, TO, AGG_MEAN>(go_, featT, proj, coords, part, grad_coords, p, s);
-    case AGG_MAX: return geom_dispatch_v<TF, TO, AGG_MAX>(go_, featT, proj, coords, part, grad_coords, p, s);
+    case AGG_SOFTMAX: return geom_dispatch_v<TF, TO, AGG_SOFTMAX, POSE>(go_, featT, proj, coords, part, grad_coords, pose_part, p, s);
+    case AGG_SUM: return geom_dispatch_v<TF, TO, AGG_SUM, POSE>(go_, featT, proj, coords, part, grad_coords, pose_part, p, s);
+    case AGG_MEAN: return geom_dispatch_v<TF, TO, AGG_MEAN, POSE>(go_, featT, proj, coords, part, grad_coords, pose_part, p, s);
+    case AGG_MAX: return geom_dispatch_v<TF, TO, AGG_MAX, POSE>(go_, featT, proj, coords, part, grad_coords, pose_part, p, s);
     }
     return hipErrorInvalidValue;
+}
+
+template <bool POSE>
+static hipError_t geom_dispatch(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_coords,
+                                float *pose_part, const Problem &p, hipStream_t s)
+{
+    if (p.out_bf16)
+        return p.feat_f16 ? hipErrorNotSupported
+                          : geom_dispatch_m<float, bf16_t, POSE>((const bf16_t *)grad_out, (const float *)featT, proj, coords, part, grad_coords, pose_part, p, s);
+    if (!p.feat_f16 && !p.out_f16)
+        return geom_dispatch_m<float, float, POSE>((const float *)grad_out, (const float *)featT, proj, coords, part, grad_coords, pose_part, p, s);
+    if (p.feat_f16 && p.out_f16)
+        return geom_dispatch_m<__half, __half, POSE>((const __half *)grad_out, (const __half *)featT, proj, coords, part, grad_coords, pose_part, p, s);
+    if (p.feat_f16 && !p.out_f16)
+        return geom_dispatch_m<__half, float, POSE>((const float *)grad_out, (const __half *)featT, proj, coords, part, grad_coords, pose_part, p, s);
+    return hipErrorNotSupported;
 }
 
 hipError_t launch_bwd_geom(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
                            float *grad_coords, const Problem &p, hipStream_t s)
 {
     if (p.V < 1 || p.V > kMaxViews || (grad_proj && !part)) return hipErrorInvalidValue;
-    hipError_t e;
-    if (p.out_bf16) e = p.feat_f16 ? hipErrorNotSupported : geom_dispatch_m((const bf16_t *)grad_out, (const float *)featT, proj, coords, part, grad_coords, p, s);
-    else if (!p.feat_f16 && !p.out_f16) e = geom_dispatch_m((const float *)grad_out, (const float *)featT, proj, coords, part, grad_coords, p, s);
-    else if (p.feat_f16 && p.out_f16) e = geom_dispatch_m((const __half *)grad_out, (const __half *)featT, proj, coords, part, grad_coords, p, s);
-    else if (p.feat_f16 && !p.out_f16) e = geom_dispatch_m((const float *)grad_out, (const __half *)featT, proj, coords, part, grad_coords, p, s);
-    else e = hipErrorNotSupported;
+    hipError_t e = geom_dispatch<false>(grad_out, featT, proj, coords, part, grad_coords, nullptr, p, s);
     if (e != hipSuccess || !grad_proj) return e;
     hipLaunchKernelGGL(k_geom_reduce, dim3((unsigned)(p.B * p.V)), dim3(256), 0, s, (const float *)part, grad_proj, p.V, (int)geom_tiles(p));
     return hipGetLastError();
+}
+
+hipError_t launch_bwd_geom_cuboid(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
+                                  float *pose_part, float *grad_rot, float *grad_center, const Problem &p, hipStream_t s)
+{
+    const bool pose = grad_rot || grad_center;
+    if (p.V < 1 || p.V > kMaxViews || coords.ptr || (grad_proj && !part) || (pose && !pose_part) || (!grad_proj && !pose))
+        return hipErrorInvalidValue;
+    hipError_t e = pose ? geom_dispatch<true>(grad_out, featT, proj, coords, grad_proj ? part : nullptr, nullptr, pose_part, p, s)
+                        : geom_dispatch<false>(grad_out, featT, proj, coords, part, nullptr, nullptr, p, s);
+    if (e != hipSuccess) return e;
+    if (grad_proj) {
+        hipLaunchKernelGGL(k_geom_reduce, dim3((unsigned)(p.B * p.V)), dim3(256), 0, s, (const float *)part, grad_proj, p.V, (int)geom_tiles(p));
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (pose) {
+        hipLaunchKernelGGL(k_pose_reduce, dim3((unsigned)p.B), dim3(256), 0, s, (const float *)pose_part, coords.rot, grad_rot, grad_center,
+                           (int)geom_tiles(p));
+        e = hipGetLastError();
+    }
+    return e;
 }
 
 }  // namespace mvhmr

@@ -1,7 +1,7 @@
 // PyTorch-ROCm C++ extension over the C ABI (include/mvhmr_unproject.h): the host side of every un-projection launch, as the ops
-// mvhmr_native::unprojection[_backward[_geometry]] / unprojection_cuboid[_backward] that multiviewhmr_amd/aggregation.py calls from its
-// torch.library ops and from _FusedAggregate.  Per call: tensor checks, descriptor, output and workspace from the caching allocator, the
-// current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
+// mvhmr_native::unprojection[_backward[_geometry]] / unprojection_cuboid[_backward[_geometry]] that multiviewhmr_amd/aggregation.py calls
+// from its torch.library ops and from _FusedAggregate, and of the DLT triangulation (triangulate_dlt[_backward], multiview.py).  Per call:
+// tensor checks, descriptor, output and workspace from the caching allocator, the current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <c10/core/DeviceGuard.h>
@@ -176,6 +176,81 @@ at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const
     return grad;
 }
 
+// gradients w.r.t. proj (B,V,3,4), rot (B,3,3) and center (B,3) of the cuboid recipe, fp32; an output not asked for comes back empty
+std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geometry_native(
+    const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
+    at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
+    int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center)
+{
+    TORCH_CHECK(want_proj || want_rot || want_center, "mvhmr_unproject: no gradient was asked for");
+    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
+    const auto opts = features.options().dtype(at::kFloat);
+    at::Tensor gp = want_proj ? at::empty({B, V, 3, 4}, opts) : at::empty({0}, opts);
+    at::Tensor gr = want_rot ? at::empty({B, 3, 3}, opts) : at::empty({0}, opts);
+    at::Tensor gc = want_center ? at::empty({B, 3}, opts) : at::empty({0}, opts);
+    run(d, features, mvhmr_unproject_backward_geometry_cuboid_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_backward_geometry_cuboid(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(),
+                                                        center.data_ptr<float>(), position.data(), sides.data(), want_proj ? gp.data_ptr<float>() : nullptr,
+                                                        want_rot ? gr.data_ptr<float>() : nullptr, want_center ? gc.data_ptr<float>() : nullptr, ws, n, s);
+    });
+    return {gp, gr, gc};
+}
+
+// DLT triangulation (mvhmr_triangulate_dlt[_weighted]) and its backward: proj (B,V,3,4), points (V,2) or (B,V,2), confidences (V) or
+// (B,V) or undefined, all fp32 and contiguous on proj's device (the same check and tail as the un-projection ops, proj in the features' place)
+void check_dlt(const at::Tensor &proj, const at::Tensor &points, const c10::optional<at::Tensor> &conf, int64_t *B, int64_t *V)
+{
+    TORCH_CHECK(proj.is_cuda() && proj.is_contiguous() && proj.dim() == 4 && proj.size(2) == 3 && proj.size(3) == 4 && proj.scalar_type() == at::kFloat,
+                "mvhmr_triangulate_dlt: proj_matricies must be a contiguous fp32 (B, V, 3, 4) tensor on a HIP device");
+    *B = proj.size(0);
+    *V = proj.size(1);
+    TORCH_CHECK(points.dim() == 2 || points.dim() == 3, "mvhmr_triangulate_dlt: points must be (V, 2) or (B, V, 2)");
+    check_tensor(points, proj, "points (V, 2) / (B, V, 2)", at::kFloat, (points.dim() == 3 ? *B : 1) * *V * 2);
+    if (conf && conf->defined()) {
+        TORCH_CHECK(conf->dim() == 1 || conf->dim() == 2, "mvhmr_triangulate_dlt: confidences must be (V,) or (B, V)");
+        check_tensor(*conf, proj, "confidences (V,) / (B, V)", at::kFloat, (conf->dim() == 2 ? *B : 1) * *V);
+    }
+}
+
+void check_status(int status)
+{
+    TORCH_CHECK(status == MVHMR_OK, "mvhmr_unproject: ", mvhmr_last_error());
+}
+
+at::Tensor triangulate_dlt_native(const at::Tensor &proj, const at::Tensor &points, const c10::optional<at::Tensor> &conf)
+{
+    int64_t B, V;
+    check_dlt(proj, points, conf, &B, &V);
+    c10::DeviceGuard guard(proj.device());
+    at::Tensor out = at::empty({B, 3}, proj.options());
+    const hipStream_t s = c10::hip::getCurrentHIPStream(proj.device().index()).stream();
+    const int pps = points.dim() == 3 ? 1 : 0;
+    if (conf && conf->defined())
+        check_status(mvhmr_triangulate_dlt_weighted(proj.data_ptr<float>(), points.data_ptr<float>(), conf->data_ptr<float>(), out.data_ptr<float>(),
+                                                    (int32_t)B, (int32_t)V, pps, conf->dim() == 2 ? 1 : 0, s));
+    else
+        check_status(mvhmr_triangulate_dlt(proj.data_ptr<float>(), points.data_ptr<float>(), out.data_ptr<float>(), (int32_t)B, (int32_t)V, pps, s));
+    return out;
+}
+
+// per-sample gradients: grad_proj (B,V,3,4), grad_points (B,V,2), grad_conf (B,V) (the caller sums shared points / confidences)
+std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(const at::Tensor &grad_out, const at::Tensor &proj, const at::Tensor &points,
+                                                                                const c10::optional<at::Tensor> &conf)
+{
+    int64_t B, V;
+    check_dlt(proj, points, conf, &B, &V);
+    check_tensor(grad_out, proj, "grad_out (B, 3)", at::kFloat, B * 3);
+    c10::DeviceGuard guard(proj.device());
+    at::Tensor gp = at::empty({B, V, 3, 4}, proj.options()), gu = at::empty({B, V, 2}, proj.options()), gc = at::empty({B, V}, proj.options());
+    const bool weighted = conf && conf->defined();
+    check_status(mvhmr_triangulate_dlt_backward(proj.data_ptr<float>(), points.data_ptr<float>(), weighted ? conf->data_ptr<float>() : nullptr,
+                                                grad_out.data_ptr<float>(), gp.data_ptr<float>(), gu.data_ptr<float>(), gc.data_ptr<float>(), (int32_t)B,
+                                                (int32_t)V, points.dim() == 3 ? 1 : 0, weighted && conf->dim() == 2 ? 1 : 0,
+                                                c10::hip::getCurrentHIPStream(proj.device().index()).stream()));
+    return {gp, gu, gc};
+}
+
 }  // namespace
 
 // the descriptor's fields after an op's tensors, and the cuboid ops' arguments
@@ -190,6 +265,10 @@ TORCH_LIBRARY(mvhmr_native, m)
           ", bool want_proj, bool want_coords) -> (Tensor, Tensor)");
     m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS ") -> Tensor");
     m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS ") -> Tensor");
+    m.def("unprojection_cuboid_backward_geometry(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS
+          ", bool want_proj, bool want_rot, bool want_center) -> (Tensor, Tensor, Tensor)");
+    m.def("triangulate_dlt(Tensor proj, Tensor points, Tensor? confidences) -> Tensor");
+    m.def("triangulate_dlt_backward(Tensor grad_out, Tensor proj, Tensor points, Tensor? confidences) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int");
 }
 
@@ -200,6 +279,9 @@ TORCH_LIBRARY_IMPL(mvhmr_native, CUDA, m)
     m.impl("unprojection_backward_geometry", &unprojection_backward_geometry_native);
     m.impl("unprojection_cuboid", &unprojection_cuboid_native);
     m.impl("unprojection_cuboid_backward", &unprojection_cuboid_backward_native);
+    m.impl("unprojection_cuboid_backward_geometry", &unprojection_cuboid_backward_geometry_native);
+    m.impl("triangulate_dlt", &triangulate_dlt_native);
+    m.impl("triangulate_dlt_backward", &triangulate_dlt_backward_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)

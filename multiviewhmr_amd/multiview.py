@@ -104,31 +104,21 @@ def triangulate_point_from_multiple_views_linear_torch(proj_matricies, points, c
 
 def triangulate_points_from_multiple_views_linear_batch(proj_matricies, points, confidences=None):
     """The same DLT for a whole batch at once: proj_matricies (B, V, 3, 4), points (V, 2) shared by the samples -> (B, 3),
-    on proj_matricies.device with no host synchronisation (HIP tensors: mvhmr_triangulate_dlt; CPU tensors -- tests without a GPU --
-    the batched float64 SVD below).  The caller (VolumeGenerator with use_triangulation, reference
+    on proj_matricies.device with no host synchronisation (HIP tensors: mvhmr_triangulate_dlt, differentiable w.r.t. proj_matricies,
+    points and confidences -- a sample whose gradient does not exist (V < 2, a repeated smallest eigenvalue) gets NaN; CPU tensors --
+    tests without a GPU -- the batched float64 SVD below).  The caller (VolumeGenerator with use_triangulation, reference
     aggregation.py:174-177) triangulates the image centre of every sample; the reference does it sample by sample with a
     device SVD and a .cpu() each.  One batched float64 SVD of the (B, 2V, 4) system here; the right singular vector of the
     smallest singular value is the homogeneous point (its sign cancels in the dehomogenisation)."""
     B, V = proj_matricies.shape[:2]
     if proj_matricies.is_cuda:
-        # the library's SVD-free kernel: one thread per sample, 4 x 4 normal matrix, float64 Jacobi rotations
-        import ctypes
-        from . import _capi
-        L = _capi.lib()
-        P32 = proj_matricies.detach().to(torch.float32).contiguous()
-        pts32 = points.detach().to(device=P32.device, dtype=torch.float32).contiguous()
-        out = torch.empty(B, 3, dtype=torch.float32, device=P32.device)
-        per_sample = 1 if pts32.dim() == 3 else 0
-        with torch.cuda.device(P32.device):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(P32.device).cuda_stream)
-            if confidences is None:
-                _capi.check(L.mvhmr_triangulate_dlt(ctypes.c_void_p(P32.data_ptr()), ctypes.c_void_p(pts32.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                                    B, V, per_sample, stream))
-            else:                                                             # A *= confidences (utils/multiview.py:156-161), (V,) or (B, V)
-                c32 = confidences.detach().to(device=P32.device, dtype=torch.float32).contiguous()
-                _capi.check(L.mvhmr_triangulate_dlt_weighted(ctypes.c_void_p(P32.data_ptr()), ctypes.c_void_p(pts32.data_ptr()), ctypes.c_void_p(c32.data_ptr()),
-                                                             ctypes.c_void_p(out.data_ptr()), B, V, per_sample, 1 if c32.dim() == 2 else 0, stream))
-        return out
+        # mvhmr::triangulate_dlt: the library's SVD-free kernel (one thread per sample, 4 x 4 normal matrix, float64 Jacobi rotations),
+        # differentiable w.r.t. all three inputs; the casts carry the gradients back to the caller's dtypes and devices
+        from . import aggregation  # noqa: F401  (registers the op)
+        P32 = proj_matricies.to(torch.float32).contiguous()
+        pts32 = points.to(device=P32.device, dtype=torch.float32).contiguous()
+        c32 = None if confidences is None else confidences.to(device=P32.device, dtype=torch.float32).contiguous()   # (V,) or (B, V)
+        return torch.ops.mvhmr.triangulate_dlt(P32, pts32, c32)
     P = proj_matricies.to(torch.float64)
     pts = points.to(device=P.device, dtype=torch.float64)
     A = P[:, :, 2:3].expand(B, V, 2, 4) * (pts.view(B, V, 2, 1) if pts.dim() == 3 else pts.view(1, V, 2, 1)) - P[:, :, :2]
