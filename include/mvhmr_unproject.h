@@ -34,7 +34,8 @@ extern "C" {
                                  workspace; explicit GATHER with QUAD input is served; MVHMR_BF16 out_dtype; mvhmr_unproject_backward_supported,
                                  mvhmr_triangulate_dlt.  4: MVHMR_LAYOUT_QUAD_LOG2E (ABI history); additive within 4:
                                  mvhmr_unproject_backward_geometry[_workspace_bytes], mvhmr_unproject_backward_geometry_cuboid[_workspace_bytes],
-                                 mvhmr_triangulate_dlt_backward */
+                                 mvhmr_triangulate_dlt_backward, mvhmr_unproject_backward_deterministic[_workspace_bytes],
+                                 mvhmr_unproject_backward_cuboid_deterministic[_workspace_bytes], mvhmr_conv1x1_wgrad_deterministic[_workspace_bytes] */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -212,6 +213,27 @@ int mvhmr_unproject_backward_cuboid(const mvhmr_unproject_desc *desc, const void
                                     void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
+ * Deterministic mode of the two feature-gradient backwards above: the same arguments, validation and error codes, and grad_features
+ * bitwise identical from run to run on the same inputs, device and batch layout (no float atomics; nothing sums across samples, so
+ * permuting the batch permutes the result).  The kernels follow the default's route, without the geometry gate: the brick kernels
+ * (their window sums flushed as int64 fixed point with u64 atomics), the plane kernels (already atomic-free), or the gather kernels (taps
+ * added as int64 fixed point).  A scale pass first fixes one power-of-two scale per (sample, channel) from max |grad_out| (and, for
+ * softmax, max |features|) so that no sum can overflow; a conversion pass writes grad_features.  A (sample, channel) whose scale bound is not finite gets NaN over its whole gradient: wherever the
+ * default route is non-finite this one is too.  Quad-planar features that neither the deterministic brick route (one sample's int64
+ * accumulator below 2 GB) nor the plane route takes need C <= 4092 and B * V <= 65535 (the gather route's channels-last conversion),
+ * else MVHMR_ERR_UNSUPPORTED.  The workspace
+ * (mvhmr_unproject_backward_deterministic_workspace_bytes, at least the default's) holds the feature copy, the int64 accumulator and
+ * the scales.
+ */
+size_t mvhmr_unproject_backward_deterministic_workspace_bytes(const mvhmr_unproject_desc *desc);
+int mvhmr_unproject_backward_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                           const float *coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
+                                                  const float *proj, const float *rot, const float *center, const double position[3],
+                                                  const double sides[3], void *grad_features, void *workspace, size_t workspace_bytes,
+                                                  void *hip_stream);
+
+/*
  * Backward w.r.t. the geometry of the cuboid recipe: grad_proj as mvhmr_unproject_backward_geometry gives it (the same partials, the
  * same bits as that call on the coordinates mvhmr_build_coord_volumes builds), and the gradients w.r.t. the pose the recipe takes,
  *   grad_rot     (B,3,3) fp32 or NULL    grad_rot[b][r][k] = sum_n gX_n[r] d_n[k],   d_n = fl(grid_n - center[b])          [write]
@@ -278,6 +300,18 @@ int mvhmr_conv1x1_planar_supported(int32_t c_in, int32_t c_out, int32_t pixels);
 int mvhmr_conv1x1_wgrad(const float *grad_y, const float *x, float *grad_weight, float *grad_bias, int32_t n_maps, int32_t c_in,
                         int32_t c_out, int32_t pixels, void *hip_stream);
 int mvhmr_conv1x1_wgrad_supported(int32_t c_in, int32_t c_out, int32_t pixels);
+
+/*
+ * Deterministic mvhmr_conv1x1_wgrad: the same arguments, shapes and error codes, but grad_weight and grad_bias are WRITTEN (not added
+ * into) and bitwise reproducible: every block stores its partial tile into a slab of `workspace`, a second kernel sums the slabs per
+ * element in a fixed order (float64).  Workspace: mvhmr_conv1x1_wgrad_deterministic_workspace_bytes, 256-byte aligned: one partial
+ * (c_out x c_in + c_out) fp32 slab per pixel slice, n_maps * slices_per_map slices.  Each map is split into as many slices as keep the grid
+ * at most 2048 blocks of 128 x 128 (about 128 MB); with n_maps * (c_out / 128) * (c_in / 128) > 2048 every map is one slice and the size is
+ * n_maps * (c_out * c_in + c_out) * 4 bytes.
+ */
+size_t mvhmr_conv1x1_wgrad_deterministic_workspace_bytes(int32_t n_maps, int32_t c_in, int32_t c_out, int32_t pixels);
+int mvhmr_conv1x1_wgrad_deterministic(const float *grad_y, const float *x, float *grad_weight, float *grad_bias, int32_t n_maps,
+                                      int32_t c_in, int32_t c_out, int32_t pixels, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
  * DLT triangulation of one 3-D point per sample from its V views: replaces triangulate_point_from_multiple_views_linear[_torch]

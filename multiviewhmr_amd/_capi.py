@@ -27,6 +27,8 @@ EXPORTS = (
     "mvhmr_unproject_forward_kernel_name",
     "mvhmr_unproject_backward_geometry_workspace_bytes", "mvhmr_unproject_backward_geometry",
     "mvhmr_unproject_backward_geometry_cuboid_workspace_bytes", "mvhmr_unproject_backward_geometry_cuboid", "mvhmr_triangulate_dlt_backward",
+    "mvhmr_unproject_backward_deterministic_workspace_bytes", "mvhmr_unproject_backward_deterministic",
+    "mvhmr_unproject_backward_cuboid_deterministic", "mvhmr_conv1x1_wgrad_deterministic_workspace_bytes", "mvhmr_conv1x1_wgrad_deterministic",
 )
 
 
@@ -96,6 +98,16 @@ def lib():
     L.mvhmr_conv1x1_wgrad.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.mvhmr_conv1x1_wgrad_supported.restype = ctypes.c_int
     L.mvhmr_conv1x1_wgrad_supported.argtypes = [i32, i32, i32]
+    L.mvhmr_conv1x1_wgrad_deterministic_workspace_bytes.restype = sz
+    L.mvhmr_conv1x1_wgrad_deterministic_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.mvhmr_conv1x1_wgrad_deterministic.restype = ctypes.c_int
+    L.mvhmr_conv1x1_wgrad_deterministic.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, sz, vp]
+    L.mvhmr_unproject_backward_deterministic_workspace_bytes.restype = sz
+    L.mvhmr_unproject_backward_deterministic_workspace_bytes.argtypes = [dp]
+    L.mvhmr_unproject_backward_deterministic.restype = ctypes.c_int
+    L.mvhmr_unproject_backward_deterministic.argtypes = [dp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.mvhmr_unproject_backward_cuboid_deterministic.restype = ctypes.c_int
+    L.mvhmr_unproject_backward_cuboid_deterministic.argtypes = [dp, vp, vp, vp, vp, vp, d3, d3, vp, vp, sz, vp]
     L.mvhmr_unproject_query_variant_cuboid.restype = ctypes.c_int
     L.mvhmr_unproject_query_variant_cuboid.argtypes = [dp, vp, vp, vp, d3, d3, vp]
     L.mvhmr_preferred_layout.restype = ctypes.c_int

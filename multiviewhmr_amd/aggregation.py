@@ -137,6 +137,13 @@ def _op_backward(grad_out, features, proj, coords, method, out_dtype, variant):
     return _native().unprojection_backward(grad_out.contiguous(), read, proj, coords, *desc)
 
 
+def _op_backward_deterministic(grad_out, features, proj, coords, method, out_dtype, variant):
+    """_op_backward with bitwise reproducible results (mvhmr_unproject_backward_deterministic): what autograd runs under
+    torch.use_deterministic_algorithms(True)"""
+    read, desc = _native_args(features, coords, method, out_dtype, variant)
+    return _native().unprojection_backward_deterministic(grad_out.contiguous(), read, proj, coords, *desc)
+
+
 def _op_backward_geometry(grad_out, features, proj, coords, method, out_dtype, variant, want_proj=True, want_coords=True):
     """gradients w.r.t. proj_matricies (B,V,3,4) and coord_volumes (B,X,Y,Z,3), fp32 (mvhmr_unproject_backward_geometry); an output
     not asked for comes back empty.  Planar features go through the library's channels-last pass, channels-last ones are read as
@@ -167,7 +174,8 @@ def _autograd_setup(ctx, inputs, output):
 
 def _autograd_backward(ctx, grad_out):
     features, proj, coords = ctx.saved_tensors
-    g = torch.ops.mvhmr.unprojection_backward(grad_out, features, proj, coords, *ctx.args) if ctx.needs_input_grad[0] else None
+    op = torch.ops.mvhmr.unprojection_backward_deterministic if torch.are_deterministic_algorithms_enabled() else torch.ops.mvhmr.unprojection_backward
+    g = op(grad_out, features, proj, coords, *ctx.args) if ctx.needs_input_grad[0] else None
     g_proj = g_coords = None
     want_proj, want_coords = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
     if want_proj or want_coords:                       # a features-only backward launches nothing more
@@ -194,6 +202,9 @@ def _register_ops():
     torch.library.impl("mvhmr::unprojection_backward", "CUDA")(_op_backward)
     torch.library.register_fake("mvhmr::unprojection")(_fake_forward)
     torch.library.register_fake("mvhmr::unprojection_backward")(_fake_backward)
+    torch.library.define("mvhmr::unprojection_backward_deterministic", "(Tensor grad_out, " + sig[1:])
+    torch.library.impl("mvhmr::unprojection_backward_deterministic", "CUDA")(_op_backward_deterministic)
+    torch.library.register_fake("mvhmr::unprojection_backward_deterministic")(_fake_backward)
     torch.library.define("mvhmr::unprojection_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
                          + ", bool want_proj=True, bool want_coords=True) -> (Tensor, Tensor)")
     torch.library.impl("mvhmr::unprojection_backward_geometry", "CUDA")(_op_backward_geometry)
@@ -277,6 +288,11 @@ def _opc_backward(grad_out, features, proj, rot, center, position, sides, vol, m
     return _native().unprojection_cuboid_backward(grad_out.contiguous(), read, proj, rot, center, position, sides, vol, *desc)
 
 
+def _opc_backward_deterministic(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant):
+    read, desc = _native_args(features, vol, method, out_dtype, variant)
+    return _native().unprojection_cuboid_backward_deterministic(grad_out.contiguous(), read, proj, rot, center, position, sides, vol, *desc)
+
+
 def _geometry_read_layout(features):
     """the features as the geometry backward reads them: channels-last as they are (C % 4 == 0), else a planar contiguous copy"""
     if _is_channels_last5(features) and features.shape[2] % 4 == 0:
@@ -306,7 +322,9 @@ def _opc_setup(ctx, inputs, output):
 
 def _opc_autograd(ctx, grad_out):
     features, proj, rot, center = ctx.saved_tensors
-    g = torch.ops.mvhmr.unprojection_cuboid_backward(grad_out, features, proj, rot, center, *ctx.args) if ctx.needs_input_grad[0] else None
+    op = (torch.ops.mvhmr.unprojection_cuboid_backward_deterministic if torch.are_deterministic_algorithms_enabled()
+          else torch.ops.mvhmr.unprojection_cuboid_backward)
+    g = op(grad_out, features, proj, rot, center, *ctx.args) if ctx.needs_input_grad[0] else None
     want = tuple(ctx.needs_input_grad[1:4])
     geo = (None, None, None)
     if any(want):                                      # a features-only backward launches nothing more
@@ -326,6 +344,10 @@ def _register_cuboid_ops():
         lambda features, proj, rot, center, position, sides, vol, method, out_dtype, variant:
         features.new_empty((features.shape[0], features.shape[2]) + tuple(vol), dtype=_DTYPES[out_dtype]))
     torch.library.register_fake("mvhmr::unprojection_cuboid_backward")(
+        lambda grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant: torch.empty_like(features))
+    torch.library.define("mvhmr::unprojection_cuboid_backward_deterministic", "(Tensor grad_out, " + sig[1:])
+    torch.library.impl("mvhmr::unprojection_cuboid_backward_deterministic", "CUDA")(_opc_backward_deterministic)
+    torch.library.register_fake("mvhmr::unprojection_cuboid_backward_deterministic")(
         lambda grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant: torch.empty_like(features))
     torch.library.define("mvhmr::unprojection_cuboid_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
                          + ", bool want_proj=True, bool want_rot=True, bool want_center=True) -> (Tensor, Tensor, Tensor)")
@@ -483,7 +505,9 @@ class _FusedAggregate(torch.autograd.Function):
         gx = gw = gb = None
         if not any(ctx.needs_input_grad[:3]):
             return (None, None, None) + g_geo + (None,) * 5
-        gy = _native().unprojection_cuboid_backward(grad_out.contiguous(), quad, proj, rot, center, *ctx.geometry, *ctx.desc).view(
+        det = torch.are_deterministic_algorithms_enabled()                                   # bitwise reproducible feature and wgrad kernels
+        bwd = _native().unprojection_cuboid_backward_deterministic if det else _native().unprojection_cuboid_backward
+        gy = bwd(grad_out.contiguous(), quad, proj, rot, center, *ctx.geometry, *ctx.desc).view(
             B * V, Cout, Hf * Wf)                                                                # gradient w.r.t. the conv output, planar
         xf = x.view(B * V, Cin, Hf * Wf)
         if ctx.needs_input_grad[0]:
@@ -495,7 +519,20 @@ class _FusedAggregate(torch.autograd.Function):
             else:
                 gx = torch.matmul(w2.t(), gy).view(B, V, Cin, Hf, Wf)
         want_b = ctx.has_bias and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[1] and L.mvhmr_conv1x1_wgrad_supported(Cin, Cout, Hf * Wf):
+        if det and ctx.needs_input_grad[1] and L.mvhmr_conv1x1_wgrad_supported(Cin, Cout, Hf * Wf):
+            gw = torch.empty(ctx.wshape, dtype=torch.float32, device=dev)                      # written: partial slabs summed in a fixed order
+            gb = torch.empty(Cout, dtype=torch.float32, device=dev) if want_b else None
+            n = L.mvhmr_conv1x1_wgrad_deterministic_workspace_bytes(B * V, Cin, Cout, Hf * Wf)
+            with torch.cuda.device(dev):
+                stream = torch.cuda.current_stream(dev)
+                # straight from the caching allocator: torch.empty would fill it under the deterministic flag, and the kernel writes every byte
+                ws = torch.cuda.caching_allocator_alloc(n, dev, stream)
+                try:
+                    _capi.check(L.mvhmr_conv1x1_wgrad_deterministic(_ptr(gy), _ptr(x), _ptr(gw), _ptr(gb) if want_b else ctypes.c_void_p(0), B * V,
+                                                                    Cin, Cout, Hf * Wf, ctypes.c_void_p(ws), n, _stream(dev)))
+                finally:
+                    torch.cuda.caching_allocator_delete(ws)                # stream-ordered: reused only after the kernels on this stream
+        elif ctx.needs_input_grad[1] and L.mvhmr_conv1x1_wgrad_supported(Cin, Cout, Hf * Wf):
             gw = torch.zeros(ctx.wshape, dtype=torch.float32, device=dev)                      # split-K GEMM adds into it
             gb = torch.zeros(Cout, dtype=torch.float32, device=dev) if want_b else None
             with torch.cuda.device(dev):

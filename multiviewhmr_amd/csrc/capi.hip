@@ -533,6 +533,122 @@ int mvhmr_unproject_backward_cuboid(const mvhmr_unproject_desc *desc, const void
     return backward_impl(desc, p, grad_out, features, proj, cs, grad_features, workspace, workspace_bytes, hip_stream);
 }
 
+// ---- deterministic mode of the feature-gradient backward (include/mvhmr_unproject.h).  The brick kernels' deterministic
+// instances where the default's rule takes the bricks (not gated: their slow path serves windows that do not fit, and no host
+// synchronisation is needed), the plane kernels where it takes those (no global atomics), else k_bwd_gather_det.  The brick and gather
+// routes run the scale pass first and a conversion pass after.
+static bool det_uses_brick(const mvhmr_unproject_desc *d, const Problem &p) { return bwd_uses_brick(d, p) && brick_bwd_det_supported(p); }
+static bool det_uses_plane(const mvhmr_unproject_desc *d, const Problem &p) { return !det_uses_brick(d, p) && bwd_uses_plane(d, p); }
+static size_t det_acc_bytes(const Problem &p) { return align_up((size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(long long)); }
+
+static size_t det_need_bytes(const mvhmr_unproject_desc *d, const Problem &p)
+{
+    if (det_uses_brick(d, p)) return (d->feat_layout != MVHMR_LAYOUT_QUAD ? brick_workspace_bytes(p) : 0) + det_acc_bytes(p) + align_up(det_scale_bytes(p));
+    if (det_uses_plane(d, p)) return (d->feat_layout == MVHMR_LAYOUT_BVCHW ? brick_workspace_bytes(p) : 0) + align_up(plane_table_bytes(p));
+    return (d->feat_layout != MVHMR_LAYOUT_BVHWC ? featT_bytes(p) : 0) + det_acc_bytes(p) + align_up(det_scale_bytes(p));
+}
+
+static int backward_det_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj,
+                             const Coords &coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    int rc;
+    // the default entry points' validation, in their order
+    if (!grad_out || !features || !proj || !grad_features)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p) && !quad_to_channels_last_supported(p))
+        return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    rc = check_ws(workspace, workspace_bytes, mvhmr_unproject_backward_deterministic_workspace_bytes(desc));
+    if (rc != MVHMR_OK) return rc;
+    if (desc->variant == MVHMR_VARIANT_BRICK && !bwd_uses_brick(desc, p))
+        return fail(MVHMR_ERR_UNSUPPORTED, "the brick variant does not support this shape / dtype / layout");
+
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    if (det_uses_brick(desc, p)) {
+        const void *featK = features;                                            // quad-planar features: the copy as it is
+        if (desc->feat_layout != MVHMR_LAYOUT_QUAD) {
+            rc = launched(launch_to_quad_planar_t(features, ws, p, s, true), "layout pass");
+            if (rc != MVHMR_OK) return rc;
+            featK = ws;
+            ws += brick_workspace_bytes(p);
+        }
+        unsigned long long *acc = reinterpret_cast<unsigned long long *>(ws);
+        void *scale = ws + det_acc_bytes(p);
+        hipError_t e = hipMemsetAsync(acc, 0, (size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(long long), s);
+        if (e != hipSuccess) return launched(e, "gradient clear");
+        rc = launched(launch_det_scale(grad_out, featK, scale, p, s, true), "deterministic scale pass");
+        if (rc != MVHMR_OK) return rc;
+        const int *kexp = det_exponents(scale, p);
+        rc = launched(launch_bwd_brick_det(featK, grad_out, proj, coords, acc, kexp, p, s), "deterministic brick backward");
+        if (rc != MVHMR_OK) return rc;
+        return launched(launch_det_quad_to_planar(acc, kexp, grad_features, p, s), "gradient layout pass");
+    }
+    if (det_uses_plane(desc, p)) {
+        const void *featK = features;
+        if (desc->feat_layout == MVHMR_LAYOUT_BVCHW) {
+            rc = launched(launch_to_quad_planar_t(features, ws, p, s), "layout pass");
+            if (rc != MVHMR_OK) return rc;
+            featK = ws;
+            ws += brick_workspace_bytes(p);
+        }
+        return launched(launch_bwd_plane(featK, grad_out, proj, coords, grad_features, ws, p, s), "plane backward");
+    }
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p))
+        return fail(MVHMR_ERR_UNSUPPORTED, "deterministic backward from quad-planar features of this shape: needs C <= 4092 and B * V <= 65535");
+    const void *featT = features;
+    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) {
+        rc = launched(desc->feat_layout == MVHMR_LAYOUT_QUAD ? launch_quad_to_channels_last(features, ws, p, s) : launch_to_channels_last(features, ws, p, s),
+                      "layout pass");
+        if (rc != MVHMR_OK) return rc;
+        featT = ws;
+        ws += featT_bytes(p);
+    }
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(ws);
+    void *scale = ws + det_acc_bytes(p);
+    hipError_t e = hipMemsetAsync(acc, 0, (size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(long long), s);
+    if (e != hipSuccess) return launched(e, "gradient clear");
+    rc = launched(launch_det_scale(grad_out, featT, scale, p, s), "deterministic scale pass");
+    if (rc != MVHMR_OK) return rc;
+    const int *kexp = det_exponents(scale, p);
+    rc = launched(launch_bwd_gather_det(grad_out, featT, proj, coords, acc, kexp, p, s), "deterministic gather backward");
+    if (rc != MVHMR_OK) return rc;
+    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_det_grad_to_planar(acc, kexp, grad_features, p, s), "gradient layout pass");
+    return launched(launch_det_grad_cast(acc, kexp, grad_features, p, s), "gradient cast");
+}
+
+size_t mvhmr_unproject_backward_deterministic_workspace_bytes(const mvhmr_unproject_desc *desc)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
+    const size_t det = det_need_bytes(desc, p), dflt = mvhmr_unproject_backward_workspace_bytes(desc);
+    return det > dflt ? det : dflt;
+}
+
+int mvhmr_unproject_backward_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                           const float *coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
+    return backward_det_impl(desc, p, grad_out, features, proj, coords_from_tensor(coords, p), grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                  const float *rot, const float *center, const double position[3], const double sides[3],
+                                                  void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    Coords cs;
+    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
+    if (rc != MVHMR_OK) return rc;
+    return backward_det_impl(desc, p, grad_out, features, proj, cs, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
 // Gradient w.r.t. proj and coords: the channels-last feature copy k_bwd_geom reads (none for channels-last input), then the fp32
 // partials of grad_proj.  desc->variant plays no part.
 size_t mvhmr_unproject_backward_geometry_workspace_bytes(const mvhmr_unproject_desc *desc)
@@ -711,6 +827,24 @@ int mvhmr_conv1x1_wgrad(const float *grad_y, const float *x, float *grad_weight,
 int mvhmr_conv1x1_wgrad_supported(int32_t c_in, int32_t c_out, int32_t pixels)
 {
     return conv1x1_wgrad_supported(c_in, c_out, pixels) ? 1 : 0;
+}
+
+size_t mvhmr_conv1x1_wgrad_deterministic_workspace_bytes(int32_t n_maps, int32_t c_in, int32_t c_out, int32_t pixels)
+{
+    return conv1x1_wgrad_det_workspace_bytes(n_maps, c_in, c_out, pixels);
+}
+
+int mvhmr_conv1x1_wgrad_deterministic(const float *grad_y, const float *x, float *grad_weight, float *grad_bias, int32_t n_maps, int32_t c_in,
+                                      int32_t c_out, int32_t pixels, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!grad_y || !x || !grad_weight) return fail(MVHMR_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n_maps <= 0 || c_in <= 0 || c_out <= 0 || pixels <= 0) return fail(MVHMR_ERR_INVALID_ARGUMENT, "non-positive extent");
+    if (!conv1x1_wgrad_supported(c_in, c_out, pixels))
+        return fail(MVHMR_ERR_UNSUPPORTED, "1x1 conv weight gradient needs C_in %% 128 == 0, C_out %% 128 == 0, pixels %% 32 == 0 (got %d -> %d, %d)", c_in, c_out, pixels);
+    const int rc = check_ws(workspace, workspace_bytes, conv1x1_wgrad_det_workspace_bytes(n_maps, c_in, c_out, pixels));
+    if (rc != MVHMR_OK) return rc;
+    return launched(launch_conv1x1_wgrad_det(grad_y, x, grad_weight, grad_bias, workspace, n_maps, c_in, c_out, pixels, static_cast<hipStream_t>(hip_stream)),
+                    "deterministic 1x1 conv weight gradient");
 }
 
 int mvhmr_unproject_query_variant_cuboid(const mvhmr_unproject_desc *desc, const float *proj, const float *rot, const float *center,

@@ -49,6 +49,22 @@ hipError_t launch_fwd_gather(const void *featT, const float *proj, const Coords 
 hipError_t launch_bwd_gather(const void *grad_out, const void *featT, const float *proj, const Coords &coords,
                              float *gradT, const Problem &p, hipStream_t s);
 
+// deterministic mode (unproject_det.hip, det_scale.h): the scale pass writes K[b][c] into `scale` (det_scale_bytes(p)) from grad_out and the
+// channels-last feature copy; k_bwd_gather_det adds int64 fixed point into gradI (zeroed, channels-last (B,V,HW,C4)); the conversion passes
+// write the caller's planar or channels-last gradient (NaN for a poisoned (b, c))
+size_t det_scale_bytes(const Problem &p);
+hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale, const Problem &p, hipStream_t s, bool quad = false);   // feat: channels-last copy, or the quad-planar one (quad)
+const int *det_exponents(const void *scale, const Problem &p);
+hipError_t launch_bwd_gather_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
+                                 const int *kexp, const Problem &p, hipStream_t s);
+hipError_t launch_det_grad_to_planar(const unsigned long long *gradI, const int *kexp, void *dst, const Problem &p, hipStream_t s);
+// brick kernels in deterministic mode: acc zeroed int64 quad-planar (B,V,C4/4,W,H,4); a smaller per-sample limit than brick_bwd_supported
+bool brick_bwd_det_supported(const Problem &p);
+hipError_t launch_bwd_brick_det(const void *featK, const void *grad_out, const float *proj, const Coords &coords, unsigned long long *acc,
+                                const int *kexp, const Problem &p, hipStream_t s);
+hipError_t launch_det_quad_to_planar(const unsigned long long *acc, const int *kexp, void *dst, const Problem &p, hipStream_t s);
+hipError_t launch_det_grad_cast(const unsigned long long *gradI, const int *kexp, void *dst, const Problem &p, hipStream_t s);
+
 // brick variant (LDS-staged windows); launches return hipErrorNotSupported when the shape does not qualify.
 //   forward : column-major quad-planar staged copy (launch_to_quad_planar_t), 4*nvox x (NT/128) x 32 bricks
 //   backward: the same column-major quad-planar staged copy, 8 x 8 x 16 (8 x 4 x 16 for 8 views) or 4 x (NT/128) x 32 bricks
@@ -96,6 +112,9 @@ bool conv1x1_quad_supported(int Cin, int Cout, int H, int W);
 bool conv1x1_planar_supported(int Cin, int Cout, int HW);
 bool conv1x1_wgrad_supported(int Cin, int Cout, int HW);
 hipError_t launch_conv1x1_wgrad(const float *gy, const float *x, float *dW, float *db, int BV, int Cin, int Cout, int HW, hipStream_t s);
+// deterministic form: per-slice partial slabs in `ws` (conv1x1_wgrad_det_workspace_bytes), summed in a fixed order; dW / db are written
+size_t conv1x1_wgrad_det_workspace_bytes(int BV, int Cin, int Cout, int HW);
+hipError_t launch_conv1x1_wgrad_det(const float *gy, const float *x, float *dW, float *db, void *ws, int BV, int Cin, int Cout, int HW, hipStream_t s);
 hipError_t launch_conv1x1_planar(const float *x, const float *w, const float *bias, float *dst, int BV, int Cin, int Cout, int HW, hipStream_t s);
 hipError_t launch_conv1x1_quad(const float *x, const float *w, const float *bias, void *dst, int BV, int Cin, int Cout, int H, int W,
                                hipStream_t s);

@@ -20,6 +20,7 @@
 // Autograd semantics as in the gather variant / the oracle: zero-weight taps (outside the image, z <= 0) receive nothing.
 // Measured at the north-star size: r01 17.1 ms, r02 14.0, r03 12.9 per call (gather backward: 104 ms); DESIGN.md 5.2.
 #include "brick_common.h"
+#include "det_scale.h"
 #include "kernels.h"
 
 namespace mvhmr {
@@ -47,12 +48,29 @@ constexpr int bwd_cap_slots(int nt, int bz)
 }
 constexpr int kAuxCmax = 12;       // BrickShared::aux word of the tap multiplicity
 
+// Deterministic mode: the brick kernels' instances that take one more argument, `const int *kexp` (K[b][c], det_scale.h),
+// accumulate into an int64 quad-planar accumulator instead of the fp32 one -- the flush shifts the block's exact int32 window sums from the
+// block's scale 2^k to 2^K and adds them with u64 atomics, the slow path and k_bwd_tail add llrint(ds * w * 2^K).  The argument is a trailing
+// parameter pack so that the default instances (empty pack) keep their signature and their code.
+__device__ __forceinline__ const int *det_exps() { return nullptr; }
+__device__ __forceinline__ const int *det_exps(const int *k) { return k; }
+// v * 2^sh as int64: exact for sh >= 0 (|v| < 2^30 and the sum stays below 2^62 by the choice of K), round half up for sh < 0
+__device__ __forceinline__ long long det_shift(int v, int sh)
+{
+    const long long x = v;
+    if (sh >= 0) return x << (sh < 62 ? sh : 62);
+    const int r = -sh < 40 ? -sh : 40;
+    return (x + (1ll << (r - 1))) >> r;
+}
+
 // Slow path of k_bwd_brick for one voxel: global float atomics per tap (bricks whose windows do not fit the LDS pool).
-template <int METHOD, int VT, typename TO>
+// Deterministic instances: gk is the sample's int64 accumulator (same element indexing), kexp_arg the sample's row of K.
+template <int METHOD, int VT, typename TO, typename... Det>
 __device__ __attribute__((noinline)) void bwd_brick_slow(const float4 *fk, const TO *gobase, float *gk, const float (*proj)[12],
                                                          float c0, float c1, float c2, unsigned vox, long long N, int q_begin, int q_end, int nqv, int C, int H,
-                                                         int W, int nv)
+                                                         int W, int nv, Det... kexp_arg)
 {
+    constexpr bool DET = sizeof...(Det) > 0;
     // channel quads q_begin .. q_end - 1 of the nqv = (C + 3) / 4 a view holds; channels below C only (C % 4 != 0: the last quad's missing
     // channels have no grad_out)
     const int HW = H * W;
@@ -91,6 +109,20 @@ __device__ __attribute__((noinline)) void bwd_brick_slow(const float4 *fk, const
             float ds[VT];
             if constexpr (METHOD == AGG_MEAN) aggregate_grad<AGG_SUM, VT>(s[i], __fdiv_rn(g, (float)nv), ds);   // g / (real views), as autograd of mean(0)
             else aggregate_grad<METHOD, VT>(s[i], g, ds);
+            if constexpr (DET) {
+                const int K = det_exps(kexp_arg...)[q * 4 + i];
+                if (K == kDetPoison) continue;                                   // a poisoned channel adds nothing (NaN in the conversion)
+                unsigned long long *gi = reinterpret_cast<unsigned long long *>(gk) + (long long)q * HW * 4;
+#pragma unroll
+                for (int v = 0; v < VT; ++v) {
+                    if (v >= nv) continue;
+                    if (w00[v] != 0.f) atomicAdd(gi + (long long)o00[v] * 4 + i, det_fixed(ds[v] * w00[v], K));
+                    if (w01[v] != 0.f) atomicAdd(gi + (long long)o01[v] * 4 + i, det_fixed(ds[v] * w01[v], K));
+                    if (w10[v] != 0.f) atomicAdd(gi + (long long)o10[v] * 4 + i, det_fixed(ds[v] * w10[v], K));
+                    if (w11[v] != 0.f) atomicAdd(gi + (long long)o11[v] * 4 + i, det_fixed(ds[v] * w11[v], K));
+                }
+                continue;
+            }
 #pragma unroll
             for (int v = 0; v < VT; ++v) {
                 if (v >= nv) continue;                                           // absent view: nothing to receive
@@ -103,12 +135,13 @@ __device__ __attribute__((noinline)) void bwd_brick_slow(const float4 *fk, const
     }
 }
 
-template <int METHOD, int VT, int NT, typename TO, int BZ>
+template <int METHOD, int VT, int NT, typename TO, int BZ, typename... Det>
 __global__ void __launch_bounds__(NT)
 k_bwd_brick(const float4 *__restrict__ featK, const TO *__restrict__ grad_out, const float *__restrict__ proj,
             const Coords coords, float *__restrict__ gradK, int C, int H, int W, int X, int Y, int Z, int nby,
-            int nbz, int bricks_per_sample, int lds_bytes, int total_blocks, int nv, Gate gate)
+            int nbz, int bricks_per_sample, int lds_bytes, int total_blocks, int nv, Gate gate, Det... kexp_arg)
 {
+    constexpr bool DET = sizeof...(Det) > 0;                                    // deterministic instance: gradK is the int64 accumulator
     // nv <= VT real views (3 views run the 4-view kernel, 5 ... 7 the 8-view one): an absent view has no camera and no window; for
     // softmax / max its samples read kAbsentSample from the zero head of the feature buffers (brick_common.h), its ds is forced to zero
     if (gated_off(gate)) return;
@@ -204,7 +237,8 @@ k_bwd_brick(const float4 *__restrict__ featK, const TO *__restrict__ grad_out, c
     int *const iplanes = reinterpret_cast<int *>(smem + NBUF * buf_bytes);
     const bool fits = used <= cap && nch[VT] <= MC * NW && max_stride + 2 <= kZeroSlots;
     const float4 *const fk = featK + (long long)b * nv * nqv * HW;
-    float *const gk = gradK + (long long)b * nv * nqv * HW * 4;
+    float *const gk = DET ? reinterpret_cast<float *>(reinterpret_cast<unsigned long long *>(gradK) + (long long)b * nv * nqv * HW * 4)
+                          : gradK + (long long)b * nv * nqv * HW * 4;
     constexpr bool kAbsentReads = METHOD == AGG_SOFTMAX || METHOD == AGG_MAX;
     const TO *const gobase = grad_out + (long long)b * C * N;
     const unsigned chan_bytes = (unsigned)(N * 4);
@@ -335,7 +369,8 @@ k_bwd_brick(const float4 *__restrict__ featK, const TO *__restrict__ grad_out, c
         const unsigned aux_base = (unsigned)(size_t)(lds_void_t *)sh->aux;
         const unsigned ch4 = 4u * (lane & 3);                                    // this lane's channel in the flush
         const unsigned long long gk_bits = (unsigned long long)(size_t)gk;
-        const int4v dgk = {uniform((int)(unsigned)gk_bits), uniform((int)((unsigned)(gk_bits >> 32) & 0xffffu)), (int)((unsigned)nv * nqv * HW * 16u), 0x00020000};
+        constexpr unsigned kSlotBytes = DET ? 32u : 16u;                          // 4 channels of fp32 / int64 per accumulator slot
+        const int4v dgk = {uniform((int)(unsigned)gk_bits), uniform((int)((unsigned)(gk_bits >> 32) & 0xffffu)), (int)((unsigned)nv * nqv * HW * kSlotBytes), 0x00020000};
         const __amdgpu_buffer_rsrc_t rgk = __builtin_amdgcn_make_buffer_rsrc(gk, 0, (int)((unsigned)nv * nqv * HW * 16u), 0x00020000);   // this sample's accumulator
         float ds[4][VT], s[4][VT];
         auto resample = [&](int q) {                                             // samples of quad q from its window buffer
@@ -479,10 +514,23 @@ k_bwd_brick(const float4 *__restrict__ featK, const TO *__restrict__ grad_out, c
                              : "s"(inv_bits[0]), "s"(inv_bits[1]), "s"(inv_bits[2]), "s"(inv_bits[3]),
                                "s"(0x2222222222222222ull), "s"(0x4444444444444444ull), "s"(0x8888888888888888ull));
             }
+            // deterministic instances: this lane's shift from the block's scale 2^(se - 127) (inv_ch = 2^(127 - se)) to 2^K of its channel; a
+            // channel that is all zero, poisoned in the block (inv_ch NaN) or poisoned in K adds nothing
+            int det_sh = 0;
+            bool det_dead = false;
+            if constexpr (DET) {
+                const int *kq = det_exps(kexp_arg...) + (long long)b * C + q * 4;
+                const int k0 = uniform(kq[0]), k1 = uniform(kq[1]), k2 = uniform(kq[2]), k3 = uniform(kq[3]);
+                const int ch = lane & 3;
+                const int K = ch == 0 ? k0 : ch == 1 ? k1 : ch == 2 ? k2 : k3;
+                const unsigned ib = __builtin_bit_cast(unsigned, inv_ch);
+                det_dead = K == kDetPoison || ib == 0u || ib >= 0x7f800000u;
+                det_sh = K + (int)(ib >> 23) - 127;
+            }
             int n_dyn = 0;                                                       // atomic instructions this wave issues in this iteration
             // flush of quad qf from its plane set (scaled back by inv: this lane's channel), planes left zero
             auto flush_quad = [&](int qf, float inv, bool pois) __attribute__((always_inline)) {
-                const int q_off = qf * HW * 16;                                  // wave-uniform byte offset of the quad (soffset)
+                const int q_off = qf * HW * (int)kSlotBytes;                     // wave-uniform byte offset of the quad (soffset)
                 int *const pset = iplanes;
                 auto flush = [&](auto masked_tag) __attribute__((always_inline)) {
                     constexpr bool MASKED = decltype(masked_tag)::value;
@@ -500,6 +548,24 @@ k_bwd_brick(const float4 *__restrict__ featK, const TO *__restrict__ grad_out, c
                         }
 #pragma unroll
                         for (int jj = 0; jj < 4; ++jj) {
+                            if constexpr (DET) {
+                                // bit 31 (not a live pixel) survives the doubling of the offset; 8-B channels
+                                const int voff = (int)((((off[jj] & 0x7fffffffu) << 1) | (off[jj] & 0x80000000u)) + 2u * ch4);
+                                const int ivd = det_dead ? 0 : iv[jj];
+                                const long long val = det_shift(ivd, det_sh);
+                                unsigned long long save;
+                                asm volatile("s_mov_b64 %[save], exec\n\t"
+                                             "v_cmpx_ne_u32_e32 vcc, 0, %[iv]\n\t"
+                                             "s_cbranch_execz .Lskip%=\n\t"
+                                             "buffer_atomic_add_x2 %[val], %[voff], %[rsrc], %[soff] offen\n\t"
+                                             "s_add_u32 %[cnt], %[cnt], 1\n"
+                                             ".Lskip%=:\n\t"
+                                             "s_mov_b64 exec, %[save]"
+                                             : [save] "=&s"(save), [cnt] "+s"(n_dyn)
+                                             : [iv] "v"(ivd), [val] "v"(val), [voff] "v"(voff), [rsrc] "s"(dgk), [soff] "s"(q_off)
+                                             : "vcc", "scc", "memory");
+                                continue;
+                            }
                             const float val = (float)iv[jj] * inv;
                             const int voff = (int)(off[jj] + ch4);
                             if constexpr (MASKED) {
@@ -529,7 +595,7 @@ k_bwd_brick(const float4 *__restrict__ featK, const TO *__restrict__ grad_out, c
             adds_of_channel(std::integral_constant<int, 3>{});
             if (q + 2 < nq) load_g(q + 2);
             lds_barrier();                                                       // adds of quad q landed; max of quad q+1 published
-            flush_quad(q, inv_ch, poisoned);
+            flush_quad(q, inv_ch, DET ? false : poisoned);                      // deterministic: zero lanes are masked, poison is in K
             if (tid < 4) sh->aux[aset * 4 + tid] = 0;                            // read by every wave before the barrier above
             // window q+2 and grad_out q+2 (requested before this quad's atomics) have landed; the atomics stay in flight
             wait_vmcnt(n_dyn);
@@ -539,7 +605,12 @@ k_bwd_brick(const float4 *__restrict__ featK, const TO *__restrict__ grad_out, c
     } else {
         // ---- windows do not fit: scatter straight to the accumulator (its own function: keeps its registers -- 16 tap
         // offsets on top of the weights -- out of the fast path's allocation, which otherwise spills in the quad loop)
-        if (inside) bwd_brick_slow<METHOD, VT, TO>(fk, gobase, gk, sh->proj, c0, c1, c2, vox, N, 0, nq, nqv, C, H, W, nv);
+        if constexpr (DET) {
+            if (inside) bwd_brick_slow<METHOD, VT, TO>(fk, gobase, gk, sh->proj, c0, c1, c2, vox, N, 0, nq, nqv, C, H, W, nv,
+                                                       det_exps(kexp_arg...) + (long long)b * C);
+        } else {
+            if (inside) bwd_brick_slow<METHOD, VT, TO>(fk, gobase, gk, sh->proj, c0, c1, c2, vox, N, 0, nq, nqv, C, H, W, nv);
+        }
     }
 }
 
@@ -594,51 +665,51 @@ int bwd_brick_z(const Problem &p)
     return 4 * c16 <= 5 * c32 ? 16 : kBZ;
 }
 
-template <int METHOD, int VT, int NT, typename TO, int BZ = kBZ>
+template <int METHOD, int VT, int NT, typename TO, int BZ = kBZ, typename... Det>
 hipError_t launch_bv(const float4 *featK, const TO *grad_out, const float *proj, const Coords &coords, float *gradK, const Problem &p,
-                     hipStream_t s)
+                     hipStream_t s, Det... kexp)
 {
     constexpr int BX = bwd_brick_x(BZ), BY = NT / (BZ * BX);
     const int nbx = (p.X + BX - 1) / BX, nby = (p.Y + BY - 1) / BY, nbz = (p.Z + BZ - 1) / BZ;
     const int bps = nbx * nby * nbz, total = bps * p.B;
     const int lds_bytes = kBwdLdsBytes;
     const size_t lds = (size_t)lds_bytes + sizeof(BrickShared<VT>);
-    auto kern = k_bwd_brick<METHOD, VT, NT, TO, BZ>;
+    auto kern = k_bwd_brick<METHOD, VT, NT, TO, BZ, Det...>;
     hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
     if (e != hipSuccess) return e;
     const int grid = ((bps + 7) / 8) * 8 * p.B;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, s, featK, grad_out, proj, coords, gradK, p.C, p.H, p.W, p.X, p.Y, p.Z, nby, nbz, bps,
-                       lds_bytes, total, p.V, make_gate(p, true));
+                       lds_bytes, total, p.V, make_gate(p, true), kexp...);
     return hipGetLastError();
 }
 
-template <int METHOD, typename TO>
+template <int METHOD, typename TO, typename... Det>
 hipError_t launch_bm(const float4 *featK, const TO *grad_out, const float *proj, const Coords &coords, float *gradK, const Problem &p,
-                     hipStream_t s)
+                     hipStream_t s, Det... kexp)
 {
     switch (brick_view_slots(p.V)) {                                       // 3 / 5 / 6 / 7 views: the next larger kernel, missing views absent
     case 2:
-        if (bwd_brick_z(p) == 16) return launch_bv<METHOD, 2, kNTb, TO, 16>(featK, grad_out, proj, coords, gradK, p, s);
-        return launch_bv<METHOD, 2, kNTb, TO>(featK, grad_out, proj, coords, gradK, p, s);
+        if (bwd_brick_z(p) == 16) return launch_bv<METHOD, 2, kNTb, TO, 16, Det...>(featK, grad_out, proj, coords, gradK, p, s, kexp...);
+        return launch_bv<METHOD, 2, kNTb, TO, kBZ, Det...>(featK, grad_out, proj, coords, gradK, p, s, kexp...);
     case 4:
-        if (bwd_brick_z(p) == 16) return launch_bv<METHOD, 4, kNTb, TO, 16>(featK, grad_out, proj, coords, gradK, p, s);
-        return launch_bv<METHOD, 4, kNTb, TO>(featK, grad_out, proj, coords, gradK, p, s);
+        if (bwd_brick_z(p) == 16) return launch_bv<METHOD, 4, kNTb, TO, 16, Det...>(featK, grad_out, proj, coords, gradK, p, s, kexp...);
+        return launch_bv<METHOD, 4, kNTb, TO, kBZ, Det...>(featK, grad_out, proj, coords, gradK, p, s, kexp...);
     case 8:
-        if (bwd_brick_z(p) == 16) return launch_bv<METHOD, 8, kNTb8, TO, 16>(featK, grad_out, proj, coords, gradK, p, s);
-        return launch_bv<METHOD, 8, kNTb8, TO>(featK, grad_out, proj, coords, gradK, p, s);
+        if (bwd_brick_z(p) == 16) return launch_bv<METHOD, 8, kNTb8, TO, 16, Det...>(featK, grad_out, proj, coords, gradK, p, s, kexp...);
+        return launch_bv<METHOD, 8, kNTb8, TO, kBZ, Det...>(featK, grad_out, proj, coords, gradK, p, s, kexp...);
         break;
     }
     return hipErrorNotSupported;
 }
 
-template <typename TO>
-hipError_t launch_bt(const float4 *fk, const TO *go, const float *proj, const Coords &coords, float *gradK, const Problem &p, hipStream_t s)
+template <typename TO, typename... Det>
+hipError_t launch_bt(const float4 *fk, const TO *go, const float *proj, const Coords &coords, float *gradK, const Problem &p, hipStream_t s, Det... kexp)
 {
     switch (p.method) {
-    case AGG_SOFTMAX: return launch_bm<AGG_SOFTMAX, TO>(fk, go, proj, coords, gradK, p, s);
-    case AGG_SUM: return launch_bm<AGG_SUM, TO>(fk, go, proj, coords, gradK, p, s);
-    case AGG_MEAN: return launch_bm<AGG_MEAN, TO>(fk, go, proj, coords, gradK, p, s);
-    case AGG_MAX: return launch_bm<AGG_MAX, TO>(fk, go, proj, coords, gradK, p, s);
+    case AGG_SOFTMAX: return launch_bm<AGG_SOFTMAX, TO>(fk, go, proj, coords, gradK, p, s, kexp...);
+    case AGG_SUM: return launch_bm<AGG_SUM, TO>(fk, go, proj, coords, gradK, p, s, kexp...);
+    case AGG_MEAN: return launch_bm<AGG_MEAN, TO>(fk, go, proj, coords, gradK, p, s, kexp...);
+    case AGG_MAX: return launch_bm<AGG_MAX, TO>(fk, go, proj, coords, gradK, p, s, kexp...);
     }
     return hipErrorInvalidValue;
 }
@@ -647,11 +718,12 @@ hipError_t launch_bt(const float4 *fk, const TO *go, const float *proj, const Co
 // ---- C % 4 != 0: k_bwd_brick's quad loop runs the C / 4 whole channel quads; the last, partial quad goes per voxel through bwd_brick_slow
 // (float atomics into the accumulator: those 1 ... 3 channels' gradient is not bit-reproducible between runs), one thread per voxel, launched
 // behind the brick kernel.  (As a cold tail inside k_bwd_brick the same code would keep kernel arguments alive through the quad loop.)
-template <int METHOD, int VT, typename TO>
+template <int METHOD, int VT, typename TO, typename... Det>
 __global__ void __launch_bounds__(256)
 k_bwd_tail(const float4 *__restrict__ featK, const TO *__restrict__ grad_out, const float *__restrict__ proj, const Coords coords, float *__restrict__ gradK,
-           int C, int H, int W, long long N, int nv, Gate gate)
+           int C, int H, int W, long long N, int nv, Gate gate, Det... kexp_arg)
 {
+    constexpr bool DET = sizeof...(Det) > 0;                                    // deterministic instance (see k_bwd_brick)
     if (gated_off(gate)) return;
     __shared__ float sproj[VT][12];
     const int b = blockIdx.y, tid = threadIdx.x;
@@ -663,33 +735,39 @@ k_bwd_tail(const float4 *__restrict__ featK, const TO *__restrict__ grad_out, co
     const long long HW = (long long)H * W;
     float c0, c1, c2;
     voxel_xyz(coords, b, N, (unsigned)n, c0, c1, c2);
+    if constexpr (DET)
+        bwd_brick_slow<METHOD, VT, TO>(featK + (long long)b * nv * nqv * HW, grad_out + (long long)b * C * N,
+                                       reinterpret_cast<float *>(reinterpret_cast<unsigned long long *>(gradK) + (long long)b * nv * nqv * HW * 4), sproj,
+                                       c0, c1, c2, (unsigned)n, N, C >> 2, nqv, nqv, C, H, W, nv, det_exps(kexp_arg...) + (long long)b * C);
+    else
     bwd_brick_slow<METHOD, VT, TO>(featK + (long long)b * nv * nqv * HW, grad_out + (long long)b * C * N, gradK + (long long)b * nv * nqv * HW * 4, sproj, c0, c1, c2,
                                    (unsigned)n, N, C >> 2, nqv, nqv, C, H, W, nv);
 }
 
 namespace {
-template <int METHOD, typename TO>
-hipError_t launch_bwd_tail_views(const float4 *fk, const TO *go, const float *proj, const Coords &coords, float *gradK, const Problem &p, hipStream_t s)
+template <int METHOD, typename TO, typename... Det>
+hipError_t launch_bwd_tail_views(const float4 *fk, const TO *go, const float *proj, const Coords &coords, float *gradK, const Problem &p, hipStream_t s,
+                                 Det... kexp)
 {
     const dim3 grid((unsigned)((p.N + 255) / 256), (unsigned)p.B);
     const Gate gate = make_gate(p, true);
     switch (brick_view_slots(p.V)) {
-    case 2: hipLaunchKernelGGL((k_bwd_tail<METHOD, 2, TO>), grid, dim3(256), 0, s, fk, go, proj, coords, gradK, p.C, p.H, p.W, p.N, p.V, gate); break;
-    case 4: hipLaunchKernelGGL((k_bwd_tail<METHOD, 4, TO>), grid, dim3(256), 0, s, fk, go, proj, coords, gradK, p.C, p.H, p.W, p.N, p.V, gate); break;
-    case 8: hipLaunchKernelGGL((k_bwd_tail<METHOD, 8, TO>), grid, dim3(256), 0, s, fk, go, proj, coords, gradK, p.C, p.H, p.W, p.N, p.V, gate); break;
+    case 2: hipLaunchKernelGGL((k_bwd_tail<METHOD, 2, TO, Det...>), grid, dim3(256), 0, s, fk, go, proj, coords, gradK, p.C, p.H, p.W, p.N, p.V, gate, kexp...); break;
+    case 4: hipLaunchKernelGGL((k_bwd_tail<METHOD, 4, TO, Det...>), grid, dim3(256), 0, s, fk, go, proj, coords, gradK, p.C, p.H, p.W, p.N, p.V, gate, kexp...); break;
+    case 8: hipLaunchKernelGGL((k_bwd_tail<METHOD, 8, TO, Det...>), grid, dim3(256), 0, s, fk, go, proj, coords, gradK, p.C, p.H, p.W, p.N, p.V, gate, kexp...); break;
     default: return hipErrorNotSupported;
     }
     return hipGetLastError();
 }
 
-template <typename TO>
-hipError_t launch_bwd_tail(const float4 *fk, const TO *go, const float *proj, const Coords &coords, float *gradK, const Problem &p, hipStream_t s)
+template <typename TO, typename... Det>
+hipError_t launch_bwd_tail(const float4 *fk, const TO *go, const float *proj, const Coords &coords, float *gradK, const Problem &p, hipStream_t s, Det... kexp)
 {
     switch (p.method) {
-    case AGG_SOFTMAX: return launch_bwd_tail_views<AGG_SOFTMAX, TO>(fk, go, proj, coords, gradK, p, s);
-    case AGG_SUM: return launch_bwd_tail_views<AGG_SUM, TO>(fk, go, proj, coords, gradK, p, s);
-    case AGG_MEAN: return launch_bwd_tail_views<AGG_MEAN, TO>(fk, go, proj, coords, gradK, p, s);
-    case AGG_MAX: return launch_bwd_tail_views<AGG_MAX, TO>(fk, go, proj, coords, gradK, p, s);
+    case AGG_SOFTMAX: return launch_bwd_tail_views<AGG_SOFTMAX, TO>(fk, go, proj, coords, gradK, p, s, kexp...);
+    case AGG_SUM: return launch_bwd_tail_views<AGG_SUM, TO>(fk, go, proj, coords, gradK, p, s, kexp...);
+    case AGG_MEAN: return launch_bwd_tail_views<AGG_MEAN, TO>(fk, go, proj, coords, gradK, p, s, kexp...);
+    case AGG_MAX: return launch_bwd_tail_views<AGG_MAX, TO>(fk, go, proj, coords, gradK, p, s, kexp...);
     }
     return hipErrorInvalidValue;
 }
@@ -709,6 +787,29 @@ hipError_t launch_bwd_brick(const void *featK, const void *grad_out, const float
     if (p.out_bf16) return launch_bwd_tail<bf16_t>(fk, static_cast<const bf16_t *>(grad_out), proj, coords, gradK, p, s);   // the last, partial quad
     return p.out_f16 ? launch_bwd_tail<__half>(fk, static_cast<const __half *>(grad_out), proj, coords, gradK, p, s)
                      : launch_bwd_tail<float>(fk, static_cast<const float *>(grad_out), proj, coords, gradK, p, s);
+}
+
+// deterministic: acc is the zeroed int64 quad-planar accumulator (same element count), kexp K[b][c] (det_scale.h)
+bool brick_bwd_det_supported(const Problem &p)
+{
+    // the flush's 32-bit buffer offsets cover one sample's accumulator: 32 B per slot instead of 16
+    return brick_bwd_supported(p) && (long long)p.V * (p.C4 / 4) * p.H * p.W < (1ll << 26);
+}
+
+hipError_t launch_bwd_brick_det(const void *featK, const void *grad_out, const float *proj, const Coords &coords, unsigned long long *acc,
+                                const int *kexp, const Problem &p, hipStream_t s)
+{
+    if (!brick_bwd_det_supported(p) || p.gate_count) return hipErrorNotSupported;
+    const float4 *fk = static_cast<const float4 *>(featK);
+    float *gk = reinterpret_cast<float *>(acc);
+    hipError_t e;
+    if (p.out_bf16) e = launch_bt<bf16_t>(fk, static_cast<const bf16_t *>(grad_out), proj, coords, gk, p, s, kexp);
+    else e = p.out_f16 ? launch_bt<__half>(fk, static_cast<const __half *>(grad_out), proj, coords, gk, p, s, kexp)
+                       : launch_bt<float>(fk, static_cast<const float *>(grad_out), proj, coords, gk, p, s, kexp);
+    if (e != hipSuccess || !(p.C & 3)) return e;
+    if (p.out_bf16) return launch_bwd_tail<bf16_t>(fk, static_cast<const bf16_t *>(grad_out), proj, coords, gk, p, s, kexp);
+    return p.out_f16 ? launch_bwd_tail<__half>(fk, static_cast<const __half *>(grad_out), proj, coords, gk, p, s, kexp)
+                     : launch_bwd_tail<float>(fk, static_cast<const float *>(grad_out), proj, coords, gk, p, s, kexp);
 }
 
 hipError_t launch_quad_grad_to_planar(const float *gradK, void *dst, const Problem &p, hipStream_t s)

@@ -12,6 +12,7 @@
 // Feature reads come from L2 / Infinity Cache (each (b,v) map is re-read by many blocks), the output is
 // written exactly once.  The brick variant (brick_fwd_kernel.h, unproject_brick_bwd.hip) replaces the L2 gather by LDS patches.
 #include "device_common.h"
+#include "det_scale.h"
 #include "kernels.h"
 
 namespace mvhmr {
@@ -288,6 +289,139 @@ k_bwd_gather(const TO *__restrict__ grad_out, const TF *__restrict__ featT, cons
     }
 }
 
+// Deterministic mode (mvhmr_unproject_backward_deterministic): k_bwd_gather with every tap added as int64 fixed point,
+// llrint(ds * w * 2^K[b][c]) (det_scale.h), into an int64 channels-last accumulator with u64 atomics -- integer sums do not depend on the
+// arrival order.  A poisoned (b, c) adds nothing: the conversion pass writes NaN over its whole gradient.  (A copy, not a template flag of
+// k_bwd_gather: that kernel's instances keep the code they had.)
+template <typename TF, typename TO, int METHOD, int VT>
+__global__ void __launch_bounds__(256)
+k_bwd_gather_det(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj,
+             const Coords coords, unsigned long long *__restrict__ gradI, const int *__restrict__ kexp, int Vrt, int C, int C4, int H, int W,
+             long long N, Gate gate)
+{
+    if (gated_off(gate)) return;
+    const int V = VT > 0 ? VT : Vrt;
+    extern __shared__ __align__(16) unsigned char smem[];
+    TapRec *recs = reinterpret_cast<TapRec *>(smem);
+    float *gtile = reinterpret_cast<float *>(smem + sizeof(TapRec) * kTileVox * V);   // [256 ch][kTileVox + 1]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, cg = blockIdx.z;
+    for (long long n0 = (long long)blockIdx.x * kTileVox; n0 < N; n0 += (long long)gridDim.x * kTileVox) {   // see k_fwd_gather
+    const long long mapsz = (long long)H * W * C4;
+
+    build_records(recs, proj, coords, b, V, n0, N, H, W, C4);
+    {   // grad_out tile, coalesced along voxels: the two half-waves load alternate channels
+        const int vl = lane & (kTileVox - 1), half = lane / kTileVox;
+        const long long n = n0 + vl;
+        for (int r = wave * 64 + half; r < wave * 64 + 64; r += 64 / kTileVox) {
+            const int c = cg * kGroupCh + r;
+            float g = 0.f;
+            if (c < C && n < N) g = to_f32<TO>(grad_out[((long long)b * C + c) * N + n]);
+            gtile[r * (kTileVox + 1) + vl] = g;
+        }
+    }
+    __syncthreads();
+
+    int ch[4];
+    bool act[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = cg * kGroupCh + i * 64 + lane;
+        act[i] = c < C;
+        ch[i] = act[i] ? c : 0;
+    }
+    int kx[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        kx[i] = act[i] ? kexp[(long long)b * C + ch[i]] : kDetPoison;
+        act[i] = act[i] && kx[i] != kDetPoison;                                 // a poisoned channel adds nothing
+    }
+    const TF *fb = featT + (long long)b * V * mapsz;
+    unsigned long long *gb = gradI + (long long)b * V * mapsz;
+
+    auto sample4 = [&](const UTap &u, int v, float (&sv)[4]) {
+        const TF *fv = fb + v * mapsz;
+        if (u.w00 == 0.f && u.w01 == 0.f && u.w10 == 0.f && u.w11 == 0.f) {        // identically zero: reads nothing (see k_fwd_gather)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sv[i] = 0.f;
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            sv[i] = bilerp(to_f32<TF>(fv[u.o00 + ch[i]]), to_f32<TF>(fv[u.o01 + ch[i]]), to_f32<TF>(fv[u.o10 + ch[i]]),
+                           to_f32<TF>(fv[u.o11 + ch[i]]), u.w00, u.w01, u.w10, u.w11);
+    };
+    auto scatter4 = [&](const UTap &u, int v, const float (&dsv)[4]) {
+        unsigned long long *gv = gb + v * mapsz;
+        // zero-weight taps (outside the map, or z <= 0) receive nothing -- wave-uniform branches
+        if (u.w00 != 0.f) { for (int i = 0; i < 4; ++i) if (act[i]) atomicAdd(gv + u.o00 + ch[i], det_fixed(dsv[i] * u.w00, kx[i])); }
+        if (u.w01 != 0.f) { for (int i = 0; i < 4; ++i) if (act[i]) atomicAdd(gv + u.o01 + ch[i], det_fixed(dsv[i] * u.w01, kx[i])); }
+        if (u.w10 != 0.f) { for (int i = 0; i < 4; ++i) if (act[i]) atomicAdd(gv + u.o10 + ch[i], det_fixed(dsv[i] * u.w10, kx[i])); }
+        if (u.w11 != 0.f) { for (int i = 0; i < 4; ++i) if (act[i]) atomicAdd(gv + u.o11 + ch[i], det_fixed(dsv[i] * u.w11, kx[i])); }
+    };
+
+    for (int jj = 0; jj < kTileVox / 4; ++jj) {
+        const int j = wave * (kTileVox / 4) + jj;
+        if (n0 + j >= N) break;
+        float g[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] = gtile[(i * 64 + lane) * (kTileVox + 1) + j];
+
+        if constexpr (VT > 0) {
+            float s[4][VT], ds[4][VT];
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                float sv[4];
+                sample4(uniform_rec(recs[j * VT + v]), v, sv);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s[i][v] = sv[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) aggregate_grad<METHOD, VT>(s[i], g[i], ds[i]);
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                const float dsv[4] = {ds[0][v], ds[1][v], ds[2][v], ds[3][v]};
+                scatter4(uniform_rec(recs[j * VT + v]), v, dsv);
+            }
+        } else {
+            // run-time view count: pass 1 accumulates the aggregate, pass 2 re-samples and scatters
+            RunningAgg<METHOD> ra[4];
+            int am[4] = {0, 0, 0, 0};
+            float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ra[i].init();
+            for (int v = 0; v < V; ++v) {
+                float sv[4];
+                sample4(uniform_rec(recs[j * V + v]), v, sv);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    ra[i].push(sv[i]);
+                    if (sv[i] > best[i]) { best[i] = sv[i]; am[i] = v; }
+                }
+            }
+            for (int v = 0; v < V; ++v) {
+                const UTap u = uniform_rec(recs[j * V + v]);
+                float sv[4], dsv[4];
+                sample4(u, v, sv);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    if constexpr (METHOD == AGG_SUM) dsv[i] = g[i];
+                    else if constexpr (METHOD == AGG_MEAN) dsv[i] = __fdiv_rn(g[i], (float)V);
+                    else if constexpr (METHOD == AGG_MAX) dsv[i] = am[i] == v ? g[i] : 0.f;
+                    else {
+                        const float rden = __builtin_amdgcn_rcpf(ra[i].den);
+                        const float o = ra[i].num * rden;
+                        dsv[i] = g[i] * __expf(sv[i] - ra[i].m) * rden * (1.f + sv[i] - o);
+                    }
+                }
+                scatter4(u, v, dsv);
+            }
+        }
+    }
+    __syncthreads();
+    }
+}
+
 // ------------------------------------------------------------------------------------------ layout passes
 // (BV, C, HW) -> (BV, HW, C4): 64 x 64 tiles turned through LDS, both sides coalesced.  VEC: 4 pixels per load and 4 channels per
 // store (16-B / 8-B accesses; HW % 4 == 0 and C4 % 4 == 0, base pointers aligned) -- 4.6 -> 5.8 TB/s for the 302 MB of configs[1].
@@ -500,6 +634,49 @@ hipError_t launch_bwd_gather(const void *grad_out, const void *featT, const floa
     if (!p.feat_f16 && !p.out_f16) return bwd_dispatch_m((const float *)grad_out, (const float *)featT, proj, coords, gradT, p, s);
     if (p.feat_f16 && p.out_f16) return bwd_dispatch_m((const __half *)grad_out, (const __half *)featT, proj, coords, gradT, p, s);
     if (p.feat_f16 && !p.out_f16) return bwd_dispatch_m((const float *)grad_out, (const __half *)featT, proj, coords, gradT, p, s);
+    return hipErrorNotSupported;
+}
+
+template <typename TF, typename TO, int METHOD>
+static hipError_t bwd_det_dispatch_v(const TO *go_, const TF *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
+                                     const int *kexp, const Problem &p, hipStream_t s)
+{
+    const size_t lds = sizeof(TapRec) * kTileVox * (size_t)p.V + sizeof(float) * kGroupCh * (kTileVox + 1);
+    const dim3 grid((unsigned)((p.N + kTileVox - 1) / kTileVox), (unsigned)p.B, (unsigned)((p.C + kGroupCh - 1) / kGroupCh));
+    auto go = [&](auto kern) -> hipError_t {
+        hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, gradI, kexp, p.V, p.C, p.C4, p.H, p.W, p.N, Gate{});
+        return hipGetLastError();
+    };
+    switch (p.V) {
+    case 2: return go(k_bwd_gather_det<TF, TO, METHOD, 2>);
+    case 4: return go(k_bwd_gather_det<TF, TO, METHOD, 4>);
+    case 8: return go(k_bwd_gather_det<TF, TO, METHOD, 8>);
+    default: return go(k_bwd_gather_det<TF, TO, METHOD, 0>);
+    }
+}
+
+template <typename TF, typename TO>
+static hipError_t bwd_det_dispatch_m(const TO *go_, const TF *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
+                                     const int *kexp, const Problem &p, hipStream_t s)
+{
+    switch (p.method) {
+    case AGG_SOFTMAX: return bwd_det_dispatch_v<TF, TO, AGG_SOFTMAX>(go_, featT, proj, coords, gradI, kexp, p, s);
+    case AGG_SUM: return bwd_det_dispatch_v<TF, TO, AGG_SUM>(go_, featT, proj, coords, gradI, kexp, p, s);
+    case AGG_MEAN: return bwd_det_dispatch_v<TF, TO, AGG_MEAN>(go_, featT, proj, coords, gradI, kexp, p, s);
+    case AGG_MAX: return bwd_det_dispatch_v<TF, TO, AGG_MAX>(go_, featT, proj, coords, gradI, kexp, p, s);
+    }
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_bwd_gather_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
+                                 const int *kexp, const Problem &p, hipStream_t s)
+{
+    if (p.out_bf16) return p.feat_f16 ? hipErrorNotSupported : bwd_det_dispatch_m((const bf16_t *)grad_out, (const float *)featT, proj, coords, gradI, kexp, p, s);
+    if (!p.feat_f16 && !p.out_f16) return bwd_det_dispatch_m((const float *)grad_out, (const float *)featT, proj, coords, gradI, kexp, p, s);
+    if (p.feat_f16 && p.out_f16) return bwd_det_dispatch_m((const __half *)grad_out, (const __half *)featT, proj, coords, gradI, kexp, p, s);
+    if (p.feat_f16 && !p.out_f16) return bwd_det_dispatch_m((const float *)grad_out, (const __half *)featT, proj, coords, gradI, kexp, p, s);
     return hipErrorNotSupported;
 }
 

@@ -89,6 +89,19 @@ void run(const mvhmr_unproject_desc &d, const at::Tensor &features, size_t (*wor
     TORCH_CHECK(status == MVHMR_OK, "mvhmr_unproject: ", mvhmr_last_error());
 }
 
+// run() for the deterministic entry points: the workspace comes straight from the device allocator, not from at::empty, which under
+// torch.use_deterministic_algorithms(True) fills new memory (torch.utils.deterministic.fill_uninitialized_memory) -- gigabytes of
+// scratch the kernels overwrite or clear themselves
+template <typename Launch>
+void run_unfilled(const mvhmr_unproject_desc &d, const at::Tensor &features, size_t (*workspace_bytes)(const mvhmr_unproject_desc *), Launch launch)
+{
+    c10::DeviceGuard guard(features.device());
+    const size_t need = workspace_bytes(&d);
+    c10::DataPtr ws = c10::GetAllocator(features.device().type())->allocate(need);
+    const int status = launch(need ? ws.get() : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream());
+    TORCH_CHECK(status == MVHMR_OK, "mvhmr_unproject: ", mvhmr_last_error());
+}
+
 // gradient w.r.t. the features in their dtype: channels-last strides for channels-last features (the permuted view's data_ptr() is
 // its storage's), planar otherwise, quad-planar features included
 at::Tensor new_feature_grad(const mvhmr_unproject_desc &d, const at::Tensor &features)
@@ -122,6 +135,21 @@ at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Te
     run(d, features, mvhmr_unproject_backward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
         return mvhmr_unproject_backward(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
                                         grad.data_ptr(), ws, n, s);
+    });
+    return grad;
+}
+
+// the feature gradient bitwise reproducible (mvhmr_unproject_backward_deterministic); the workspace is not filled
+at::Tensor unprojection_backward_deterministic_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
+                                                      const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
+                                                      int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
+    at::Tensor grad = new_feature_grad(d, features);
+    run_unfilled(d, features, mvhmr_unproject_backward_deterministic_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_backward_deterministic(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
+                                                      grad.data_ptr(), ws, n, s);
     });
     return grad;
 }
@@ -172,6 +200,22 @@ at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const
     run(d, features, mvhmr_unproject_backward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
         return mvhmr_unproject_backward_cuboid(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(),
                                                center.data_ptr<float>(), position.data(), sides.data(), grad.data_ptr(), ws, n, s);
+    });
+    return grad;
+}
+
+// the same for the cuboid recipe (mvhmr_unproject_backward_cuboid_deterministic)
+at::Tensor unprojection_cuboid_backward_deterministic_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
+                                                             const at::Tensor &rot, const at::Tensor &center, at::ArrayRef<double> position,
+                                                             at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H,
+                                                             int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
+    at::Tensor grad = new_feature_grad(d, features);
+    run_unfilled(d, features, mvhmr_unproject_backward_deterministic_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_backward_cuboid_deterministic(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(),
+                                                             center.data_ptr<float>(), position.data(), sides.data(), grad.data_ptr(), ws, n, s);
     });
     return grad;
 }
@@ -261,6 +305,8 @@ TORCH_LIBRARY(mvhmr_native, m)
 {
     m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS ") -> Tensor");
     m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS ") -> Tensor");
+    m.def("unprojection_backward_deterministic(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS ") -> Tensor");
+    m.def("unprojection_cuboid_backward_deterministic(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS ") -> Tensor");
     m.def("unprojection_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS
           ", bool want_proj, bool want_coords) -> (Tensor, Tensor)");
     m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS ") -> Tensor");
@@ -276,6 +322,8 @@ TORCH_LIBRARY_IMPL(mvhmr_native, CUDA, m)
 {
     m.impl("unprojection", &unprojection_native);
     m.impl("unprojection_backward", &unprojection_backward_native);
+    m.impl("unprojection_backward_deterministic", &unprojection_backward_deterministic_native);
+    m.impl("unprojection_cuboid_backward_deterministic", &unprojection_cuboid_backward_deterministic_native);
     m.impl("unprojection_backward_geometry", &unprojection_backward_geometry_native);
     m.impl("unprojection_cuboid", &unprojection_cuboid_native);
     m.impl("unprojection_cuboid_backward", &unprojection_cuboid_backward_native);
