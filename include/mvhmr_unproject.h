@@ -35,7 +35,8 @@ extern "C" {
                                  mvhmr_triangulate_dlt.  4: MVHMR_LAYOUT_QUAD_LOG2E (ABI history); additive within 4:
                                  mvhmr_unproject_backward_geometry[_workspace_bytes], mvhmr_unproject_backward_geometry_cuboid[_workspace_bytes],
                                  mvhmr_triangulate_dlt_backward, mvhmr_unproject_backward_deterministic[_workspace_bytes],
-                                 mvhmr_unproject_backward_cuboid_deterministic[_workspace_bytes], mvhmr_conv1x1_wgrad_deterministic[_workspace_bytes] */
+                                 mvhmr_unproject_backward_cuboid_deterministic[_workspace_bytes], mvhmr_conv1x1_wgrad_deterministic[_workspace_bytes],
+                                 the *_masked entry points and their *_masked_workspace_bytes queries (per-sample view masks) */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -249,6 +250,61 @@ int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, c
                                              const float *rot, const float *center, const double position[3], const double sides[3],
                                              float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
                                              void *hip_stream);
+
+/*
+ * Per-sample view masks (additive within ABI 4): the same calls for a batch whose samples do not all have the same cameras.
+ *   view_mask  (B,V) uint8, DEVICE, row-major: nonzero = the view is present.  NULL = every view present: the call is then exactly the
+ *              unmasked entry point of the same name (same kernels, same bits, same workspace).
+ * Sample b with present views P_b (n_b = |P_b|) gets what the unmasked call gives for features[b, P_b], proj[b, P_b] alone: mean divides
+ * by n_b, softmax and max range over P_b.  The masked views' features and projection rows are never read (any bits, NaN / Inf included,
+ * give the same result); their gradients (grad_features, grad_proj rows) are written as exact zeros.  A sample with n_b = 0 gets a zero
+ * volume and zero gradients.  The per-voxel rule (z <= 0 or outside the map: the sample is 0 and still counted) is unchanged.
+ * How: a table kernel packs every sample's present views into view slots 0 .. n_b - 1 (increasing view order) and a copy of the
+ * features and projections is made in that order; the GATHER kernel family (forward, per-tap scatter backward and its deterministic form)
+ * and the geometry kernels then take n_b per sample; gradients are unpacked back into view order.  Stream-ordered, no host
+ * synchronisation, graph-capturable; the deterministic and geometry forms keep their bitwise reproducibility.
+ * Limits: features in MVHMR_LAYOUT_BVCHW or MVHMR_LAYOUT_BVHWC -- MVHMR_LAYOUT_QUAD / _QUAD_LOG2E with a non-null mask is
+ * MVHMR_ERR_UNSUPPORTED (hand over the planar features); desc->variant AUTO or GATHER (MVHMR_VARIANT_BRICK with a mask is
+ * MVHMR_ERR_UNSUPPORTED: the brick kernels, the plane backward and the wave-specialised forward take no per-sample view count yet).
+ * An all-true mask therefore reproduces the unmasked call with MVHMR_VARIANT_GATHER bit for bit where that call's backward is the
+ * per-tap scatter (channels-last features, or maps too large for the plane kernel), and within the variants' tolerance elsewhere.
+ * Workspace: the *_masked_workspace_bytes queries (a table, one or two packed copies of the features / gradient, and the gather route's
+ * own workspace; never less than the unmasked call needs, so a NULL mask is served by the same buffer).  Storage pairings, 1 ... 16 views
+ * and every other validation as the unmasked calls.
+ */
+size_t mvhmr_unproject_forward_masked_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_forward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_masked_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_masked_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc);
+int mvhmr_unproject_forward_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+                                   const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_forward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
+                                          const float *center, const double position[3], const double sides[3], const uint8_t *view_mask,
+                                          void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                    const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes,
+                                    void *hip_stream);
+int mvhmr_unproject_backward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                           const float *rot, const float *center, const double position[3], const double sides[3],
+                                           const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                  const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace,
+                                                  size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
+                                                         const float *proj, const float *rot, const float *center, const double position[3],
+                                                         const double sides[3], const uint8_t *view_mask, void *grad_features, void *workspace,
+                                                         size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                             const float *coords, const uint8_t *view_mask, float *grad_proj, float *grad_coords, void *workspace,
+                                             size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                    const float *rot, const float *center, const double position[3], const double sides[3],
+                                                    const uint8_t *view_mask, float *grad_proj, float *grad_rot, float *grad_center, void *workspace,
+                                                    size_t workspace_bytes, void *hip_stream);
 
 /*
  * Layout pass on its own: features (B,V,C,Hf,Wf) -> dst in `dst_layout` (MVHMR_LAYOUT_BVHWC with the channel

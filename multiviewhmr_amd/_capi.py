@@ -29,7 +29,9 @@ EXPORTS = (
     "mvhmr_unproject_backward_geometry_cuboid_workspace_bytes", "mvhmr_unproject_backward_geometry_cuboid", "mvhmr_triangulate_dlt_backward",
     "mvhmr_unproject_backward_deterministic_workspace_bytes", "mvhmr_unproject_backward_deterministic",
     "mvhmr_unproject_backward_cuboid_deterministic", "mvhmr_conv1x1_wgrad_deterministic_workspace_bytes", "mvhmr_conv1x1_wgrad_deterministic",
-)
+) + tuple("mvhmr_unproject_%s_masked%s" % (n, w) for n in ("forward", "forward_cuboid", "backward", "backward_cuboid", "backward_deterministic",
+                                                           "backward_cuboid_deterministic", "backward_geometry", "backward_geometry_cuboid")
+          for w in ("", "_workspace_bytes"))      # per-sample view masks
 
 
 class Desc(ctypes.Structure):

@@ -247,7 +247,7 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
 
 
 def unprojection(features, proj_matricies, coord_volumes, aggregation_method='softmax', *, out_dtype=None,
-                 variant='auto'):
+                 variant='auto', view_mask=None):
     """Fused project -> bilinear-sample -> cross-view aggregate (reference: models/aggregation.py:20-87).
 
     features        (B, V, C, Hf, Wf) float32 (or float16, this package's storage mode) on a HIP device;
@@ -260,12 +260,18 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
                     bfloat16 volume -- what a half-precision consumer reads -- and then take a bfloat16 grad_out)
 
     `out_dtype` and `variant` ('auto' | 'gather' | 'brick') are keyword-only extensions.
+    view_mask       (B, V) bool / integer tensor, any device, nonzero = the view is present (keyword-only; None = all present):
+                    out[b] is the un-projection of sample b's present views alone (mean divides by their count, softmax and max range
+                    over them; no views -> zeros), masked views are never read and get zero gradients.  Runs the gather kernels
+                    ('brick' is refused); DESIGN.md 5.8.
     """
     def volume_shape(B):
         if coord_volumes.dim() != 5 or coord_volumes.shape[0] != B or coord_volumes.shape[4] != 3:
             raise RuntimeError("unprojection: coord_volumes must be (%d, X, Y, Z, 3), got %s" % (B, tuple(coord_volumes.shape)))
         return tuple(coord_volumes.shape[1:4])
 
+    if view_mask is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_view_mask(view_mask, features)
     out_dtype, _, empty = _check_call(features, proj_matricies, (coord_volumes,), volume_shape, aggregation_method, variant, out_dtype,
                                       same_device=True)
     if empty is not None:
@@ -273,7 +279,107 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
     # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
     proj = proj_matricies.to(torch.float32).contiguous()
     coords = coord_volumes.to(torch.float32).contiguous()
+    if view_mask is not None:
+        mask = _mask_bytes(view_mask, features)
+        return torch.ops.mvhmr.unprojection_masked(features, proj, coords, mask, _capi.AGG[aggregation_method], _dtype_code(out_dtype),
+                                                   _capi.VARIANT[variant])
     return torch.ops.mvhmr.unprojection(features, proj, coords, _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
+
+
+# Per-sample view masks (mvhmr_unproject_*_masked): mvhmr::unprojection_masked and its backward ops.  view_mask (B, V) uint8 on the
+# features' device, nonzero = present.  The masked route reads planar or channels-last features (never a quad-planar copy) and runs the
+# gather kernels with a per-sample view count; the unmasked ops keep their schemas and routes.
+def _masked_args(features, coords, method, out_dtype, variant):
+    features, layout = _geometry_read_layout(features)
+    return _native_args(features, coords, method, out_dtype, variant, layout)
+
+
+def _opm_forward(features, proj, coords, view_mask, method, out_dtype, variant):
+    read, desc = _masked_args(features, coords, method, out_dtype, variant)
+    return _native().unprojection_masked(read, proj, coords, view_mask, *desc)
+
+
+def _opm_backward(grad_out, features, proj, coords, view_mask, method, out_dtype, variant):
+    read, desc = _masked_args(features, coords, method, out_dtype, variant)
+    return _native().unprojection_masked_backward(grad_out.contiguous(), read, proj, coords, view_mask, *desc)
+
+
+def _opm_backward_deterministic(grad_out, features, proj, coords, view_mask, method, out_dtype, variant):
+    read, desc = _masked_args(features, coords, method, out_dtype, variant)
+    return _native().unprojection_masked_backward_deterministic(grad_out.contiguous(), read, proj, coords, view_mask, *desc)
+
+
+def _opm_backward_geometry(grad_out, features, proj, coords, view_mask, method, out_dtype, variant, want_proj=True, want_coords=True):
+    read, desc = _masked_args(features, coords, method, out_dtype, variant)
+    return tuple(_native().unprojection_masked_backward_geometry(grad_out.contiguous(), read, proj, coords, view_mask, *desc, want_proj,
+                                                                   want_coords))
+
+
+def _fake_masked_forward(features, proj, coords, view_mask, method, out_dtype, variant):
+    return _fake_forward(features, proj, coords, method, out_dtype, variant)
+
+
+def _fake_masked_backward(grad_out, features, proj, coords, view_mask, method, out_dtype, variant):
+    return torch.empty_like(features)
+
+
+def _fake_masked_backward_geometry(grad_out, features, proj, coords, view_mask, method, out_dtype, variant, want_proj=True, want_coords=True):
+    return _fake_backward_geometry(grad_out, features, proj, coords, method, out_dtype, variant, want_proj, want_coords)
+
+
+def _opm_setup(ctx, inputs, output):
+    features, proj, coords, view_mask, method, out_dtype, variant = inputs
+    ctx.save_for_backward(features, proj, coords, view_mask)
+    ctx.args = (method, out_dtype, variant)
+
+
+def _opm_autograd(ctx, grad_out):
+    features, proj, coords, view_mask = ctx.saved_tensors
+    op = (torch.ops.mvhmr.unprojection_masked_backward_deterministic if torch.are_deterministic_algorithms_enabled()
+          else torch.ops.mvhmr.unprojection_masked_backward)
+    g = op(grad_out, features, proj, coords, view_mask, *ctx.args) if ctx.needs_input_grad[0] else None
+    g_proj = g_coords = None
+    want_proj, want_coords = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+    if want_proj or want_coords:
+        g_proj, g_coords = torch.ops.mvhmr.unprojection_masked_backward_geometry(grad_out, features, proj, coords, view_mask, *ctx.args,
+                                                                                 want_proj, want_coords)
+    return g, (g_proj if want_proj else None), (g_coords if want_coords else None), None, None, None, None
+
+
+def _register_masked_ops():
+    if _op_defined("unprojection_masked"):
+        return
+    sig = "(Tensor features, Tensor proj, Tensor coords, Tensor view_mask, int method, int out_dtype, int variant) -> Tensor"
+    torch.library.define("mvhmr::unprojection_masked", sig)
+    torch.library.impl("mvhmr::unprojection_masked", "CUDA")(_opm_forward)
+    torch.library.register_fake("mvhmr::unprojection_masked")(_fake_masked_forward)
+    for name, fn in (("unprojection_masked_backward", _opm_backward), ("unprojection_masked_backward_deterministic", _opm_backward_deterministic)):
+        torch.library.define("mvhmr::" + name, "(Tensor grad_out, " + sig[1:])
+        torch.library.impl("mvhmr::" + name, "CUDA")(fn)
+        torch.library.register_fake("mvhmr::" + name)(_fake_masked_backward)
+    torch.library.define("mvhmr::unprojection_masked_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
+                         + ", bool want_proj=True, bool want_coords=True) -> (Tensor, Tensor)")
+    torch.library.impl("mvhmr::unprojection_masked_backward_geometry", "CUDA")(_opm_backward_geometry)
+    torch.library.register_fake("mvhmr::unprojection_masked_backward_geometry")(_fake_masked_backward_geometry)
+    torch.library.register_autograd("mvhmr::unprojection_masked", _opm_autograd, setup_context=_opm_setup)
+
+
+_register_masked_ops()
+
+
+def _check_view_mask(view_mask, features):
+    """view_mask (B, V) bool or an integer dtype, any device: raises TypeError / RuntimeError as _check_call does"""
+    if not torch.is_tensor(view_mask):
+        raise TypeError("unprojection: view_mask must be a (B, V) tensor of bool or integers, got %s" % type(view_mask).__name__)
+    if view_mask.dtype.is_floating_point or view_mask.dtype.is_complex:
+        raise TypeError("unprojection: view_mask must be bool or an integer dtype, got %s" % view_mask.dtype)
+    if tuple(view_mask.shape) != tuple(features.shape[:2]):
+        raise RuntimeError("unprojection: view_mask must be %s, got %s" % (tuple(features.shape[:2]), tuple(view_mask.shape)))
+
+
+def _mask_bytes(view_mask, features):
+    """the checked mask as the library reads it: contiguous uint8 on features.device, nonzero = present"""
+    return (view_mask != 0).to(device=features.device, dtype=torch.uint8).contiguous()
 
 
 # The same kernels fed by the cuboid recipe instead of a coordinate tensor (mvhmr_unproject_*_cuboid), registered the same way
@@ -359,6 +465,76 @@ def _register_cuboid_ops():
 _register_cuboid_ops()
 
 
+# the cuboid recipe's masked ops (mvhmr::unprojection_cuboid_masked ...): view_mask after center, otherwise as the unmasked cuboid ops
+def _opcm_forward(features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant):
+    read, desc = _masked_args(features, vol, method, out_dtype, variant)
+    return _native().unprojection_cuboid_masked(read, proj, rot, center, view_mask, position, sides, vol, *desc)
+
+
+def _opcm_backward(grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant):
+    read, desc = _masked_args(features, vol, method, out_dtype, variant)
+    return _native().unprojection_cuboid_masked_backward(grad_out.contiguous(), read, proj, rot, center, view_mask, position, sides, vol, *desc)
+
+
+def _opcm_backward_deterministic(grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant):
+    read, desc = _masked_args(features, vol, method, out_dtype, variant)
+    return _native().unprojection_cuboid_masked_backward_deterministic(grad_out.contiguous(), read, proj, rot, center, view_mask, position, sides,
+                                                                       vol, *desc)
+
+
+def _opcm_backward_geometry(grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant, want_proj=True,
+                            want_rot=True, want_center=True):
+    read, desc = _masked_args(features, vol, method, out_dtype, variant)
+    return tuple(_native().unprojection_cuboid_masked_backward_geometry(grad_out.contiguous(), read, proj, rot, center, view_mask, position, sides,
+                                                                        vol, *desc, want_proj, want_rot, want_center))
+
+
+def _opcm_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:5])
+    ctx.args = tuple(inputs[5:])
+
+
+def _opcm_autograd(ctx, grad_out):
+    features, proj, rot, center, view_mask = ctx.saved_tensors
+    op = (torch.ops.mvhmr.unprojection_cuboid_masked_backward_deterministic if torch.are_deterministic_algorithms_enabled()
+          else torch.ops.mvhmr.unprojection_cuboid_masked_backward)
+    g = op(grad_out, features, proj, rot, center, view_mask, *ctx.args) if ctx.needs_input_grad[0] else None
+    want = tuple(ctx.needs_input_grad[1:4])
+    geo = (None, None, None)
+    if any(want):
+        geo = torch.ops.mvhmr.unprojection_cuboid_masked_backward_geometry(grad_out, features, proj, rot, center, view_mask, *ctx.args, *want)
+    return (g,) + tuple(t if w else None for t, w in zip(geo, want)) + (None,) * 7
+
+
+def _register_cuboid_masked_ops():
+    if _op_defined("unprojection_cuboid_masked"):
+        return
+    sig = ("(Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, float[] position, float[] sides, int[] vol, int method, "
+           "int out_dtype, int variant) -> Tensor")
+    torch.library.define("mvhmr::unprojection_cuboid_masked", sig)
+    torch.library.impl("mvhmr::unprojection_cuboid_masked", "CUDA")(_opcm_forward)
+    torch.library.register_fake("mvhmr::unprojection_cuboid_masked")(
+        lambda features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant:
+        features.new_empty((features.shape[0], features.shape[2]) + tuple(vol), dtype=_DTYPES[out_dtype]))
+    for name, fn in (("unprojection_cuboid_masked_backward", _opcm_backward),
+                     ("unprojection_cuboid_masked_backward_deterministic", _opcm_backward_deterministic)):
+        torch.library.define("mvhmr::" + name, "(Tensor grad_out, " + sig[1:])
+        torch.library.impl("mvhmr::" + name, "CUDA")(fn)
+        torch.library.register_fake("mvhmr::" + name)(
+            lambda grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant: torch.empty_like(features))
+    torch.library.define("mvhmr::unprojection_cuboid_masked_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
+                         + ", bool want_proj=True, bool want_rot=True, bool want_center=True) -> (Tensor, Tensor, Tensor)")
+    torch.library.impl("mvhmr::unprojection_cuboid_masked_backward_geometry", "CUDA")(_opcm_backward_geometry)
+    torch.library.register_fake("mvhmr::unprojection_cuboid_masked_backward_geometry")(
+        lambda grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant, want_proj=True, want_rot=True,
+        want_center=True: _fake_backward_geometry_cuboid(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant,
+                                                         want_proj, want_rot, want_center))
+    torch.library.register_autograd("mvhmr::unprojection_cuboid_masked", _opcm_autograd, setup_context=_opcm_setup)
+
+
+_register_cuboid_masked_ops()
+
+
 # DLT triangulation (mvhmr_triangulate_dlt[_weighted] and mvhmr_triangulate_dlt_backward) as mvhmr::triangulate_dlt[_backward]: proj (B,V,3,4),
 # points (V,2) shared or (B,V,2), confidences None, (V,) shared or (B,V), all fp32 on one HIP device -> (B,3)
 def _dlt_forward(proj, points, confidences):
@@ -407,19 +583,22 @@ _register_dlt_op()
 
 
 def unprojection_cuboid(features, proj_matricies, rotations, centers, position, sides, volume_shape,
-                        aggregation_method='softmax', *, out_dtype=None, variant='auto'):
+                        aggregation_method='softmax', *, out_dtype=None, variant='auto', view_mask=None):
     """`unprojection` for the volumes VolumeGenerator builds (aggregation.py:138-187), without the coordinate tensor: voxel centres
     are rot[b] @ (position + sides / (S - 1) * (i,j,k) - center[b]) + center[b], evaluated inside the kernels (bit-equal to
     mvhmr_build_coord_volumes followed by `unprojection`).
 
     rotations (B,3,3) and centers (B,3): float32 tensors on features.device; position, sides: 3 numbers each (cuboid corner and
-    edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers."""
+    edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers.  view_mask: as for
+    `unprojection`."""
     def checked_shape(B):
         if tuple(rotations.shape) != (B, 3, 3) or tuple(centers.shape) != (B, 3):
             raise RuntimeError("unprojection: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
                                % (B, B, tuple(rotations.shape), tuple(centers.shape)))
         return tuple(int(v) for v in volume_shape)
 
+    if view_mask is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_view_mask(view_mask, features)
     out_dtype, vol, empty = _check_call(features, proj_matricies, (rotations, centers), checked_shape, aggregation_method, variant,
                                         out_dtype, same_device=False)
     if empty is not None:
@@ -429,6 +608,10 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     proj = proj_matricies.to(device=dev, dtype=torch.float32).contiguous()
     rot = rotations.to(device=dev, dtype=torch.float32).contiguous()
     cen = centers.to(device=dev, dtype=torch.float32).contiguous()
+    if view_mask is not None:
+        return torch.ops.mvhmr.unprojection_cuboid_masked(features, proj, rot, cen, _mask_bytes(view_mask, features), [float(x) for x in position],
+                                                          [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method],
+                                                          _dtype_code(out_dtype), _capi.VARIANT[variant])
     return torch.ops.mvhmr.unprojection_cuboid(features, proj, rot, cen, [float(x) for x in position], [float(x) for x in sides], list(vol),
                                                _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
 
@@ -608,13 +791,14 @@ class VolumeGenerator(nn.Module):
             return [0, 0, 1]
         raise ValueError("Unknown kind: {}".format(self.kind))  # the reference fails with UnboundLocalError here
 
-    def volume_pose(self, batch, proj_matricies_org, images_shape):
+    def volume_pose(self, batch, proj_matricies_org, images_shape, view_mask=None):
         """Per-sample rotation (B,3,3) and pivot (B,3), float32 numpy/tensor (aggregation.py:163-181).
 
         Training draws theta ~ U(0, 2 pi) from the GLOBAL numpy stream, one draw per sample in order
         (quirk Q6); eval uses theta = 0.  The pivot is keypoints_3d[b][6, :3], or the DLT-triangulated
         image centre when use_triangulation is set -- a function of proj_matricies_org that carries its gradient (the reference
-        triangulates from the caller's proj_matricies with torch.svd)."""
+        triangulates from the caller's proj_matricies with torch.svd).  With a view mask (B, V) the pivot is the weighted DLT with the mask as
+        the confidences, on projections whose masked rows are zeroed first (0 * NaN is not 0); fewer than two present views is undefined."""
         batch_size = proj_matricies_org.shape[0]
         axis = self.rotation_axis()
         if self.training:
@@ -634,7 +818,13 @@ class VolumeGenerator(nn.Module):
             # one batched DLT on the device, no per-sample .cpu(); stays a device tensor
             n_views = proj_matricies_org.shape[1]
             images_center = (torch.tensor(images_shape, dtype=torch.float32) / 2).expand(n_views, 2)
-            centers = multiview.triangulate_points_from_multiple_views_linear_batch(proj_matricies_org, images_center)   # differentiable
+            if view_mask is None:
+                centers = multiview.triangulate_points_from_multiple_views_linear_batch(proj_matricies_org, images_center)   # differentiable
+            else:
+                present = view_mask.to(device=proj_matricies_org.device) != 0
+                P = torch.where(present[:, :, None, None], proj_matricies_org, torch.zeros((), dtype=proj_matricies_org.dtype,
+                                                                                          device=proj_matricies_org.device))
+                centers = multiview.triangulate_points_from_multiple_views_linear_batch(P, images_center, present.to(torch.float32))
         else:
             kp = batch['keypoints_3d']
             if torch.is_tensor(kp):                                          # already a (B, 17, 3|4) tensor (any device)
@@ -673,13 +863,17 @@ class VolumeGenerator(nn.Module):
             proj = torch.from_numpy(feature_level_projections(batch['cameras'], images_shape, features_shape))
         # the kernels take raw device pointers: whatever device the packed cameras live on (a loader may pack them on the host)
         proj = proj.to(device=device, dtype=torch.float32).contiguous()
-        rots, centers = self.volume_pose(batch, proj_org, images_shape)
+        view_mask = batch.get('view_mask')                                  # optional (B, V): per-sample present views
+        if view_mask is not None:
+            _check_view_mask(view_mask, proj)                               # (only its (B, V) leading shape is read)
+        rots, centers = (self.volume_pose(batch, proj_org, images_shape) if view_mask is None
+                         else self.volume_pose(batch, proj_org, images_shape, view_mask))
         cub = self.cuboid()
         S = self.volume_size
         rots = rots.to(device=device, dtype=torch.float32).contiguous()
         centers = centers.to(device=device, dtype=torch.float32).contiguous()
 
-        if self._fused_path_applies(features, S):
+        if view_mask is None and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask does not take)
             # 1x1 conv and layout pass in one MFMA GEMM, its output only ever exists in the layout the brick forward stages
             conv = self.process_feature[0]
             return _FusedAggregate.apply(features, conv.weight, conv.bias, proj, rots, centers, tuple(cub.position), tuple(cub.sides),
@@ -689,8 +883,9 @@ class VolumeGenerator(nn.Module):
         features = self.process_feature(features)
         features = features.view(batch_size, n_views, *features.shape[1:])
         # the coordinate volumes (aggregation.py:138-187) are never materialised: the kernels evaluate the cuboid recipe per voxel
+        masked = {} if view_mask is None else {"view_mask": view_mask}       # (an unmasked batch calls exactly as before)
         return unprojection_cuboid(features, proj, rots, centers, cub.position, cub.sides, (S, S, S),
-                                   aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype)
+                                   aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **masked)
 
     def _fused_path_applies(self, features, S):
         """The fused conv writes the quad-planar layout, which the un-projection consumes for every geometry (brick kernels as it

@@ -147,7 +147,7 @@ bool bwd_uses_brick(const mvhmr_unproject_desc *d, const Problem &p)
 // the per-tap scatter.  Channels-last features keep the scatter (its accumulator is the caller's own tensor).
 bool bwd_uses_plane(const mvhmr_unproject_desc *d, const Problem &p)
 {
-    return d->feat_layout != MVHMR_LAYOUT_BVHWC && plane_bwd_supported(p);
+    return d->feat_layout != MVHMR_LAYOUT_BVHWC && plane_bwd_supported(p) && !p.masked;   // (masked calls: the per-tap scatter)
 }
 // bytes between the converted feature copy and the gate counter of a gated backward: the brick side's accumulator or the plane
 // side's tap table, whichever is larger
@@ -312,16 +312,21 @@ size_t mvhmr_unproject_forward_workspace_bytes(const mvhmr_unproject_desc *desc)
     return pick_variant(desc, p) == MVHMR_VARIANT_BRICK ? brick_workspace_bytes(p) : featT_bytes(p);
 }
 
-size_t mvhmr_unproject_backward_workspace_bytes(const mvhmr_unproject_desc *desc)
+static size_t backward_ws_bytes(const mvhmr_unproject_desc *desc, const Problem &p)
 {
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
     if (geometry_gated_bwd(desc, p) && bwd_uses_brick(desc, p)) return conv_bytes(p) + bwd_mid_bytes(desc, p) + kGateBytes;
     if (bwd_uses_brick(desc, p)) return brick_workspace_bytes(p) + gradT_bytes(p);
     if (bwd_uses_plane(desc, p)) return (desc->feat_layout == MVHMR_LAYOUT_BVCHW ? brick_workspace_bytes(p) : 0) + align_up(plane_table_bytes(p));
     size_t need = desc->feat_layout != MVHMR_LAYOUT_BVHWC ? featT_bytes(p) : 0;
     if (!grad_in_place(desc, p)) need += gradT_bytes(p);
     return need;
+}
+
+size_t mvhmr_unproject_backward_workspace_bytes(const mvhmr_unproject_desc *desc)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
+    return backward_ws_bytes(desc, p);
 }
 
 static int forward_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *features, const float *proj, const Coords &coords,
@@ -421,7 +426,7 @@ static int backward_impl(const mvhmr_unproject_desc *desc, Problem &p, const voi
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p) && !quad_to_channels_last_supported(p))
         return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    rc = check_ws(workspace, workspace_bytes, mvhmr_unproject_backward_workspace_bytes(desc));
+    rc = check_ws(workspace, workspace_bytes, backward_ws_bytes(desc, p));
     if (rc != MVHMR_OK) return rc;
 
     unsigned char *ws = static_cast<unsigned char *>(workspace);
@@ -548,6 +553,8 @@ static size_t det_need_bytes(const mvhmr_unproject_desc *d, const Problem &p)
     return (d->feat_layout != MVHMR_LAYOUT_BVHWC ? featT_bytes(p) : 0) + det_acc_bytes(p) + align_up(det_scale_bytes(p));
 }
 
+static size_t backward_det_ws_bytes(const mvhmr_unproject_desc *desc, const Problem &p);
+
 static int backward_det_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj,
                              const Coords &coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
@@ -560,7 +567,7 @@ static int backward_det_impl(const mvhmr_unproject_desc *desc, Problem &p, const
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p) && !quad_to_channels_last_supported(p))
         return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    rc = check_ws(workspace, workspace_bytes, mvhmr_unproject_backward_deterministic_workspace_bytes(desc));
+    rc = check_ws(workspace, workspace_bytes, backward_det_ws_bytes(desc, p));
     if (rc != MVHMR_OK) return rc;
     if (desc->variant == MVHMR_VARIANT_BRICK && !bwd_uses_brick(desc, p))
         return fail(MVHMR_ERR_UNSUPPORTED, "the brick variant does not support this shape / dtype / layout");
@@ -618,12 +625,17 @@ static int backward_det_impl(const mvhmr_unproject_desc *desc, Problem &p, const
     return launched(launch_det_grad_cast(acc, kexp, grad_features, p, s), "gradient cast");
 }
 
+static size_t backward_det_ws_bytes(const mvhmr_unproject_desc *desc, const Problem &p)
+{
+    const size_t det = det_need_bytes(desc, p), dflt = backward_ws_bytes(desc, p);
+    return det > dflt ? det : dflt;
+}
+
 size_t mvhmr_unproject_backward_deterministic_workspace_bytes(const mvhmr_unproject_desc *desc)
 {
     Problem p;
     if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
-    const size_t det = det_need_bytes(desc, p), dflt = mvhmr_unproject_backward_workspace_bytes(desc);
-    return det > dflt ? det : dflt;
+    return backward_det_ws_bytes(desc, p);
 }
 
 int mvhmr_unproject_backward_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
@@ -658,13 +670,11 @@ size_t mvhmr_unproject_backward_geometry_workspace_bytes(const mvhmr_unproject_d
     return (desc->feat_layout == MVHMR_LAYOUT_BVHWC ? 0 : featT_bytes(p)) + align_up(geom_partial_bytes(p));
 }
 
-int mvhmr_unproject_backward_geometry(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                      const float *coords, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes,
-                                      void *hip_stream)
+static int backward_geometry_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj,
+                                  const float *coords, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes,
+                                  void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
+    int rc;
     if (!grad_out || !features || !proj || !coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / coords must be non-null");
     if (!grad_proj && !grad_coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj and grad_coords are both null: nothing to compute");
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
@@ -688,6 +698,16 @@ int mvhmr_unproject_backward_geometry(const mvhmr_unproject_desc *desc, const vo
                     "geometry backward");
 }
 
+int mvhmr_unproject_backward_geometry(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                      const float *coords, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes,
+                                      void *hip_stream)
+{
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    return backward_geometry_impl(desc, p, grad_out, features, proj, coords, grad_proj, grad_coords, workspace, workspace_bytes, hip_stream);
+}
+
 size_t mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(const mvhmr_unproject_desc *desc)
 {
     Problem p;
@@ -695,14 +715,12 @@ size_t mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(const mvhmr_unpr
     return (desc->feat_layout == MVHMR_LAYOUT_BVHWC ? 0 : featT_bytes(p)) + align_up(geom_partial_bytes(p)) + align_up(pose_partial_bytes(p));
 }
 
-int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                             const float *rot, const float *center, const double position[3], const double sides[3],
-                                             float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
-                                             void *hip_stream)
+static int backward_geometry_cuboid_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features,
+                                         const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+                                         float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
+                                         void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
+    int rc;
     if (!grad_out || !features || !proj) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj must be non-null");
     Coords cs;
     rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
@@ -729,6 +747,18 @@ int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, c
     return launched(launch_bwd_geom_cuboid(grad_out, featT, proj, cs, grad_proj ? part : nullptr, grad_proj, (grad_rot || grad_center) ? pose_part : nullptr,
                                            grad_rot, grad_center, p, s),
                     "cuboid geometry backward");
+}
+
+int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                             const float *rot, const float *center, const double position[3], const double sides[3],
+                                             float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
+                                             void *hip_stream)
+{
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    return backward_geometry_cuboid_impl(desc, p, grad_out, features, proj, rot, center, position, sides, grad_proj, grad_rot, grad_center,
+                                         workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)
@@ -907,6 +937,280 @@ int mvhmr_build_coord_volumes(float *coords, const float *rot, const float *cent
     if (batch < 1 || volume_size < 1) return fail(MVHMR_ERR_INVALID_ARGUMENT, "batch and volume_size must be >= 1");
     return launched(launch_build_coords(coords, rot, center, batch, volume_size, position, sides, static_cast<hipStream_t>(hip_stream)),
                     "coord volume build");
+}
+
+}  // extern "C"
+
+// ---- per-sample view masks (include/mvhmr_unproject.h).  k_view_table turns the mask into slot tables and the projections
+// packed into slot order, the features are packed the same way (absent slots zero), and the unmasked route runs on the packed problem with
+// Problem::view_count set: the gather family (forward, per-tap scatter backward, its deterministic form) and the geometry kernels.  Gradients
+// are unpacked back into view order, masked views zero-filled.  A null mask is the unmasked entry point.
+namespace {
+
+size_t masked_view_bytes(const Problem &p) { return (size_t)p.C * p.H * p.W * feat_elem(p); }   // one view, planar or channels-last (C4 == C)
+size_t masked_head_bytes(const Problem &p, int copies)
+{
+    return align_up(view_table_bytes(p.B, p.V)) + (size_t)copies * align_up((size_t)p.B * p.V * masked_view_bytes(p));
+}
+
+// the layouts and variants a masked call serves; *inner: the descriptor of the packed problem
+int masked_desc(const mvhmr_unproject_desc *desc, Problem &p, mvhmr_unproject_desc *inner)
+{
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "a view mask needs planar or channels-last features (quad-planar copies: pass the planar features)");
+    if (desc->variant == MVHMR_VARIANT_BRICK) return fail(MVHMR_ERR_UNSUPPORTED, "a view mask runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
+    *inner = *desc;
+    inner->variant = MVHMR_VARIANT_GATHER;
+    p.masked = 1;                                               // the route; view_count is set once the table exists (masked_setup)
+    return MVHMR_OK;
+}
+
+size_t max_size(size_t a, size_t b) { return a > b ? a : b; }
+
+// table + packed features (+ the packed gradient) at the head of the workspace, the unmasked route's workspace behind them
+struct MaskedWs {
+    void *table;
+    unsigned char *feat, *grad, *inner;
+    size_t inner_bytes;
+};
+int masked_setup(const Problem &p, const uint8_t *mask, const float *proj, const void *features, int copies, void *workspace, size_t workspace_bytes,
+                 size_t need, hipStream_t s, MaskedWs *m, Problem *pm)
+{
+    int rc = check_ws(workspace, workspace_bytes, need);
+    if (rc != MVHMR_OK) return rc;
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    m->table = ws;
+    m->feat = ws + align_up(view_table_bytes(p.B, p.V));
+    m->grad = copies > 1 ? m->feat + align_up((size_t)p.B * p.V * masked_view_bytes(p)) : nullptr;
+    m->inner = ws + masked_head_bytes(p, copies);
+    m->inner_bytes = workspace_bytes - masked_head_bytes(p, copies);
+    rc = launched(launch_view_table(mask, proj, m->table, p.B, p.V, s), "view table");
+    if (rc != MVHMR_OK) return rc;
+    rc = launched(launch_view_pack(features, m->feat, m->table, p.B, p.V, masked_view_bytes(p), s), "view pack");
+    if (rc != MVHMR_OK) return rc;
+    *pm = p;
+    pm->view_count = view_table_counts(m->table);
+    return MVHMR_OK;
+}
+
+size_t forward_masked_ws(const mvhmr_unproject_desc *desc)
+{
+    Problem p;
+    mvhmr_unproject_desc in;
+    if (check_desc(desc, &p) != MVHMR_OK || masked_desc(desc, p, &in) != MVHMR_OK) return 0;
+    return max_size(masked_head_bytes(p, 1) + mvhmr_unproject_forward_workspace_bytes(&in), mvhmr_unproject_forward_workspace_bytes(desc));
+}
+size_t backward_masked_ws(const mvhmr_unproject_desc *desc, bool det)
+{
+    Problem p, pu;
+    mvhmr_unproject_desc in;
+    if (check_desc(desc, &p) != MVHMR_OK) return 0;
+    pu = p;
+    if (masked_desc(desc, p, &in) != MVHMR_OK) return 0;
+    const size_t unmasked = det ? backward_det_ws_bytes(desc, pu) : backward_ws_bytes(desc, pu);
+    return max_size(masked_head_bytes(p, 2) + (det ? backward_det_ws_bytes(&in, p) : backward_ws_bytes(&in, p)), unmasked);
+}
+size_t geometry_masked_ws(const mvhmr_unproject_desc *desc, bool cuboid)
+{
+    Problem p;
+    mvhmr_unproject_desc in;
+    if (check_desc(desc, &p) != MVHMR_OK || masked_desc(desc, p, &in) != MVHMR_OK) return 0;
+    const size_t inner = cuboid ? mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(&in) : mvhmr_unproject_backward_geometry_workspace_bytes(&in);
+    const size_t unmasked = cuboid ? mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(desc) : mvhmr_unproject_backward_geometry_workspace_bytes(desc);
+    return max_size(masked_head_bytes(p, 1) + align_up((size_t)p.B * p.V * 12 * sizeof(float)) + inner, unmasked);
+}
+
+int forward_masked(const mvhmr_unproject_desc *desc, Problem &p, const void *features, const float *proj, const Coords &coords, const uint8_t *mask,
+                   void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    mvhmr_unproject_desc in;
+    if (!features || !proj || !out) return fail(MVHMR_ERR_INVALID_ARGUMENT, "features / proj / out must be non-null");
+    int rc = masked_desc(desc, p, &in);
+    if (rc != MVHMR_OK) return rc;
+    MaskedWs m;
+    Problem pm;
+    rc = masked_setup(p, mask, proj, features, 1, workspace, workspace_bytes, forward_masked_ws(desc), static_cast<hipStream_t>(hip_stream), &m, &pm);
+    if (rc != MVHMR_OK) return rc;
+    return forward_impl(&in, pm, m.feat, view_table_proj(m.table, p.B, p.V), coords, out, m.inner, m.inner_bytes, hip_stream);
+}
+
+int backward_masked(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj, const Coords &coords,
+                    const uint8_t *mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream, bool det)
+{
+    mvhmr_unproject_desc in;
+    if (!grad_out || !features || !proj || !grad_features)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
+    int rc = masked_desc(desc, p, &in);
+    if (rc != MVHMR_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    MaskedWs m;
+    Problem pm;
+    rc = masked_setup(p, mask, proj, features, 2, workspace, workspace_bytes, backward_masked_ws(desc, det), s, &m, &pm);
+    if (rc != MVHMR_OK) return rc;
+    const float *pp = view_table_proj(m.table, p.B, p.V);
+    rc = det ? backward_det_impl(&in, pm, grad_out, m.feat, pp, coords, m.grad, m.inner, m.inner_bytes, hip_stream)
+             : backward_impl(&in, pm, grad_out, m.feat, pp, coords, m.grad, m.inner, m.inner_bytes, hip_stream);
+    if (rc != MVHMR_OK) return rc;
+    return launched(launch_view_unpack(m.grad, grad_features, m.table, p.B, p.V, masked_view_bytes(p), s), "view unpack");
+}
+
+// geometry: grad_proj comes packed (B,V,3,4) behind the head and is unpacked; grad_coords / grad_rot / grad_center are per sample
+int geometry_masked(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj, const float *coords,
+                    const float *rot, const float *center, const double position[3], const double sides[3], const uint8_t *mask, float *grad_proj,
+                    float *grad_coords, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    mvhmr_unproject_desc in;
+    const bool cuboid = !coords;
+    if (!grad_out || !features || !proj) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj must be non-null");
+    if (cuboid && (!rot || !center || !position || !sides)) return fail(MVHMR_ERR_INVALID_ARGUMENT, "rot / center / position / sides must be non-null");
+    if (!grad_proj && !grad_coords && !grad_rot && !grad_center) return fail(MVHMR_ERR_INVALID_ARGUMENT, "every gradient output is null: nothing to compute");
+    int rc = masked_desc(desc, p, &in);
+    if (rc != MVHMR_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    MaskedWs m;
+    Problem pm;
+    rc = masked_setup(p, mask, proj, features, 1, workspace, workspace_bytes, geometry_masked_ws(desc, cuboid), s, &m, &pm);
+    if (rc != MVHMR_OK) return rc;
+    float *gp = grad_proj ? reinterpret_cast<float *>(m.inner) : nullptr;
+    const size_t gpb = align_up((size_t)p.B * p.V * 12 * sizeof(float));
+    const float *pp = view_table_proj(m.table, p.B, p.V);
+    rc = cuboid ? backward_geometry_cuboid_impl(&in, pm, grad_out, m.feat, pp, rot, center, position, sides, gp, grad_rot, grad_center, m.inner + gpb,
+                                                m.inner_bytes - gpb, hip_stream)
+                : backward_geometry_impl(&in, pm, grad_out, m.feat, pp, coords, gp, grad_coords, m.inner + gpb, m.inner_bytes - gpb, hip_stream);
+    if (rc != MVHMR_OK || !grad_proj) return rc;
+    return launched(launch_view_unpack(gp, grad_proj, m.table, p.B, p.V, 12 * sizeof(float), s), "view unpack");
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mvhmr_unproject_forward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_masked_ws(desc); }
+size_t mvhmr_unproject_forward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_masked_ws(desc); }
+size_t mvhmr_unproject_backward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_masked_ws(desc, false); }
+size_t mvhmr_unproject_backward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_masked_ws(desc, false); }
+size_t mvhmr_unproject_backward_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_masked_ws(desc, true); }
+size_t mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_masked_ws(desc, true); }
+size_t mvhmr_unproject_backward_geometry_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_masked_ws(desc, false); }
+size_t mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_masked_ws(desc, true); }
+
+int mvhmr_unproject_forward_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+                                   const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!view_mask) return mvhmr_unproject_forward(desc, features, proj, coords, out, workspace, workspace_bytes, hip_stream);
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
+    return forward_masked(desc, p, features, proj, coords_from_tensor(coords, p), view_mask, out, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_forward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
+                                          const float *center, const double position[3], const double sides[3], const uint8_t *view_mask,
+                                          void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!view_mask)
+        return mvhmr_unproject_forward_cuboid(desc, features, proj, rot, center, position, sides, out, workspace, workspace_bytes, hip_stream);
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    Coords cs;
+    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
+    if (rc != MVHMR_OK) return rc;
+    return forward_masked(desc, p, features, proj, cs, view_mask, out, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                    const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes,
+                                    void *hip_stream)
+{
+    if (!view_mask) return mvhmr_unproject_backward(desc, grad_out, features, proj, coords, grad_features, workspace, workspace_bytes, hip_stream);
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
+    return backward_masked(desc, p, grad_out, features, proj, coords_from_tensor(coords, p), view_mask, grad_features, workspace, workspace_bytes,
+                           hip_stream, false);
+}
+
+int mvhmr_unproject_backward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                           const float *rot, const float *center, const double position[3], const double sides[3],
+                                           const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!view_mask)
+        return mvhmr_unproject_backward_cuboid(desc, grad_out, features, proj, rot, center, position, sides, grad_features, workspace, workspace_bytes,
+                                               hip_stream);
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    Coords cs;
+    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
+    if (rc != MVHMR_OK) return rc;
+    return backward_masked(desc, p, grad_out, features, proj, cs, view_mask, grad_features, workspace, workspace_bytes, hip_stream, false);
+}
+
+int mvhmr_unproject_backward_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                  const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace,
+                                                  size_t workspace_bytes, void *hip_stream)
+{
+    if (!view_mask)
+        return mvhmr_unproject_backward_deterministic(desc, grad_out, features, proj, coords, grad_features, workspace, workspace_bytes, hip_stream);
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
+    return backward_masked(desc, p, grad_out, features, proj, coords_from_tensor(coords, p), view_mask, grad_features, workspace, workspace_bytes,
+                           hip_stream, true);
+}
+
+int mvhmr_unproject_backward_cuboid_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
+                                                         const float *proj, const float *rot, const float *center, const double position[3],
+                                                         const double sides[3], const uint8_t *view_mask, void *grad_features, void *workspace,
+                                                         size_t workspace_bytes, void *hip_stream)
+{
+    if (!view_mask)
+        return mvhmr_unproject_backward_cuboid_deterministic(desc, grad_out, features, proj, rot, center, position, sides, grad_features, workspace,
+                                                             workspace_bytes, hip_stream);
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    Coords cs;
+    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
+    if (rc != MVHMR_OK) return rc;
+    return backward_masked(desc, p, grad_out, features, proj, cs, view_mask, grad_features, workspace, workspace_bytes, hip_stream, true);
+}
+
+int mvhmr_unproject_backward_geometry_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                             const float *coords, const uint8_t *view_mask, float *grad_proj, float *grad_coords, void *workspace,
+                                             size_t workspace_bytes, void *hip_stream)
+{
+    if (!view_mask)
+        return mvhmr_unproject_backward_geometry(desc, grad_out, features, proj, coords, grad_proj, grad_coords, workspace, workspace_bytes, hip_stream);
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / coords must be non-null");
+    if (!grad_proj && !grad_coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj and grad_coords are both null: nothing to compute");
+    return geometry_masked(desc, p, grad_out, features, proj, coords, nullptr, nullptr, nullptr, nullptr, view_mask, grad_proj, grad_coords, nullptr,
+                           nullptr, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                    const float *rot, const float *center, const double position[3], const double sides[3],
+                                                    const uint8_t *view_mask, float *grad_proj, float *grad_rot, float *grad_center, void *workspace,
+                                                    size_t workspace_bytes, void *hip_stream)
+{
+    if (!view_mask)
+        return mvhmr_unproject_backward_geometry_cuboid(desc, grad_out, features, proj, rot, center, position, sides, grad_proj, grad_rot, grad_center,
+                                                        workspace, workspace_bytes, hip_stream);
+    Problem p;
+    int rc = check_desc(desc, &p);
+    if (rc != MVHMR_OK) return rc;
+    if (!rot || !center || !position || !sides) return fail(MVHMR_ERR_INVALID_ARGUMENT, "rot / center / position / sides must be non-null");
+    if (!grad_proj && !grad_rot && !grad_center)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj, grad_rot and grad_center are all null: nothing to compute");
+    return geometry_masked(desc, p, grad_out, features, proj, nullptr, rot, center, position, sides, view_mask, grad_proj, nullptr, grad_rot, grad_center,
+                           workspace, workspace_bytes, hip_stream);
 }
 
 }  // extern "C"

@@ -285,6 +285,42 @@ __device__ __forceinline__ void aggregate_grad(const float (&s)[V], float g, flo
     }
 }
 
+// Per-sample view masks: the views of a sample are packed into slots 0 .. nv - 1 (nv >= 1 here) and slots nv .. V - 1
+// are ABSENT -- no part in the aggregate.  With nv == V both forms below are the unmasked aggregate<> / aggregate_grad<> bit for bit.
+constexpr float kMaskedSample = -3.4028234663852886e38f;                   // -FLT_MAX: exp(that - m) = 0, never a maximum
+template <int METHOD, int V>
+__device__ __forceinline__ float masked_aggregate(float (&s)[V], int nv)
+{
+    if constexpr (METHOD == AGG_SUM || METHOD == AGG_MEAN) {
+        float r = s[0];
+#pragma unroll
+        for (int v = 1; v < V; ++v) r = v < nv ? __fadd_rn(r, s[v]) : r;
+        return METHOD == AGG_MEAN ? __fdiv_rn(r, (float)nv) : r;
+    } else {
+#pragma unroll
+        for (int v = 1; v < V; ++v) s[v] = v < nv ? s[v] : kMaskedSample;
+        return aggregate<METHOD, V>(s);
+    }
+}
+// the absent slots get ds = 0 exactly (their -FLT_MAX samples must not reach a product)
+template <int METHOD, int V>
+__device__ __forceinline__ void masked_aggregate_grad(float (&s)[V], float g, float (&ds)[V], int nv)
+{
+    if constexpr (METHOD == AGG_MEAN) {
+        const float gv = __fdiv_rn(g, (float)nv);
+#pragma unroll
+        for (int v = 0; v < V; ++v) ds[v] = v < nv ? gv : 0.f;
+    } else {
+        if constexpr (METHOD != AGG_SUM) {
+#pragma unroll
+            for (int v = 1; v < V; ++v) s[v] = v < nv ? s[v] : kMaskedSample;
+        }
+        aggregate_grad<METHOD, V>(s, g, ds);
+#pragma unroll
+        for (int v = 1; v < V; ++v) ds[v] = v < nv ? ds[v] : 0.f;
+    }
+}
+
 // Running form for a view count only known at run time (V > 8): one pass, same result up to rounding.
 template <int METHOD>
 struct RunningAgg {

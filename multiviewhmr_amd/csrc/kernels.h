@@ -21,6 +21,11 @@ struct Problem {
     // and returns at once otherwise.  Null = no gate.
     const int *gate_count = nullptr;
     int gate_limit = 0;
+    // View masks: per-sample count of present views (device, B ints), which the layout pass packed into view slots
+    // 0 .. n_b - 1 of every sample.  Null = every view present; the kernels that take it (gather, geometry) launch MASK instances.
+    const int *view_count = nullptr;
+    // the view-mask route (set before the table exists, for the workspace queries): the gather family with the per-tap scatter backward
+    int masked = 0;
 };
 
 inline Gate make_gate(const Problem &p, bool wants_brick) { return Gate{p.gate_count, p.gate_limit, wants_brick ? 1 : 0}; }
@@ -137,6 +142,16 @@ hipError_t launch_bwd_geom(const void *grad_out, const void *featT, const float 
 size_t pose_partial_bytes(const Problem &p);
 hipError_t launch_bwd_geom_cuboid(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
                                   float *pose_part, float *grad_rot, float *grad_center, const Problem &p, hipStream_t s);
+
+// view masks (view_mask.hip): from mask (B,V) bytes, one thread per sample writes n_b (B ints), slot -> view and view -> slot (-1: masked)
+// tables (B,V ints each) and the projections packed into slot order (absent slots zero); then per-(sample, slot) copies of `bytes_per_view`
+// bytes in and out of slot order: pack (absent slots zero-filled) and unpack (masked views zero-filled)
+size_t view_table_bytes(int B, int V);
+hipError_t launch_view_table(const uint8_t *mask, const float *proj, void *table, int B, int V, hipStream_t s);
+const int *view_table_counts(const void *table);
+const float *view_table_proj(const void *table, int B, int V);
+hipError_t launch_view_pack(const void *src, void *dst, const void *table, int B, int V, size_t bytes_per_view, hipStream_t s);
+hipError_t launch_view_unpack(const void *src, void *dst, const void *table, int B, int V, size_t bytes_per_view, hipStream_t s);
 
 hipError_t launch_build_coords(float *coords_out, const float *rot, const float *center, int B, int S,
                                const double pos[3], const double sides[3], hipStream_t s);

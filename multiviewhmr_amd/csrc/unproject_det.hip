@@ -96,6 +96,25 @@ __global__ void __launch_bounds__(256) k_det_exponent(const unsigned *__restrict
     kexp[i] = 62 - log2n - e;
 }
 
+// the same for a view-masked call: the mean's ds is g / n_b with n_b = nvs[b] present views, so the bound divides by n_b
+// (>= 1; a sample without views adds nothing) -- with every view present exactly k_det_exponent's
+__global__ void __launch_bounds__(256) k_masked_det_exponent(const unsigned *__restrict__ gmax, const unsigned *__restrict__ fmax, int *__restrict__ kexp,
+                                                             long long BC, int method, int C, int log2n, const int *__restrict__ nvs)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= BC) return;
+    const unsigned gb = gmax[i], fb = method == AGG_SOFTMAX ? fmax[i] : 0u;
+    if (gb >= 0x7f800000u || fb >= 0x7f800000u) { kexp[i] = kDetPoison; return; }
+    const int nv = nvs[i / C];
+    const double g = (double)__builtin_bit_cast(float, gb), f = (double)__builtin_bit_cast(float, fb);
+    const double bound = method == AGG_SOFTMAX ? g * (1.0 + 2.0 * f) : method == AGG_MEAN ? g / (nv > 1 ? nv : 1) : g;
+    if (bound == 0.0) { kexp[i] = 0; return; }
+    if (bound >= 3.4028234663852886e38) { kexp[i] = kDetPoison; return; }
+    int e;
+    frexp(bound, &e);
+    kexp[i] = 62 - log2n - e;
+}
+
 __device__ __forceinline__ float det_value(unsigned long long acc, int k)
 {
     if (k == kDetPoison) return __builtin_nanf("");
@@ -193,7 +212,11 @@ hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale,
         else hipLaunchKernelGGL(k_det_fmax<float>, g2, dim3(256), 0, s, (const float *)featT, fmax, p.V, p.C, p.C4, HW);
     }
     const int log2n = p.N > 1 ? 64 - __builtin_clzll((unsigned long long)(p.N - 1)) : 0;
-    hipLaunchKernelGGL(k_det_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gmax, fmax, kexp, BC, p.method, p.V, log2n);
+    if (p.view_count)
+        hipLaunchKernelGGL(k_masked_det_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gmax, fmax, kexp, BC, p.method, p.C, log2n,
+                           p.view_count);
+    else
+        hipLaunchKernelGGL(k_det_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gmax, fmax, kexp, BC, p.method, p.V, log2n);
     return hipGetLastError();
 }
 

@@ -70,13 +70,16 @@ __device__ __forceinline__ UTap uniform_rec(const TapRec &r)
 }
 
 // ------------------------------------------------------------------------------------------ forward
-template <typename TF, typename TO, int METHOD, int VT>
+// MASK (view masks): nvs[b] of the V view slots are present, packed first; the others take no part, and a sample
+// without views gets zeros.  The unmasked instances (MASK = false) are compiled exactly as before.
+template <typename TF, typename TO, int METHOD, int VT, bool MASK = false>
 __global__ void __launch_bounds__(256)
 k_fwd_gather(const TF *__restrict__ featT, const float *__restrict__ proj, const Coords coords,
-             TO *__restrict__ out, int Vrt, int C, int C4, int H, int W, long long N, int tstride, Gate gate)
+             TO *__restrict__ out, int Vrt, int C, int C4, int H, int W, long long N, int tstride, Gate gate, const int *__restrict__ nvs = nullptr)
 {
     if (gated_off(gate)) return;
     const int V = VT > 0 ? VT : Vrt;
+    const int nvb = MASK ? nvs[blockIdx.y] : V;               // present views of this sample (block-uniform)
     extern __shared__ __align__(16) unsigned char smem[];
     TapRec *recs = reinterpret_cast<TapRec *>(smem);
     f32x4 *tile = reinterpret_cast<f32x4 *>(smem + sizeof(TapRec) * kTileVox * V);
@@ -106,8 +109,8 @@ k_fwd_gather(const TF *__restrict__ featT, const float *__restrict__ proj, const
                 const UTap u = uniform_rec(recs[j * VT + v]);
                 const TF *fv = fb + v * mapsz;
                 // a sample that is identically zero (z <= 0, or all four taps outside the map) reads nothing: its dummy taps
-                // must not turn a non-finite pixel (0, 0) into 0 * Inf (wave-uniform branch)
-                if (u.w00 == 0.f && u.w01 == 0.f && u.w10 == 0.f && u.w11 == 0.f) {
+                // must not turn a non-finite pixel (0, 0) into 0 * Inf (wave-uniform branch); an absent view reads nothing either
+                if ((MASK && v >= nvb) || (u.w00 == 0.f && u.w01 == 0.f && u.w10 == 0.f && u.w11 == 0.f)) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) s[i][v] = 0.f;
                     continue;
@@ -118,12 +121,12 @@ k_fwd_gather(const TF *__restrict__ featT, const float *__restrict__ proj, const
                 for (int i = 0; i < 4; ++i) s[i][v] = bilerp(a.v[i], bb.v[i], c.v[i], d.v[i], u.w00, u.w01, u.w10, u.w11);
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) o.v[i] = aggregate<METHOD, VT>(s[i]);
+            for (int i = 0; i < 4; ++i) o.v[i] = MASK ? masked_aggregate<METHOD, VT>(s[i], nvb) : aggregate<METHOD, VT>(s[i]);
         } else {
             RunningAgg<METHOD> ra[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) ra[i].init();
-            for (int v = 0; v < V; ++v) {
+            for (int v = 0; v < nvb; ++v) {
                 const UTap u = uniform_rec(recs[j * V + v]);
                 const TF *fv = fb + v * mapsz;
                 if (u.w00 == 0.f && u.w01 == 0.f && u.w10 == 0.f && u.w11 == 0.f) {
@@ -137,8 +140,9 @@ k_fwd_gather(const TF *__restrict__ featT, const float *__restrict__ proj, const
                 for (int i = 0; i < 4; ++i) ra[i].push(bilerp(a.v[i], bb.v[i], c.v[i], d.v[i], u.w00, u.w01, u.w10, u.w11));
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) o.v[i] = ra[i].result(V);
+            for (int i = 0; i < 4; ++i) o.v[i] = ra[i].result(nvb);
         }
+        if (MASK && nvb == 0) o = f32x4{{0.f, 0.f, 0.f, 0.f}};    // a sample without views: the reference's zero volume
         if (q_active) tile[j * tstride + lane] = o;
     }
     __syncthreads();
@@ -166,14 +170,16 @@ k_fwd_gather(const TF *__restrict__ featT, const float *__restrict__ proj, const
 // ------------------------------------------------------------------------------------------ backward
 // lane <-> channels {l, l+64, l+128, l+192} of the group so that every float-atomic wave instruction
 // adds 256 contiguous bytes of the channels-last gradient row (the full-rate shape on gfx950).
-template <typename TF, typename TO, int METHOD, int VT>
+template <typename TF, typename TO, int METHOD, int VT, bool MASK = false>
 __global__ void __launch_bounds__(256)
 k_bwd_gather(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj,
              const Coords coords, float *__restrict__ gradT, int Vrt, int C, int C4, int H, int W,
-             long long N, Gate gate)
+             long long N, Gate gate, const int *__restrict__ nvs = nullptr)
 {
     if (gated_off(gate)) return;
     const int V = VT > 0 ? VT : Vrt;
+    const int nvb = MASK ? nvs[blockIdx.y] : V;               // present views (k_fwd_gather); none: nothing to scatter
+    if (MASK && nvb == 0) return;
     extern __shared__ __align__(16) unsigned char smem[];
     TapRec *recs = reinterpret_cast<TapRec *>(smem);
     float *gtile = reinterpret_cast<float *>(smem + sizeof(TapRec) * kTileVox * V);   // [256 ch][kTileVox + 1]
@@ -238,15 +244,19 @@ k_bwd_gather(const TO *__restrict__ grad_out, const TF *__restrict__ featT, cons
             float s[4][VT], ds[4][VT];
 #pragma unroll
             for (int v = 0; v < VT; ++v) {
-                float sv[4];
-                sample4(uniform_rec(recs[j * VT + v]), v, sv);
+                float sv[4] = {0.f, 0.f, 0.f, 0.f};
+                if (!MASK || v < nvb) sample4(uniform_rec(recs[j * VT + v]), v, sv);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) s[i][v] = sv[i];
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) aggregate_grad<METHOD, VT>(s[i], g[i], ds[i]);
+            for (int i = 0; i < 4; ++i) {
+                if constexpr (MASK) masked_aggregate_grad<METHOD, VT>(s[i], g[i], ds[i], nvb);
+                else aggregate_grad<METHOD, VT>(s[i], g[i], ds[i]);
+            }
 #pragma unroll
             for (int v = 0; v < VT; ++v) {
+                if (MASK && v >= nvb) continue;                             // an absent view receives nothing
                 const float dsv[4] = {ds[0][v], ds[1][v], ds[2][v], ds[3][v]};
                 scatter4(uniform_rec(recs[j * VT + v]), v, dsv);
             }
@@ -257,7 +267,7 @@ k_bwd_gather(const TO *__restrict__ grad_out, const TF *__restrict__ featT, cons
             float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
             for (int i = 0; i < 4; ++i) ra[i].init();
-            for (int v = 0; v < V; ++v) {
+            for (int v = 0; v < nvb; ++v) {
                 float sv[4];
                 sample4(uniform_rec(recs[j * V + v]), v, sv);
 #pragma unroll
@@ -266,14 +276,14 @@ k_bwd_gather(const TO *__restrict__ grad_out, const TF *__restrict__ featT, cons
                     if (sv[i] > best[i]) { best[i] = sv[i]; am[i] = v; }
                 }
             }
-            for (int v = 0; v < V; ++v) {
+            for (int v = 0; v < nvb; ++v) {
                 const UTap u = uniform_rec(recs[j * V + v]);
                 float sv[4], dsv[4];
                 sample4(u, v, sv);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     if constexpr (METHOD == AGG_SUM) dsv[i] = g[i];
-                    else if constexpr (METHOD == AGG_MEAN) dsv[i] = __fdiv_rn(g[i], (float)V);
+                    else if constexpr (METHOD == AGG_MEAN) dsv[i] = __fdiv_rn(g[i], (float)nvb);
                     else if constexpr (METHOD == AGG_MAX) dsv[i] = am[i] == v ? g[i] : 0.f;
                     else {
                         const float rden = __builtin_amdgcn_rcpf(ra[i].den);
@@ -293,14 +303,17 @@ k_bwd_gather(const TO *__restrict__ grad_out, const TF *__restrict__ featT, cons
 // llrint(ds * w * 2^K[b][c]) (det_scale.h), into an int64 channels-last accumulator with u64 atomics -- integer sums do not depend on the
 // arrival order.  A poisoned (b, c) adds nothing: the conversion pass writes NaN over its whole gradient.  (A copy, not a template flag of
 // k_bwd_gather: that kernel's instances keep the code they had.)
-template <typename TF, typename TO, int METHOD, int VT>
-__global__ void __launch_bounds__(256)
-k_bwd_gather_det(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj,
-             const Coords coords, unsigned long long *__restrict__ gradI, const int *__restrict__ kexp, int Vrt, int C, int C4, int H, int W,
-             long long N, Gate gate)
+// (the body of k_bwd_gather_det and of its masked form k_masked_bwd_gather_det, below)
+template <typename TF, typename TO, int METHOD, int VT, bool MASK>
+__device__ __forceinline__ void
+bwd_gather_det_body(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj,
+             const Coords &coords, unsigned long long *__restrict__ gradI, const int *__restrict__ kexp, int Vrt, int C, int C4, int H, int W,
+             long long N, const Gate &gate, const int *__restrict__ nvs)
 {
     if (gated_off(gate)) return;
     const int V = VT > 0 ? VT : Vrt;
+    const int nvb = MASK ? nvs[blockIdx.y] : V;               // present views (k_fwd_gather); none: nothing to scatter
+    if (MASK && nvb == 0) return;
     extern __shared__ __align__(16) unsigned char smem[];
     TapRec *recs = reinterpret_cast<TapRec *>(smem);
     float *gtile = reinterpret_cast<float *>(smem + sizeof(TapRec) * kTileVox * V);   // [256 ch][kTileVox + 1]
@@ -371,15 +384,19 @@ k_bwd_gather_det(const TO *__restrict__ grad_out, const TF *__restrict__ featT, 
             float s[4][VT], ds[4][VT];
 #pragma unroll
             for (int v = 0; v < VT; ++v) {
-                float sv[4];
-                sample4(uniform_rec(recs[j * VT + v]), v, sv);
+                float sv[4] = {0.f, 0.f, 0.f, 0.f};
+                if (!MASK || v < nvb) sample4(uniform_rec(recs[j * VT + v]), v, sv);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) s[i][v] = sv[i];
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) aggregate_grad<METHOD, VT>(s[i], g[i], ds[i]);
+            for (int i = 0; i < 4; ++i) {
+                if constexpr (MASK) masked_aggregate_grad<METHOD, VT>(s[i], g[i], ds[i], nvb);
+                else aggregate_grad<METHOD, VT>(s[i], g[i], ds[i]);
+            }
 #pragma unroll
             for (int v = 0; v < VT; ++v) {
+                if (MASK && v >= nvb) continue;                             // an absent view receives nothing
                 const float dsv[4] = {ds[0][v], ds[1][v], ds[2][v], ds[3][v]};
                 scatter4(uniform_rec(recs[j * VT + v]), v, dsv);
             }
@@ -390,7 +407,7 @@ k_bwd_gather_det(const TO *__restrict__ grad_out, const TF *__restrict__ featT, 
             float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
             for (int i = 0; i < 4; ++i) ra[i].init();
-            for (int v = 0; v < V; ++v) {
+            for (int v = 0; v < nvb; ++v) {
                 float sv[4];
                 sample4(uniform_rec(recs[j * V + v]), v, sv);
 #pragma unroll
@@ -399,14 +416,14 @@ k_bwd_gather_det(const TO *__restrict__ grad_out, const TF *__restrict__ featT, 
                     if (sv[i] > best[i]) { best[i] = sv[i]; am[i] = v; }
                 }
             }
-            for (int v = 0; v < V; ++v) {
+            for (int v = 0; v < nvb; ++v) {
                 const UTap u = uniform_rec(recs[j * V + v]);
                 float sv[4], dsv[4];
                 sample4(u, v, sv);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     if constexpr (METHOD == AGG_SUM) dsv[i] = g[i];
-                    else if constexpr (METHOD == AGG_MEAN) dsv[i] = __fdiv_rn(g[i], (float)V);
+                    else if constexpr (METHOD == AGG_MEAN) dsv[i] = __fdiv_rn(g[i], (float)nvb);
                     else if constexpr (METHOD == AGG_MAX) dsv[i] = am[i] == v ? g[i] : 0.f;
                     else {
                         const float rden = __builtin_amdgcn_rcpf(ra[i].den);
@@ -420,6 +437,25 @@ k_bwd_gather_det(const TO *__restrict__ grad_out, const TF *__restrict__ featT, 
     }
     __syncthreads();
     }
+}
+
+template <typename TF, typename TO, int METHOD, int VT>
+__global__ void __launch_bounds__(256)
+k_bwd_gather_det(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj,
+             const Coords coords, unsigned long long *__restrict__ gradI, const int *__restrict__ kexp, int Vrt, int C, int C4, int H, int W,
+             long long N, Gate gate)
+{
+    bwd_gather_det_body<TF, TO, METHOD, VT, false>(grad_out, featT, proj, coords, gradI, kexp, Vrt, C, C4, H, W, N, gate, nullptr);
+}
+
+// view masks: nvs[b] present views packed first (k_fwd_gather)
+template <typename TF, typename TO, int METHOD, int VT>
+__global__ void __launch_bounds__(256)
+k_masked_bwd_gather_det(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj,
+             const Coords coords, unsigned long long *__restrict__ gradI, const int *__restrict__ kexp, int Vrt, int C, int C4, int H, int W,
+             long long N, Gate gate, const int *__restrict__ nvs)
+{
+    bwd_gather_det_body<TF, TO, METHOD, VT, true>(grad_out, featT, proj, coords, gradI, kexp, Vrt, C, C4, H, W, N, gate, nvs);
 }
 
 // ------------------------------------------------------------------------------------------ layout passes
@@ -559,9 +595,18 @@ static hipError_t fwd_dispatch_v(const TF *featT, const float *proj, const Coord
     auto go = [&](auto kern) -> hipError_t {
         hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, featT, proj, coords, out, p.V, p.C, p.C4, p.H, p.W, p.N, tstride, make_gate(p, false));
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, featT, proj, coords, out, p.V, p.C, p.C4, p.H, p.W, p.N, tstride, make_gate(p, false),
+                           p.view_count);
         return hipGetLastError();
     };
+    if (p.view_count) {
+        switch (p.V) {
+        case 2: return go(k_fwd_gather<TF, TO, METHOD, 2, true>);
+        case 4: return go(k_fwd_gather<TF, TO, METHOD, 4, true>);
+        case 8: return go(k_fwd_gather<TF, TO, METHOD, 8, true>);
+        default: return go(k_fwd_gather<TF, TO, METHOD, 0, true>);
+        }
+    }
     switch (p.V) {
     case 2: return go(k_fwd_gather<TF, TO, METHOD, 2>);
     case 4: return go(k_fwd_gather<TF, TO, METHOD, 4>);
@@ -603,9 +648,18 @@ static hipError_t bwd_dispatch_v(const TO *go_, const TF *featT, const float *pr
     auto go = [&](auto kern) -> hipError_t {
         hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, gradT, p.V, p.C, p.C4, p.H, p.W, p.N, make_gate(p, false));
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, gradT, p.V, p.C, p.C4, p.H, p.W, p.N, make_gate(p, false),
+                           p.view_count);
         return hipGetLastError();
     };
+    if (p.view_count) {
+        switch (p.V) {
+        case 2: return go(k_bwd_gather<TF, TO, METHOD, 2, true>);
+        case 4: return go(k_bwd_gather<TF, TO, METHOD, 4, true>);
+        case 8: return go(k_bwd_gather<TF, TO, METHOD, 8, true>);
+        default: return go(k_bwd_gather<TF, TO, METHOD, 0, true>);
+        }
+    }
     switch (p.V) {
     case 2: return go(k_bwd_gather<TF, TO, METHOD, 2>);
     case 4: return go(k_bwd_gather<TF, TO, METHOD, 4>);
@@ -649,6 +703,20 @@ static hipError_t bwd_det_dispatch_v(const TO *go_, const TF *featT, const float
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, gradI, kexp, p.V, p.C, p.C4, p.H, p.W, p.N, Gate{});
         return hipGetLastError();
     };
+    auto go_masked = [&](auto kern) -> hipError_t {
+        hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, gradI, kexp, p.V, p.C, p.C4, p.H, p.W, p.N, Gate{}, p.view_count);
+        return hipGetLastError();
+    };
+    if (p.view_count) {
+        switch (p.V) {
+        case 2: return go_masked(k_masked_bwd_gather_det<TF, TO, METHOD, 2>);
+        case 4: return go_masked(k_masked_bwd_gather_det<TF, TO, METHOD, 4>);
+        case 8: return go_masked(k_masked_bwd_gather_det<TF, TO, METHOD, 8>);
+        default: return go_masked(k_masked_bwd_gather_det<TF, TO, METHOD, 0>);
+        }
+    }
     switch (p.V) {
     case 2: return go(k_bwd_gather_det<TF, TO, METHOD, 2>);
     case 4: return go(k_bwd_gather_det<TF, TO, METHOD, 4>);

@@ -154,10 +154,12 @@ size_t geo_lds_bytes(int V)
 
 }  // namespace
 
-template <typename TF, typename TO, int METHOD, int VT, bool POSE>
+// MASK: nvs[b] present views packed into the first slots (k_fwd_gather); the absent ones take no part and have dh = 0
+template <typename TF, typename TO, int METHOD, int VT, bool POSE, bool MASK = false>
 __global__ void __launch_bounds__(256)
 k_bwd_geom(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj, const Coords coords,
-           float *__restrict__ part, float *__restrict__ grad_coords, int C, int C4, int H, int W, long long N, float *__restrict__ pose_part)
+           float *__restrict__ part, float *__restrict__ grad_coords, int C, int C4, int H, int W, long long N, float *__restrict__ pose_part,
+           const int *__restrict__ nvs = nullptr)
 {
     constexpr int CPL = geo_cpl(VT);
     constexpr int kPass = kGeoGroup / (64 * CPL);
@@ -168,6 +170,7 @@ k_bwd_geom(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const 
     float *gtile = xyz + kGeoTile * 4;                                                    // [kGeoTile][kGeoLd]; phase 3: dh [kGeoTile * VT][3]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.y;
+    const int nvb = MASK ? nvs[b] : VT;
     const long long n0 = (long long)blockIdx.x * kGeoTile;
     const long long mapsz = (long long)H * W * C4;
 
@@ -216,7 +219,7 @@ k_bwd_geom(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const 
 #pragma unroll
                 for (int v = 0; v < VT; ++v) {
                     const GeoRec u = uniform_geo(recs[j * VT + v]);
-                    if (!(u.mask & 16)) {               // the view takes no part: s = 0 and no gradient (wave-uniform)
+                    if ((MASK && v >= nvb) || !(u.mask & 16)) {   // the view takes no part: s = 0 and no gradient (wave-uniform)
 #pragma unroll
                         for (int i = 0; i < CPL; ++i) s[i][v] = dx[i][v] = dy[i][v] = 0.f;
                         continue;
@@ -241,7 +244,8 @@ k_bwd_geom(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const 
 #pragma unroll
                 for (int i = 0; i < CPL; ++i) {
                     float ds[VT];
-                    aggregate_grad<METHOD, VT>(s[i], g[i], ds);
+                    if constexpr (MASK) masked_aggregate_grad<METHOD, VT>(s[i], g[i], ds, nvb > 0 ? nvb : 1);   // (none present: dx = dy = 0)
+                    else aggregate_grad<METHOD, VT>(s[i], g[i], ds);
 #pragma unroll
                     for (int v = 0; v < VT; ++v) {
                         gx[v] = act ? fmaf(ds[v], dx[i][v], gx[v]) : gx[v];
@@ -269,7 +273,7 @@ k_bwd_geom(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const 
     for (int idx = tid; idx < kGeoTile * VT; idx += blockDim.x) {
         const int j = idx / VT, v = idx - j * VT;
         float d0 = 0.f, d1 = 0.f, d2 = 0.f;
-        if (n0 + j < N && (recs[idx].mask & 16)) {
+        if (n0 + j < N && (recs[idx].mask & 16) && (!MASK || v < nvb)) {
             const float *P = proj + ((long long)b * VT + v) * 12;
             const float X0 = xyz[j * 3 + 0], X1 = xyz[j * 3 + 1], X2 = xyz[j * 3 + 2];
             const float a = __fmaf_rn(P[3], 1.f, __fmaf_rn(P[2], X2, __fmaf_rn(P[1], X1, __fmul_rn(P[0], X0))));
@@ -417,9 +421,31 @@ static hipError_t geom_dispatch_v(const TO *go_, const TF *featT, const float *p
     auto go = [&](auto kern) -> hipError_t {
         hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, part, grad_coords, p.C, p.C4, p.H, p.W, p.N, pose_part);
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, part, grad_coords, p.C, p.C4, p.H, p.W, p.N, pose_part,
+                           p.view_count);
         return hipGetLastError();
     };
+    if (p.view_count) {
+        switch (p.V) {
+        case 1: return go(k_bwd_geom<TF, TO, METHOD, 1, POSE, true>);
+        case 2: return go(k_bwd_geom<TF, TO, METHOD, 2, POSE, true>);
+        case 3: return go(k_bwd_geom<TF, TO, METHOD, 3, POSE, true>);
+        case 4: return go(k_bwd_geom<TF, TO, METHOD, 4, POSE, true>);
+        case 5: return go(k_bwd_geom<TF, TO, METHOD, 5, POSE, true>);
+        case 6: return go(k_bwd_geom<TF, TO, METHOD, 6, POSE, true>);
+        case 7: return go(k_bwd_geom<TF, TO, METHOD, 7, POSE, true>);
+        case 8: return go(k_bwd_geom<TF, TO, METHOD, 8, POSE, true>);
+        case 9: return go(k_bwd_geom<TF, TO, METHOD, 9, POSE, true>);
+        case 10: return go(k_bwd_geom<TF, TO, METHOD, 10, POSE, true>);
+        case 11: return go(k_bwd_geom<TF, TO, METHOD, 11, POSE, true>);
+        case 12: return go(k_bwd_geom<TF, TO, METHOD, 12, POSE, true>);
+        case 13: return go(k_bwd_geom<TF, TO, METHOD, 13, POSE, true>);
+        case 14: return go(k_bwd_geom<TF, TO, METHOD, 14, POSE, true>);
+        case 15: return go(k_bwd_geom<TF, TO, METHOD, 15, POSE, true>);
+        case 16: return go(k_bwd_geom<TF, TO, METHOD, 16, POSE, true>);
+        }
+        return hipErrorNotSupported;
+    }
     switch (p.V) {
     case 1: return go(k_bwd_geom<TF, TO, METHOD, 1, POSE>);
     case 2: return go(k_bwd_geom<TF, TO, METHOD, 2, POSE>);

@@ -295,11 +295,165 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(c
     return {gp, gu, gc};
 }
 
+// per-sample view masks (mvhmr_unproject_*_masked): view_mask (B, V) uint8 on the features' device, nonzero = present
+void check_mask(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &mask)
+{
+    check_tensor(mask, features, "view_mask (B, V)", at::kByte, (int64_t)d.batch * d.views);
+}
+
+at::Tensor unprojection_masked_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, const at::Tensor &mask, int64_t B,
+                                      int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
+                                      int64_t variant)
+{
+    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, &coords, nullptr, nullptr, nullptr);
+    check_mask(d, features, mask);
+    at::Tensor out = at::empty({B, C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(out_dtype)));
+    run(d, features, mvhmr_unproject_forward_masked_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_forward_masked(&d, features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(), mask.data_ptr<uint8_t>(),
+                                              out.data_ptr(), ws, n, s);
+    });
+    return out;
+}
+
+at::Tensor unprojection_masked_backward_impl(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
+                                             const at::Tensor &mask, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
+                                             int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool det)
+{
+    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
+    check_mask(d, features, mask);
+    at::Tensor grad = new_feature_grad(d, features);
+    auto launch = [&](void *ws, size_t n, hipStream_t s) {
+        return (det ? mvhmr_unproject_backward_deterministic_masked : mvhmr_unproject_backward_masked)(
+            &d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(), mask.data_ptr<uint8_t>(), grad.data_ptr(),
+            ws, n, s);
+    };
+    if (det) run_unfilled(d, features, mvhmr_unproject_backward_deterministic_masked_workspace_bytes, launch);
+    else run(d, features, mvhmr_unproject_backward_masked_workspace_bytes, launch);
+    return grad;
+}
+
+at::Tensor unprojection_masked_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
+                                               const at::Tensor &mask, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
+                                               int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    return unprojection_masked_backward_impl(grad_out, features, proj, coords, mask, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, false);
+}
+
+at::Tensor unprojection_masked_backward_deterministic_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
+                                                             const at::Tensor &coords, const at::Tensor &mask, int64_t B, int64_t V, int64_t C, int64_t H,
+                                                             int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
+                                                             int64_t variant)
+{
+    return unprojection_masked_backward_impl(grad_out, features, proj, coords, mask, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, true);
+}
+
+std::tuple<at::Tensor, at::Tensor> unprojection_masked_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features,
+                                                                                 const at::Tensor &proj, const at::Tensor &coords, const at::Tensor &mask,
+                                                                                 int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
+                                                                                 int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
+                                                                                 bool want_proj, bool want_coords)
+{
+    TORCH_CHECK(want_proj || want_coords, "mvhmr_unproject: neither gradient was asked for");
+    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
+    check_mask(d, features, mask);
+    const auto opts = features.options().dtype(at::kFloat);
+    at::Tensor gp = want_proj ? at::empty({B, V, 3, 4}, opts) : at::empty({0}, opts);
+    at::Tensor gc = want_coords ? at::empty(coords.sizes(), opts) : at::empty({0}, opts);
+    run(d, features, mvhmr_unproject_backward_geometry_masked_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_backward_geometry_masked(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
+                                                        mask.data_ptr<uint8_t>(), want_proj ? gp.data_ptr<float>() : nullptr,
+                                                        want_coords ? gc.data_ptr<float>() : nullptr, ws, n, s);
+    });
+    return {gp, gc};
+}
+
+// the cuboid recipe's masked forms (mvhmr_unproject_*_cuboid_masked)
+at::Tensor unprojection_cuboid_masked_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
+                                             const at::Tensor &mask, at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol,
+                                             int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
+                                             int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, nullptr, &rot, &center, nullptr);
+    check_mask(d, features, mask);
+    at::Tensor out = at::empty({B, C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(out_dtype)));
+    run(d, features, mvhmr_unproject_forward_cuboid_masked_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_forward_cuboid_masked(&d, features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(),
+                                                     position.data(), sides.data(), mask.data_ptr<uint8_t>(), out.data_ptr(), ws, n, s);
+    });
+    return out;
+}
+
+at::Tensor unprojection_cuboid_masked_backward_impl(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
+                                                    const at::Tensor &center, const at::Tensor &mask, at::ArrayRef<double> position,
+                                                    at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
+                                                    int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool det)
+{
+    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
+    check_mask(d, features, mask);
+    at::Tensor grad = new_feature_grad(d, features);
+    auto launch = [&](void *ws, size_t n, hipStream_t s) {
+        return (det ? mvhmr_unproject_backward_cuboid_deterministic_masked : mvhmr_unproject_backward_cuboid_masked)(
+            &d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(), position.data(),
+            sides.data(), mask.data_ptr<uint8_t>(), grad.data_ptr(), ws, n, s);
+    };
+    if (det) run_unfilled(d, features, mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes, launch);
+    else run(d, features, mvhmr_unproject_backward_cuboid_masked_workspace_bytes, launch);
+    return grad;
+}
+
+at::Tensor unprojection_cuboid_masked_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
+                                                      const at::Tensor &center, const at::Tensor &mask, at::ArrayRef<double> position,
+                                                      at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H,
+                                                      int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    return unprojection_cuboid_masked_backward_impl(grad_out, features, proj, rot, center, mask, position, sides, vol, B, V, C, H, W, method, feat_dtype,
+                                                    out_dtype, layout, variant, false);
+}
+
+at::Tensor unprojection_cuboid_masked_backward_deterministic_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
+                                                                    const at::Tensor &rot, const at::Tensor &center, const at::Tensor &mask,
+                                                                    at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol,
+                                                                    int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
+                                                                    int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+{
+    return unprojection_cuboid_masked_backward_impl(grad_out, features, proj, rot, center, mask, position, sides, vol, B, V, C, H, W, method, feat_dtype,
+                                                    out_dtype, layout, variant, true);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_masked_backward_geometry_native(
+    const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
+    const at::Tensor &mask, at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H,
+    int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center)
+{
+    TORCH_CHECK(want_proj || want_rot || want_center, "mvhmr_unproject: no gradient was asked for");
+    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
+    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
+    check_mask(d, features, mask);
+    const auto opts = features.options().dtype(at::kFloat);
+    at::Tensor gp = want_proj ? at::empty({B, V, 3, 4}, opts) : at::empty({0}, opts);
+    at::Tensor gr = want_rot ? at::empty({B, 3, 3}, opts) : at::empty({0}, opts);
+    at::Tensor gc = want_center ? at::empty({B, 3}, opts) : at::empty({0}, opts);
+    run(d, features, mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
+        return mvhmr_unproject_backward_geometry_cuboid_masked(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(),
+                                                               rot.data_ptr<float>(), center.data_ptr<float>(), position.data(), sides.data(),
+                                                               mask.data_ptr<uint8_t>(), want_proj ? gp.data_ptr<float>() : nullptr,
+                                                               want_rot ? gr.data_ptr<float>() : nullptr, want_center ? gc.data_ptr<float>() : nullptr,
+                                                               ws, n, s);
+    });
+    return {gp, gr, gc};
+}
+
 }  // namespace
 
 // the descriptor's fields after an op's tensors, and the cuboid ops' arguments
 #define MVHMR_DESC_ARGS "int B, int V, int C, int H, int W, int method, int feat_dtype, int out_dtype, int layout, int variant"
 #define MVHMR_CUBOID_ARGS "Tensor proj, Tensor rot, Tensor center, float[] position, float[] sides, int[] vol, " MVHMR_DESC_ARGS
+#define MVHMR_MASKED_CUBOID_ARGS "float[] position, float[] sides, int[] vol, " MVHMR_DESC_ARGS
 
 TORCH_LIBRARY(mvhmr_native, m)
 {
@@ -315,6 +469,19 @@ TORCH_LIBRARY(mvhmr_native, m)
           ", bool want_proj, bool want_rot, bool want_center) -> (Tensor, Tensor, Tensor)");
     m.def("triangulate_dlt(Tensor proj, Tensor points, Tensor? confidences) -> Tensor");
     m.def("triangulate_dlt_backward(Tensor grad_out, Tensor proj, Tensor points, Tensor? confidences) -> (Tensor, Tensor, Tensor)");
+    m.def("unprojection_masked(Tensor features, Tensor proj, Tensor coords, Tensor view_mask, " MVHMR_DESC_ARGS ") -> Tensor");
+    m.def("unprojection_masked_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, Tensor view_mask, " MVHMR_DESC_ARGS ") -> Tensor");
+    m.def("unprojection_masked_backward_deterministic(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, Tensor view_mask, " MVHMR_DESC_ARGS
+          ") -> Tensor");
+    m.def("unprojection_masked_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, Tensor view_mask, " MVHMR_DESC_ARGS
+          ", bool want_proj, bool want_coords) -> (Tensor, Tensor)");
+    m.def("unprojection_cuboid_masked(Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, " MVHMR_MASKED_CUBOID_ARGS ") -> Tensor");
+    m.def("unprojection_cuboid_masked_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, "
+          MVHMR_MASKED_CUBOID_ARGS ") -> Tensor");
+    m.def("unprojection_cuboid_masked_backward_deterministic(Tensor grad_out, Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, "
+          MVHMR_MASKED_CUBOID_ARGS ") -> Tensor");
+    m.def("unprojection_cuboid_masked_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, "
+          MVHMR_MASKED_CUBOID_ARGS ", bool want_proj, bool want_rot, bool want_center) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int");
 }
 
@@ -330,6 +497,14 @@ TORCH_LIBRARY_IMPL(mvhmr_native, CUDA, m)
     m.impl("unprojection_cuboid_backward_geometry", &unprojection_cuboid_backward_geometry_native);
     m.impl("triangulate_dlt", &triangulate_dlt_native);
     m.impl("triangulate_dlt_backward", &triangulate_dlt_backward_native);
+    m.impl("unprojection_masked", &unprojection_masked_native);
+    m.impl("unprojection_masked_backward", &unprojection_masked_backward_native);
+    m.impl("unprojection_masked_backward_deterministic", &unprojection_masked_backward_deterministic_native);
+    m.impl("unprojection_masked_backward_geometry", &unprojection_masked_backward_geometry_native);
+    m.impl("unprojection_cuboid_masked", &unprojection_cuboid_masked_native);
+    m.impl("unprojection_cuboid_masked_backward", &unprojection_cuboid_masked_backward_native);
+    m.impl("unprojection_cuboid_masked_backward_deterministic", &unprojection_cuboid_masked_backward_deterministic_native);
+    m.impl("unprojection_cuboid_masked_backward_geometry", &unprojection_cuboid_masked_backward_geometry_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)
