@@ -395,17 +395,20 @@ __device__ __forceinline__ void ws_compute_role(unsigned char *smem, FwdShared<V
     // request view 2, second half of the previous aggregate, fold view 1 / request view 3, fold views 2 and 3.  Barrier B sits in front of
     // the quad's first write to R.  The last job is aggregated behind the loop, then lgkmcnt(0) + barrier A of the next quad.
     // before a quad's first write to R: the memory waves must have read the previous quad's results (counter >= 64 NMW q).  The counter
-    // is requested at the head of the job and looked at here, behind sixteen tap reads: normally it has long been raised
-    // (ds_read_b32 as inline asm: through a volatile pointer hipcc makes it a FLAT load, whose wait drains every tap read in flight.
-    // LDS operations return in order, so with at most 15 younger ones outstanding -- lgkmcnt(15) -- the counter has arrived)
+    // is requested at the head of the job and looked at here, behind the tap reads of views 0 and 1: normally it has long been raised
+    // (ds_read_b32 as inline asm: through a volatile pointer hipcc makes it a FLAT load, whose wait drains every tap read in flight).
+    // hipcc does not see the inline-asm read, so the wait in front of `seen` is counted by hand: LDS operations return in order, so
+    // once at most YOUNGER operations are outstanding -- the LDS instructions the job issued behind the counter read, lgkmcnt(YOUNGER)
+    // -- the counter has arrived while those tap reads may stay in flight.  A larger count does not wait for the counter at all
+    // (lgkmcnt(15), the field's maximum, is no wait); check_asm_waits.py holds every instance to this on the assembly.
     int r_need = 0;                                                              // 64 NMW q
     auto read_r_counter = [&]() __attribute__((always_inline)) {
         int seen;
         asm volatile("ds_read_b32 %0, %1" : "=v"(seen) : "v"(kWsSyncOff) : "memory");
         return seen;
     };
-    auto wait_r_free = [&](int seen) __attribute__((always_inline)) {
-        asm volatile("s_waitcnt lgkmcnt(15)" : "+v"(seen) : : "memory");
+    auto wait_r_free = [&](int seen, auto younger) __attribute__((always_inline)) {
+        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(seen) : "n"(decltype(younger)::value) : "memory");
         while (uniform(seen) < r_need) {
             __builtin_amdgcn_s_sleep(1);
             asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(seen) : "v"(kWsSyncOff) : "memory");
@@ -423,7 +426,7 @@ __device__ __forceinline__ void ws_compute_role(unsigned char *smem, FwdShared<V
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (u > 0) {
                 agg_half(prev, std::integral_constant<int, 0>{});
-                if constexpr (u == 1) wait_r_free(seen);                         // the memory waves have read the previous quad's results
+                if constexpr (u == 1) wait_r_free(seen, std::integral_constant<int, 4 * (VT > 1 ? 2 : 1)>{});   // behind read_view 0 (and 1): 4 ds_read_b128 each
                 write_half(std::integral_constant<int, (u > 0 ? u - 1 : 0)>{}, std::integral_constant<int, 0>{});
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -459,7 +462,7 @@ __device__ __forceinline__ void ws_compute_role(unsigned char *smem, FwdShared<V
         // the quad's last job (its samples are in sq for an odd NVOX, in sp for an even one)
         auto &last = ((NVOX - 1) & 1) ? sp : sq;
         agg_half(last, std::integral_constant<int, 0>{});
-        if constexpr (NVOX == 1) wait_r_free(read_r_counter());
+        if constexpr (NVOX == 1) wait_r_free(read_r_counter(), std::integral_constant<int, 0>{});   // nothing younger: wait for the read itself
         write_half(std::integral_constant<int, NVOX - 1>{}, std::integral_constant<int, 0>{});
         agg_half(last, std::integral_constant<int, 1>{});
         write_half(std::integral_constant<int, NVOX - 1>{}, std::integral_constant<int, 1>{});
