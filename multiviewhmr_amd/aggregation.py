@@ -16,6 +16,7 @@ route of every un-projection launch, VolumeGenerator's fused conv + un-projectio
 call raises if the tensors are not on a HIP device or the library or the extension is not built.
 """
 import ctypes
+import functools
 import os
 
 import numpy as np
@@ -92,8 +93,8 @@ def _make_desc(features, coord_volumes, method, out_dtype, layout, variant):
     return d
 
 
-# The op is registered with torch.library (mvhmr::unprojection / mvhmr::unprojection_backward): eager calls dispatch to the C++ extension,
-# FakeTensor / meta calls to the shape functions, autograd to the registered formula -- so torch.compile and AOT autograd see one
+# The ops are registered with torch.library (mvhmr::unprojection / mvhmr::unprojection_backward ...): eager calls dispatch to the C++
+# extension, FakeTensor / meta calls to the shape functions, autograd to the registered formula -- so torch.compile and AOT autograd see one
 # opaque node with a known output shape and a known backward instead of a Python autograd.Function they cannot trace into.
 _DTYPES = {_capi.F32: torch.float32, _capi.F16: torch.float16, _capi.BF16: torch.bfloat16}
 _ext = None
@@ -126,61 +127,12 @@ def _native_args(features, vol, method, out_dtype, variant, layout=None):
     return read, (B, V, C, Hf, Wf, method, _dtype_code(like.dtype), out_dtype, layout, variant)
 
 
-def _op_forward(features, proj, coords, method, out_dtype, variant):
-    read, desc = _native_args(features, coords, method, out_dtype, variant)
-    return _native().unprojection(read, proj, coords, *desc)
-
-
-def _op_backward(grad_out, features, proj, coords, method, out_dtype, variant):
-    """gradient w.r.t. features (the geometry's is _op_backward_geometry)"""
-    read, desc = _native_args(features, coords, method, out_dtype, variant)
-    return _native().unprojection_backward(grad_out.contiguous(), read, proj, coords, *desc)
-
-
-def _op_backward_deterministic(grad_out, features, proj, coords, method, out_dtype, variant):
-    """_op_backward with bitwise reproducible results (mvhmr_unproject_backward_deterministic): what autograd runs under
-    torch.use_deterministic_algorithms(True)"""
-    read, desc = _native_args(features, coords, method, out_dtype, variant)
-    return _native().unprojection_backward_deterministic(grad_out.contiguous(), read, proj, coords, *desc)
-
-
-def _op_backward_geometry(grad_out, features, proj, coords, method, out_dtype, variant, want_proj=True, want_coords=True):
-    """gradients w.r.t. proj_matricies (B,V,3,4) and coord_volumes (B,X,Y,Z,3), fp32 (mvhmr_unproject_backward_geometry); an output
-    not asked for comes back empty.  Planar features go through the library's channels-last pass, channels-last ones are read as
-    they are; `variant` plays no part."""
-    features, layout = _geometry_read_layout(features)
-    read, desc = _native_args(features, coords, method, out_dtype, variant, layout)
-    return tuple(_native().unprojection_backward_geometry(grad_out.contiguous(), read, proj, coords, *desc, want_proj, want_coords))
-
-
-def _fake_forward(features, proj, coords, method, out_dtype, variant):
-    return features.new_empty((features.shape[0], features.shape[2]) + tuple(coords.shape[1:4]), dtype=_DTYPES[out_dtype])
-
-
-def _fake_backward(grad_out, features, proj, coords, method, out_dtype, variant):
-    return torch.empty_like(features)
-
-
-def _fake_backward_geometry(grad_out, features, proj, coords, method, out_dtype, variant, want_proj=True, want_coords=True):
-    return (proj.new_empty(proj.shape if want_proj else (0,), dtype=torch.float32),
-            coords.new_empty(coords.shape if want_coords else (0,), dtype=torch.float32))
-
-
-def _autograd_setup(ctx, inputs, output):
-    features, proj, coords, method, out_dtype, variant = inputs
-    ctx.save_for_backward(features, proj, coords)
-    ctx.args = (method, out_dtype, variant)
-
-
-def _autograd_backward(ctx, grad_out):
-    features, proj, coords = ctx.saved_tensors
-    op = torch.ops.mvhmr.unprojection_backward_deterministic if torch.are_deterministic_algorithms_enabled() else torch.ops.mvhmr.unprojection_backward
-    g = op(grad_out, features, proj, coords, *ctx.args) if ctx.needs_input_grad[0] else None
-    g_proj = g_coords = None
-    want_proj, want_coords = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-    if want_proj or want_coords:                       # a features-only backward launches nothing more
-        g_proj, g_coords = torch.ops.mvhmr.unprojection_backward_geometry(grad_out, features, proj, coords, *ctx.args, want_proj, want_coords)
-    return g, (g_proj if want_proj else None), (g_coords if want_coords else None), None, None, None
+def _geometry_read_layout(features):
+    """the features as the geometry backward and every masked call read them: channels-last as they are (C % 4 == 0), else a planar
+    contiguous copy"""
+    if _is_channels_last5(features) and features.shape[2] % 4 == 0:
+        return features, _capi.LAYOUT_BVHWC
+    return features.contiguous(), _capi.LAYOUT_BVCHW
 
 
 def _op_defined(name):
@@ -192,27 +144,116 @@ def _op_defined(name):
         return False
 
 
-def _register_ops():
-    if _op_defined("unprojection"):
-        return
-    sig = "(Tensor features, Tensor proj, Tensor coords, int method, int out_dtype, int variant) -> Tensor"
-    torch.library.define("mvhmr::unprojection", sig)
-    torch.library.define("mvhmr::unprojection_backward", "(Tensor grad_out, " + sig[1:])
-    torch.library.impl("mvhmr::unprojection", "CUDA")(_op_forward)
-    torch.library.impl("mvhmr::unprojection_backward", "CUDA")(_op_backward)
-    torch.library.register_fake("mvhmr::unprojection")(_fake_forward)
-    torch.library.register_fake("mvhmr::unprojection_backward")(_fake_backward)
-    torch.library.define("mvhmr::unprojection_backward_deterministic", "(Tensor grad_out, " + sig[1:])
-    torch.library.impl("mvhmr::unprojection_backward_deterministic", "CUDA")(_op_backward_deterministic)
-    torch.library.register_fake("mvhmr::unprojection_backward_deterministic")(_fake_backward)
-    torch.library.define("mvhmr::unprojection_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
-                         + ", bool want_proj=True, bool want_coords=True) -> (Tensor, Tensor)")
-    torch.library.impl("mvhmr::unprojection_backward_geometry", "CUDA")(_op_backward_geometry)
-    torch.library.register_fake("mvhmr::unprojection_backward_geometry")(_fake_backward_geometry)
-    torch.library.register_autograd("mvhmr::unprojection", _autograd_backward, setup_context=_autograd_setup)
+# The four families of un-projection ops: family -> (the tensors that place the volume, the non-tensor arguments that go with them, masked).
+# Each family is mvhmr::<family> with <family>_backward, <family>_backward_deterministic (the feature gradient, bitwise reproducible: what
+# autograd runs under torch.use_deterministic_algorithms(True)) and <family>_backward_geometry (fp32 gradients w.r.t. proj_matricies and
+# the placing tensors -- coord_volumes, or the cuboid's rotations and centers; an output not asked for comes back empty; `variant` plays
+# no part).  Arguments: features, proj, the placing tensors, view_mask (B, V) uint8 on the features' device, nonzero = present (masked
+# families), the placing arguments, then method, out_dtype, variant.  The cuboid families feed the same kernels from the cuboid recipe
+# (mvhmr_unproject_*_cuboid) instead of a coordinate tensor.  The masked families (mvhmr_unproject_*_masked) read planar or channels-last
+# features, never a quad-planar copy, and run the gather kernels with a per-sample view count.
+_CUBOID_ARGS = ("float[] position", "float[] sides", "int[] vol")
+_FAMILIES = {
+    "unprojection": (("coords",), (), False),
+    "unprojection_masked": (("coords",), (), True),
+    "unprojection_cuboid": (("rot", "center"), _CUBOID_ARGS, False),
+    "unprojection_cuboid_masked": (("rot", "center"), _CUBOID_ARGS, True),
+}
 
 
-_register_ops()
+class _Family:
+    """the implementations of one family's ops, each taking the ops' arguments positionally"""
+
+    def __init__(self, name, places, extras, masked):
+        self.name, self.masked = name, masked
+        self.native = "unprojection_cuboid" if extras else "unprojection"       # the extension's op: view_mask is a trailing argument there
+        self.tensors = ("features", "proj") + places + (("view_mask",) if masked else ())
+        self.grads = ("proj",) + places                                         # what the geometry backward differentiates
+        self.extras = extras
+        self.n_inputs = len(self.tensors) + len(extras) + 3
+
+    def schema(self):
+        return ", ".join(["Tensor " + t for t in self.tensors] + list(self.extras) + ["int method", "int out_dtype", "int variant"])
+
+    def split(self, args):
+        """-> features, (proj, *placing tensors), view_mask or None, placing arguments, (method, out_dtype, variant), want_* flags (default True)"""
+        n, k = len(self.tensors), len(self.tensors) + len(self.extras)
+        want = tuple(args[k + 3:])
+        return (args[0], tuple(args[1:1 + len(self.grads)]), args[n - 1] if self.masked else None, tuple(args[n:k]), tuple(args[k:k + 3]),
+                want + (True,) * (len(self.grads) - len(want)))
+
+    def volume(self, geo, extra):
+        return tuple(extra[2]) if extra else tuple(geo[1].shape[1:4])
+
+    def native_args(self, args, geometry=False):
+        """the extension's leading arguments (the view the library reads, proj, placing tensors and arguments, descriptor fields), view_mask"""
+        features, geo, mask, extra, (method, out_dtype, variant), _ = self.split(args)
+        layout = None
+        if self.masked or geometry:
+            features, layout = _geometry_read_layout(features)
+        read, desc = _native_args(features, self.volume(geo, extra), method, out_dtype, variant, layout)
+        return (read,) + geo + extra + desc, mask
+
+    def forward(self, *args):
+        lead, mask = self.native_args(args)
+        return getattr(_native(), self.native)(*lead, mask)
+
+    def backward(self, deterministic, grad_out, *args):
+        """gradient w.r.t. features (the geometry's is backward_geometry)"""
+        lead, mask = self.native_args(args)
+        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic)
+
+    def backward_geometry(self, grad_out, *args):
+        """planar features go through the library's channels-last pass, channels-last ones are read as they are"""
+        lead, mask = self.native_args(args, geometry=True)
+        return tuple(getattr(_native(), self.native + "_backward_geometry")(grad_out.contiguous(), *lead, *self.split(args)[5], mask))
+
+    def fake_forward(self, *args):
+        features, geo, _, extra, (_, out_dtype, _), _ = self.split(args)
+        return features.new_empty((features.shape[0], features.shape[2]) + self.volume(geo, extra), dtype=_DTYPES[out_dtype])
+
+    def fake_backward(self, grad_out, features, *args):
+        return torch.empty_like(features)
+
+    def fake_backward_geometry(self, grad_out, *args):
+        _, geo, _, _, _, want = self.split(args)
+        return tuple(t.new_empty(t.shape if w else (0,), dtype=torch.float32) for t, w in zip(geo, want))
+
+    def setup_context(self, ctx, inputs, output):
+        ctx.save_for_backward(*inputs[:len(self.tensors)])
+        ctx.args = tuple(inputs[len(self.tensors):])
+
+    def autograd(self, ctx, grad_out):
+        ops, saved = torch.ops.mvhmr, ctx.saved_tensors
+        op = getattr(ops, self.name + ("_backward_deterministic" if torch.are_deterministic_algorithms_enabled() else "_backward"))
+        g = op(grad_out, *saved, *ctx.args) if ctx.needs_input_grad[0] else None
+        want = tuple(ctx.needs_input_grad[1:1 + len(self.grads)])
+        geo = (None,) * len(want)
+        if any(want):                                      # a features-only backward launches nothing more
+            geo = getattr(ops, self.name + "_backward_geometry")(grad_out, *saved, *ctx.args, *want)
+        return (g,) + tuple(t if w else None for t, w in zip(geo, want)) + (None,) * (self.n_inputs - 1 - len(want))
+
+    def register(self):
+        if _op_defined(self.name):
+            return
+        sig, name = self.schema(), "mvhmr::" + self.name
+        wants = "".join(", bool want_%s=True" % g for g in self.grads)
+        for op, schema, impl, fake in (
+                (name, "(%s) -> Tensor" % sig, self.forward, self.fake_forward),
+                (name + "_backward", "(Tensor grad_out, %s) -> Tensor" % sig, functools.partial(self.backward, False), self.fake_backward),
+                (name + "_backward_deterministic", "(Tensor grad_out, %s) -> Tensor" % sig, functools.partial(self.backward, True), self.fake_backward),
+                (name + "_backward_geometry", "(Tensor grad_out, %s%s) -> (%s)" % (sig, wants, ", ".join(["Tensor"] * len(self.grads))),
+                 self.backward_geometry, self.fake_backward_geometry)):
+            torch.library.define(op, schema)
+            torch.library.impl(op, "CUDA")(impl)
+            torch.library.register_fake(op)(fake)
+        torch.library.register_autograd(name, self.autograd, setup_context=self.setup_context)
+
+
+_OPS = {name: _Family(name, *spec) for name, spec in _FAMILIES.items()}
+for _family in _OPS.values():
+    _family.register()
+_op_backward = functools.partial(_OPS["unprojection"].backward, False)          # (grad_out, features, proj, coords, method, out_dtype, variant)
 
 
 def _check_call(features, proj_matricies, volume, volume_shape, aggregation_method, variant, out_dtype, same_device):
@@ -286,87 +327,6 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
     return torch.ops.mvhmr.unprojection(features, proj, coords, _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
 
 
-# Per-sample view masks (mvhmr_unproject_*_masked): mvhmr::unprojection_masked and its backward ops.  view_mask (B, V) uint8 on the
-# features' device, nonzero = present.  The masked route reads planar or channels-last features (never a quad-planar copy) and runs the
-# gather kernels with a per-sample view count; the unmasked ops keep their schemas and routes.
-def _masked_args(features, coords, method, out_dtype, variant):
-    features, layout = _geometry_read_layout(features)
-    return _native_args(features, coords, method, out_dtype, variant, layout)
-
-
-def _opm_forward(features, proj, coords, view_mask, method, out_dtype, variant):
-    read, desc = _masked_args(features, coords, method, out_dtype, variant)
-    return _native().unprojection_masked(read, proj, coords, view_mask, *desc)
-
-
-def _opm_backward(grad_out, features, proj, coords, view_mask, method, out_dtype, variant):
-    read, desc = _masked_args(features, coords, method, out_dtype, variant)
-    return _native().unprojection_masked_backward(grad_out.contiguous(), read, proj, coords, view_mask, *desc)
-
-
-def _opm_backward_deterministic(grad_out, features, proj, coords, view_mask, method, out_dtype, variant):
-    read, desc = _masked_args(features, coords, method, out_dtype, variant)
-    return _native().unprojection_masked_backward_deterministic(grad_out.contiguous(), read, proj, coords, view_mask, *desc)
-
-
-def _opm_backward_geometry(grad_out, features, proj, coords, view_mask, method, out_dtype, variant, want_proj=True, want_coords=True):
-    read, desc = _masked_args(features, coords, method, out_dtype, variant)
-    return tuple(_native().unprojection_masked_backward_geometry(grad_out.contiguous(), read, proj, coords, view_mask, *desc, want_proj,
-                                                                   want_coords))
-
-
-def _fake_masked_forward(features, proj, coords, view_mask, method, out_dtype, variant):
-    return _fake_forward(features, proj, coords, method, out_dtype, variant)
-
-
-def _fake_masked_backward(grad_out, features, proj, coords, view_mask, method, out_dtype, variant):
-    return torch.empty_like(features)
-
-
-def _fake_masked_backward_geometry(grad_out, features, proj, coords, view_mask, method, out_dtype, variant, want_proj=True, want_coords=True):
-    return _fake_backward_geometry(grad_out, features, proj, coords, method, out_dtype, variant, want_proj, want_coords)
-
-
-def _opm_setup(ctx, inputs, output):
-    features, proj, coords, view_mask, method, out_dtype, variant = inputs
-    ctx.save_for_backward(features, proj, coords, view_mask)
-    ctx.args = (method, out_dtype, variant)
-
-
-def _opm_autograd(ctx, grad_out):
-    features, proj, coords, view_mask = ctx.saved_tensors
-    op = (torch.ops.mvhmr.unprojection_masked_backward_deterministic if torch.are_deterministic_algorithms_enabled()
-          else torch.ops.mvhmr.unprojection_masked_backward)
-    g = op(grad_out, features, proj, coords, view_mask, *ctx.args) if ctx.needs_input_grad[0] else None
-    g_proj = g_coords = None
-    want_proj, want_coords = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-    if want_proj or want_coords:
-        g_proj, g_coords = torch.ops.mvhmr.unprojection_masked_backward_geometry(grad_out, features, proj, coords, view_mask, *ctx.args,
-                                                                                 want_proj, want_coords)
-    return g, (g_proj if want_proj else None), (g_coords if want_coords else None), None, None, None, None
-
-
-def _register_masked_ops():
-    if _op_defined("unprojection_masked"):
-        return
-    sig = "(Tensor features, Tensor proj, Tensor coords, Tensor view_mask, int method, int out_dtype, int variant) -> Tensor"
-    torch.library.define("mvhmr::unprojection_masked", sig)
-    torch.library.impl("mvhmr::unprojection_masked", "CUDA")(_opm_forward)
-    torch.library.register_fake("mvhmr::unprojection_masked")(_fake_masked_forward)
-    for name, fn in (("unprojection_masked_backward", _opm_backward), ("unprojection_masked_backward_deterministic", _opm_backward_deterministic)):
-        torch.library.define("mvhmr::" + name, "(Tensor grad_out, " + sig[1:])
-        torch.library.impl("mvhmr::" + name, "CUDA")(fn)
-        torch.library.register_fake("mvhmr::" + name)(_fake_masked_backward)
-    torch.library.define("mvhmr::unprojection_masked_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
-                         + ", bool want_proj=True, bool want_coords=True) -> (Tensor, Tensor)")
-    torch.library.impl("mvhmr::unprojection_masked_backward_geometry", "CUDA")(_opm_backward_geometry)
-    torch.library.register_fake("mvhmr::unprojection_masked_backward_geometry")(_fake_masked_backward_geometry)
-    torch.library.register_autograd("mvhmr::unprojection_masked", _opm_autograd, setup_context=_opm_setup)
-
-
-_register_masked_ops()
-
-
 def _check_view_mask(view_mask, features):
     """view_mask (B, V) bool or an integer dtype, any device: raises TypeError / RuntimeError as _check_call does"""
     if not torch.is_tensor(view_mask):
@@ -380,159 +340,6 @@ def _check_view_mask(view_mask, features):
 def _mask_bytes(view_mask, features):
     """the checked mask as the library reads it: contiguous uint8 on features.device, nonzero = present"""
     return (view_mask != 0).to(device=features.device, dtype=torch.uint8).contiguous()
-
-
-# The same kernels fed by the cuboid recipe instead of a coordinate tensor (mvhmr_unproject_*_cuboid), registered the same way
-# (mvhmr::unprojection_cuboid / mvhmr::unprojection_cuboid_backward).
-def _opc_forward(features, proj, rot, center, position, sides, vol, method, out_dtype, variant):
-    read, desc = _native_args(features, vol, method, out_dtype, variant)
-    return _native().unprojection_cuboid(read, proj, rot, center, position, sides, vol, *desc)
-
-
-def _opc_backward(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant):
-    read, desc = _native_args(features, vol, method, out_dtype, variant)
-    return _native().unprojection_cuboid_backward(grad_out.contiguous(), read, proj, rot, center, position, sides, vol, *desc)
-
-
-def _opc_backward_deterministic(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant):
-    read, desc = _native_args(features, vol, method, out_dtype, variant)
-    return _native().unprojection_cuboid_backward_deterministic(grad_out.contiguous(), read, proj, rot, center, position, sides, vol, *desc)
-
-
-def _geometry_read_layout(features):
-    """the features as the geometry backward reads them: channels-last as they are (C % 4 == 0), else a planar contiguous copy"""
-    if _is_channels_last5(features) and features.shape[2] % 4 == 0:
-        return features, _capi.LAYOUT_BVHWC
-    return features.contiguous(), _capi.LAYOUT_BVCHW
-
-
-def _opc_backward_geometry(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant, want_proj=True,
-                           want_rot=True, want_center=True):
-    """gradients w.r.t. proj_matricies (B,V,3,4), rotations (B,3,3) and centers (B,3), fp32 (mvhmr_unproject_backward_geometry_cuboid);
-    an output not asked for comes back empty.  Layouts as _op_backward_geometry."""
-    features, layout = _geometry_read_layout(features)
-    read, desc = _native_args(features, vol, method, out_dtype, variant, layout)
-    return tuple(_native().unprojection_cuboid_backward_geometry(grad_out.contiguous(), read, proj, rot, center, position, sides, vol, *desc,
-                                                                 want_proj, want_rot, want_center))
-
-
-def _fake_backward_geometry_cuboid(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant, want_proj=True,
-                                   want_rot=True, want_center=True):
-    return tuple(t.new_empty(t.shape if want else (0,), dtype=torch.float32) for t, want in ((proj, want_proj), (rot, want_rot), (center, want_center)))
-
-
-def _opc_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:4])
-    ctx.args = tuple(inputs[4:])
-
-
-def _opc_autograd(ctx, grad_out):
-    features, proj, rot, center = ctx.saved_tensors
-    op = (torch.ops.mvhmr.unprojection_cuboid_backward_deterministic if torch.are_deterministic_algorithms_enabled()
-          else torch.ops.mvhmr.unprojection_cuboid_backward)
-    g = op(grad_out, features, proj, rot, center, *ctx.args) if ctx.needs_input_grad[0] else None
-    want = tuple(ctx.needs_input_grad[1:4])
-    geo = (None, None, None)
-    if any(want):                                      # a features-only backward launches nothing more
-        geo = torch.ops.mvhmr.unprojection_cuboid_backward_geometry(grad_out, features, proj, rot, center, *ctx.args, *want)
-    return (g,) + tuple(t if w else None for t, w in zip(geo, want)) + (None,) * 6
-
-
-def _register_cuboid_ops():
-    if _op_defined("unprojection_cuboid"):
-        return
-    sig = "(Tensor features, Tensor proj, Tensor rot, Tensor center, float[] position, float[] sides, int[] vol, int method, int out_dtype, int variant) -> Tensor"
-    torch.library.define("mvhmr::unprojection_cuboid", sig)
-    torch.library.define("mvhmr::unprojection_cuboid_backward", "(Tensor grad_out, " + sig[1:])
-    torch.library.impl("mvhmr::unprojection_cuboid", "CUDA")(_opc_forward)
-    torch.library.impl("mvhmr::unprojection_cuboid_backward", "CUDA")(_opc_backward)
-    torch.library.register_fake("mvhmr::unprojection_cuboid")(
-        lambda features, proj, rot, center, position, sides, vol, method, out_dtype, variant:
-        features.new_empty((features.shape[0], features.shape[2]) + tuple(vol), dtype=_DTYPES[out_dtype]))
-    torch.library.register_fake("mvhmr::unprojection_cuboid_backward")(
-        lambda grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant: torch.empty_like(features))
-    torch.library.define("mvhmr::unprojection_cuboid_backward_deterministic", "(Tensor grad_out, " + sig[1:])
-    torch.library.impl("mvhmr::unprojection_cuboid_backward_deterministic", "CUDA")(_opc_backward_deterministic)
-    torch.library.register_fake("mvhmr::unprojection_cuboid_backward_deterministic")(
-        lambda grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant: torch.empty_like(features))
-    torch.library.define("mvhmr::unprojection_cuboid_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
-                         + ", bool want_proj=True, bool want_rot=True, bool want_center=True) -> (Tensor, Tensor, Tensor)")
-    torch.library.impl("mvhmr::unprojection_cuboid_backward_geometry", "CUDA")(_opc_backward_geometry)
-    torch.library.register_fake("mvhmr::unprojection_cuboid_backward_geometry")(_fake_backward_geometry_cuboid)
-    torch.library.register_autograd("mvhmr::unprojection_cuboid", _opc_autograd, setup_context=_opc_setup)
-
-
-_register_cuboid_ops()
-
-
-# the cuboid recipe's masked ops (mvhmr::unprojection_cuboid_masked ...): view_mask after center, otherwise as the unmasked cuboid ops
-def _opcm_forward(features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant):
-    read, desc = _masked_args(features, vol, method, out_dtype, variant)
-    return _native().unprojection_cuboid_masked(read, proj, rot, center, view_mask, position, sides, vol, *desc)
-
-
-def _opcm_backward(grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant):
-    read, desc = _masked_args(features, vol, method, out_dtype, variant)
-    return _native().unprojection_cuboid_masked_backward(grad_out.contiguous(), read, proj, rot, center, view_mask, position, sides, vol, *desc)
-
-
-def _opcm_backward_deterministic(grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant):
-    read, desc = _masked_args(features, vol, method, out_dtype, variant)
-    return _native().unprojection_cuboid_masked_backward_deterministic(grad_out.contiguous(), read, proj, rot, center, view_mask, position, sides,
-                                                                       vol, *desc)
-
-
-def _opcm_backward_geometry(grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant, want_proj=True,
-                            want_rot=True, want_center=True):
-    read, desc = _masked_args(features, vol, method, out_dtype, variant)
-    return tuple(_native().unprojection_cuboid_masked_backward_geometry(grad_out.contiguous(), read, proj, rot, center, view_mask, position, sides,
-                                                                        vol, *desc, want_proj, want_rot, want_center))
-
-
-def _opcm_setup(ctx, inputs, output):
-    ctx.save_for_backward(*inputs[:5])
-    ctx.args = tuple(inputs[5:])
-
-
-def _opcm_autograd(ctx, grad_out):
-    features, proj, rot, center, view_mask = ctx.saved_tensors
-    op = (torch.ops.mvhmr.unprojection_cuboid_masked_backward_deterministic if torch.are_deterministic_algorithms_enabled()
-          else torch.ops.mvhmr.unprojection_cuboid_masked_backward)
-    g = op(grad_out, features, proj, rot, center, view_mask, *ctx.args) if ctx.needs_input_grad[0] else None
-    want = tuple(ctx.needs_input_grad[1:4])
-    geo = (None, None, None)
-    if any(want):
-        geo = torch.ops.mvhmr.unprojection_cuboid_masked_backward_geometry(grad_out, features, proj, rot, center, view_mask, *ctx.args, *want)
-    return (g,) + tuple(t if w else None for t, w in zip(geo, want)) + (None,) * 7
-
-
-def _register_cuboid_masked_ops():
-    if _op_defined("unprojection_cuboid_masked"):
-        return
-    sig = ("(Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, float[] position, float[] sides, int[] vol, int method, "
-           "int out_dtype, int variant) -> Tensor")
-    torch.library.define("mvhmr::unprojection_cuboid_masked", sig)
-    torch.library.impl("mvhmr::unprojection_cuboid_masked", "CUDA")(_opcm_forward)
-    torch.library.register_fake("mvhmr::unprojection_cuboid_masked")(
-        lambda features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant:
-        features.new_empty((features.shape[0], features.shape[2]) + tuple(vol), dtype=_DTYPES[out_dtype]))
-    for name, fn in (("unprojection_cuboid_masked_backward", _opcm_backward),
-                     ("unprojection_cuboid_masked_backward_deterministic", _opcm_backward_deterministic)):
-        torch.library.define("mvhmr::" + name, "(Tensor grad_out, " + sig[1:])
-        torch.library.impl("mvhmr::" + name, "CUDA")(fn)
-        torch.library.register_fake("mvhmr::" + name)(
-            lambda grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant: torch.empty_like(features))
-    torch.library.define("mvhmr::unprojection_cuboid_masked_backward_geometry", "(Tensor grad_out, " + sig[1:].replace(") -> Tensor", "")
-                         + ", bool want_proj=True, bool want_rot=True, bool want_center=True) -> (Tensor, Tensor, Tensor)")
-    torch.library.impl("mvhmr::unprojection_cuboid_masked_backward_geometry", "CUDA")(_opcm_backward_geometry)
-    torch.library.register_fake("mvhmr::unprojection_cuboid_masked_backward_geometry")(
-        lambda grad_out, features, proj, rot, center, view_mask, position, sides, vol, method, out_dtype, variant, want_proj=True, want_rot=True,
-        want_center=True: _fake_backward_geometry_cuboid(grad_out, features, proj, rot, center, position, sides, vol, method, out_dtype, variant,
-                                                         want_proj, want_rot, want_center))
-    torch.library.register_autograd("mvhmr::unprojection_cuboid_masked", _opcm_autograd, setup_context=_opcm_setup)
-
-
-_register_cuboid_masked_ops()
 
 
 # DLT triangulation (mvhmr_triangulate_dlt[_weighted] and mvhmr_triangulate_dlt_backward) as mvhmr::triangulate_dlt[_backward]: proj (B,V,3,4),
@@ -689,8 +496,7 @@ class _FusedAggregate(torch.autograd.Function):
         if not any(ctx.needs_input_grad[:3]):
             return (None, None, None) + g_geo + (None,) * 5
         det = torch.are_deterministic_algorithms_enabled()                                   # bitwise reproducible feature and wgrad kernels
-        bwd = _native().unprojection_cuboid_backward_deterministic if det else _native().unprojection_cuboid_backward
-        gy = bwd(grad_out.contiguous(), quad, proj, rot, center, *ctx.geometry, *ctx.desc).view(
+        gy = _native().unprojection_cuboid_backward(grad_out.contiguous(), quad, proj, rot, center, *ctx.geometry, *ctx.desc, None, det).view(
             B * V, Cout, Hf * Wf)                                                                # gradient w.r.t. the conv output, planar
         xf = x.view(B * V, Cin, Hf * Wf)
         if ctx.needs_input_grad[0]:

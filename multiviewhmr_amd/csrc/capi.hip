@@ -229,6 +229,563 @@ int launched(hipError_t e, const char *what)
     return fail(MVHMR_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
 }
 
+size_t max_size(size_t a, size_t b) { return a > b ? a : b; }
+
+// ---- opening a call: what places the volume is either the coordinate tensor or the cuboid recipe
+struct VolumeSource {
+    const float *coords;                        // tensor form
+    const float *rot, *center;                  // cuboid form
+    const double *position, *sides;
+    bool cuboid;
+};
+VolumeSource tensor_volume(const float *coords) { return VolumeSource{coords, nullptr, nullptr, nullptr, nullptr, false}; }
+VolumeSource cuboid_volume(const float *rot, const float *center, const double position[3], const double sides[3])
+{
+    return VolumeSource{nullptr, rot, center, position, sides, true};
+}
+
+int make_coords(const VolumeSource &v, const Problem &p, Coords *out)
+{
+    if (v.cuboid) return coords_from_cuboid(v.rot, v.center, v.position, v.sides, p, out);
+    if (!v.coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
+    *out = coords_from_tensor(v.coords, p);
+    return MVHMR_OK;
+}
+
+// the descriptor, then the volume: every forward and feature-backward entry point starts here
+int open_call(const mvhmr_unproject_desc *desc, const VolumeSource &v, Problem *p, Coords *coords)
+{
+    const int rc = check_desc(desc, p);
+    return rc != MVHMR_OK ? rc : make_coords(v, *p, coords);
+}
+
+// ---- per-sample view masks (include/mvhmr_unproject.h, DESIGN.md 5.8).  k_view_table turns the mask into slot tables and the projections
+// packed into slot order, the features are packed the same way (absent slots zero), and the unmasked route runs on the packed problem with
+// Problem::view_count set: the gather family (forward, per-tap scatter backward, its deterministic form) and the geometry kernels.  Gradients
+// are unpacked back into view order, masked views zero-filled.  A null mask is the unmasked call.
+int mask_refused(const mvhmr_unproject_desc *desc)
+{
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "a view mask needs planar or channels-last features (quad-planar copies: pass the planar features)");
+    if (desc->variant == MVHMR_VARIANT_BRICK) return fail(MVHMR_ERR_UNSUPPORTED, "a view mask runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
+    return MVHMR_OK;
+}
+// the descriptor and problem of the packed call; view_count is set once the table exists (pack_views)
+void mask_route(mvhmr_unproject_desc *desc, Problem *p)
+{
+    desc->variant = MVHMR_VARIANT_GATHER;
+    p->masked = 1;
+}
+size_t masked_view_bytes(const Problem &p) { return (size_t)p.C * p.H * p.W * feat_elem(p); }   // one view, planar or channels-last (C4 == C)
+
+// ---- workspace plans.  One plan per kind of call says which route runs and where every region of the workspace lies; it is computed
+// by one function from (descriptor, problem, deterministic, masked).  The *_workspace_bytes queries return its total, the launch
+// sequences read its offsets: no other code sizes or places a region.
+constexpr size_t kNoRegion = ~(size_t)0;
+struct Arena {                                  // regions one behind the other; every size handed in is a multiple of kAlign
+    size_t top = 0;
+    size_t take(size_t bytes) { const size_t at = top; top += bytes; return at; }
+};
+unsigned char *at(void *workspace, size_t offset) { return offset == kNoRegion ? nullptr : static_cast<unsigned char *>(workspace) + offset; }
+
+// a masked call's head: table + packed features (+ the packed gradient); the unmasked route's regions lie behind it
+struct MaskHead {
+    size_t table = kNoRegion, feat = kNoRegion, grad = kNoRegion;
+};
+MaskHead plan_mask_head(Arena &a, const Problem &p, int copies)
+{
+    MaskHead h;
+    h.table = a.take(align_up(view_table_bytes(p.B, p.V)));
+    h.feat = a.take(align_up((size_t)p.B * p.V * masked_view_bytes(p)));
+    if (copies > 1) h.grad = a.take(align_up((size_t)p.B * p.V * masked_view_bytes(p)));
+    return h;
+}
+// builds the table, packs the features; from here on the call reads the packed features and projections
+int pack_views(const MaskHead &h, const uint8_t *mask, void *workspace, const void **features, const float **proj, Problem &p, hipStream_t s)
+{
+    void *table = at(workspace, h.table);
+    int rc = launched(launch_view_table(mask, *proj, table, p.B, p.V, s), "view table");
+    if (rc != MVHMR_OK) return rc;
+    rc = launched(launch_view_pack(*features, at(workspace, h.feat), table, p.B, p.V, masked_view_bytes(p), s), "view pack");
+    if (rc != MVHMR_OK) return rc;
+    p.view_count = view_table_counts(table);
+    *features = at(workspace, h.feat);
+    *proj = view_table_proj(table, p.B, p.V);
+    return MVHMR_OK;
+}
+
+enum class Fwd { Gated, Brick, Gather };        // Gated: both variants are launched, the device-side brick count lets one run
+struct ForwardPlan {
+    mvhmr_unproject_desc desc;                  // what the kernels run on: the caller's descriptor and problem, or those of the packed call
+    Problem p;
+    Fwd route;
+    MaskHead head;
+    size_t staged = kNoRegion;                  // the converted feature copy (gated: either layout); none = the features are read as they are
+    size_t gate = kNoRegion;
+    size_t total = 0;                           // a masked call's workspace also serves the unmasked one (a null mask)
+};
+ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, bool masked)
+{
+    ForwardPlan f;
+    Arena a;
+    f.desc = *desc;
+    f.p = p;
+    if (masked) {
+        mask_route(&f.desc, &f.p);
+        f.head = plan_mask_head(a, p, 1);
+    }
+    const mvhmr_unproject_desc *d = &f.desc;
+    const bool brick = pick_variant(d, f.p) == MVHMR_VARIANT_BRICK;
+    f.route = geometry_gated(d, f.p) ? Fwd::Gated : brick ? Fwd::Brick : Fwd::Gather;
+    if (d->feat_layout == MVHMR_LAYOUT_BVHWC || d->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) {
+        // read as they are
+    } else if (f.route == Fwd::Gated) {
+        f.staged = a.take(conv_bytes(f.p));
+        f.gate = a.take(kGateBytes);
+    } else if (!brick) {
+        f.staged = a.take(featT_bytes(f.p));
+    } else if (d->feat_layout == MVHMR_LAYOUT_BVCHW) {
+        f.staged = a.take(brick_workspace_bytes(f.p));
+    }
+    f.total = masked ? max_size(a.top, plan_forward(desc, p, false).total) : a.top;
+    return f;
+}
+
+// The deterministic mode of the feature backward (include/mvhmr_unproject.h) runs the brick kernels' deterministic
+// instances where the default's rule takes the bricks (not gated: their slow path serves windows that do not fit, and no host
+// synchronisation is needed), the plane kernels where it takes those (no global atomics), else k_bwd_gather_det.  The brick and gather
+// routes run the scale pass first and a conversion pass after.
+bool det_uses_brick(const mvhmr_unproject_desc *d, const Problem &p) { return bwd_uses_brick(d, p) && brick_bwd_det_supported(p); }
+bool det_uses_plane(const mvhmr_unproject_desc *d, const Problem &p) { return !det_uses_brick(d, p) && bwd_uses_plane(d, p); }
+size_t det_acc_bytes(const Problem &p) { return align_up((size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(long long)); }
+
+enum class Bwd { GatedBrickPlane, GatedBrickGather, Brick, Plane, Scatter, DetBrick, DetGather };
+struct BackwardPlan {
+    mvhmr_unproject_desc desc;                  // as in ForwardPlan
+    Problem p;
+    Bwd route;
+    MaskHead head;
+    size_t staged = kNoRegion;                  // the converted feature copy
+    size_t acc = kNoRegion;                     // fp32 (default) or int64 (deterministic) accumulator; none = grad_features itself (Scatter)
+    size_t table = kNoRegion;                   // the plane kernels' tap table (a gated call: where the brick side's accumulator is)
+    size_t scale = kNoRegion;                   // deterministic: the scale pass's output
+    size_t gate = kNoRegion;
+    size_t total = 0;                           // deterministic: also serves the default route; masked: also the unmasked call
+};
+// the plane kernels read the quad copy: the caller's own, or one made from planar features
+void place_plane_backward(BackwardPlan &b, Arena &a)
+{
+    b.route = Bwd::Plane;
+    if (b.desc.feat_layout == MVHMR_LAYOUT_BVCHW) b.staged = a.take(brick_workspace_bytes(b.p));
+    b.table = a.take(align_up(plane_table_bytes(b.p)));
+}
+void place_default_backward(BackwardPlan &b, Arena &a)
+{
+    const mvhmr_unproject_desc *d = &b.desc;
+    const Problem &p = b.p;
+    if (geometry_gated_bwd(d, p) && bwd_uses_brick(d, p)) {
+        b.route = bwd_uses_plane(d, p) ? Bwd::GatedBrickPlane : Bwd::GatedBrickGather;
+        b.staged = a.take(conv_bytes(p));
+        b.acc = b.table = a.take(bwd_mid_bytes(d, p));
+        b.gate = a.take(kGateBytes);
+    } else if (bwd_uses_brick(d, p)) {
+        b.route = Bwd::Brick;
+        b.staged = a.take(brick_workspace_bytes(p));        // reserved for quad-planar features too, which are read as they are
+        b.acc = a.take(gradT_bytes(p));
+    } else if (bwd_uses_plane(d, p)) {
+        place_plane_backward(b, a);
+    } else {
+        b.route = Bwd::Scatter;
+        if (d->feat_layout != MVHMR_LAYOUT_BVHWC) b.staged = a.take(featT_bytes(p));
+        if (!grad_in_place(d, p)) b.acc = a.take(gradT_bytes(p));
+    }
+}
+void place_det_backward(BackwardPlan &b, Arena &a)
+{
+    const mvhmr_unproject_desc *d = &b.desc;
+    const Problem &p = b.p;
+    if (det_uses_plane(d, p)) return place_plane_backward(b, a);        // no global atomics: deterministic as it is
+    const bool brick = det_uses_brick(d, p);
+    b.route = brick ? Bwd::DetBrick : Bwd::DetGather;
+    if (d->feat_layout != (brick ? MVHMR_LAYOUT_QUAD : MVHMR_LAYOUT_BVHWC)) b.staged = a.take(brick ? brick_workspace_bytes(p) : featT_bytes(p));
+    b.acc = a.take(det_acc_bytes(p));
+    b.scale = a.take(align_up(det_scale_bytes(p)));
+}
+BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, bool det, bool masked)
+{
+    BackwardPlan b;
+    Arena a;
+    b.desc = *desc;
+    b.p = p;
+    if (masked) {
+        mask_route(&b.desc, &b.p);
+        b.head = plan_mask_head(a, p, 2);
+    }
+    if (det) {
+        BackwardPlan dflt = b;
+        Arena da = a;
+        place_default_backward(dflt, da);
+        place_det_backward(b, a);
+        a.top = max_size(a.top, da.top);
+    } else {
+        place_default_backward(b, a);
+    }
+    b.total = masked ? max_size(a.top, plan_backward(desc, p, det, false).total) : a.top;
+    return b;
+}
+
+// Gradient w.r.t. proj and coords / the pose: the channels-last feature copy k_bwd_geom reads (none for channels-last input), then the
+// fp32 partials of grad_proj and (cuboid) of the pose gradients.  desc->variant plays no part.
+struct GeometryPlan {
+    mvhmr_unproject_desc desc;                  // as in ForwardPlan
+    Problem p;
+    MaskHead head;
+    size_t packed_grad_proj = kNoRegion;        // masked: grad_proj (B,V,3,4) in slot order, unpacked at the end
+    size_t staged = kNoRegion;
+    size_t part = kNoRegion, pose_part = kNoRegion;
+    size_t total = 0;
+};
+GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, bool cuboid, bool masked)
+{
+    GeometryPlan g;
+    Arena a;
+    g.desc = *desc;
+    g.p = p;
+    if (masked) {
+        mask_route(&g.desc, &g.p);
+        g.head = plan_mask_head(a, p, 1);
+        g.packed_grad_proj = a.take(align_up((size_t)p.B * p.V * 12 * sizeof(float)));
+    }
+    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) g.staged = a.take(featT_bytes(p));
+    g.part = a.take(align_up(geom_partial_bytes(p)));
+    if (cuboid) g.pose_part = a.take(align_up(pose_partial_bytes(p)));
+    g.total = masked ? max_size(a.top, plan_geometry(desc, p, cuboid, false).total) : a.top;
+    return g;
+}
+
+// ---- the pieces every route shares
+// channels-last copy, in the feature dtype, of whatever layout came in
+int stage_channels_last(const mvhmr_unproject_desc *d, const void *features, void *dst, const Problem &p, hipStream_t s)
+{
+    return launched(d->feat_layout == MVHMR_LAYOUT_QUAD ? launch_quad_to_channels_last(features, dst, p, s) : launch_to_channels_last(features, dst, p, s),
+                    "layout pass");
+}
+int clear_gradient(void *acc, const Problem &p, size_t elem, hipStream_t s)
+{
+    return launched(hipMemsetAsync(acc, 0, (size_t)p.B * p.V * p.H * p.W * p.C4 * elem, s), "gradient clear");
+}
+// the forward gate's answer fetched to the host: both mvhmr_unproject_query_variant forms
+int query_variant(const mvhmr_unproject_desc *desc, const VolumeSource &v, const float *proj, void *hip_stream)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK) return -1;
+    const int variant = pick_variant(desc, p);
+    if (variant_conflict(desc, p, variant) != MVHMR_OK) return -1;
+    if (desc->variant != MVHMR_VARIANT_AUTO || !brick_fwd_preferred(p)) return variant;   // nothing to decide
+    Coords coords;
+    if (!proj || make_coords(v, p, &coords) != MVHMR_OK) { fail(MVHMR_ERR_INVALID_ARGUMENT, v.cuboid ? "null pointer" : "proj / coords must be non-null"); return -1; }
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    int *count = nullptr, host = 0;
+    if (hipMalloc(&count, sizeof(int)) != hipSuccess) { fail(MVHMR_ERR_LAUNCH, "query: allocation failed"); return -1; }
+    hipError_t e = hipMemsetAsync(count, 0, sizeof(int), s);
+    const GateGeom g = brick_fwd_gate_geom(p);
+    if (e == hipSuccess) e = launch_brick_gate(proj, coords, count, g, p, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&host, count, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(count);
+    if (e != hipSuccess) { fail(MVHMR_ERR_LAUNCH, "query: %s", hipGetErrorString(e)); return -1; }
+    return host <= brick_count(p, g) / 8 ? MVHMR_VARIANT_BRICK : MVHMR_VARIANT_GATHER;
+}
+
+// ---- forward
+int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *features, const float *proj, const uint8_t *mask, void *out,
+                void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    Problem p0;
+    Coords coords;
+    int rc = open_call(desc, v, &p0, &coords);
+    if (rc != MVHMR_OK) return rc;
+    if (!features || !proj || !out) return fail(MVHMR_ERR_INVALID_ARGUMENT, "features / proj / out must be non-null");
+    if (mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    mvhmr_unproject_desc dq;
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) {
+        // the quad-planar copy times log2(e): only the wave-specialised softmax forward reads it (mvhmr_preferred_layout says when)
+        if (!brick_fwd_prescales(p0) || desc->variant == MVHMR_VARIANT_GATHER)
+            return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E feeds the softmax brick forward of 3 / 4 views with an fp32 volume only "
+                                               "(ask mvhmr_preferred_layout)");
+        dq = *desc;
+        dq.feat_layout = MVHMR_LAYOUT_QUAD;
+        dq.variant = MVHMR_VARIANT_BRICK;
+        desc = &dq;
+        p0.feat_log2e = 1;
+    }
+    ForwardPlan f = plan_forward(desc, p0, mask != nullptr);
+    desc = &f.desc;
+    Problem &p = f.p;
+    rc = variant_conflict(desc, p, pick_variant(desc, p));
+    if (rc != MVHMR_OK) return rc;
+    rc = check_ws(workspace, workspace_bytes, f.total);
+    if (rc != MVHMR_OK) return rc;
+    if (mask && (rc = pack_views(f.head, mask, workspace, &features, &proj, p, s)) != MVHMR_OK) return rc;
+    // planar input whose staged copy this call makes itself: scaled by log2(e) when the kernel that reads it wants that
+    if (desc->feat_layout == MVHMR_LAYOUT_BVCHW && brick_fwd_prescales(p)) p.feat_log2e = 1;
+
+    void *staged = at(workspace, f.staged);
+    switch (f.route) {
+    case Fwd::Gated: {
+        rc = arm_gate(p, at(workspace, f.gate), proj, coords, brick_fwd_gate_geom(p), s);
+        if (rc != MVHMR_OK) return rc;
+        const bool quad = desc->feat_layout == MVHMR_LAYOUT_QUAD;
+        if (!quad) {
+            rc = launched(launch_to_quad_planar_t(features, staged, p, s), "layout pass");
+            if (rc != MVHMR_OK) return rc;
+        }
+        rc = stage_channels_last(desc, features, staged, p, s);
+        if (rc != MVHMR_OK) return rc;
+        rc = launched(launch_fwd_brick(quad ? features : staged, proj, coords, out, p, s), "brick forward");
+        if (rc != MVHMR_OK) return rc;
+        return launched(launch_fwd_gather(staged, proj, coords, out, p, s), "gather forward");
+    }
+    case Fwd::Brick:
+        if (staged) {
+            rc = launched(launch_to_quad_planar_t(features, staged, p, s), "layout pass");
+            if (rc != MVHMR_OK) return rc;
+        }
+        return launched(launch_fwd_brick(staged ? staged : features, proj, coords, out, p, s), "brick forward");
+    case Fwd::Gather:
+        if (staged) {
+            rc = stage_channels_last(desc, features, staged, p, s);
+            if (rc != MVHMR_OK) return rc;
+        }
+        return launched(launch_fwd_gather(staged ? staged : features, proj, coords, out, p, s), "gather forward");
+    }
+    return fail(MVHMR_ERR_INVALID_ARGUMENT, "unknown forward route");
+}
+
+// ---- feature backward.  The default and the deterministic form share the opening (validation, plan, view packing) and the plane
+// route; their launch sequences differ in accumulator type, scale pass and conversion pass and are kept apart.
+struct BackwardArgs {
+    const void *grad_out, *features;
+    const float *proj;
+    const Coords *coords;
+    void *grad_features, *workspace;
+    hipStream_t s;
+};
+
+// the quad copy for the plane kernels (planar input), then the kernels: no global atomics, deterministic as they are
+int launch_plane_route(const BackwardPlan &b, const BackwardArgs &c)
+{
+    void *staged = at(c.workspace, b.staged);
+    if (staged) {
+        const int rc = launched(launch_to_quad_planar_t(c.features, staged, b.p, c.s), "layout pass");
+        if (rc != MVHMR_OK) return rc;
+    }
+    return launched(launch_bwd_plane(staged ? staged : c.features, c.grad_out, c.proj, *c.coords, c.grad_features, at(c.workspace, b.table), b.p, c.s),
+                    "plane backward");
+}
+
+int launch_backward_default(BackwardPlan &b, const BackwardArgs &c)
+{
+    const mvhmr_unproject_desc *desc = &b.desc;
+    Problem &p = b.p;
+    const Coords &coords = *c.coords;
+    hipStream_t s = c.s;
+    const bool quad = desc->feat_layout == MVHMR_LAYOUT_QUAD;
+    void *staged = at(c.workspace, b.staged);
+    float *acc = reinterpret_cast<float *>(at(c.workspace, b.acc));
+    int rc;
+    switch (b.route) {
+    case Bwd::GatedBrickPlane:
+    case Bwd::GatedBrickGather:
+    case Bwd::Brick: {
+        // The brick side: the column-major quad copy (the caller's own when the features came quad-planar), LDS windows, float-atomic
+        // flush into the quad-planar `acc`, layout pass.  A gated call launches its gather side as well, and the device-side brick
+        // count lets one side run: the per-tap scatter on a channels-last copy into a channels-last `acc`, or the plane kernels, which
+        // read the quad copy too (so it is made ungated: either side needs it) and have their scratch where `acc` would be.
+        const bool scatter_side = b.route == Bwd::GatedBrickGather, plane_side = b.route == Bwd::GatedBrickPlane;
+        if (b.route != Bwd::Brick) {
+            rc = arm_gate(p, at(c.workspace, b.gate), c.proj, coords, brick_bwd_gate_geom(p), s);
+            if (rc != MVHMR_OK) return rc;
+        }
+        if (!quad) {
+            Problem pc = p;
+            if (plane_side) pc.gate_count = nullptr;
+            rc = launched(launch_to_quad_planar_t(c.features, staged, pc, s, true), "layout pass");
+            if (rc != MVHMR_OK) return rc;
+        }
+        const void *featK = quad ? c.features : staged;
+        if (scatter_side) {
+            rc = stage_channels_last(desc, c.features, staged, p, s);
+            if (rc != MVHMR_OK) return rc;
+        }
+        rc = clear_gradient(acc, p, sizeof(float), s);
+        if (rc != MVHMR_OK) return rc;
+        rc = launched(launch_bwd_brick(featK, c.grad_out, c.proj, coords, acc, p, s), "brick backward");
+        if (rc != MVHMR_OK) return rc;
+        if (scatter_side) {
+            rc = launched(launch_bwd_gather(c.grad_out, staged, c.proj, coords, acc, p, s), "gather backward");
+            if (rc != MVHMR_OK) return rc;
+        }
+        rc = launched(launch_quad_grad_to_planar(acc, c.grad_features, p, s), "gradient layout pass");
+        if (rc != MVHMR_OK || b.route == Bwd::Brick) return rc;
+        if (scatter_side) return launched(launch_grad_to_planar(acc, c.grad_features, p, s), "gradient layout pass");
+        return launched(launch_bwd_plane(featK, c.grad_out, c.proj, coords, c.grad_features, at(c.workspace, b.table), p, s), "plane backward");
+    }
+    case Bwd::Plane:
+        return launch_plane_route(b, c);
+    case Bwd::Scatter: {
+        if (staged) {
+            rc = stage_channels_last(desc, c.features, staged, p, s);
+            if (rc != MVHMR_OK) return rc;
+        }
+        float *gradT = acc ? acc : static_cast<float *>(c.grad_features);      // in place: fp32 channels-last grad_features is the accumulator
+        rc = clear_gradient(gradT, p, sizeof(float), s);
+        if (rc != MVHMR_OK) return rc;
+        rc = launched(launch_bwd_gather(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "gather backward");
+        if (rc != MVHMR_OK || !acc) return rc;
+        if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_grad_to_planar(gradT, c.grad_features, p, s), "gradient layout pass");   // planar gradient for planar and quad-planar features alike
+        return launched(launch_grad_cast(gradT, c.grad_features, p, s), "gradient cast");
+    }
+    default:
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "unknown backward route");
+    }
+}
+
+int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
+{
+    const mvhmr_unproject_desc *desc = &b.desc;
+    const Problem &p = b.p;
+    const Coords &coords = *c.coords;
+    hipStream_t s = c.s;
+    if (b.route == Bwd::Plane) return launch_plane_route(b, c);
+    const bool brick = b.route == Bwd::DetBrick;
+    if (!brick && desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p))
+        return fail(MVHMR_ERR_UNSUPPORTED, "deterministic backward from quad-planar features of this shape: needs C <= 4092 and B * V <= 65535");
+    void *staged = at(c.workspace, b.staged);
+    int rc;
+    if (staged) {
+        rc = brick ? launched(launch_to_quad_planar_t(c.features, staged, p, s, true), "layout pass") : stage_channels_last(desc, c.features, staged, p, s);
+        if (rc != MVHMR_OK) return rc;
+    }
+    const void *feat = staged ? staged : c.features;                            // quad-planar (brick) or channels-last (gather) features: as they are
+    unsigned long long *acc = reinterpret_cast<unsigned long long *>(at(c.workspace, b.acc));
+    void *scale = at(c.workspace, b.scale);
+    rc = clear_gradient(acc, p, sizeof(long long), s);
+    if (rc != MVHMR_OK) return rc;
+    rc = launched(launch_det_scale(c.grad_out, feat, scale, p, s, brick), "deterministic scale pass");
+    if (rc != MVHMR_OK) return rc;
+    const int *kexp = det_exponents(scale, p);
+    if (brick) {
+        rc = launched(launch_bwd_brick_det(feat, c.grad_out, c.proj, coords, acc, kexp, p, s), "deterministic brick backward");
+        if (rc != MVHMR_OK) return rc;
+        return launched(launch_det_quad_to_planar(acc, kexp, c.grad_features, p, s), "gradient layout pass");
+    }
+    rc = launched(launch_bwd_gather_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic gather backward");
+    if (rc != MVHMR_OK) return rc;
+    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_det_grad_to_planar(acc, kexp, c.grad_features, p, s), "gradient layout pass");
+    return launched(launch_det_grad_cast(acc, kexp, c.grad_features, p, s), "gradient cast");
+}
+
+int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
+                 const uint8_t *mask, bool det, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    Problem p0;
+    Coords coords;
+    int rc = open_call(desc, v, &p0, &coords);
+    if (rc != MVHMR_OK) return rc;
+    if (!grad_out || !features || !proj || !grad_features)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
+    if (mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p0) && !quad_to_channels_last_supported(p0))
+        return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
+    BackwardPlan b = plan_backward(desc, p0, det, mask != nullptr);
+    rc = check_ws(workspace, workspace_bytes, b.total);
+    if (rc != MVHMR_OK) return rc;
+    if (b.desc.variant == MVHMR_VARIANT_BRICK && !bwd_uses_brick(&b.desc, b.p))
+        return fail(MVHMR_ERR_UNSUPPORTED, "the brick variant does not support this shape / dtype / layout");
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (mask && (rc = pack_views(b.head, mask, workspace, &features, &proj, b.p, s)) != MVHMR_OK) return rc;
+    // a masked call's gradient comes in slot order and is unpacked into view order, masked views zero-filled
+    void *grad = mask ? at(workspace, b.head.grad) : grad_features;
+    const BackwardArgs c{grad_out, features, proj, &coords, grad, workspace, s};
+    rc = det ? launch_backward_det(b, c) : launch_backward_default(b, c);
+    if (rc != MVHMR_OK || !mask) return rc;
+    return launched(launch_view_unpack(grad, grad_features, at(workspace, b.head.table), b.p.B, b.p.V, masked_view_bytes(b.p), s), "view unpack");
+}
+
+// ---- geometry backward
+int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
+                 const uint8_t *mask, float *grad_proj, float *grad_coords, float *grad_rot, float *grad_center, void *workspace,
+                 size_t workspace_bytes, void *hip_stream)
+{
+    Problem p0;
+    Coords coords;
+    int rc = check_desc(desc, &p0);
+    if (rc != MVHMR_OK) return rc;
+    // (the order and the texts of ABI 4: an unmasked call names the data pointers first, a masked one after the geometry and the outputs)
+    const bool data = grad_out && features && proj;
+    const char *no_data = "grad_out / features / proj must be non-null", *no_tensor = "grad_out / features / proj / coords must be non-null";
+    if (!mask && !data) return fail(MVHMR_ERR_INVALID_ARGUMENT, v.cuboid ? no_data : no_tensor);
+    if (!v.cuboid && !v.coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, no_tensor);
+    rc = make_coords(v, p0, &coords);
+    if (rc != MVHMR_OK) return rc;
+    if (!v.cuboid && !grad_proj && !grad_coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj and grad_coords are both null: nothing to compute");
+    if (v.cuboid && !grad_proj && !grad_rot && !grad_center)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj, grad_rot and grad_center are all null: nothing to compute");
+    if (!data) return fail(MVHMR_ERR_INVALID_ARGUMENT, no_data);
+    if (mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p0))
+        return fail(MVHMR_ERR_UNSUPPORTED, "quad-planar features of this shape cannot be converted to channels-last (C %% 4 == 0, C <= 4092, B * V <= 65535)");
+    GeometryPlan g = plan_geometry(desc, p0, v.cuboid, mask != nullptr);
+    rc = check_ws(workspace, workspace_bytes, g.total);
+    if (rc != MVHMR_OK) return rc;
+    const Problem &p = g.p;
+    hipStream_t s = static_cast<hipStream_t>(hip_stream);
+    if (mask && (rc = pack_views(g.head, mask, workspace, &features, &proj, g.p, s)) != MVHMR_OK) return rc;
+    // a masked call's grad_proj comes in slot order behind the head and is unpacked; the other gradients are per sample
+    float *gp = mask && grad_proj ? reinterpret_cast<float *>(at(workspace, g.packed_grad_proj)) : grad_proj;
+    void *staged = at(workspace, g.staged);
+    if (staged) {
+        rc = stage_channels_last(&g.desc, features, staged, p, s);
+        if (rc != MVHMR_OK) return rc;
+    }
+    const void *featT = staged ? staged : features;
+    float *part = gp ? reinterpret_cast<float *>(at(workspace, g.part)) : nullptr;
+    if (v.cuboid) {
+        float *pose_part = (grad_rot || grad_center) ? reinterpret_cast<float *>(at(workspace, g.pose_part)) : nullptr;
+        rc = launched(launch_bwd_geom_cuboid(grad_out, featT, proj, coords, part, gp, pose_part, grad_rot, grad_center, p, s), "cuboid geometry backward");
+    } else {
+        rc = launched(launch_bwd_geom(grad_out, featT, proj, coords, part, gp, grad_coords, p, s), "geometry backward");
+    }
+    if (rc != MVHMR_OK || !mask || !grad_proj) return rc;
+    return launched(launch_view_unpack(gp, grad_proj, at(workspace, g.head.table), p.B, p.V, 12 * sizeof(float), s), "view unpack");
+}
+
+// the workspace queries: a descriptor the call would refuse outright needs none
+size_t forward_need(const mvhmr_unproject_desc *desc, bool masked)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || (masked && mask_refused(desc) != MVHMR_OK)) return 0;
+    return plan_forward(desc, p, masked).total;
+}
+size_t backward_need(const mvhmr_unproject_desc *desc, bool det, bool masked)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E || (masked && mask_refused(desc) != MVHMR_OK)) return 0;
+    return plan_backward(desc, p, det, masked).total;
+}
+size_t geometry_need(const mvhmr_unproject_desc *desc, bool cuboid, bool masked)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E || (masked && mask_refused(desc) != MVHMR_OK)) return 0;
+    return plan_geometry(desc, p, cuboid, masked).total;
+}
+
 }  // namespace
 
 extern "C" {
@@ -261,23 +818,13 @@ int mvhmr_unproject_selected_variant(const mvhmr_unproject_desc *desc)
 
 int mvhmr_unproject_query_variant(const mvhmr_unproject_desc *desc, const float *proj, const float *coords, void *hip_stream)
 {
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK) return -1;
-    const int variant = pick_variant(desc, p);
-    if (variant_conflict(desc, p, variant) != MVHMR_OK) return -1;
-    if (desc->variant != MVHMR_VARIANT_AUTO || !brick_fwd_preferred(p)) return variant;   // nothing to decide
-    if (!proj || !coords) { fail(MVHMR_ERR_INVALID_ARGUMENT, "proj / coords must be non-null"); return -1; }
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    int *count = nullptr, host = 0;
-    if (hipMalloc(&count, sizeof(int)) != hipSuccess) { fail(MVHMR_ERR_LAUNCH, "query: allocation failed"); return -1; }
-    hipError_t e = hipMemsetAsync(count, 0, sizeof(int), s);
-    const GateGeom g = brick_fwd_gate_geom(p);
-    if (e == hipSuccess) e = launch_brick_gate(proj, coords_from_tensor(coords, p), count, g, p, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&host, count, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(count);
-    if (e != hipSuccess) { fail(MVHMR_ERR_LAUNCH, "query: %s", hipGetErrorString(e)); return -1; }
-    return host <= brick_count(p, g) / 8 ? MVHMR_VARIANT_BRICK : MVHMR_VARIANT_GATHER;
+    return query_variant(desc, tensor_volume(coords), proj, hip_stream);
+}
+
+int mvhmr_unproject_query_variant_cuboid(const mvhmr_unproject_desc *desc, const float *proj, const float *rot, const float *center,
+                                         const double position[3], const double sides[3], void *hip_stream)
+{
+    return query_variant(desc, cuboid_volume(rot, center, position, sides), proj, hip_stream);
 }
 
 const char *mvhmr_unproject_forward_kernel_name(const mvhmr_unproject_desc *desc)
@@ -302,451 +849,114 @@ int mvhmr_unproject_backward_supported(const mvhmr_unproject_desc *desc)
     return 1;
 }
 
-size_t mvhmr_unproject_forward_workspace_bytes(const mvhmr_unproject_desc *desc)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK) return 0;
-    if (desc->feat_layout == MVHMR_LAYOUT_BVHWC || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
-    if (geometry_gated(desc, p)) return conv_bytes(p) + kGateBytes;   // one converted copy (either layout) + the gate counter
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD) return pick_variant(desc, p) == MVHMR_VARIANT_BRICK ? 0 : featT_bytes(p);
-    return pick_variant(desc, p) == MVHMR_VARIANT_BRICK ? brick_workspace_bytes(p) : featT_bytes(p);
-}
 
-static size_t backward_ws_bytes(const mvhmr_unproject_desc *desc, const Problem &p)
-{
-    if (geometry_gated_bwd(desc, p) && bwd_uses_brick(desc, p)) return conv_bytes(p) + bwd_mid_bytes(desc, p) + kGateBytes;
-    if (bwd_uses_brick(desc, p)) return brick_workspace_bytes(p) + gradT_bytes(p);
-    if (bwd_uses_plane(desc, p)) return (desc->feat_layout == MVHMR_LAYOUT_BVCHW ? brick_workspace_bytes(p) : 0) + align_up(plane_table_bytes(p));
-    size_t need = desc->feat_layout != MVHMR_LAYOUT_BVHWC ? featT_bytes(p) : 0;
-    if (!grad_in_place(desc, p)) need += gradT_bytes(p);
-    return need;
-}
+size_t mvhmr_unproject_forward_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, false); }
+size_t mvhmr_unproject_backward_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, false); }
+size_t mvhmr_unproject_backward_deterministic_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, false); }
+size_t mvhmr_unproject_backward_geometry_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, false); }
+size_t mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, false); }
+size_t mvhmr_unproject_forward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, true); }
+size_t mvhmr_unproject_forward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, true); }
+size_t mvhmr_unproject_backward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, true); }
+size_t mvhmr_unproject_backward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, true); }
+size_t mvhmr_unproject_backward_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, true); }
+size_t mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, true); }
+size_t mvhmr_unproject_backward_geometry_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, true); }
+size_t mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, true); }
 
-size_t mvhmr_unproject_backward_workspace_bytes(const mvhmr_unproject_desc *desc)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
-    return backward_ws_bytes(desc, p);
-}
-
-static int forward_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *features, const float *proj, const Coords &coords,
-                        void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    int rc;
-    if (!features || !proj || !out) return fail(MVHMR_ERR_INVALID_ARGUMENT, "features / proj / out must be non-null");
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    mvhmr_unproject_desc dq;
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) {
-        // the quad-planar copy times log2(e): only the wave-specialised softmax forward reads it (mvhmr_preferred_layout says when)
-        if (!brick_fwd_prescales(p) || desc->variant == MVHMR_VARIANT_GATHER)
-            return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E feeds the softmax brick forward of 3 / 4 views with an fp32 volume only "
-                                               "(ask mvhmr_preferred_layout)");
-        dq = *desc;
-        dq.feat_layout = MVHMR_LAYOUT_QUAD;
-        dq.variant = MVHMR_VARIANT_BRICK;
-        desc = &dq;
-        p.feat_log2e = 1;
-    }
-    const int variant = pick_variant(desc, p);
-    rc = variant_conflict(desc, p, variant);
-    if (rc != MVHMR_OK) return rc;
-    rc = check_ws(workspace, workspace_bytes, mvhmr_unproject_forward_workspace_bytes(desc));
-    if (rc != MVHMR_OK) return rc;
-    // planar input whose staged copy this call makes itself: scaled by log2(e) when the kernel that reads it wants that
-    if (desc->feat_layout == MVHMR_LAYOUT_BVCHW && brick_fwd_prescales(p)) p.feat_log2e = 1;
-
-    if (geometry_gated(desc, p)) {
-        // both variants are launched; the device-side brick count lets exactly one of them (and its layout pass) run
-        unsigned char *ws = static_cast<unsigned char *>(workspace);
-        rc = arm_gate(p, ws + conv_bytes(p), proj, coords, brick_fwd_gate_geom(p), s);
-        if (rc != MVHMR_OK) return rc;
-        const bool quad = desc->feat_layout == MVHMR_LAYOUT_QUAD;
-        if (!quad) {
-            rc = launched(launch_to_quad_planar_t(features, ws, p, s), "layout pass");
-            if (rc != MVHMR_OK) return rc;
-        }
-        rc = launched(quad ? launch_quad_to_channels_last(features, ws, p, s) : launch_to_channels_last(features, ws, p, s), "layout pass");
-        if (rc != MVHMR_OK) return rc;
-        rc = launched(launch_fwd_brick(quad ? features : ws, proj, coords, out, p, s), "brick forward");
-        if (rc != MVHMR_OK) return rc;
-        return launched(launch_fwd_gather(ws, proj, coords, out, p, s), "gather forward");
-    }
-
-    if (variant == MVHMR_VARIANT_BRICK) {
-        const void *featK = features;
-        if (desc->feat_layout == MVHMR_LAYOUT_BVCHW) {
-            rc = launched(launch_to_quad_planar_t(features, workspace, p, s), "layout pass");
-            if (rc != MVHMR_OK) return rc;
-            featK = workspace;
-        }
-        return launched(launch_fwd_brick(featK, proj, coords, out, p, s), "brick forward");
-    }
-
-    const void *featT = features;
-    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) {
-        rc = launched(desc->feat_layout == MVHMR_LAYOUT_QUAD ? launch_quad_to_channels_last(features, workspace, p, s)
-                                                             : launch_to_channels_last(features, workspace, p, s), "layout pass");
-        if (rc != MVHMR_OK) return rc;
-        featT = workspace;
-    }
-    return launched(launch_fwd_gather(featT, proj, coords, out, p, s), "gather forward");
-}
-
+// The launching entry points: each names what places the volume (tensor / cuboid), the mask (null: none) and, for the feature backward,
+// the mode, and forwards to the one route of its kind of call.
 int mvhmr_unproject_forward(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
                             void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
-    return forward_impl(desc, p, features, proj, coords_from_tensor(coords, p), out, workspace, workspace_bytes, hip_stream);
+    return run_forward(desc, tensor_volume(coords), features, proj, nullptr, out, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_forward_cuboid(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
                                    const float *center, const double position[3], const double sides[3], void *out, void *workspace,
                                    size_t workspace_bytes, void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    Coords cs;
-    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
-    if (rc != MVHMR_OK) return rc;
-    return forward_impl(desc, p, features, proj, cs, out, workspace, workspace_bytes, hip_stream);
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, nullptr, out, workspace, workspace_bytes, hip_stream);
 }
 
-static int backward_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj,
-                         const Coords &coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+int mvhmr_unproject_forward_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+                                   const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    int rc;
-    if (!grad_out || !features || !proj || !grad_features)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
-        return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p) && !quad_to_channels_last_supported(p))
-        return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    rc = check_ws(workspace, workspace_bytes, backward_ws_bytes(desc, p));
-    if (rc != MVHMR_OK) return rc;
+    return run_forward(desc, tensor_volume(coords), features, proj, view_mask, out, workspace, workspace_bytes, hip_stream);
+}
 
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    if (desc->variant == MVHMR_VARIANT_BRICK && !bwd_uses_brick(desc, p))
-        return fail(MVHMR_ERR_UNSUPPORTED, "the brick variant does not support this shape / dtype / layout");
-    if (geometry_gated_bwd(desc, p) && bwd_uses_brick(desc, p)) {
-        float *acc = reinterpret_cast<float *>(ws + conv_bytes(p));               // quad-planar or channels-last accumulator
-        rc = arm_gate(p, ws + conv_bytes(p) + bwd_mid_bytes(desc, p), proj, coords, brick_bwd_gate_geom(p), s);
-        if (rc != MVHMR_OK) return rc;
-        const bool quad = desc->feat_layout == MVHMR_LAYOUT_QUAD;
-        if (bwd_uses_plane(desc, p)) {
-            // both sides read the column-major quad copy (the caller's own when the features came quad-planar).  Brick side: LDS windows,
-            // float-atomic flush into `acc`, layout pass; gather side: the plane kernels, their scratch where `acc` would be
-            if (!quad) {
-                Problem pu = p;
-                pu.gate_count = nullptr;                                         // not gated: either side needs the copy
-                rc = launched(launch_to_quad_planar_t(features, ws, pu, s, true), "layout pass");
-                if (rc != MVHMR_OK) return rc;
-            }
-            const void *featK = quad ? features : ws;
-            hipError_t e = hipMemsetAsync(acc, 0, (size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(float), s);
-            if (e != hipSuccess) return launched(e, "gradient clear");
-            rc = launched(launch_bwd_brick(featK, grad_out, proj, coords, acc, p, s), "brick backward");
-            if (rc != MVHMR_OK) return rc;
-            rc = launched(launch_quad_grad_to_planar(acc, grad_features, p, s), "gradient layout pass");
-            if (rc != MVHMR_OK) return rc;
-            return launched(launch_bwd_plane(featK, grad_out, proj, coords, grad_features, acc, p, s), "plane backward");
-        }
-        // brick side: the column-major quad copy (the caller's own when the features came quad-planar); gather side: channels-last
-        if (!quad) {
-            rc = launched(launch_to_quad_planar_t(features, ws, p, s, true), "layout pass");
-            if (rc != MVHMR_OK) return rc;
-        }
-        rc = launched(quad ? launch_quad_to_channels_last(features, ws, p, s) : launch_to_channels_last(features, ws, p, s), "layout pass");
-        if (rc != MVHMR_OK) return rc;
-        hipError_t e = hipMemsetAsync(acc, 0, (size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(float), s);
-        if (e != hipSuccess) return launched(e, "gradient clear");
-        rc = launched(launch_bwd_brick(quad ? features : ws, grad_out, proj, coords, acc, p, s), "brick backward");
-        if (rc != MVHMR_OK) return rc;
-        rc = launched(launch_bwd_gather(grad_out, ws, proj, coords, acc, p, s), "gather backward");
-        if (rc != MVHMR_OK) return rc;
-        rc = launched(launch_quad_grad_to_planar(acc, grad_features, p, s), "gradient layout pass");
-        if (rc != MVHMR_OK) return rc;
-        return launched(launch_grad_to_planar(acc, grad_features, p, s), "gradient layout pass");
-    }
-    if (bwd_uses_brick(desc, p)) {
-        float *gradK = reinterpret_cast<float *>(ws + brick_workspace_bytes(p));
-        const void *featK = features;                                            // quad-planar features: the copy as it is (column-major)
-        if (desc->feat_layout != MVHMR_LAYOUT_QUAD) {
-            rc = launched(launch_to_quad_planar_t(features, ws, p, s, true), "layout pass");
-            if (rc != MVHMR_OK) return rc;
-            featK = ws;
-        }
-        hipError_t e = hipMemsetAsync(gradK, 0, (size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(float), s);
-        if (e != hipSuccess) return launched(e, "gradient clear");
-        rc = launched(launch_bwd_brick(featK, grad_out, proj, coords, gradK, p, s), "brick backward");
-        if (rc != MVHMR_OK) return rc;
-        return launched(launch_quad_grad_to_planar(gradK, grad_features, p, s), "gradient layout pass");
-    }
-    if (bwd_uses_plane(desc, p)) {
-        const void *featK = features;
-        if (desc->feat_layout == MVHMR_LAYOUT_BVCHW) {
-            rc = launched(launch_to_quad_planar_t(features, ws, p, s), "layout pass");
-            if (rc != MVHMR_OK) return rc;
-            featK = ws;
-            ws += brick_workspace_bytes(p);
-        }
-        return launched(launch_bwd_plane(featK, grad_out, proj, coords, grad_features, ws, p, s), "plane backward");
-    }
-    const void *featT = features;
-    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) {
-        rc = launched(desc->feat_layout == MVHMR_LAYOUT_QUAD ? launch_quad_to_channels_last(features, ws, p, s) : launch_to_channels_last(features, ws, p, s),
-                      "layout pass");
-        if (rc != MVHMR_OK) return rc;
-        featT = ws;
-        ws += featT_bytes(p);
-    }
-    const bool in_place = grad_in_place(desc, p);
-    float *gradT = in_place ? static_cast<float *>(grad_features) : reinterpret_cast<float *>(ws);
-    const size_t gbytes = (size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(float);
-    hipError_t e = hipMemsetAsync(gradT, 0, gbytes, s);
-    if (e != hipSuccess) return launched(e, "gradient clear");
-    rc = launched(launch_bwd_gather(grad_out, featT, proj, coords, gradT, p, s), "gather backward");
-    if (rc != MVHMR_OK || in_place) return rc;
-    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_grad_to_planar(gradT, grad_features, p, s), "gradient layout pass");   // planar gradient for planar and quad-planar features alike
-    return launched(launch_grad_cast(gradT, grad_features, p, s), "gradient cast");
+int mvhmr_unproject_forward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
+                                          const float *center, const double position[3], const double sides[3], const uint8_t *view_mask,
+                                          void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, view_mask, out, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                              const float *coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
-    return backward_impl(desc, p, grad_out, features, proj, coords_from_tensor(coords, p), grad_features, workspace, workspace_bytes, hip_stream);
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, nullptr, false, grad_features, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                                     const float *rot, const float *center, const double position[3], const double sides[3],
                                     void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    Coords cs;
-    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
-    if (rc != MVHMR_OK) return rc;
-    return backward_impl(desc, p, grad_out, features, proj, cs, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-// ---- deterministic mode of the feature-gradient backward (include/mvhmr_unproject.h).  The brick kernels' deterministic
-// instances where the default's rule takes the bricks (not gated: their slow path serves windows that do not fit, and no host
-// synchronisation is needed), the plane kernels where it takes those (no global atomics), else k_bwd_gather_det.  The brick and gather
-// routes run the scale pass first and a conversion pass after.
-static bool det_uses_brick(const mvhmr_unproject_desc *d, const Problem &p) { return bwd_uses_brick(d, p) && brick_bwd_det_supported(p); }
-static bool det_uses_plane(const mvhmr_unproject_desc *d, const Problem &p) { return !det_uses_brick(d, p) && bwd_uses_plane(d, p); }
-static size_t det_acc_bytes(const Problem &p) { return align_up((size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(long long)); }
-
-static size_t det_need_bytes(const mvhmr_unproject_desc *d, const Problem &p)
-{
-    if (det_uses_brick(d, p)) return (d->feat_layout != MVHMR_LAYOUT_QUAD ? brick_workspace_bytes(p) : 0) + det_acc_bytes(p) + align_up(det_scale_bytes(p));
-    if (det_uses_plane(d, p)) return (d->feat_layout == MVHMR_LAYOUT_BVCHW ? brick_workspace_bytes(p) : 0) + align_up(plane_table_bytes(p));
-    return (d->feat_layout != MVHMR_LAYOUT_BVHWC ? featT_bytes(p) : 0) + det_acc_bytes(p) + align_up(det_scale_bytes(p));
-}
-
-static size_t backward_det_ws_bytes(const mvhmr_unproject_desc *desc, const Problem &p);
-
-static int backward_det_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj,
-                             const Coords &coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    int rc;
-    // the default entry points' validation, in their order
-    if (!grad_out || !features || !proj || !grad_features)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
-        return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p) && !quad_to_channels_last_supported(p))
-        return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    rc = check_ws(workspace, workspace_bytes, backward_det_ws_bytes(desc, p));
-    if (rc != MVHMR_OK) return rc;
-    if (desc->variant == MVHMR_VARIANT_BRICK && !bwd_uses_brick(desc, p))
-        return fail(MVHMR_ERR_UNSUPPORTED, "the brick variant does not support this shape / dtype / layout");
-
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    if (det_uses_brick(desc, p)) {
-        const void *featK = features;                                            // quad-planar features: the copy as it is
-        if (desc->feat_layout != MVHMR_LAYOUT_QUAD) {
-            rc = launched(launch_to_quad_planar_t(features, ws, p, s, true), "layout pass");
-            if (rc != MVHMR_OK) return rc;
-            featK = ws;
-            ws += brick_workspace_bytes(p);
-        }
-        unsigned long long *acc = reinterpret_cast<unsigned long long *>(ws);
-        void *scale = ws + det_acc_bytes(p);
-        hipError_t e = hipMemsetAsync(acc, 0, (size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(long long), s);
-        if (e != hipSuccess) return launched(e, "gradient clear");
-        rc = launched(launch_det_scale(grad_out, featK, scale, p, s, true), "deterministic scale pass");
-        if (rc != MVHMR_OK) return rc;
-        const int *kexp = det_exponents(scale, p);
-        rc = launched(launch_bwd_brick_det(featK, grad_out, proj, coords, acc, kexp, p, s), "deterministic brick backward");
-        if (rc != MVHMR_OK) return rc;
-        return launched(launch_det_quad_to_planar(acc, kexp, grad_features, p, s), "gradient layout pass");
-    }
-    if (det_uses_plane(desc, p)) {
-        const void *featK = features;
-        if (desc->feat_layout == MVHMR_LAYOUT_BVCHW) {
-            rc = launched(launch_to_quad_planar_t(features, ws, p, s), "layout pass");
-            if (rc != MVHMR_OK) return rc;
-            featK = ws;
-            ws += brick_workspace_bytes(p);
-        }
-        return launched(launch_bwd_plane(featK, grad_out, proj, coords, grad_features, ws, p, s), "plane backward");
-    }
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p))
-        return fail(MVHMR_ERR_UNSUPPORTED, "deterministic backward from quad-planar features of this shape: needs C <= 4092 and B * V <= 65535");
-    const void *featT = features;
-    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) {
-        rc = launched(desc->feat_layout == MVHMR_LAYOUT_QUAD ? launch_quad_to_channels_last(features, ws, p, s) : launch_to_channels_last(features, ws, p, s),
-                      "layout pass");
-        if (rc != MVHMR_OK) return rc;
-        featT = ws;
-        ws += featT_bytes(p);
-    }
-    unsigned long long *acc = reinterpret_cast<unsigned long long *>(ws);
-    void *scale = ws + det_acc_bytes(p);
-    hipError_t e = hipMemsetAsync(acc, 0, (size_t)p.B * p.V * p.H * p.W * p.C4 * sizeof(long long), s);
-    if (e != hipSuccess) return launched(e, "gradient clear");
-    rc = launched(launch_det_scale(grad_out, featT, scale, p, s), "deterministic scale pass");
-    if (rc != MVHMR_OK) return rc;
-    const int *kexp = det_exponents(scale, p);
-    rc = launched(launch_bwd_gather_det(grad_out, featT, proj, coords, acc, kexp, p, s), "deterministic gather backward");
-    if (rc != MVHMR_OK) return rc;
-    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_det_grad_to_planar(acc, kexp, grad_features, p, s), "gradient layout pass");
-    return launched(launch_det_grad_cast(acc, kexp, grad_features, p, s), "gradient cast");
-}
-
-static size_t backward_det_ws_bytes(const mvhmr_unproject_desc *desc, const Problem &p)
-{
-    const size_t det = det_need_bytes(desc, p), dflt = backward_ws_bytes(desc, p);
-    return det > dflt ? det : dflt;
-}
-
-size_t mvhmr_unproject_backward_deterministic_workspace_bytes(const mvhmr_unproject_desc *desc)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
-    return backward_det_ws_bytes(desc, p);
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, nullptr, false, grad_features, workspace,
+                        workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                                            const float *coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
-    return backward_det_impl(desc, p, grad_out, features, proj, coords_from_tensor(coords, p), grad_features, workspace, workspace_bytes, hip_stream);
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, nullptr, true, grad_features, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_cuboid_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                                                   const float *rot, const float *center, const double position[3], const double sides[3],
                                                   void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    Coords cs;
-    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
-    if (rc != MVHMR_OK) return rc;
-    return backward_det_impl(desc, p, grad_out, features, proj, cs, grad_features, workspace, workspace_bytes, hip_stream);
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, nullptr, true, grad_features, workspace,
+                        workspace_bytes, hip_stream);
 }
 
-// Gradient w.r.t. proj and coords: the channels-last feature copy k_bwd_geom reads (none for channels-last input), then the fp32
-// partials of grad_proj.  desc->variant plays no part.
-size_t mvhmr_unproject_backward_geometry_workspace_bytes(const mvhmr_unproject_desc *desc)
+int mvhmr_unproject_backward_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                    const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes,
+                                    void *hip_stream)
 {
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
-    return (desc->feat_layout == MVHMR_LAYOUT_BVHWC ? 0 : featT_bytes(p)) + align_up(geom_partial_bytes(p));
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, view_mask, false, grad_features, workspace, workspace_bytes, hip_stream);
 }
 
-static int backward_geometry_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj,
-                                  const float *coords, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes,
-                                  void *hip_stream)
+int mvhmr_unproject_backward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                           const float *rot, const float *center, const double position[3], const double sides[3],
+                                           const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    int rc;
-    if (!grad_out || !features || !proj || !coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / coords must be non-null");
-    if (!grad_proj && !grad_coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj and grad_coords are both null: nothing to compute");
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
-        return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p))
-        return fail(MVHMR_ERR_UNSUPPORTED, "quad-planar features of this shape cannot be converted to channels-last (C %% 4 == 0, C <= 4092, B * V <= 65535)");
-    rc = check_ws(workspace, workspace_bytes, mvhmr_unproject_backward_geometry_workspace_bytes(desc));
-    if (rc != MVHMR_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    const void *featT = features;
-    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) {
-        rc = launched(desc->feat_layout == MVHMR_LAYOUT_QUAD ? launch_quad_to_channels_last(features, ws, p, s) : launch_to_channels_last(features, ws, p, s),
-                      "layout pass");
-        if (rc != MVHMR_OK) return rc;
-        featT = ws;
-        ws += featT_bytes(p);
-    }
-    return launched(launch_bwd_geom(grad_out, featT, proj, coords_from_tensor(coords, p), grad_proj ? reinterpret_cast<float *>(ws) : nullptr,
-                                    grad_proj, grad_coords, p, s),
-                    "geometry backward");
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, view_mask, false, grad_features, workspace,
+                        workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                  const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace,
+                                                  size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, view_mask, true, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
+                                                         const float *proj, const float *rot, const float *center, const double position[3],
+                                                         const double sides[3], const uint8_t *view_mask, void *grad_features, void *workspace,
+                                                         size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, view_mask, true, grad_features, workspace,
+                        workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_geometry(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                                       const float *coords, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes,
                                       void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    return backward_geometry_impl(desc, p, grad_out, features, proj, coords, grad_proj, grad_coords, workspace, workspace_bytes, hip_stream);
-}
-
-size_t mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(const mvhmr_unproject_desc *desc)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return 0;
-    return (desc->feat_layout == MVHMR_LAYOUT_BVHWC ? 0 : featT_bytes(p)) + align_up(geom_partial_bytes(p)) + align_up(pose_partial_bytes(p));
-}
-
-static int backward_geometry_cuboid_impl(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features,
-                                         const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-                                         float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
-                                         void *hip_stream)
-{
-    int rc;
-    if (!grad_out || !features || !proj) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj must be non-null");
-    Coords cs;
-    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
-    if (rc != MVHMR_OK) return rc;
-    if (!grad_proj && !grad_rot && !grad_center)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj, grad_rot and grad_center are all null: nothing to compute");
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
-        return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p))
-        return fail(MVHMR_ERR_UNSUPPORTED, "quad-planar features of this shape cannot be converted to channels-last (C %% 4 == 0, C <= 4092, B * V <= 65535)");
-    rc = check_ws(workspace, workspace_bytes, mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(desc));
-    if (rc != MVHMR_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    const void *featT = features;
-    if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) {
-        rc = launched(desc->feat_layout == MVHMR_LAYOUT_QUAD ? launch_quad_to_channels_last(features, ws, p, s) : launch_to_channels_last(features, ws, p, s),
-                      "layout pass");
-        if (rc != MVHMR_OK) return rc;
-        featT = ws;
-        ws += featT_bytes(p);
-    }
-    float *part = reinterpret_cast<float *>(ws), *pose_part = reinterpret_cast<float *>(ws + align_up(geom_partial_bytes(p)));
-    return launched(launch_bwd_geom_cuboid(grad_out, featT, proj, cs, grad_proj ? part : nullptr, grad_proj, (grad_rot || grad_center) ? pose_part : nullptr,
-                                           grad_rot, grad_center, p, s),
-                    "cuboid geometry backward");
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, nullptr, grad_proj, grad_coords, nullptr, nullptr, workspace,
+                        workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
@@ -754,11 +964,25 @@ int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, c
                                              float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
                                              void *hip_stream)
 {
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    return backward_geometry_cuboid_impl(desc, p, grad_out, features, proj, rot, center, position, sides, grad_proj, grad_rot, grad_center,
-                                         workspace, workspace_bytes, hip_stream);
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, nullptr, grad_proj, nullptr, grad_rot, grad_center,
+                        workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                             const float *coords, const uint8_t *view_mask, float *grad_proj, float *grad_coords, void *workspace,
+                                             size_t workspace_bytes, void *hip_stream)
+{
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, view_mask, grad_proj, grad_coords, nullptr, nullptr, workspace,
+                        workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                    const float *rot, const float *center, const double position[3], const double sides[3],
+                                                    const uint8_t *view_mask, float *grad_proj, float *grad_rot, float *grad_center, void *workspace,
+                                                    size_t workspace_bytes, void *hip_stream)
+{
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, view_mask, grad_proj, nullptr, grad_rot,
+                        grad_center, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)
@@ -877,29 +1101,6 @@ int mvhmr_conv1x1_wgrad_deterministic(const float *grad_y, const float *x, float
                     "deterministic 1x1 conv weight gradient");
 }
 
-int mvhmr_unproject_query_variant_cuboid(const mvhmr_unproject_desc *desc, const float *proj, const float *rot, const float *center,
-                                         const double position[3], const double sides[3], void *hip_stream)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK) return -1;
-    const int variant = pick_variant(desc, p);
-    if (variant_conflict(desc, p, variant) != MVHMR_OK) return -1;
-    if (desc->variant != MVHMR_VARIANT_AUTO || !brick_fwd_preferred(p)) return variant;
-    Coords cs;
-    if (!proj || coords_from_cuboid(rot, center, position, sides, p, &cs) != MVHMR_OK) { fail(MVHMR_ERR_INVALID_ARGUMENT, "null pointer"); return -1; }
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    int *count = nullptr, host = 0;
-    if (hipMalloc(&count, sizeof(int)) != hipSuccess) { fail(MVHMR_ERR_LAUNCH, "query: allocation failed"); return -1; }
-    hipError_t e = hipMemsetAsync(count, 0, sizeof(int), s);
-    const GateGeom g = brick_fwd_gate_geom(p);
-    if (e == hipSuccess) e = launch_brick_gate(proj, cs, count, g, p, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&host, count, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(count);
-    if (e != hipSuccess) { fail(MVHMR_ERR_LAUNCH, "query: %s", hipGetErrorString(e)); return -1; }
-    return host <= brick_count(p, g) / 8 ? MVHMR_VARIANT_BRICK : MVHMR_VARIANT_GATHER;
-}
-
 int mvhmr_triangulate_dlt(const float *proj, const float *points, float *out, int32_t batch, int32_t views, int32_t points_per_sample,
                           void *hip_stream)
 {
@@ -937,280 +1138,6 @@ int mvhmr_build_coord_volumes(float *coords, const float *rot, const float *cent
     if (batch < 1 || volume_size < 1) return fail(MVHMR_ERR_INVALID_ARGUMENT, "batch and volume_size must be >= 1");
     return launched(launch_build_coords(coords, rot, center, batch, volume_size, position, sides, static_cast<hipStream_t>(hip_stream)),
                     "coord volume build");
-}
-
-}  // extern "C"
-
-// ---- per-sample view masks (include/mvhmr_unproject.h, DESIGN.md 5.8).  k_view_table turns the mask into slot tables and the projections
-// packed into slot order, the features are packed the same way (absent slots zero), and the unmasked route runs on the packed problem with
-// Problem::view_count set: the gather family (forward, per-tap scatter backward, its deterministic form) and the geometry kernels.  Gradients
-// are unpacked back into view order, masked views zero-filled.  A null mask is the unmasked entry point.
-namespace {
-
-size_t masked_view_bytes(const Problem &p) { return (size_t)p.C * p.H * p.W * feat_elem(p); }   // one view, planar or channels-last (C4 == C)
-size_t masked_head_bytes(const Problem &p, int copies)
-{
-    return align_up(view_table_bytes(p.B, p.V)) + (size_t)copies * align_up((size_t)p.B * p.V * masked_view_bytes(p));
-}
-
-// the layouts and variants a masked call serves; *inner: the descriptor of the packed problem
-int masked_desc(const mvhmr_unproject_desc *desc, Problem &p, mvhmr_unproject_desc *inner)
-{
-    if (desc->feat_layout == MVHMR_LAYOUT_QUAD || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
-        return fail(MVHMR_ERR_UNSUPPORTED, "a view mask needs planar or channels-last features (quad-planar copies: pass the planar features)");
-    if (desc->variant == MVHMR_VARIANT_BRICK) return fail(MVHMR_ERR_UNSUPPORTED, "a view mask runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
-    *inner = *desc;
-    inner->variant = MVHMR_VARIANT_GATHER;
-    p.masked = 1;                                               // the route; view_count is set once the table exists (masked_setup)
-    return MVHMR_OK;
-}
-
-size_t max_size(size_t a, size_t b) { return a > b ? a : b; }
-
-// table + packed features (+ the packed gradient) at the head of the workspace, the unmasked route's workspace behind them
-struct MaskedWs {
-    void *table;
-    unsigned char *feat, *grad, *inner;
-    size_t inner_bytes;
-};
-int masked_setup(const Problem &p, const uint8_t *mask, const float *proj, const void *features, int copies, void *workspace, size_t workspace_bytes,
-                 size_t need, hipStream_t s, MaskedWs *m, Problem *pm)
-{
-    int rc = check_ws(workspace, workspace_bytes, need);
-    if (rc != MVHMR_OK) return rc;
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    m->table = ws;
-    m->feat = ws + align_up(view_table_bytes(p.B, p.V));
-    m->grad = copies > 1 ? m->feat + align_up((size_t)p.B * p.V * masked_view_bytes(p)) : nullptr;
-    m->inner = ws + masked_head_bytes(p, copies);
-    m->inner_bytes = workspace_bytes - masked_head_bytes(p, copies);
-    rc = launched(launch_view_table(mask, proj, m->table, p.B, p.V, s), "view table");
-    if (rc != MVHMR_OK) return rc;
-    rc = launched(launch_view_pack(features, m->feat, m->table, p.B, p.V, masked_view_bytes(p), s), "view pack");
-    if (rc != MVHMR_OK) return rc;
-    *pm = p;
-    pm->view_count = view_table_counts(m->table);
-    return MVHMR_OK;
-}
-
-size_t forward_masked_ws(const mvhmr_unproject_desc *desc)
-{
-    Problem p;
-    mvhmr_unproject_desc in;
-    if (check_desc(desc, &p) != MVHMR_OK || masked_desc(desc, p, &in) != MVHMR_OK) return 0;
-    return max_size(masked_head_bytes(p, 1) + mvhmr_unproject_forward_workspace_bytes(&in), mvhmr_unproject_forward_workspace_bytes(desc));
-}
-size_t backward_masked_ws(const mvhmr_unproject_desc *desc, bool det)
-{
-    Problem p, pu;
-    mvhmr_unproject_desc in;
-    if (check_desc(desc, &p) != MVHMR_OK) return 0;
-    pu = p;
-    if (masked_desc(desc, p, &in) != MVHMR_OK) return 0;
-    const size_t unmasked = det ? backward_det_ws_bytes(desc, pu) : backward_ws_bytes(desc, pu);
-    return max_size(masked_head_bytes(p, 2) + (det ? backward_det_ws_bytes(&in, p) : backward_ws_bytes(&in, p)), unmasked);
-}
-size_t geometry_masked_ws(const mvhmr_unproject_desc *desc, bool cuboid)
-{
-    Problem p;
-    mvhmr_unproject_desc in;
-    if (check_desc(desc, &p) != MVHMR_OK || masked_desc(desc, p, &in) != MVHMR_OK) return 0;
-    const size_t inner = cuboid ? mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(&in) : mvhmr_unproject_backward_geometry_workspace_bytes(&in);
-    const size_t unmasked = cuboid ? mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(desc) : mvhmr_unproject_backward_geometry_workspace_bytes(desc);
-    return max_size(masked_head_bytes(p, 1) + align_up((size_t)p.B * p.V * 12 * sizeof(float)) + inner, unmasked);
-}
-
-int forward_masked(const mvhmr_unproject_desc *desc, Problem &p, const void *features, const float *proj, const Coords &coords, const uint8_t *mask,
-                   void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    mvhmr_unproject_desc in;
-    if (!features || !proj || !out) return fail(MVHMR_ERR_INVALID_ARGUMENT, "features / proj / out must be non-null");
-    int rc = masked_desc(desc, p, &in);
-    if (rc != MVHMR_OK) return rc;
-    MaskedWs m;
-    Problem pm;
-    rc = masked_setup(p, mask, proj, features, 1, workspace, workspace_bytes, forward_masked_ws(desc), static_cast<hipStream_t>(hip_stream), &m, &pm);
-    if (rc != MVHMR_OK) return rc;
-    return forward_impl(&in, pm, m.feat, view_table_proj(m.table, p.B, p.V), coords, out, m.inner, m.inner_bytes, hip_stream);
-}
-
-int backward_masked(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj, const Coords &coords,
-                    const uint8_t *mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream, bool det)
-{
-    mvhmr_unproject_desc in;
-    if (!grad_out || !features || !proj || !grad_features)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
-    int rc = masked_desc(desc, p, &in);
-    if (rc != MVHMR_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    MaskedWs m;
-    Problem pm;
-    rc = masked_setup(p, mask, proj, features, 2, workspace, workspace_bytes, backward_masked_ws(desc, det), s, &m, &pm);
-    if (rc != MVHMR_OK) return rc;
-    const float *pp = view_table_proj(m.table, p.B, p.V);
-    rc = det ? backward_det_impl(&in, pm, grad_out, m.feat, pp, coords, m.grad, m.inner, m.inner_bytes, hip_stream)
-             : backward_impl(&in, pm, grad_out, m.feat, pp, coords, m.grad, m.inner, m.inner_bytes, hip_stream);
-    if (rc != MVHMR_OK) return rc;
-    return launched(launch_view_unpack(m.grad, grad_features, m.table, p.B, p.V, masked_view_bytes(p), s), "view unpack");
-}
-
-// geometry: grad_proj comes packed (B,V,3,4) behind the head and is unpacked; grad_coords / grad_rot / grad_center are per sample
-int geometry_masked(const mvhmr_unproject_desc *desc, Problem &p, const void *grad_out, const void *features, const float *proj, const float *coords,
-                    const float *rot, const float *center, const double position[3], const double sides[3], const uint8_t *mask, float *grad_proj,
-                    float *grad_coords, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    mvhmr_unproject_desc in;
-    const bool cuboid = !coords;
-    if (!grad_out || !features || !proj) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj must be non-null");
-    if (cuboid && (!rot || !center || !position || !sides)) return fail(MVHMR_ERR_INVALID_ARGUMENT, "rot / center / position / sides must be non-null");
-    if (!grad_proj && !grad_coords && !grad_rot && !grad_center) return fail(MVHMR_ERR_INVALID_ARGUMENT, "every gradient output is null: nothing to compute");
-    int rc = masked_desc(desc, p, &in);
-    if (rc != MVHMR_OK) return rc;
-    hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    MaskedWs m;
-    Problem pm;
-    rc = masked_setup(p, mask, proj, features, 1, workspace, workspace_bytes, geometry_masked_ws(desc, cuboid), s, &m, &pm);
-    if (rc != MVHMR_OK) return rc;
-    float *gp = grad_proj ? reinterpret_cast<float *>(m.inner) : nullptr;
-    const size_t gpb = align_up((size_t)p.B * p.V * 12 * sizeof(float));
-    const float *pp = view_table_proj(m.table, p.B, p.V);
-    rc = cuboid ? backward_geometry_cuboid_impl(&in, pm, grad_out, m.feat, pp, rot, center, position, sides, gp, grad_rot, grad_center, m.inner + gpb,
-                                                m.inner_bytes - gpb, hip_stream)
-                : backward_geometry_impl(&in, pm, grad_out, m.feat, pp, coords, gp, grad_coords, m.inner + gpb, m.inner_bytes - gpb, hip_stream);
-    if (rc != MVHMR_OK || !grad_proj) return rc;
-    return launched(launch_view_unpack(gp, grad_proj, m.table, p.B, p.V, 12 * sizeof(float), s), "view unpack");
-}
-
-}  // namespace
-
-extern "C" {
-
-size_t mvhmr_unproject_forward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_masked_ws(desc); }
-size_t mvhmr_unproject_forward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_masked_ws(desc); }
-size_t mvhmr_unproject_backward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_masked_ws(desc, false); }
-size_t mvhmr_unproject_backward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_masked_ws(desc, false); }
-size_t mvhmr_unproject_backward_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_masked_ws(desc, true); }
-size_t mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_masked_ws(desc, true); }
-size_t mvhmr_unproject_backward_geometry_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_masked_ws(desc, false); }
-size_t mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_masked_ws(desc, true); }
-
-int mvhmr_unproject_forward_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
-                                   const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    if (!view_mask) return mvhmr_unproject_forward(desc, features, proj, coords, out, workspace, workspace_bytes, hip_stream);
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
-    return forward_masked(desc, p, features, proj, coords_from_tensor(coords, p), view_mask, out, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_forward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
-                                          const float *center, const double position[3], const double sides[3], const uint8_t *view_mask,
-                                          void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    if (!view_mask)
-        return mvhmr_unproject_forward_cuboid(desc, features, proj, rot, center, position, sides, out, workspace, workspace_bytes, hip_stream);
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    Coords cs;
-    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
-    if (rc != MVHMR_OK) return rc;
-    return forward_masked(desc, p, features, proj, cs, view_mask, out, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                    const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes,
-                                    void *hip_stream)
-{
-    if (!view_mask) return mvhmr_unproject_backward(desc, grad_out, features, proj, coords, grad_features, workspace, workspace_bytes, hip_stream);
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
-    return backward_masked(desc, p, grad_out, features, proj, coords_from_tensor(coords, p), view_mask, grad_features, workspace, workspace_bytes,
-                           hip_stream, false);
-}
-
-int mvhmr_unproject_backward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                           const float *rot, const float *center, const double position[3], const double sides[3],
-                                           const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    if (!view_mask)
-        return mvhmr_unproject_backward_cuboid(desc, grad_out, features, proj, rot, center, position, sides, grad_features, workspace, workspace_bytes,
-                                               hip_stream);
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    Coords cs;
-    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
-    if (rc != MVHMR_OK) return rc;
-    return backward_masked(desc, p, grad_out, features, proj, cs, view_mask, grad_features, workspace, workspace_bytes, hip_stream, false);
-}
-
-int mvhmr_unproject_backward_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                                  const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace,
-                                                  size_t workspace_bytes, void *hip_stream)
-{
-    if (!view_mask)
-        return mvhmr_unproject_backward_deterministic(desc, grad_out, features, proj, coords, grad_features, workspace, workspace_bytes, hip_stream);
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "coords must be non-null");
-    return backward_masked(desc, p, grad_out, features, proj, coords_from_tensor(coords, p), view_mask, grad_features, workspace, workspace_bytes,
-                           hip_stream, true);
-}
-
-int mvhmr_unproject_backward_cuboid_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
-                                                         const float *proj, const float *rot, const float *center, const double position[3],
-                                                         const double sides[3], const uint8_t *view_mask, void *grad_features, void *workspace,
-                                                         size_t workspace_bytes, void *hip_stream)
-{
-    if (!view_mask)
-        return mvhmr_unproject_backward_cuboid_deterministic(desc, grad_out, features, proj, rot, center, position, sides, grad_features, workspace,
-                                                             workspace_bytes, hip_stream);
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    Coords cs;
-    rc = coords_from_cuboid(rot, center, position, sides, p, &cs);
-    if (rc != MVHMR_OK) return rc;
-    return backward_masked(desc, p, grad_out, features, proj, cs, view_mask, grad_features, workspace, workspace_bytes, hip_stream, true);
-}
-
-int mvhmr_unproject_backward_geometry_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                             const float *coords, const uint8_t *view_mask, float *grad_proj, float *grad_coords, void *workspace,
-                                             size_t workspace_bytes, void *hip_stream)
-{
-    if (!view_mask)
-        return mvhmr_unproject_backward_geometry(desc, grad_out, features, proj, coords, grad_proj, grad_coords, workspace, workspace_bytes, hip_stream);
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    if (!coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / coords must be non-null");
-    if (!grad_proj && !grad_coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj and grad_coords are both null: nothing to compute");
-    return geometry_masked(desc, p, grad_out, features, proj, coords, nullptr, nullptr, nullptr, nullptr, view_mask, grad_proj, grad_coords, nullptr,
-                           nullptr, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                                    const float *rot, const float *center, const double position[3], const double sides[3],
-                                                    const uint8_t *view_mask, float *grad_proj, float *grad_rot, float *grad_center, void *workspace,
-                                                    size_t workspace_bytes, void *hip_stream)
-{
-    if (!view_mask)
-        return mvhmr_unproject_backward_geometry_cuboid(desc, grad_out, features, proj, rot, center, position, sides, grad_proj, grad_rot, grad_center,
-                                                        workspace, workspace_bytes, hip_stream);
-    Problem p;
-    int rc = check_desc(desc, &p);
-    if (rc != MVHMR_OK) return rc;
-    if (!rot || !center || !position || !sides) return fail(MVHMR_ERR_INVALID_ARGUMENT, "rot / center / position / sides must be non-null");
-    if (!grad_proj && !grad_rot && !grad_center)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj, grad_rot and grad_center are all null: nothing to compute");
-    return geometry_masked(desc, p, grad_out, features, proj, nullptr, rot, center, position, sides, view_mask, grad_proj, nullptr, grad_rot, grad_center,
-                           workspace, workspace_bytes, hip_stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 // PyTorch-ROCm C++ extension over the C ABI (include/mvhmr_unproject.h): the host side of every un-projection launch, as the ops
 // mvhmr_native::unprojection[_backward[_geometry]] / unprojection_cuboid[_backward[_geometry]] that multiviewhmr_amd/aggregation.py calls
-// from its torch.library ops and from _FusedAggregate, and of the DLT triangulation (triangulate_dlt[_backward], multiview.py).  Per call:
+// from its torch.library ops and from _FusedAggregate, and of the DLT triangulation (triangulate_dlt[_backward], multiview.py).  Every
+// un-projection op takes a trailing `Tensor? view_mask` (None: the unmasked C entry point), the two feature backwards a trailing
+// `bool deterministic`; the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
 // tensor checks, descriptor, output and workspace from the caching allocator, the current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -78,27 +80,35 @@ void check_inputs(const mvhmr_unproject_desc &d, const at::Tensor &features, con
         check_tensor(*grad_out, features, "grad_out (B, C, X, Y, Z)", scalar_of(d.out_dtype), B * C * d.vol_x * d.vol_y * d.vol_z);
 }
 
-// the common tail: workspace from the caching allocator, the features' device, the current HIP stream, one C-ABI call
-template <typename Launch>
-void run(const mvhmr_unproject_desc &d, const at::Tensor &features, size_t (*workspace_bytes)(const mvhmr_unproject_desc *), Launch launch)
+
+// per-sample view masks (mvhmr_unproject_*_masked): view_mask (B, V) uint8 on the features' device, nonzero = present
+void check_mask(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &mask)
 {
-    c10::DeviceGuard guard(features.device());
-    const size_t need = workspace_bytes(&d);
-    at::Tensor ws = at::empty({(int64_t)need}, features.options().dtype(at::kByte));
-    const int status = launch(need ? ws.data_ptr() : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream());
-    TORCH_CHECK(status == MVHMR_OK, "mvhmr_unproject: ", mvhmr_last_error());
+    check_tensor(mask, features, "view_mask (B, V)", at::kByte, (int64_t)d.batch * d.views);
 }
 
-// run() for the deterministic entry points: the workspace comes straight from the device allocator, not from at::empty, which under
-// torch.use_deterministic_algorithms(True) fills new memory (torch.utils.deterministic.fill_uninitialized_memory) -- gigabytes of
-// scratch the kernels overwrite or clear themselves
+// the mask the library reads: null for None, which selects the unmasked entry point
+const uint8_t *mask_ptr(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_mask)
+{
+    if (!view_mask || !view_mask->defined()) return nullptr;
+    check_mask(d, features, *view_mask);
+    return view_mask->data_ptr<uint8_t>();
+}
+
+// the common tail: workspace, the features' device, the current HIP stream, one C-ABI call.  The workspace comes from the caching
+// allocator through at::empty -- except `unfilled` (the deterministic entry points), straight from the device allocator: under
+// torch.use_deterministic_algorithms(True) at::empty fills new memory (torch.utils.deterministic.fill_uninitialized_memory) --
+// gigabytes of scratch the kernels overwrite or clear themselves
 template <typename Launch>
-void run_unfilled(const mvhmr_unproject_desc &d, const at::Tensor &features, size_t (*workspace_bytes)(const mvhmr_unproject_desc *), Launch launch)
+void run(const at::Tensor &features, size_t need, bool unfilled, Launch launch)
 {
     c10::DeviceGuard guard(features.device());
-    const size_t need = workspace_bytes(&d);
-    c10::DataPtr ws = c10::GetAllocator(features.device().type())->allocate(need);
-    const int status = launch(need ? ws.get() : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream());
+    c10::DataPtr raw;
+    at::Tensor filled;
+    if (unfilled) raw = c10::GetAllocator(features.device().type())->allocate(need);
+    else filled = at::empty({(int64_t)need}, features.options().dtype(at::kByte));
+    void *ws = unfilled ? raw.get() : filled.data_ptr();
+    const int status = launch(need ? ws : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream());
     TORCH_CHECK(status == MVHMR_OK, "mvhmr_unproject: ", mvhmr_last_error());
 }
 
@@ -112,133 +122,228 @@ at::Tensor new_feature_grad(const mvhmr_unproject_desc &d, const at::Tensor &fea
     return at::empty({d.batch, d.views, d.channels, d.feat_h, d.feat_w}, opts);
 }
 
-// features: the tensor the library reads (planar, channels-last or the quad-planar byte buffer); B..W: the logical feature shape
-at::Tensor unprojection_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C,
-                               int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+// the descriptor's fields as the ops take them: B..W the logical feature shape
+struct DescArgs {
+    int64_t B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant;
+};
+
+// ---- what places the volume.  Each form knows its descriptor, its tensors' checks, the shapes of its geometry gradients and its C
+// entry points (mask == null: the unmasked one; det: the _deterministic one).
+struct TensorVolume {
+    const at::Tensor &coords;                                   // (B, X, Y, Z, 3)
+    static constexpr const char *kNothingAsked = "mvhmr_unproject: neither gradient was asked for";
+
+    mvhmr_unproject_desc desc(const DescArgs &a) const
+    {
+        return coords_desc(coords, a.B, a.V, a.C, a.H, a.W, a.method, a.feat_dtype, a.out_dtype, a.layout, a.variant);
+    }
+    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out) const
+    {
+        check_inputs(d, features, proj, &coords, nullptr, nullptr, grad_out);
+    }
+    // gradients w.r.t. proj (B,V,3,4) and coords (B,X,Y,Z,3)
+    std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, coords.sizes().vec()}; }
+
+    size_t forward_bytes(const mvhmr_unproject_desc &d, bool masked) const
+    {
+        return masked ? mvhmr_unproject_forward_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
+    }
+    int forward(const mvhmr_unproject_desc &d, const void *features, const float *proj, const uint8_t *mask, void *out, void *ws, size_t n, hipStream_t s) const
+    {
+        const float *c = coords.data_ptr<float>();
+        return mask ? mvhmr_unproject_forward_masked(&d, features, proj, c, mask, out, ws, n, s) : mvhmr_unproject_forward(&d, features, proj, c, out, ws, n, s);
+    }
+    size_t backward_bytes(const mvhmr_unproject_desc &d, bool masked, bool det) const
+    {
+        if (masked) return det ? mvhmr_unproject_backward_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_masked_workspace_bytes(&d);
+        return det ? mvhmr_unproject_backward_deterministic_workspace_bytes(&d) : mvhmr_unproject_backward_workspace_bytes(&d);
+    }
+    int backward(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const uint8_t *mask, bool det, void *grad,
+                 void *ws, size_t n, hipStream_t s) const
+    {
+        const float *c = coords.data_ptr<float>();
+        if (mask) return (det ? mvhmr_unproject_backward_deterministic_masked : mvhmr_unproject_backward_masked)(&d, grad_out, features, proj, c, mask, grad, ws, n, s);
+        return (det ? mvhmr_unproject_backward_deterministic : mvhmr_unproject_backward)(&d, grad_out, features, proj, c, grad, ws, n, s);
+    }
+    size_t geometry_bytes(const mvhmr_unproject_desc &d, bool masked) const
+    {
+        return masked ? mvhmr_unproject_backward_geometry_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_workspace_bytes(&d);
+    }
+    int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const uint8_t *mask, float *const *g, void *ws,
+                 size_t n, hipStream_t s) const
+    {
+        const float *c = coords.data_ptr<float>();
+        return mask ? mvhmr_unproject_backward_geometry_masked(&d, grad_out, features, proj, c, mask, g[0], g[1], ws, n, s)
+                    : mvhmr_unproject_backward_geometry(&d, grad_out, features, proj, c, g[0], g[1], ws, n, s);
+    }
+};
+
+// the cuboid recipe (mvhmr_unproject_*_cuboid): rot (B,3,3) and center (B,3) on the device, position / sides / vol 3 values each
+struct CuboidVolume {
+    const at::Tensor &rot, &center;
+    at::ArrayRef<double> position, sides;
+    at::IntArrayRef vol;
+    static constexpr const char *kNothingAsked = "mvhmr_unproject: no gradient was asked for";
+
+    mvhmr_unproject_desc desc(const DescArgs &a) const
+    {
+        return cuboid_desc(position, sides, vol, a.B, a.V, a.C, a.H, a.W, a.method, a.feat_dtype, a.out_dtype, a.layout, a.variant);
+    }
+    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out) const
+    {
+        check_inputs(d, features, proj, nullptr, &rot, &center, grad_out);
+    }
+    // gradients w.r.t. proj (B,V,3,4), rot (B,3,3) and center (B,3)
+    std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, {d.batch, 3, 3}, {d.batch, 3}}; }
+
+    size_t forward_bytes(const mvhmr_unproject_desc &d, bool masked) const
+    {
+        return masked ? mvhmr_unproject_forward_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
+    }
+    int forward(const mvhmr_unproject_desc &d, const void *features, const float *proj, const uint8_t *mask, void *out, void *ws, size_t n, hipStream_t s) const
+    {
+        const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
+        return mask ? mvhmr_unproject_forward_cuboid_masked(&d, features, proj, r, c, position.data(), sides.data(), mask, out, ws, n, s)
+                    : mvhmr_unproject_forward_cuboid(&d, features, proj, r, c, position.data(), sides.data(), out, ws, n, s);
+    }
+    size_t backward_bytes(const mvhmr_unproject_desc &d, bool masked, bool det) const
+    {
+        if (masked) return det ? mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_masked_workspace_bytes(&d);
+        return det ? mvhmr_unproject_backward_deterministic_workspace_bytes(&d) : mvhmr_unproject_backward_workspace_bytes(&d);
+    }
+    int backward(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const uint8_t *mask, bool det, void *grad,
+                 void *ws, size_t n, hipStream_t s) const
+    {
+        const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
+        if (mask)
+            return (det ? mvhmr_unproject_backward_cuboid_deterministic_masked : mvhmr_unproject_backward_cuboid_masked)(
+                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, grad, ws, n, s);
+        return (det ? mvhmr_unproject_backward_cuboid_deterministic : mvhmr_unproject_backward_cuboid)(&d, grad_out, features, proj, r, c, position.data(),
+                                                                                                     sides.data(), grad, ws, n, s);
+    }
+    size_t geometry_bytes(const mvhmr_unproject_desc &d, bool masked) const
+    {
+        return masked ? mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(&d);
+    }
+    int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const uint8_t *mask, float *const *g, void *ws,
+                 size_t n, hipStream_t s) const
+    {
+        const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
+        return mask ? mvhmr_unproject_backward_geometry_cuboid_masked(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, g[0], g[1], g[2],
+                                                                      ws, n, s)
+                    : mvhmr_unproject_backward_geometry_cuboid(&d, grad_out, features, proj, r, c, position.data(), sides.data(), g[0], g[1], g[2], ws, n, s);
+    }
+};
+
+// ---- one body per kind of call.  features: the tensor the library reads (planar, channels-last or the quad-planar byte buffer)
+template <typename Volume>
+at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a, const c10::optional<at::Tensor> &view_mask)
 {
-    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, &coords, nullptr, nullptr, nullptr);
-    at::Tensor out = at::empty({B, C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(out_dtype)));
-    run(d, features, mvhmr_unproject_forward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_forward(&d, features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(), out.data_ptr(), ws, n, s);
+    const mvhmr_unproject_desc d = vol.desc(a);
+    vol.check(d, features, proj, nullptr);
+    const uint8_t *mask = mask_ptr(d, features, view_mask);
+    at::Tensor out = at::empty({a.B, a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
+    run(features, vol.forward_bytes(d, mask != nullptr), false, [&](void *ws, size_t n, hipStream_t s) {
+        return vol.forward(d, features.data_ptr(), proj.data_ptr<float>(), mask, out.data_ptr(), ws, n, s);
     });
     return out;
+}
+
+// deterministic: the feature gradient bitwise reproducible (mvhmr_unproject_backward*_deterministic); the workspace is not filled
+template <typename Volume>
+at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
+                    const c10::optional<at::Tensor> &view_mask, bool deterministic)
+{
+    const mvhmr_unproject_desc d = vol.desc(a);
+    vol.check(d, features, proj, &grad_out);
+    const uint8_t *mask = mask_ptr(d, features, view_mask);
+    at::Tensor grad = new_feature_grad(d, features);
+    run(features, vol.backward_bytes(d, mask != nullptr, deterministic), deterministic, [&](void *ws, size_t n, hipStream_t s) {
+        return vol.backward(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), mask, deterministic, grad.data_ptr(), ws, n, s);
+    });
+    return grad;
+}
+
+// the geometry gradients of the form, all fp32, grad_proj first; an output not asked for comes back as an empty tensor
+template <typename Volume>
+std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
+                                          std::initializer_list<bool> want, const c10::optional<at::Tensor> &view_mask)
+{
+    TORCH_CHECK(std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
+    const mvhmr_unproject_desc d = vol.desc(a);
+    vol.check(d, features, proj, &grad_out);
+    const uint8_t *mask = mask_ptr(d, features, view_mask);
+    const auto opts = features.options().dtype(at::kFloat);
+    const auto shapes = vol.geometry_shapes(d);
+    std::vector<at::Tensor> grads;
+    std::vector<float *> ptrs;
+    for (size_t i = 0; i < shapes.size(); i++) {
+        const bool w = want.begin()[i];
+        grads.push_back(w ? at::empty(shapes[i], opts) : at::empty({0}, opts));
+        ptrs.push_back(w ? grads.back().data_ptr<float>() : nullptr);
+    }
+    run(features, vol.geometry_bytes(d, mask != nullptr), false, [&](void *ws, size_t n, hipStream_t s) {
+        return vol.geometry(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), mask, ptrs.data(), ws, n, s);
+    });
+    return grads;
+}
+
+// ---- the six ops
+using OptTensor = c10::optional<at::Tensor>;
+
+at::Tensor unprojection_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C,
+                               int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
+                               const OptTensor &view_mask)
+{
+    return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask);
 }
 
 at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
                                         int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
-                                        int64_t out_dtype, int64_t layout, int64_t variant)
+                                        int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask, bool deterministic)
 {
-    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
-    at::Tensor grad = new_feature_grad(d, features);
-    run(d, features, mvhmr_unproject_backward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_backward(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
-                                        grad.data_ptr(), ws, n, s);
-    });
-    return grad;
+    return backward(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask,
+                    deterministic);
 }
 
-// the feature gradient bitwise reproducible (mvhmr_unproject_backward_deterministic); the workspace is not filled
-at::Tensor unprojection_backward_deterministic_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
-                                                      const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
-                                                      int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
-{
-    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
-    at::Tensor grad = new_feature_grad(d, features);
-    run_unfilled(d, features, mvhmr_unproject_backward_deterministic_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_backward_deterministic(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
-                                                      grad.data_ptr(), ws, n, s);
-    });
-    return grad;
-}
-
-// gradients w.r.t. proj (B,V,3,4) and coords (B,X,Y,Z,3), both fp32; an output not asked for comes back as an empty tensor
 std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
                                                                           const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H,
                                                                           int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
-                                                                          int64_t variant, bool want_proj, bool want_coords)
+                                                                          int64_t variant, bool want_proj, bool want_coords, const OptTensor &view_mask)
 {
-    TORCH_CHECK(want_proj || want_coords, "mvhmr_unproject: neither gradient was asked for");
-    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
-    const auto opts = features.options().dtype(at::kFloat);
-    at::Tensor gp = want_proj ? at::empty({B, V, 3, 4}, opts) : at::empty({0}, opts);
-    at::Tensor gc = want_coords ? at::empty(coords.sizes(), opts) : at::empty({0}, opts);
-    run(d, features, mvhmr_unproject_backward_geometry_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_backward_geometry(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
-                                                 want_proj ? gp.data_ptr<float>() : nullptr, want_coords ? gc.data_ptr<float>() : nullptr, ws, n, s);
-    });
-    return {gp, gc};
+    const auto g = backward_geometry(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
+                                     {want_proj, want_coords}, view_mask);
+    return {g[0], g[1]};
 }
 
-// the same two launches for the cuboid recipe (mvhmr_unproject_*_cuboid): rot (B,3,3) and center (B,3) on the device, position / sides / vol
-// 3 values each
 at::Tensor unprojection_cuboid_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
                                       at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C,
-                                      int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+                                      int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
+                                      const OptTensor &view_mask)
 {
-    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, nullptr, &rot, &center, nullptr);
-    at::Tensor out = at::empty({B, C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(out_dtype)));
-    run(d, features, mvhmr_unproject_forward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_forward_cuboid(&d, features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(),
-                                              position.data(), sides.data(), out.data_ptr(), ws, n, s);
-    });
-    return out;
+    return forward(CuboidVolume{rot, center, position, sides, vol}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
+                   view_mask);
 }
 
 at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
                                                const at::Tensor &center, at::ArrayRef<double> position, at::ArrayRef<double> sides,
                                                at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
-                                               int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+                                               int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask,
+                                               bool deterministic)
 {
-    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
-    at::Tensor grad = new_feature_grad(d, features);
-    run(d, features, mvhmr_unproject_backward_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_backward_cuboid(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(),
-                                               center.data_ptr<float>(), position.data(), sides.data(), grad.data_ptr(), ws, n, s);
-    });
-    return grad;
+    return backward(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
+                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, deterministic);
 }
 
-// the same for the cuboid recipe (mvhmr_unproject_backward_cuboid_deterministic)
-at::Tensor unprojection_cuboid_backward_deterministic_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
-                                                             const at::Tensor &rot, const at::Tensor &center, at::ArrayRef<double> position,
-                                                             at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H,
-                                                             int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
-{
-    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
-    at::Tensor grad = new_feature_grad(d, features);
-    run_unfilled(d, features, mvhmr_unproject_backward_deterministic_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_backward_cuboid_deterministic(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(),
-                                                             center.data_ptr<float>(), position.data(), sides.data(), grad.data_ptr(), ws, n, s);
-    });
-    return grad;
-}
-
-// gradients w.r.t. proj (B,V,3,4), rot (B,3,3) and center (B,3) of the cuboid recipe, fp32; an output not asked for comes back empty
 std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geometry_native(
     const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
     at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
-    int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center)
+    int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center,
+    const OptTensor &view_mask)
 {
-    TORCH_CHECK(want_proj || want_rot || want_center, "mvhmr_unproject: no gradient was asked for");
-    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
-    const auto opts = features.options().dtype(at::kFloat);
-    at::Tensor gp = want_proj ? at::empty({B, V, 3, 4}, opts) : at::empty({0}, opts);
-    at::Tensor gr = want_rot ? at::empty({B, 3, 3}, opts) : at::empty({0}, opts);
-    at::Tensor gc = want_center ? at::empty({B, 3}, opts) : at::empty({0}, opts);
-    run(d, features, mvhmr_unproject_backward_geometry_cuboid_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_backward_geometry_cuboid(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(),
-                                                        center.data_ptr<float>(), position.data(), sides.data(), want_proj ? gp.data_ptr<float>() : nullptr,
-                                                        want_rot ? gr.data_ptr<float>() : nullptr, want_center ? gc.data_ptr<float>() : nullptr, ws, n, s);
-    });
-    return {gp, gr, gc};
+    const auto g = backward_geometry(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
+                                     DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, {want_proj, want_rot, want_center}, view_mask);
+    return {g[0], g[1], g[2]};
 }
 
 // DLT triangulation (mvhmr_triangulate_dlt[_weighted]) and its backward: proj (B,V,3,4), points (V,2) or (B,V,2), confidences (V) or
@@ -295,193 +400,27 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(c
     return {gp, gu, gc};
 }
 
-// per-sample view masks (mvhmr_unproject_*_masked): view_mask (B, V) uint8 on the features' device, nonzero = present
-void check_mask(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &mask)
-{
-    check_tensor(mask, features, "view_mask (B, V)", at::kByte, (int64_t)d.batch * d.views);
-}
-
-at::Tensor unprojection_masked_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, const at::Tensor &mask, int64_t B,
-                                      int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
-                                      int64_t variant)
-{
-    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, &coords, nullptr, nullptr, nullptr);
-    check_mask(d, features, mask);
-    at::Tensor out = at::empty({B, C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(out_dtype)));
-    run(d, features, mvhmr_unproject_forward_masked_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_forward_masked(&d, features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(), mask.data_ptr<uint8_t>(),
-                                              out.data_ptr(), ws, n, s);
-    });
-    return out;
-}
-
-at::Tensor unprojection_masked_backward_impl(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
-                                             const at::Tensor &mask, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
-                                             int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool det)
-{
-    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
-    check_mask(d, features, mask);
-    at::Tensor grad = new_feature_grad(d, features);
-    auto launch = [&](void *ws, size_t n, hipStream_t s) {
-        return (det ? mvhmr_unproject_backward_deterministic_masked : mvhmr_unproject_backward_masked)(
-            &d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(), mask.data_ptr<uint8_t>(), grad.data_ptr(),
-            ws, n, s);
-    };
-    if (det) run_unfilled(d, features, mvhmr_unproject_backward_deterministic_masked_workspace_bytes, launch);
-    else run(d, features, mvhmr_unproject_backward_masked_workspace_bytes, launch);
-    return grad;
-}
-
-at::Tensor unprojection_masked_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
-                                               const at::Tensor &mask, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
-                                               int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
-{
-    return unprojection_masked_backward_impl(grad_out, features, proj, coords, mask, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, false);
-}
-
-at::Tensor unprojection_masked_backward_deterministic_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
-                                                             const at::Tensor &coords, const at::Tensor &mask, int64_t B, int64_t V, int64_t C, int64_t H,
-                                                             int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
-                                                             int64_t variant)
-{
-    return unprojection_masked_backward_impl(grad_out, features, proj, coords, mask, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, true);
-}
-
-std::tuple<at::Tensor, at::Tensor> unprojection_masked_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features,
-                                                                                 const at::Tensor &proj, const at::Tensor &coords, const at::Tensor &mask,
-                                                                                 int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
-                                                                                 int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
-                                                                                 bool want_proj, bool want_coords)
-{
-    TORCH_CHECK(want_proj || want_coords, "mvhmr_unproject: neither gradient was asked for");
-    const mvhmr_unproject_desc d = coords_desc(coords, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, &coords, nullptr, nullptr, &grad_out);
-    check_mask(d, features, mask);
-    const auto opts = features.options().dtype(at::kFloat);
-    at::Tensor gp = want_proj ? at::empty({B, V, 3, 4}, opts) : at::empty({0}, opts);
-    at::Tensor gc = want_coords ? at::empty(coords.sizes(), opts) : at::empty({0}, opts);
-    run(d, features, mvhmr_unproject_backward_geometry_masked_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_backward_geometry_masked(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), coords.data_ptr<float>(),
-                                                        mask.data_ptr<uint8_t>(), want_proj ? gp.data_ptr<float>() : nullptr,
-                                                        want_coords ? gc.data_ptr<float>() : nullptr, ws, n, s);
-    });
-    return {gp, gc};
-}
-
-// the cuboid recipe's masked forms (mvhmr_unproject_*_cuboid_masked)
-at::Tensor unprojection_cuboid_masked_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
-                                             const at::Tensor &mask, at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol,
-                                             int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
-                                             int64_t out_dtype, int64_t layout, int64_t variant)
-{
-    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, nullptr, &rot, &center, nullptr);
-    check_mask(d, features, mask);
-    at::Tensor out = at::empty({B, C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(out_dtype)));
-    run(d, features, mvhmr_unproject_forward_cuboid_masked_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_forward_cuboid_masked(&d, features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(),
-                                                     position.data(), sides.data(), mask.data_ptr<uint8_t>(), out.data_ptr(), ws, n, s);
-    });
-    return out;
-}
-
-at::Tensor unprojection_cuboid_masked_backward_impl(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
-                                                    const at::Tensor &center, const at::Tensor &mask, at::ArrayRef<double> position,
-                                                    at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
-                                                    int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool det)
-{
-    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
-    check_mask(d, features, mask);
-    at::Tensor grad = new_feature_grad(d, features);
-    auto launch = [&](void *ws, size_t n, hipStream_t s) {
-        return (det ? mvhmr_unproject_backward_cuboid_deterministic_masked : mvhmr_unproject_backward_cuboid_masked)(
-            &d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(), position.data(),
-            sides.data(), mask.data_ptr<uint8_t>(), grad.data_ptr(), ws, n, s);
-    };
-    if (det) run_unfilled(d, features, mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes, launch);
-    else run(d, features, mvhmr_unproject_backward_cuboid_masked_workspace_bytes, launch);
-    return grad;
-}
-
-at::Tensor unprojection_cuboid_masked_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
-                                                      const at::Tensor &center, const at::Tensor &mask, at::ArrayRef<double> position,
-                                                      at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H,
-                                                      int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
-{
-    return unprojection_cuboid_masked_backward_impl(grad_out, features, proj, rot, center, mask, position, sides, vol, B, V, C, H, W, method, feat_dtype,
-                                                    out_dtype, layout, variant, false);
-}
-
-at::Tensor unprojection_cuboid_masked_backward_deterministic_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
-                                                                    const at::Tensor &rot, const at::Tensor &center, const at::Tensor &mask,
-                                                                    at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol,
-                                                                    int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
-                                                                    int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
-{
-    return unprojection_cuboid_masked_backward_impl(grad_out, features, proj, rot, center, mask, position, sides, vol, B, V, C, H, W, method, feat_dtype,
-                                                    out_dtype, layout, variant, true);
-}
-
-std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_masked_backward_geometry_native(
-    const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
-    const at::Tensor &mask, at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H,
-    int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center)
-{
-    TORCH_CHECK(want_proj || want_rot || want_center, "mvhmr_unproject: no gradient was asked for");
-    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant);
-    check_inputs(d, features, proj, nullptr, &rot, &center, &grad_out);
-    check_mask(d, features, mask);
-    const auto opts = features.options().dtype(at::kFloat);
-    at::Tensor gp = want_proj ? at::empty({B, V, 3, 4}, opts) : at::empty({0}, opts);
-    at::Tensor gr = want_rot ? at::empty({B, 3, 3}, opts) : at::empty({0}, opts);
-    at::Tensor gc = want_center ? at::empty({B, 3}, opts) : at::empty({0}, opts);
-    run(d, features, mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes, [&](void *ws, size_t n, hipStream_t s) {
-        return mvhmr_unproject_backward_geometry_cuboid_masked(&d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(),
-                                                               rot.data_ptr<float>(), center.data_ptr<float>(), position.data(), sides.data(),
-                                                               mask.data_ptr<uint8_t>(), want_proj ? gp.data_ptr<float>() : nullptr,
-                                                               want_rot ? gr.data_ptr<float>() : nullptr, want_center ? gc.data_ptr<float>() : nullptr,
-                                                               ws, n, s);
-    });
-    return {gp, gr, gc};
-}
 
 }  // namespace
 
 // the descriptor's fields after an op's tensors, and the cuboid ops' arguments
 #define MVHMR_DESC_ARGS "int B, int V, int C, int H, int W, int method, int feat_dtype, int out_dtype, int layout, int variant"
 #define MVHMR_CUBOID_ARGS "Tensor proj, Tensor rot, Tensor center, float[] position, float[] sides, int[] vol, " MVHMR_DESC_ARGS
-#define MVHMR_MASKED_CUBOID_ARGS "float[] position, float[] sides, int[] vol, " MVHMR_DESC_ARGS
+#define MVHMR_MASK_ARG ", Tensor? view_mask=None"
 
 TORCH_LIBRARY(mvhmr_native, m)
 {
-    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS ") -> Tensor");
-    m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS ") -> Tensor");
-    m.def("unprojection_backward_deterministic(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS ") -> Tensor");
-    m.def("unprojection_cuboid_backward_deterministic(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS ") -> Tensor");
+    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG ") -> Tensor");
+    m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG
+          ", bool deterministic=False) -> Tensor");
     m.def("unprojection_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS
-          ", bool want_proj, bool want_coords) -> (Tensor, Tensor)");
-    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS ") -> Tensor");
-    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS ") -> Tensor");
+          ", bool want_proj, bool want_coords" MVHMR_MASK_ARG ") -> (Tensor, Tensor)");
+    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ") -> Tensor");
+    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ", bool deterministic=False) -> Tensor");
     m.def("unprojection_cuboid_backward_geometry(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS
-          ", bool want_proj, bool want_rot, bool want_center) -> (Tensor, Tensor, Tensor)");
+          ", bool want_proj, bool want_rot, bool want_center" MVHMR_MASK_ARG ") -> (Tensor, Tensor, Tensor)");
     m.def("triangulate_dlt(Tensor proj, Tensor points, Tensor? confidences) -> Tensor");
     m.def("triangulate_dlt_backward(Tensor grad_out, Tensor proj, Tensor points, Tensor? confidences) -> (Tensor, Tensor, Tensor)");
-    m.def("unprojection_masked(Tensor features, Tensor proj, Tensor coords, Tensor view_mask, " MVHMR_DESC_ARGS ") -> Tensor");
-    m.def("unprojection_masked_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, Tensor view_mask, " MVHMR_DESC_ARGS ") -> Tensor");
-    m.def("unprojection_masked_backward_deterministic(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, Tensor view_mask, " MVHMR_DESC_ARGS
-          ") -> Tensor");
-    m.def("unprojection_masked_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, Tensor view_mask, " MVHMR_DESC_ARGS
-          ", bool want_proj, bool want_coords) -> (Tensor, Tensor)");
-    m.def("unprojection_cuboid_masked(Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, " MVHMR_MASKED_CUBOID_ARGS ") -> Tensor");
-    m.def("unprojection_cuboid_masked_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, "
-          MVHMR_MASKED_CUBOID_ARGS ") -> Tensor");
-    m.def("unprojection_cuboid_masked_backward_deterministic(Tensor grad_out, Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, "
-          MVHMR_MASKED_CUBOID_ARGS ") -> Tensor");
-    m.def("unprojection_cuboid_masked_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor rot, Tensor center, Tensor view_mask, "
-          MVHMR_MASKED_CUBOID_ARGS ", bool want_proj, bool want_rot, bool want_center) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int");
 }
 
@@ -489,22 +428,12 @@ TORCH_LIBRARY_IMPL(mvhmr_native, CUDA, m)
 {
     m.impl("unprojection", &unprojection_native);
     m.impl("unprojection_backward", &unprojection_backward_native);
-    m.impl("unprojection_backward_deterministic", &unprojection_backward_deterministic_native);
-    m.impl("unprojection_cuboid_backward_deterministic", &unprojection_cuboid_backward_deterministic_native);
     m.impl("unprojection_backward_geometry", &unprojection_backward_geometry_native);
     m.impl("unprojection_cuboid", &unprojection_cuboid_native);
     m.impl("unprojection_cuboid_backward", &unprojection_cuboid_backward_native);
     m.impl("unprojection_cuboid_backward_geometry", &unprojection_cuboid_backward_geometry_native);
     m.impl("triangulate_dlt", &triangulate_dlt_native);
     m.impl("triangulate_dlt_backward", &triangulate_dlt_backward_native);
-    m.impl("unprojection_masked", &unprojection_masked_native);
-    m.impl("unprojection_masked_backward", &unprojection_masked_backward_native);
-    m.impl("unprojection_masked_backward_deterministic", &unprojection_masked_backward_deterministic_native);
-    m.impl("unprojection_masked_backward_geometry", &unprojection_masked_backward_geometry_native);
-    m.impl("unprojection_cuboid_masked", &unprojection_cuboid_masked_native);
-    m.impl("unprojection_cuboid_masked_backward", &unprojection_cuboid_masked_backward_native);
-    m.impl("unprojection_cuboid_masked_backward_deterministic", &unprojection_cuboid_masked_backward_deterministic_native);
-    m.impl("unprojection_cuboid_masked_backward_geometry", &unprojection_cuboid_masked_backward_geometry_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)

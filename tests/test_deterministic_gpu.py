@@ -195,15 +195,18 @@ def test_fused_volume_generator_train_step_repeats_bitwise(gpu):
         finally:
             torch.use_deterministic_algorithms(was)
         conv = gen.process_feature[0]
-        return [f.grad.clone(), conv.weight.grad.clone(), conv.bias.grad.clone(), P.grad.clone()], rec.names
+        return [f.grad.clone(), conv.weight.grad.clone(), conv.bias.grad.clone(), P.grad.clone()], rec
 
-    a, names = step(True)
-    assert any("unprojection_cuboid_backward_deterministic" in n for n in names), names
+    # the extension's feature backward takes the mode as its `deterministic` argument (it selects mvhmr_unproject_backward_cuboid_deterministic)
+    native_bwd = "mvhmr_native.unprojection_cuboid_backward.default"
+    a, rec_on = step(True)
+    assert (native_bwd, True) in rec_on.modes and (native_bwd, False) not in rec_on.modes, (rec_on.modes, rec_on.names)
     b, _ = step(True)
     for name, x, y in zip(("features", "weight", "bias", "proj_org"), a, b):
         assert torch.equal(x, y), name
-    c, names_off = step(False)
-    assert not any("_deterministic" in n for n in names_off), names_off
+    c, rec_off = step(False)
+    assert not any("_deterministic" in n for n in rec_off.names), rec_off.names
+    assert (native_bwd, False) in rec_off.modes and (native_bwd, True) not in rec_off.modes, (rec_off.modes, rec_off.names)
     for name, x, y in zip(("features", "weight", "bias", "proj_org"), a, c):
         ref = y.double().cpu().numpy()
         record_err("fused det step %s vs default" % name, _err(x.cpu().numpy(), ref), _bound(ref) if name != "proj_org"
@@ -214,9 +217,14 @@ class _Rec(torch.utils._python_dispatch.TorchDispatchMode):
     def __init__(self):
         super().__init__()
         self.names = []
+        self.modes = []                 # (op, value of its `deterministic` argument) of every op that has one
 
     def __torch_dispatch__(self, func, types, args=(), kwargs=None):
         self.names.append(str(func))
+        schema = [a.name for a in func._schema.arguments]
+        if "deterministic" in schema:   # (an argument at its default, False, may be left out of args)
+            i = schema.index("deterministic")
+            self.modes.append((str(func), bool(args[i] if i < len(args) else (kwargs or {}).get("deterministic", False))))
         return func(*args, **(kwargs or {}))
 
 
