@@ -36,7 +36,8 @@ extern "C" {
                                  mvhmr_unproject_backward_geometry[_workspace_bytes], mvhmr_unproject_backward_geometry_cuboid[_workspace_bytes],
                                  mvhmr_triangulate_dlt_backward, mvhmr_unproject_backward_deterministic[_workspace_bytes],
                                  mvhmr_unproject_backward_cuboid_deterministic[_workspace_bytes], mvhmr_conv1x1_wgrad_deterministic[_workspace_bytes],
-                                 the *_masked entry points and their *_masked_workspace_bytes queries (per-sample view masks) */
+                                 the *_masked entry points and their *_masked_workspace_bytes queries (per-sample view masks), the
+                                 *_weighted entry points and their *_weighted_workspace_bytes queries (per-view confidence weights) */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -305,6 +306,65 @@ int mvhmr_unproject_backward_geometry_cuboid_masked(const mvhmr_unproject_desc *
                                                     const float *rot, const float *center, const double position[3], const double sides[3],
                                                     const uint8_t *view_mask, float *grad_proj, float *grad_rot, float *grad_center, void *workspace,
                                                     size_t workspace_bytes, void *hip_stream);
+
+/*
+ * Per-view confidence weights (additive within ABI 4): the *_masked calls with one more argument beside view_mask.
+ *   view_weights  (B,V) fp32, DEVICE, row-major.  NULL = unweighted: the call is then exactly the *_masked entry point of the same name
+ *                 (same kernels, same bits, same workspace need).  view_mask may be NULL as well (every view the weights leave present).
+ * Per sample b the present views are P_b = { v : (no mask or view_mask[b,v] != 0) and view_weights[b,v] > 0 }: a weight that is zero,
+ * negative or NaN means ABSENT in the view masks' sense -- features and projection row never read, grad_features, grad_proj row and
+ * grad_weights entry written as exact zeros.  The values are not inspected on the host; nothing synchronises.  With s_v the per-view
+ * sample of a voxel and channel (zero where z <= 0 or the taps leave the map; such zeros take part) and W = sum_{P_b} w_v:
+ *     sum      out = sum_P w_v s_v                                          d out / d w_v = s_v
+ *     mean     out = sum_P w_v s_v / W                                      d out / d w_v = (s_v - out) / W
+ *     softmax  out = sum_P p_v s_v,  p_v = w_v e^{s_v} / sum_P w_u e^{s_u}   d out / d w_v = (p_v / w_v) (s_v - out)
+ *     max      MVHMR_ERR_UNSUPPORTED with non-null weights (no weighted form)
+ * all in fp32.  P_b empty: a zero volume and zero gradients.  Weights in {0, 1} are the view_mask call, all ones the unweighted one, an
+ * integer weight k the unweighted call on a sample that holds the view k times; mean and softmax do not change when a sample's weights
+ * are multiplied by one positive constant.
+ * The two geometry calls gain grad_weights (B,V) fp32 (nullable; every element written): the sum over the sample's voxels and channels
+ * of grad_out times the derivative above, as fp32 partials per block in a fixed order summed in float64 -- bitwise reproducible like
+ * grad_proj.  It may be the only output asked for; all outputs null is MVHMR_ERR_INVALID_ARGUMENT, and so is grad_weights without
+ * view_weights.  The deterministic backward bounds its fixed-point scale with the weights (sum: max |grad_out| times the sample's largest
+ * weight).  Limits, layouts, storage pairings, variants (quad-planar layouts and MVHMR_VARIANT_BRICK refused) as the masked calls.
+ * Workspace: the *_weighted_workspace_bytes queries, never less than the masked ones.
+ */
+size_t mvhmr_unproject_forward_weighted_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_forward_cuboid_weighted_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_weighted_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_weighted_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_deterministic_weighted_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_deterministic_weighted_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_weighted_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_cuboid_weighted_workspace_bytes(const mvhmr_unproject_desc *desc);
+int mvhmr_unproject_forward_weighted(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+                                     const uint8_t *view_mask, const float *view_weights, void *out, void *workspace, size_t workspace_bytes,
+                                     void *hip_stream);
+int mvhmr_unproject_forward_cuboid_weighted(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
+                                            const float *center, const double position[3], const double sides[3], const uint8_t *view_mask,
+                                            const float *view_weights, void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                      const float *coords, const uint8_t *view_mask, const float *view_weights, void *grad_features, void *workspace,
+                                      size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                             const float *rot, const float *center, const double position[3], const double sides[3],
+                                             const uint8_t *view_mask, const float *view_weights, void *grad_features, void *workspace,
+                                             size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_deterministic_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                    const float *coords, const uint8_t *view_mask, const float *view_weights, void *grad_features,
+                                                    void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_deterministic_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
+                                                           const float *proj, const float *rot, const float *center, const double position[3],
+                                                           const double sides[3], const uint8_t *view_mask, const float *view_weights,
+                                                           void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                               const float *coords, const uint8_t *view_mask, const float *view_weights, float *grad_proj,
+                                               float *grad_coords, float *grad_weights, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_cuboid_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                      const float *rot, const float *center, const double position[3], const double sides[3],
+                                                      const uint8_t *view_mask, const float *view_weights, float *grad_proj, float *grad_rot,
+                                                      float *grad_center, float *grad_weights, void *workspace, size_t workspace_bytes,
+                                                      void *hip_stream);
 
 /*
  * Layout pass on its own: features (B,V,C,Hf,Wf) -> dst in `dst_layout` (MVHMR_LAYOUT_BVHWC with the channel

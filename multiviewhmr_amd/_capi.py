@@ -29,9 +29,10 @@ EXPORTS = (
     "mvhmr_unproject_backward_geometry_cuboid_workspace_bytes", "mvhmr_unproject_backward_geometry_cuboid", "mvhmr_triangulate_dlt_backward",
     "mvhmr_unproject_backward_deterministic_workspace_bytes", "mvhmr_unproject_backward_deterministic",
     "mvhmr_unproject_backward_cuboid_deterministic", "mvhmr_conv1x1_wgrad_deterministic_workspace_bytes", "mvhmr_conv1x1_wgrad_deterministic",
-) + tuple("mvhmr_unproject_%s_masked%s" % (n, w) for n in ("forward", "forward_cuboid", "backward", "backward_cuboid", "backward_deterministic",
+) + tuple("mvhmr_unproject_%s_%s%s" % (n, tag, w) for n in ("forward", "forward_cuboid", "backward", "backward_cuboid", "backward_deterministic",
                                                            "backward_cuboid_deterministic", "backward_geometry", "backward_geometry_cuboid")
-          for w in ("", "_workspace_bytes"))      # per-sample view masks
+          for w in ("", "_workspace_bytes")       # per-sample view masks, per-view confidence weights
+          for tag in ("masked", "weighted"))
 
 
 class Desc(ctypes.Structure):
@@ -129,6 +130,17 @@ def lib():
     L.mvhmr_build_coord_volumes.restype = ctypes.c_int
     L.mvhmr_build_coord_volumes.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), vp]
+    # the *_weighted family: the *_masked signatures with view_weights behind view_mask, the geometry calls also with grad_weights
+    for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
+        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
+                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
+                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 4 if vol else 3)):
+            fn = getattr(L, "mvhmr_unproject_%s_weighted" % name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = lead + place + [vp, vp] + [vp] * outs + [vp, sz, vp]
+            q = getattr(L, "mvhmr_unproject_%s_weighted_workspace_bytes" % name)
+            q.restype = sz
+            q.argtypes = [dp]
     if L.mvhmr_abi_version() != ABI_VERSION:
         raise RuntimeError("libmvhmr_unproject.so speaks ABI %d, this binding %d: rebuild" %
                            (L.mvhmr_abi_version(), ABI_VERSION))

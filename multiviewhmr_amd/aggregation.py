@@ -149,7 +149,9 @@ def _op_defined(name):
 # autograd runs under torch.use_deterministic_algorithms(True)) and <family>_backward_geometry (fp32 gradients w.r.t. proj_matricies and
 # the placing tensors -- coord_volumes, or the cuboid's rotations and centers; an output not asked for comes back empty; `variant` plays
 # no part).  Arguments: features, proj, the placing tensors, view_mask (B, V) uint8 on the features' device, nonzero = present (masked
-# families), the placing arguments, then method, out_dtype, variant.  The cuboid families feed the same kernels from the cuboid recipe
+# and weighted families), view_weights (B, V) fp32 there as well (weighted families: per-view confidence weights, a view is present when its
+# mask byte is nonzero and its weight > 0; DESIGN.md 5.9 -- the geometry backward differentiates w.r.t. them too), the placing arguments,
+# then method, out_dtype, variant.  The cuboid families feed the same kernels from the cuboid recipe
 # (mvhmr_unproject_*_cuboid) instead of a coordinate tensor.  The masked families (mvhmr_unproject_*_masked) read planar or channels-last
 # features, never a quad-planar copy, and run the gather kernels with a per-sample view count.
 _CUBOID_ARGS = ("float[] position", "float[] sides", "int[] vol")
@@ -158,17 +160,20 @@ _FAMILIES = {
     "unprojection_masked": (("coords",), (), True),
     "unprojection_cuboid": (("rot", "center"), _CUBOID_ARGS, False),
     "unprojection_cuboid_masked": (("rot", "center"), _CUBOID_ARGS, True),
+    "unprojection_weighted": (("coords",), (), True, True),
+    "unprojection_cuboid_weighted": (("rot", "center"), _CUBOID_ARGS, True, True),
 }
 
 
 class _Family:
     """the implementations of one family's ops, each taking the ops' arguments positionally"""
 
-    def __init__(self, name, places, extras, masked):
-        self.name, self.masked = name, masked
-        self.native = "unprojection_cuboid" if extras else "unprojection"       # the extension's op: view_mask is a trailing argument there
-        self.tensors = ("features", "proj") + places + (("view_mask",) if masked else ())
-        self.grads = ("proj",) + places                                         # what the geometry backward differentiates
+    def __init__(self, name, places, extras, masked, weighted=False):
+        self.name, self.masked, self.weighted = name, masked, weighted
+        self.native = "unprojection_cuboid" if extras else "unprojection"       # the extension's op: view_mask / view_weights are trailing arguments there
+        self.geo = ("proj",) + places                                           # the geometry tensors, behind features
+        self.tensors = ("features",) + self.geo + (("view_mask",) if masked else ()) + (("view_weights",) if weighted else ())
+        self.grads = self.geo + (("view_weights",) if weighted else ())         # what the geometry backward differentiates
         self.extras = extras
         self.n_inputs = len(self.tensors) + len(extras) + 3
 
@@ -176,37 +181,49 @@ class _Family:
         return ", ".join(["Tensor " + t for t in self.tensors] + list(self.extras) + ["int method", "int out_dtype", "int variant"])
 
     def split(self, args):
-        """-> features, (proj, *placing tensors), view_mask or None, placing arguments, (method, out_dtype, variant), want_* flags (default True)"""
+        """-> features, (proj, *placing tensors), (view_mask or None, view_weights or None), placing arguments, (method, out_dtype, variant),
+        want_* flags (default True)"""
         n, k = len(self.tensors), len(self.tensors) + len(self.extras)
+        g = 1 + len(self.geo)
         want = tuple(args[k + 3:])
-        return (args[0], tuple(args[1:1 + len(self.grads)]), args[n - 1] if self.masked else None, tuple(args[n:k]), tuple(args[k:k + 3]),
-                want + (True,) * (len(self.grads) - len(want)))
+        views = (args[g] if self.masked else None, args[g + 1] if self.weighted else None)
+        return (args[0], tuple(args[1:g]), views, tuple(args[n:k]), tuple(args[k:k + 3]), want + (True,) * (len(self.grads) - len(want)))
 
     def volume(self, geo, extra):
         return tuple(extra[2]) if extra else tuple(geo[1].shape[1:4])
 
     def native_args(self, args, geometry=False):
-        """the extension's leading arguments (the view the library reads, proj, placing tensors and arguments, descriptor fields), view_mask"""
-        features, geo, mask, extra, (method, out_dtype, variant), _ = self.split(args)
+        """the extension's leading arguments (the view the library reads, proj, placing tensors and arguments, descriptor fields), then
+        (view_mask, view_weights)"""
+        features, geo, views, extra, (method, out_dtype, variant), _ = self.split(args)
         layout = None
         if self.masked or geometry:
             features, layout = _geometry_read_layout(features)
         read, desc = _native_args(features, self.volume(geo, extra), method, out_dtype, variant, layout)
-        return (read,) + geo + extra + desc, mask
+        return (read,) + geo + extra + desc, views
 
     def forward(self, *args):
-        lead, mask = self.native_args(args)
-        return getattr(_native(), self.native)(*lead, mask)
+        lead, (mask, weights) = self.native_args(args)
+        return getattr(_native(), self.native)(*lead, mask, weights)
 
     def backward(self, deterministic, grad_out, *args):
         """gradient w.r.t. features (the geometry's is backward_geometry)"""
-        lead, mask = self.native_args(args)
-        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic)
+        lead, (mask, weights) = self.native_args(args)
+        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights)
 
     def backward_geometry(self, grad_out, *args):
-        """planar features go through the library's channels-last pass, channels-last ones are read as they are"""
-        lead, mask = self.native_args(args, geometry=True)
-        return tuple(getattr(_native(), self.native + "_backward_geometry")(grad_out.contiguous(), *lead, *self.split(args)[5], mask))
+        """planar features go through the library's channels-last pass, channels-last ones are read as they are; the gradient w.r.t.
+        view_weights (weighted families, last) is written by the extension into the tensor handed to it"""
+        lead, (mask, weights) = self.native_args(args, geometry=True)
+        want = self.split(args)[5]
+        op = getattr(_native(), self.native + "_backward_geometry")
+        if not self.weighted:
+            return tuple(op(grad_out.contiguous(), *lead, *want, mask))
+        gw = weights.new_empty(weights.shape if want[-1] else (0,))
+        if not any(want[:-1]):                             # the weights' gradient alone: the extension's outputs stay empty
+            op(grad_out.contiguous(), *lead, *want[:-1], mask, weights, gw)
+            return tuple(weights.new_empty((0,)) for _ in self.geo) + (gw,)
+        return tuple(op(grad_out.contiguous(), *lead, *want[:-1], mask, weights, gw if want[-1] else None)) + (gw,)
 
     def fake_forward(self, *args):
         features, geo, _, extra, (_, out_dtype, _), _ = self.split(args)
@@ -216,8 +233,9 @@ class _Family:
         return torch.empty_like(features)
 
     def fake_backward_geometry(self, grad_out, *args):
-        _, geo, _, _, _, want = self.split(args)
-        return tuple(t.new_empty(t.shape if w else (0,), dtype=torch.float32) for t, w in zip(geo, want))
+        _, geo, views, _, _, want = self.split(args)
+        diff = geo + ((views[1],) if self.weighted else ())
+        return tuple(t.new_empty(t.shape if w else (0,), dtype=torch.float32) for t, w in zip(diff, want))
 
     def setup_context(self, ctx, inputs, output):
         ctx.save_for_backward(*inputs[:len(self.tensors)])
@@ -227,11 +245,14 @@ class _Family:
         ops, saved = torch.ops.mvhmr, ctx.saved_tensors
         op = getattr(ops, self.name + ("_backward_deterministic" if torch.are_deterministic_algorithms_enabled() else "_backward"))
         g = op(grad_out, *saved, *ctx.args) if ctx.needs_input_grad[0] else None
-        want = tuple(ctx.needs_input_grad[1:1 + len(self.grads)])
-        geo = (None,) * len(want)
+        at = [1 + i for i in range(len(self.geo))] + ([len(self.tensors) - 1] if self.weighted else [])   # the differentiable inputs behind features
+        want = tuple(ctx.needs_input_grad[i] for i in at)
+        grads = [g] + [None] * (self.n_inputs - 1)
         if any(want):                                      # a features-only backward launches nothing more
             geo = getattr(ops, self.name + "_backward_geometry")(grad_out, *saved, *ctx.args, *want)
-        return (g,) + tuple(t if w else None for t, w in zip(geo, want)) + (None,) * (self.n_inputs - 1 - len(want))
+            for i, t, w in zip(at, geo, want):
+                grads[i] = t if w else None
+        return tuple(grads)
 
     def register(self):
         if _op_defined(self.name):
@@ -288,7 +309,7 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
 
 
 def unprojection(features, proj_matricies, coord_volumes, aggregation_method='softmax', *, out_dtype=None,
-                 variant='auto', view_mask=None):
+                 variant='auto', view_mask=None, view_weights=None):
     """Fused project -> bilinear-sample -> cross-view aggregate (reference: models/aggregation.py:20-87).
 
     features        (B, V, C, Hf, Wf) float32 (or float16, this package's storage mode) on a HIP device;
@@ -305,6 +326,10 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
                     out[b] is the un-projection of sample b's present views alone (mean divides by their count, softmax and max range
                     over them; no views -> zeros), masked views are never read and get zero gradients.  Runs the gather kernels
                     ('brick' is refused); DESIGN.md 5.8.
+    view_weights    (B, V) floating tensor, any device (keyword-only; None = unweighted): per-view confidences w.  A view with w <= 0 or
+                    NaN is absent exactly as under view_mask (with a mask too: present = mask and w > 0); over the present views sum is
+                    sum w_v s_v, mean that over sum w_v, softmax weighs e^{s_v} by w_v; 'max' raises ValueError.  Differentiable (the
+                    gradient comes back in the caller's dtype and device); runs the gather kernels; DESIGN.md 5.9.
     """
     def volume_shape(B):
         if coord_volumes.dim() != 5 or coord_volumes.shape[0] != B or coord_volumes.shape[4] != 3:
@@ -313,6 +338,8 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
 
     if view_mask is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_view_mask(view_mask, features)
+    if view_weights is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_view_weights(view_weights, features, aggregation_method)
     out_dtype, _, empty = _check_call(features, proj_matricies, (coord_volumes,), volume_shape, aggregation_method, variant, out_dtype,
                                       same_device=True)
     if empty is not None:
@@ -320,6 +347,9 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
     # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
     proj = proj_matricies.to(torch.float32).contiguous()
     coords = coord_volumes.to(torch.float32).contiguous()
+    if view_weights is not None:
+        return torch.ops.mvhmr.unprojection_weighted(features, proj, coords, _weighted_mask(view_mask, features), _weights_fp32(view_weights, features),
+                                                     _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
     if view_mask is not None:
         mask = _mask_bytes(view_mask, features)
         return torch.ops.mvhmr.unprojection_masked(features, proj, coords, mask, _capi.AGG[aggregation_method], _dtype_code(out_dtype),
@@ -340,6 +370,30 @@ def _check_view_mask(view_mask, features):
 def _mask_bytes(view_mask, features):
     """the checked mask as the library reads it: contiguous uint8 on features.device, nonzero = present"""
     return (view_mask != 0).to(device=features.device, dtype=torch.uint8).contiguous()
+
+
+def _check_view_weights(view_weights, features, aggregation_method):
+    """view_weights (B, V) of a floating dtype, any device: raises TypeError / RuntimeError as _check_view_mask does, ValueError for 'max'"""
+    if not torch.is_tensor(view_weights):
+        raise TypeError("unprojection: view_weights must be a (B, V) floating tensor, got %s" % type(view_weights).__name__)
+    if not view_weights.dtype.is_floating_point:
+        raise TypeError("unprojection: view_weights must be a floating dtype (a bool / integer tensor is a view_mask), got %s" % view_weights.dtype)
+    if tuple(view_weights.shape) != tuple(features.shape[:2]):
+        raise RuntimeError("unprojection: view_weights must be %s, got %s" % (tuple(features.shape[:2]), tuple(view_weights.shape)))
+    if aggregation_method == "max":
+        raise ValueError("unprojection: aggregation_method 'max' has no weighted form (pass a view_mask, not view_weights)")
+
+
+def _weights_fp32(view_weights, features):
+    """the checked weights as the library reads them: contiguous fp32 on features.device (no detach: the cast carries the gradient back)"""
+    return view_weights.to(device=features.device, dtype=torch.float32).contiguous()
+
+
+def _weighted_mask(view_mask, features):
+    """the weighted ops' view_mask: the caller's, or all present"""
+    if view_mask is None:
+        return torch.ones(tuple(features.shape[:2]), dtype=torch.uint8, device=features.device)
+    return _mask_bytes(view_mask, features)
 
 
 # DLT triangulation (mvhmr_triangulate_dlt[_weighted] and mvhmr_triangulate_dlt_backward) as mvhmr::triangulate_dlt[_backward]: proj (B,V,3,4),
@@ -390,14 +444,14 @@ _register_dlt_op()
 
 
 def unprojection_cuboid(features, proj_matricies, rotations, centers, position, sides, volume_shape,
-                        aggregation_method='softmax', *, out_dtype=None, variant='auto', view_mask=None):
+                        aggregation_method='softmax', *, out_dtype=None, variant='auto', view_mask=None, view_weights=None):
     """`unprojection` for the volumes VolumeGenerator builds (aggregation.py:138-187), without the coordinate tensor: voxel centres
     are rot[b] @ (position + sides / (S - 1) * (i,j,k) - center[b]) + center[b], evaluated inside the kernels (bit-equal to
     mvhmr_build_coord_volumes followed by `unprojection`).
 
     rotations (B,3,3) and centers (B,3): float32 tensors on features.device; position, sides: 3 numbers each (cuboid corner and
-    edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers.  view_mask: as for
-    `unprojection`."""
+    edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers (and view_weights).
+    view_mask, view_weights: as for `unprojection`."""
     def checked_shape(B):
         if tuple(rotations.shape) != (B, 3, 3) or tuple(centers.shape) != (B, 3):
             raise RuntimeError("unprojection: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
@@ -406,6 +460,8 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
 
     if view_mask is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_view_mask(view_mask, features)
+    if view_weights is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_view_weights(view_weights, features, aggregation_method)
     out_dtype, vol, empty = _check_call(features, proj_matricies, (rotations, centers), checked_shape, aggregation_method, variant,
                                         out_dtype, same_device=False)
     if empty is not None:
@@ -415,6 +471,11 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     proj = proj_matricies.to(device=dev, dtype=torch.float32).contiguous()
     rot = rotations.to(device=dev, dtype=torch.float32).contiguous()
     cen = centers.to(device=dev, dtype=torch.float32).contiguous()
+    if view_weights is not None:
+        return torch.ops.mvhmr.unprojection_cuboid_weighted(features, proj, rot, cen, _weighted_mask(view_mask, features),
+                                                            _weights_fp32(view_weights, features), [float(x) for x in position],
+                                                            [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method],
+                                                            _dtype_code(out_dtype), _capi.VARIANT[variant])
     if view_mask is not None:
         return torch.ops.mvhmr.unprojection_cuboid_masked(features, proj, rot, cen, _mask_bytes(view_mask, features), [float(x) for x in position],
                                                           [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method],
@@ -535,6 +596,17 @@ class _FusedAggregate(torch.autograd.Function):
         return (gx, gw, gb) + g_geo + (None,) * 5
 
 
+def _effective_weights(view_mask, view_weights, like):
+    """-> (present (B, V) bool, the DLT's confidences (B, V) fp32) on like.device: the mask as 0 / 1, or the weights where mask and w > 0
+    (differentiable w.r.t. view_weights) and 0 elsewhere"""
+    present = None if view_mask is None else view_mask.to(device=like.device) != 0
+    if view_weights is None:
+        return present, present.to(torch.float32)
+    w = view_weights.to(device=like.device, dtype=torch.float32)
+    present = (w > 0) if present is None else present & (w > 0)
+    return present, torch.where(present, w, torch.zeros((), dtype=torch.float32, device=like.device))
+
+
 def pack_cameras(cameras, device):
     """One pass over batch['cameras'] (list[V] of list[B] of Camera) -> float64 device tensors K (B,V,3,3) and Rt (B,V,3,4).
     A data loader that hands `batch['cameras_packed'] = pack_cameras(...)` (or builds the two tensors itself) lets
@@ -597,14 +669,15 @@ class VolumeGenerator(nn.Module):
             return [0, 0, 1]
         raise ValueError("Unknown kind: {}".format(self.kind))  # the reference fails with UnboundLocalError here
 
-    def volume_pose(self, batch, proj_matricies_org, images_shape, view_mask=None):
+    def volume_pose(self, batch, proj_matricies_org, images_shape, view_mask=None, view_weights=None):
         """Per-sample rotation (B,3,3) and pivot (B,3), float32 numpy/tensor (aggregation.py:163-181).
 
         Training draws theta ~ U(0, 2 pi) from the GLOBAL numpy stream, one draw per sample in order
         (quirk Q6); eval uses theta = 0.  The pivot is keypoints_3d[b][6, :3], or the DLT-triangulated
         image centre when use_triangulation is set -- a function of proj_matricies_org that carries its gradient (the reference
         triangulates from the caller's proj_matricies with torch.svd).  With a view mask (B, V) the pivot is the weighted DLT with the mask as
-        the confidences, on projections whose masked rows are zeroed first (0 * NaN is not 0); fewer than two present views is undefined."""
+        the confidences, on projections whose masked rows are zeroed first (0 * NaN is not 0); fewer than two present views is undefined.
+        With view_weights (B, V) the confidences are the effective weights (mask ? w : 0 where w > 0, else 0), which carry their gradient."""
         batch_size = proj_matricies_org.shape[0]
         axis = self.rotation_axis()
         if self.training:
@@ -624,13 +697,13 @@ class VolumeGenerator(nn.Module):
             # one batched DLT on the device, no per-sample .cpu(); stays a device tensor
             n_views = proj_matricies_org.shape[1]
             images_center = (torch.tensor(images_shape, dtype=torch.float32) / 2).expand(n_views, 2)
-            if view_mask is None:
+            if view_mask is None and view_weights is None:
                 centers = multiview.triangulate_points_from_multiple_views_linear_batch(proj_matricies_org, images_center)   # differentiable
             else:
-                present = view_mask.to(device=proj_matricies_org.device) != 0
+                present, conf = _effective_weights(view_mask, view_weights, proj_matricies_org)
                 P = torch.where(present[:, :, None, None], proj_matricies_org, torch.zeros((), dtype=proj_matricies_org.dtype,
                                                                                           device=proj_matricies_org.device))
-                centers = multiview.triangulate_points_from_multiple_views_linear_batch(P, images_center, present.to(torch.float32))
+                centers = multiview.triangulate_points_from_multiple_views_linear_batch(P, images_center, conf)
         else:
             kp = batch['keypoints_3d']
             if torch.is_tensor(kp):                                          # already a (B, 17, 3|4) tensor (any device)
@@ -672,14 +745,20 @@ class VolumeGenerator(nn.Module):
         view_mask = batch.get('view_mask')                                  # optional (B, V): per-sample present views
         if view_mask is not None:
             _check_view_mask(view_mask, proj)                               # (only its (B, V) leading shape is read)
-        rots, centers = (self.volume_pose(batch, proj_org, images_shape) if view_mask is None
-                         else self.volume_pose(batch, proj_org, images_shape, view_mask))
+        view_weights = batch.get('view_weights')                            # optional (B, V): per-view confidences
+        if view_weights is not None:
+            _check_view_weights(view_weights, proj, self.aggregation_method)
+        if view_weights is not None:
+            rots, centers = self.volume_pose(batch, proj_org, images_shape, view_mask, view_weights)
+        else:
+            rots, centers = (self.volume_pose(batch, proj_org, images_shape) if view_mask is None
+                             else self.volume_pose(batch, proj_org, images_shape, view_mask))
         cub = self.cuboid()
         S = self.volume_size
         rots = rots.to(device=device, dtype=torch.float32).contiguous()
         centers = centers.to(device=device, dtype=torch.float32).contiguous()
 
-        if view_mask is None and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask does not take)
+        if view_mask is None and view_weights is None and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask or weights do not take)
             # 1x1 conv and layout pass in one MFMA GEMM, its output only ever exists in the layout the brick forward stages
             conv = self.process_feature[0]
             return _FusedAggregate.apply(features, conv.weight, conv.bias, proj, rots, centers, tuple(cub.position), tuple(cub.sides),
@@ -690,6 +769,8 @@ class VolumeGenerator(nn.Module):
         features = features.view(batch_size, n_views, *features.shape[1:])
         # the coordinate volumes (aggregation.py:138-187) are never materialised: the kernels evaluate the cuboid recipe per voxel
         masked = {} if view_mask is None else {"view_mask": view_mask}       # (an unmasked batch calls exactly as before)
+        if view_weights is not None:
+            masked["view_weights"] = view_weights
         return unprojection_cuboid(features, proj, rots, centers, cub.position, cub.sides, (S, S, S),
                                    aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **masked)
 

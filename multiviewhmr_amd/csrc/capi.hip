@@ -270,6 +270,32 @@ int mask_refused(const mvhmr_unproject_desc *desc)
     if (desc->variant == MVHMR_VARIANT_BRICK) return fail(MVHMR_ERR_UNSUPPORTED, "a view mask runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
     return MVHMR_OK;
 }
+// ---- per-view confidence weights (include/mvhmr_unproject.h): the packed route of the masks -- presence is mask && weight > 0,
+// the weights are packed into slot order beside the projections (Problem::view_weights) and the gather / geometry kernels launch their
+// weighted instances.  Null weights are the masked (or unmasked) call.  Refused where a mask is, and for max, which has no weighted form.
+int weights_refused(const mvhmr_unproject_desc *desc)
+{
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "view weights need planar or channels-last features (quad-planar copies: pass the planar features)");
+    if (desc->variant == MVHMR_VARIANT_BRICK) return fail(MVHMR_ERR_UNSUPPORTED, "view weights run the gather kernels: MVHMR_VARIANT_BRICK is not served");
+    if (desc->method == MVHMR_AGG_MAX) return fail(MVHMR_ERR_UNSUPPORTED, "aggregation method max has no weighted form: pass a view mask instead of view weights");
+    return MVHMR_OK;
+}
+// what selects the packed route of a call, and whether the descriptor can take it
+struct Views {
+    const uint8_t *mask;
+    const float *weights;
+    bool packed() const { return mask || weights; }
+};
+int views_refused(const mvhmr_unproject_desc *desc, const Views &w)
+{
+    int rc = MVHMR_OK;
+    if (w.mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
+    return w.weights ? weights_refused(desc) : MVHMR_OK;
+}
+// the three kinds of plan: every view, a mask, weights (with or without a mask)
+enum class Pack { None, Masked, Weighted };
+Pack pack_of(const Views &w) { return w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None; }
 // the descriptor and problem of the packed call; view_count is set once the table exists (pack_views)
 void mask_route(mvhmr_unproject_desc *desc, Problem *p)
 {
@@ -292,20 +318,22 @@ unsigned char *at(void *workspace, size_t offset) { return offset == kNoRegion ?
 struct MaskHead {
     size_t table = kNoRegion, feat = kNoRegion, grad = kNoRegion;
 };
-MaskHead plan_mask_head(Arena &a, const Problem &p, int copies)
+MaskHead plan_mask_head(Arena &a, const Problem &p, int copies, bool weighted = false)
 {
     MaskHead h;
-    h.table = a.take(align_up(view_table_bytes(p.B, p.V)));
+    h.table = a.take(align_up(weighted ? weighted_view_table_bytes(p.B, p.V) : view_table_bytes(p.B, p.V)));
     h.feat = a.take(align_up((size_t)p.B * p.V * masked_view_bytes(p)));
     if (copies > 1) h.grad = a.take(align_up((size_t)p.B * p.V * masked_view_bytes(p)));
     return h;
 }
 // builds the table, packs the features; from here on the call reads the packed features and projections
-int pack_views(const MaskHead &h, const uint8_t *mask, void *workspace, const void **features, const float **proj, Problem &p, hipStream_t s)
+int pack_views(const MaskHead &h, const Views &w, void *workspace, const void **features, const float **proj, Problem &p, hipStream_t s)
 {
     void *table = at(workspace, h.table);
-    int rc = launched(launch_view_table(mask, *proj, table, p.B, p.V, s), "view table");
+    int rc = launched(w.weights ? launch_view_table_weighted(w.mask, w.weights, *proj, table, p.B, p.V, s) : launch_view_table(w.mask, *proj, table, p.B, p.V, s),
+                      "view table");
     if (rc != MVHMR_OK) return rc;
+    if (w.weights) p.view_weights = view_table_weights(table, p.B, p.V);
     rc = launched(launch_view_pack(*features, at(workspace, h.feat), table, p.B, p.V, masked_view_bytes(p), s), "view pack");
     if (rc != MVHMR_OK) return rc;
     p.view_count = view_table_counts(table);
@@ -324,15 +352,15 @@ struct ForwardPlan {
     size_t gate = kNoRegion;
     size_t total = 0;                           // a masked call's workspace also serves the unmasked one (a null mask)
 };
-ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, bool masked)
+ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pack pack)
 {
     ForwardPlan f;
     Arena a;
     f.desc = *desc;
     f.p = p;
-    if (masked) {
+    if (pack != Pack::None) {
         mask_route(&f.desc, &f.p);
-        f.head = plan_mask_head(a, p, 1);
+        f.head = plan_mask_head(a, p, 1, pack == Pack::Weighted);
     }
     const mvhmr_unproject_desc *d = &f.desc;
     const bool brick = pick_variant(d, f.p) == MVHMR_VARIANT_BRICK;
@@ -347,7 +375,8 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, boo
     } else if (d->feat_layout == MVHMR_LAYOUT_BVCHW) {
         f.staged = a.take(brick_workspace_bytes(f.p));
     }
-    f.total = masked ? max_size(a.top, plan_forward(desc, p, false).total) : a.top;
+    // (a weighted call's workspace also serves the masked one, a masked call's the unmasked one)
+    f.total = pack == Pack::None ? a.top : max_size(a.top, plan_forward(desc, p, pack == Pack::Weighted ? Pack::Masked : Pack::None).total);
     return f;
 }
 
@@ -411,15 +440,15 @@ void place_det_backward(BackwardPlan &b, Arena &a)
     b.acc = a.take(det_acc_bytes(p));
     b.scale = a.take(align_up(det_scale_bytes(p)));
 }
-BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, bool det, bool masked)
+BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, bool det, Pack pack)
 {
     BackwardPlan b;
     Arena a;
     b.desc = *desc;
     b.p = p;
-    if (masked) {
+    if (pack != Pack::None) {
         mask_route(&b.desc, &b.p);
-        b.head = plan_mask_head(a, p, 2);
+        b.head = plan_mask_head(a, p, 2, pack == Pack::Weighted);
     }
     if (det) {
         BackwardPlan dflt = b;
@@ -430,7 +459,7 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
     } else {
         place_default_backward(b, a);
     }
-    b.total = masked ? max_size(a.top, plan_backward(desc, p, det, false).total) : a.top;
+    b.total = pack == Pack::None ? a.top : max_size(a.top, plan_backward(desc, p, det, pack == Pack::Weighted ? Pack::Masked : Pack::None).total);
     return b;
 }
 
@@ -443,23 +472,29 @@ struct GeometryPlan {
     size_t packed_grad_proj = kNoRegion;        // masked: grad_proj (B,V,3,4) in slot order, unpacked at the end
     size_t staged = kNoRegion;
     size_t part = kNoRegion, pose_part = kNoRegion;
+    size_t packed_grad_weights = kNoRegion;     // weighted: grad_weights (B,V) in slot order, unpacked at the end; weight_part: its fp32 partials
+    size_t weight_part = kNoRegion;
     size_t total = 0;
 };
-GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, bool cuboid, bool masked)
+GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, bool cuboid, Pack pack)
 {
     GeometryPlan g;
     Arena a;
     g.desc = *desc;
     g.p = p;
-    if (masked) {
+    if (pack != Pack::None) {
         mask_route(&g.desc, &g.p);
-        g.head = plan_mask_head(a, p, 1);
+        g.head = plan_mask_head(a, p, 1, pack == Pack::Weighted);
         g.packed_grad_proj = a.take(align_up((size_t)p.B * p.V * 12 * sizeof(float)));
+    }
+    if (pack == Pack::Weighted) {
+        g.packed_grad_weights = a.take(align_up((size_t)p.B * p.V * sizeof(float)));
+        g.weight_part = a.take(align_up(geom_weight_partial_bytes(p)));
     }
     if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) g.staged = a.take(featT_bytes(p));
     g.part = a.take(align_up(geom_partial_bytes(p)));
     if (cuboid) g.pose_part = a.take(align_up(pose_partial_bytes(p)));
-    g.total = masked ? max_size(a.top, plan_geometry(desc, p, cuboid, false).total) : a.top;
+    g.total = pack == Pack::None ? a.top : max_size(a.top, plan_geometry(desc, p, cuboid, pack == Pack::Weighted ? Pack::Masked : Pack::None).total);
     return g;
 }
 
@@ -498,7 +533,7 @@ int query_variant(const mvhmr_unproject_desc *desc, const VolumeSource &v, const
 }
 
 // ---- forward
-int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *features, const float *proj, const uint8_t *mask, void *out,
+int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *features, const float *proj, const Views &views, void *out,
                 void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     Problem p0;
@@ -506,7 +541,7 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
     int rc = open_call(desc, v, &p0, &coords);
     if (rc != MVHMR_OK) return rc;
     if (!features || !proj || !out) return fail(MVHMR_ERR_INVALID_ARGUMENT, "features / proj / out must be non-null");
-    if (mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
+    if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     mvhmr_unproject_desc dq;
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) {
@@ -520,14 +555,14 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
         desc = &dq;
         p0.feat_log2e = 1;
     }
-    ForwardPlan f = plan_forward(desc, p0, mask != nullptr);
+    ForwardPlan f = plan_forward(desc, p0, pack_of(views));
     desc = &f.desc;
     Problem &p = f.p;
     rc = variant_conflict(desc, p, pick_variant(desc, p));
     if (rc != MVHMR_OK) return rc;
     rc = check_ws(workspace, workspace_bytes, f.total);
     if (rc != MVHMR_OK) return rc;
-    if (mask && (rc = pack_views(f.head, mask, workspace, &features, &proj, p, s)) != MVHMR_OK) return rc;
+    if (views.packed() && (rc = pack_views(f.head, views, workspace, &features, &proj, p, s)) != MVHMR_OK) return rc;
     // planar input whose staged copy this call makes itself: scaled by log2(e) when the kernel that reads it wants that
     if (desc->feat_layout == MVHMR_LAYOUT_BVCHW && brick_fwd_prescales(p)) p.feat_log2e = 1;
 
@@ -688,7 +723,7 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
 }
 
 int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
-                 const uint8_t *mask, bool det, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+                 const Views &views, bool det, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     Problem p0;
     Coords coords;
@@ -696,31 +731,33 @@ int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     if (rc != MVHMR_OK) return rc;
     if (!grad_out || !features || !proj || !grad_features)
         return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
-    if (mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
+    if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
         return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p0) && !quad_to_channels_last_supported(p0))
         return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
-    BackwardPlan b = plan_backward(desc, p0, det, mask != nullptr);
+    BackwardPlan b = plan_backward(desc, p0, det, pack_of(views));
     rc = check_ws(workspace, workspace_bytes, b.total);
     if (rc != MVHMR_OK) return rc;
     if (b.desc.variant == MVHMR_VARIANT_BRICK && !bwd_uses_brick(&b.desc, b.p))
         return fail(MVHMR_ERR_UNSUPPORTED, "the brick variant does not support this shape / dtype / layout");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (mask && (rc = pack_views(b.head, mask, workspace, &features, &proj, b.p, s)) != MVHMR_OK) return rc;
-    // a masked call's gradient comes in slot order and is unpacked into view order, masked views zero-filled
-    void *grad = mask ? at(workspace, b.head.grad) : grad_features;
+    const bool packed = views.packed();
+    if (packed && (rc = pack_views(b.head, views, workspace, &features, &proj, b.p, s)) != MVHMR_OK) return rc;
+    // a masked or weighted call's gradient comes in slot order and is unpacked into view order, absent views zero-filled
+    void *grad = packed ? at(workspace, b.head.grad) : grad_features;
     const BackwardArgs c{grad_out, features, proj, &coords, grad, workspace, s};
     rc = det ? launch_backward_det(b, c) : launch_backward_default(b, c);
-    if (rc != MVHMR_OK || !mask) return rc;
+    if (rc != MVHMR_OK || !packed) return rc;
     return launched(launch_view_unpack(grad, grad_features, at(workspace, b.head.table), b.p.B, b.p.V, masked_view_bytes(b.p), s), "view unpack");
 }
 
 // ---- geometry backward
 int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
-                 const uint8_t *mask, float *grad_proj, float *grad_coords, float *grad_rot, float *grad_center, void *workspace,
+                 const Views &views, float *grad_proj, float *grad_coords, float *grad_rot, float *grad_center, float *grad_weights, void *workspace,
                  size_t workspace_bytes, void *hip_stream)
 {
+    const bool mask = views.packed();
     Problem p0;
     Coords coords;
     int rc = check_desc(desc, &p0);
@@ -732,21 +769,25 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     if (!v.cuboid && !v.coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, no_tensor);
     rc = make_coords(v, p0, &coords);
     if (rc != MVHMR_OK) return rc;
-    if (!v.cuboid && !grad_proj && !grad_coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj and grad_coords are both null: nothing to compute");
-    if (v.cuboid && !grad_proj && !grad_rot && !grad_center)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_proj, grad_rot and grad_center are all null: nothing to compute");
+    if (grad_weights && !views.weights) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_weights without view_weights: nothing to differentiate");
+    if (!v.cuboid && !grad_proj && !grad_coords && !grad_weights)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, views.weights ? "grad_proj, grad_coords and grad_weights are all null: nothing to compute"
+                                                              : "grad_proj and grad_coords are both null: nothing to compute");
+    if (v.cuboid && !grad_proj && !grad_rot && !grad_center && !grad_weights)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, views.weights ? "grad_proj, grad_rot, grad_center and grad_weights are all null: nothing to compute"
+                                                              : "grad_proj, grad_rot and grad_center are all null: nothing to compute");
     if (!data) return fail(MVHMR_ERR_INVALID_ARGUMENT, no_data);
-    if (mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
+    if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
         return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p0))
         return fail(MVHMR_ERR_UNSUPPORTED, "quad-planar features of this shape cannot be converted to channels-last (C %% 4 == 0, C <= 4092, B * V <= 65535)");
-    GeometryPlan g = plan_geometry(desc, p0, v.cuboid, mask != nullptr);
+    GeometryPlan g = plan_geometry(desc, p0, v.cuboid, pack_of(views));
     rc = check_ws(workspace, workspace_bytes, g.total);
     if (rc != MVHMR_OK) return rc;
     const Problem &p = g.p;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (mask && (rc = pack_views(g.head, mask, workspace, &features, &proj, g.p, s)) != MVHMR_OK) return rc;
+    if (mask && (rc = pack_views(g.head, views, workspace, &features, &proj, g.p, s)) != MVHMR_OK) return rc;
     // a masked call's grad_proj comes in slot order behind the head and is unpacked; the other gradients are per sample
     float *gp = mask && grad_proj ? reinterpret_cast<float *>(at(workspace, g.packed_grad_proj)) : grad_proj;
     void *staged = at(workspace, g.staged);
@@ -756,34 +797,44 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     }
     const void *featT = staged ? staged : features;
     float *part = gp ? reinterpret_cast<float *>(at(workspace, g.part)) : nullptr;
+    // grad_weights likewise: fp32 partials, summed into slot order, unpacked (absent views zero-filled)
+    float *gw = grad_weights ? reinterpret_cast<float *>(at(workspace, g.packed_grad_weights)) : nullptr;
+    float *wpart = grad_weights ? reinterpret_cast<float *>(at(workspace, g.weight_part)) : nullptr;
     if (v.cuboid) {
         float *pose_part = (grad_rot || grad_center) ? reinterpret_cast<float *>(at(workspace, g.pose_part)) : nullptr;
-        rc = launched(launch_bwd_geom_cuboid(grad_out, featT, proj, coords, part, gp, pose_part, grad_rot, grad_center, p, s), "cuboid geometry backward");
+        rc = launched(launch_bwd_geom_cuboid(grad_out, featT, proj, coords, part, gp, pose_part, grad_rot, grad_center, p, s, wpart, gw), "cuboid geometry backward");
     } else {
-        rc = launched(launch_bwd_geom(grad_out, featT, proj, coords, part, gp, grad_coords, p, s), "geometry backward");
+        rc = launched(launch_bwd_geom(grad_out, featT, proj, coords, part, gp, grad_coords, p, s, wpart, gw), "geometry backward");
     }
-    if (rc != MVHMR_OK || !mask || !grad_proj) return rc;
-    return launched(launch_view_unpack(gp, grad_proj, at(workspace, g.head.table), p.B, p.V, 12 * sizeof(float), s), "view unpack");
+    if (rc != MVHMR_OK || !mask) return rc;
+    if (grad_proj && (rc = launched(launch_view_unpack(gp, grad_proj, at(workspace, g.head.table), p.B, p.V, 12 * sizeof(float), s), "view unpack")) != MVHMR_OK)
+        return rc;
+    if (!grad_weights) return rc;
+    return launched(launch_view_unpack(gw, grad_weights, at(workspace, g.head.table), p.B, p.V, sizeof(float), s), "view unpack");
 }
 
 // the workspace queries: a descriptor the call would refuse outright needs none
-size_t forward_need(const mvhmr_unproject_desc *desc, bool masked)
+bool pack_refused(const mvhmr_unproject_desc *desc, Pack pack)
 {
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || (masked && mask_refused(desc) != MVHMR_OK)) return 0;
-    return plan_forward(desc, p, masked).total;
+    return (pack == Pack::Masked && mask_refused(desc) != MVHMR_OK) || (pack == Pack::Weighted && weights_refused(desc) != MVHMR_OK);
 }
-size_t backward_need(const mvhmr_unproject_desc *desc, bool det, bool masked)
+size_t forward_need(const mvhmr_unproject_desc *desc, Pack pack)
 {
     Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E || (masked && mask_refused(desc) != MVHMR_OK)) return 0;
-    return plan_backward(desc, p, det, masked).total;
+    if (check_desc(desc, &p) != MVHMR_OK || pack_refused(desc, pack)) return 0;
+    return plan_forward(desc, p, pack).total;
 }
-size_t geometry_need(const mvhmr_unproject_desc *desc, bool cuboid, bool masked)
+size_t backward_need(const mvhmr_unproject_desc *desc, bool det, Pack pack)
 {
     Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E || (masked && mask_refused(desc) != MVHMR_OK)) return 0;
-    return plan_geometry(desc, p, cuboid, masked).total;
+    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E || pack_refused(desc, pack)) return 0;
+    return plan_backward(desc, p, det, pack).total;
+}
+size_t geometry_need(const mvhmr_unproject_desc *desc, bool cuboid, Pack pack)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E || pack_refused(desc, pack)) return 0;
+    return plan_geometry(desc, p, cuboid, pack).total;
 }
 
 }  // namespace
@@ -850,73 +901,73 @@ int mvhmr_unproject_backward_supported(const mvhmr_unproject_desc *desc)
 }
 
 
-size_t mvhmr_unproject_forward_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, false); }
-size_t mvhmr_unproject_backward_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, false); }
-size_t mvhmr_unproject_backward_deterministic_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, false); }
-size_t mvhmr_unproject_backward_geometry_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, false); }
-size_t mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, false); }
-size_t mvhmr_unproject_forward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, true); }
-size_t mvhmr_unproject_forward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, true); }
-size_t mvhmr_unproject_backward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, true); }
-size_t mvhmr_unproject_backward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, true); }
-size_t mvhmr_unproject_backward_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, true); }
-size_t mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, true); }
-size_t mvhmr_unproject_backward_geometry_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, true); }
-size_t mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, true); }
+size_t mvhmr_unproject_forward_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::None); }
+size_t mvhmr_unproject_backward_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::None); }
+size_t mvhmr_unproject_backward_deterministic_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::None); }
+size_t mvhmr_unproject_backward_geometry_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::None); }
+size_t mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::None); }
+size_t mvhmr_unproject_forward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Masked); }
+size_t mvhmr_unproject_forward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Masked); }
+size_t mvhmr_unproject_backward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Masked); }
+size_t mvhmr_unproject_backward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Masked); }
+size_t mvhmr_unproject_backward_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Masked); }
+size_t mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Masked); }
+size_t mvhmr_unproject_backward_geometry_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Masked); }
+size_t mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Masked); }
 
 // The launching entry points: each names what places the volume (tensor / cuboid), the mask (null: none) and, for the feature backward,
 // the mode, and forwards to the one route of its kind of call.
 int mvhmr_unproject_forward(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
                             void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_forward(desc, tensor_volume(coords), features, proj, nullptr, out, workspace, workspace_bytes, hip_stream);
+    return run_forward(desc, tensor_volume(coords), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_forward_cuboid(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
                                    const float *center, const double position[3], const double sides[3], void *out, void *workspace,
                                    size_t workspace_bytes, void *hip_stream)
 {
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, nullptr, out, workspace, workspace_bytes, hip_stream);
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_forward_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
                                    const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_forward(desc, tensor_volume(coords), features, proj, view_mask, out, workspace, workspace_bytes, hip_stream);
+    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, nullptr}, out, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_forward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
                                           const float *center, const double position[3], const double sides[3], const uint8_t *view_mask,
                                           void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, view_mask, out, workspace, workspace_bytes, hip_stream);
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, nullptr}, out, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                              const float *coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, nullptr, false, grad_features, workspace, workspace_bytes, hip_stream);
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                                     const float *rot, const float *center, const double position[3], const double sides[3],
                                     void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, nullptr, false, grad_features, workspace,
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace,
                         workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                                            const float *coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, nullptr, true, grad_features, workspace, workspace_bytes, hip_stream);
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_cuboid_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                                                   const float *rot, const float *center, const double position[3], const double sides[3],
                                                   void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, nullptr, true, grad_features, workspace,
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace,
                         workspace_bytes, hip_stream);
 }
 
@@ -924,14 +975,14 @@ int mvhmr_unproject_backward_masked(const mvhmr_unproject_desc *desc, const void
                                     const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes,
                                     void *hip_stream)
 {
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, view_mask, false, grad_features, workspace, workspace_bytes, hip_stream);
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr}, false, grad_features, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                                            const float *rot, const float *center, const double position[3], const double sides[3],
                                            const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, view_mask, false, grad_features, workspace,
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr}, false, grad_features, workspace,
                         workspace_bytes, hip_stream);
 }
 
@@ -939,7 +990,7 @@ int mvhmr_unproject_backward_deterministic_masked(const mvhmr_unproject_desc *de
                                                   const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace,
                                                   size_t workspace_bytes, void *hip_stream)
 {
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, view_mask, true, grad_features, workspace, workspace_bytes, hip_stream);
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr}, true, grad_features, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_cuboid_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
@@ -947,7 +998,7 @@ int mvhmr_unproject_backward_cuboid_deterministic_masked(const mvhmr_unproject_d
                                                          const double sides[3], const uint8_t *view_mask, void *grad_features, void *workspace,
                                                          size_t workspace_bytes, void *hip_stream)
 {
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, view_mask, true, grad_features, workspace,
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr}, true, grad_features, workspace,
                         workspace_bytes, hip_stream);
 }
 
@@ -955,8 +1006,8 @@ int mvhmr_unproject_backward_geometry(const mvhmr_unproject_desc *desc, const vo
                                       const float *coords, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes,
                                       void *hip_stream)
 {
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, nullptr, grad_proj, grad_coords, nullptr, nullptr, workspace,
-                        workspace_bytes, hip_stream);
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
+                        workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
@@ -964,16 +1015,16 @@ int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, c
                                              float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
                                              void *hip_stream)
 {
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, nullptr, grad_proj, nullptr, grad_rot, grad_center,
-                        workspace, workspace_bytes, hip_stream);
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, nullptr, grad_rot,
+                        grad_center, nullptr, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_geometry_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
                                              const float *coords, const uint8_t *view_mask, float *grad_proj, float *grad_coords, void *workspace,
                                              size_t workspace_bytes, void *hip_stream)
 {
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, view_mask, grad_proj, grad_coords, nullptr, nullptr, workspace,
-                        workspace_bytes, hip_stream);
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
+                        workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_unproject_backward_geometry_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
@@ -981,8 +1032,85 @@ int mvhmr_unproject_backward_geometry_cuboid_masked(const mvhmr_unproject_desc *
                                                     const uint8_t *view_mask, float *grad_proj, float *grad_rot, float *grad_center, void *workspace,
                                                     size_t workspace_bytes, void *hip_stream)
 {
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, view_mask, grad_proj, nullptr, grad_rot,
-                        grad_center, workspace, workspace_bytes, hip_stream);
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr}, grad_proj, nullptr, grad_rot,
+                        grad_center, nullptr, workspace, workspace_bytes, hip_stream);
+}
+
+// ---- per-view confidence weights: the _masked entry points with `view_weights` beside `view_mask` (either may be null)
+size_t mvhmr_unproject_forward_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Weighted); }
+size_t mvhmr_unproject_forward_cuboid_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Weighted); }
+size_t mvhmr_unproject_backward_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Weighted); }
+size_t mvhmr_unproject_backward_cuboid_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Weighted); }
+size_t mvhmr_unproject_backward_deterministic_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Weighted); }
+size_t mvhmr_unproject_backward_cuboid_deterministic_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Weighted); }
+size_t mvhmr_unproject_backward_geometry_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Weighted); }
+size_t mvhmr_unproject_backward_geometry_cuboid_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Weighted); }
+
+int mvhmr_unproject_forward_weighted(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+                                     const uint8_t *view_mask, const float *view_weights, void *out, void *workspace, size_t workspace_bytes,
+                                     void *hip_stream)
+{
+    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, view_weights}, out, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_forward_cuboid_weighted(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
+                                            const float *center, const double position[3], const double sides[3], const uint8_t *view_mask,
+                                            const float *view_weights, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, view_weights}, out, workspace, workspace_bytes,
+                       hip_stream);
+}
+
+int mvhmr_unproject_backward_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                      const float *coords, const uint8_t *view_mask, const float *view_weights, void *grad_features, void *workspace,
+                                      size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, view_weights}, false, grad_features, workspace,
+                        workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                             const float *rot, const float *center, const double position[3], const double sides[3],
+                                             const uint8_t *view_mask, const float *view_weights, void *grad_features, void *workspace,
+                                             size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, view_weights}, false, grad_features,
+                        workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_deterministic_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                    const float *coords, const uint8_t *view_mask, const float *view_weights, void *grad_features,
+                                                    void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, view_weights}, true, grad_features, workspace,
+                        workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_deterministic_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
+                                                           const float *proj, const float *rot, const float *center, const double position[3],
+                                                           const double sides[3], const uint8_t *view_mask, const float *view_weights,
+                                                           void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, view_weights}, true, grad_features,
+                        workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                               const float *coords, const uint8_t *view_mask, const float *view_weights, float *grad_proj,
+                                               float *grad_coords, float *grad_weights, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, view_weights}, grad_proj, grad_coords, nullptr, nullptr,
+                        grad_weights, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_cuboid_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                      const float *rot, const float *center, const double position[3], const double sides[3],
+                                                      const uint8_t *view_mask, const float *view_weights, float *grad_proj, float *grad_rot,
+                                                      float *grad_center, float *grad_weights, void *workspace, size_t workspace_bytes,
+                                                      void *hip_stream)
+{
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, view_weights}, grad_proj, nullptr,
+                        grad_rot, grad_center, grad_weights, workspace, workspace_bytes, hip_stream);
 }
 
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)

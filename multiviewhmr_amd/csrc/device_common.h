@@ -321,6 +321,82 @@ __device__ __forceinline__ void masked_aggregate_grad(float (&s)[V], float g, fl
     }
 }
 
+// Per-view confidence weights: slot v < nv carries the weight w[v] > 0 of a present view, slots nv .. V - 1 are absent
+// (the kernels hand them s = 0, the table w = 0) and take no part.  W = sum w_v; sum = sum w_v s_v, mean = that / W, softmax
+// p_v = w_v e^{s_v} / sum_u w_u e^{s_u}, the exponentials relative to the present views' maximum.  No weighted max.
+template <int METHOD, int V>
+__device__ __forceinline__ float weighted_aggregate(const float (&s)[V], const float (&w)[V], int nv)
+{
+    static_assert(METHOD != AGG_MAX, "max has no weighted form");
+    if constexpr (METHOD == AGG_SUM || METHOD == AGG_MEAN) {
+        float r = 0.f, W = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            r = v < nv ? fmaf(w[v], s[v], r) : r;
+            W = v < nv ? W + w[v] : W;
+        }
+        return METHOD == AGG_MEAN ? __fdiv_rn(r, W) : r;
+    } else {
+        float m = s[0];
+#pragma unroll
+        for (int v = 1; v < V; ++v) m = v < nv ? fmaxf(m, s[v]) : m;
+        float den = 0.f, num = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float e = v < nv ? w[v] * __builtin_amdgcn_exp2f((s[v] - m) * 1.4426950408889634f) : 0.f;
+            den += e;
+            num = fmaf(e, s[v], num);
+        }
+        return __fdiv_rn(num, den);                                             // den >= the maximum's weight > 0
+    }
+}
+
+// g * d(weighted_aggregate)/d(s_v) into ds[v] and g * d(weighted_aggregate)/d(w_v) into dw[v] (the table of DESIGN.md 5.9); absent slots
+// and a sample without views get exact zeros
+template <int METHOD, int V>
+__device__ __forceinline__ void weighted_aggregate_grad(const float (&s)[V], const float (&w)[V], float g, float (&ds)[V], float (&dw)[V], int nv)
+{
+    static_assert(METHOD != AGG_MAX, "max has no weighted form");
+    if constexpr (METHOD == AGG_SUM) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            ds[v] = v < nv ? g * w[v] : 0.f;
+            dw[v] = v < nv ? g * s[v] : 0.f;
+        }
+    } else if constexpr (METHOD == AGG_MEAN) {
+        float r = 0.f, W = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            r = v < nv ? fmaf(w[v], s[v], r) : r;
+            W = v < nv ? W + w[v] : W;
+        }
+        const float gW = W > 0.f ? __fdiv_rn(g, W) : 0.f, o = W > 0.f ? __fdiv_rn(r, W) : 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            ds[v] = v < nv ? gW * w[v] : 0.f;
+            dw[v] = v < nv ? gW * (s[v] - o) : 0.f;
+        }
+    } else {
+        float m = s[0];
+#pragma unroll
+        for (int v = 1; v < V; ++v) m = v < nv ? fmaxf(m, s[v]) : m;
+        float e[V], den = 0.f, num = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            e[v] = v < nv ? __builtin_amdgcn_exp2f((s[v] - m) * 1.4426950408889634f) : 0.f;      // p_v / w_v, before the division
+            den = fmaf(w[v], e[v], den);
+            num = fmaf(w[v] * e[v], s[v], num);
+        }
+        const float gr = den > 0.f ? __fdiv_rn(g, den) : 0.f, o = den > 0.f ? __fdiv_rn(num, den) : 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float q = gr * e[v];                                          // g p_v / w_v
+            ds[v] = v < nv ? q * w[v] * (1.f + s[v] - o) : 0.f;
+            dw[v] = v < nv ? q * (s[v] - o) : 0.f;
+        }
+    }
+}
+
 // Running form for a view count only known at run time (V > 8): one pass, same result up to rounding.
 template <int METHOD>
 struct RunningAgg {
@@ -344,6 +420,35 @@ struct RunningAgg {
         else if constexpr (METHOD == AGG_MEAN) return __fdiv_rn(num, (float)V);
         else if constexpr (METHOD == AGG_MAX) return m;
         else return num * __builtin_amdgcn_rcpf(den);
+    }
+};
+
+// the running form under per-view weights (present views only are pushed): den is W for sum / mean, sum_v w_v e^{s_v - m} for softmax
+template <int METHOD>
+struct WeightedRunningAgg {
+    float m, den, num;
+    __device__ __forceinline__ void init() { m = -INFINITY; den = 0.f; num = 0.f; }
+    __device__ __forceinline__ void push(float s, float w)
+    {
+        static_assert(METHOD != AGG_MAX, "max has no weighted form");
+        if constexpr (METHOD == AGG_SUM || METHOD == AGG_MEAN) {
+            num = fmaf(w, s, num);
+            den += w;
+        } else {
+            const float mn = fmaxf(m, s);
+            const float c = __expf(m - mn), e = w * __expf(s - mn);   // exp(-inf) = 0 on the first push
+            den = fmaf(den, c, e);
+            num = fmaf(num, c, e * s);
+            m = mn;
+        }
+    }
+    __device__ __forceinline__ float result() const { return METHOD == AGG_SUM ? num : __fdiv_rn(num, den); }
+    // g * d(result)/d(s) of a view pushed before with sample s and weight w
+    __device__ __forceinline__ float grad(float g, float s, float w) const
+    {
+        if constexpr (METHOD == AGG_SUM) return g * w;
+        else if constexpr (METHOD == AGG_MEAN) return __fdiv_rn(g, den) * w;
+        else return __fdiv_rn(g, den) * (w * __expf(s - m)) * (1.f + s - __fdiv_rn(num, den));
     }
 };
 

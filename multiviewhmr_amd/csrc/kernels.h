@@ -24,6 +24,9 @@ struct Problem {
     // View masks: per-sample count of present views (device, B ints), which the layout pass packed into view slots
     // 0 .. n_b - 1 of every sample.  Null = every view present; the kernels that take it (gather, geometry) launch MASK instances.
     const int *view_count = nullptr;
+    // Per-view confidence weights: the packed weights (device, (B, V) fp32 in slot order, > 0 for the view_count[b] present
+    // views, 0 behind them).  Null = unweighted; set together with view_count, the kernels that take it launch their weighted instances.
+    const float *view_weights = nullptr;
     // the view-mask route (set before the table exists, for the workspace queries): the gather family with the per-tap scatter backward
     int masked = 0;
 };
@@ -135,13 +138,20 @@ hipError_t launch_triangulate_dlt_bwd(const float *proj, const float *points, co
 // gradient w.r.t. proj and coords (unproject_geom_bwd.hip): featT channels-last (B,V,HW,C4) in the feature dtype; `part` holds
 // geom_partial_bytes(p) of fp32 partials of grad_proj (needed when grad_proj is non-null); either output may be null
 size_t geom_partial_bytes(const Problem &p);
+// per-view weights (Problem::view_weights): grad_weights (B, V) fp32 in SLOT order from wpart (geom_weight_partial_bytes(p) of fp32
+// partials), both null when not asked for; it may be the only output
+size_t geom_weight_partial_bytes(const Problem &p);
+// (the weighted instances of k_bwd_geom live in unproject_geom_bwd_weighted.hip; launch_bwd_geom[_cuboid] call this for them)
+hipError_t launch_bwd_geom_weighted_kernel(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part,
+                                           float *grad_coords, float *pose_part, float *wpart, bool pose, const Problem &p, hipStream_t s);
 hipError_t launch_bwd_geom(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
-                           float *grad_coords, const Problem &p, hipStream_t s);
+                           float *grad_coords, const Problem &p, hipStream_t s, float *wpart = nullptr, float *grad_weights = nullptr);
 // the same for the cuboid recipe (coords.ptr == null): grad_proj as above, and the gradients w.r.t. the pose, grad_rot (B,3,3) and
 // grad_center (B,3), from pose_part (pose_partial_bytes(p) of fp32 partials, needed when either is non-null); grad_coords is not written
 size_t pose_partial_bytes(const Problem &p);
 hipError_t launch_bwd_geom_cuboid(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
-                                  float *pose_part, float *grad_rot, float *grad_center, const Problem &p, hipStream_t s);
+                                  float *pose_part, float *grad_rot, float *grad_center, const Problem &p, hipStream_t s, float *wpart = nullptr,
+                                  float *grad_weights = nullptr);
 
 // view masks (view_mask.hip): from mask (B,V) bytes, one thread per sample writes n_b (B ints), slot -> view and view -> slot (-1: masked)
 // tables (B,V ints each) and the projections packed into slot order (absent slots zero); then per-(sample, slot) copies of `bytes_per_view`
@@ -150,6 +160,10 @@ size_t view_table_bytes(int B, int V);
 hipError_t launch_view_table(const uint8_t *mask, const float *proj, void *table, int B, int V, hipStream_t s);
 const int *view_table_counts(const void *table);
 const float *view_table_proj(const void *table, int B, int V);
+// per-view weights: presence = mask (null: all) and weight > 0; the table as above, then the weights packed into slot order (absent slots 0)
+size_t weighted_view_table_bytes(int B, int V);
+hipError_t launch_view_table_weighted(const uint8_t *mask, const float *weights, const float *proj, void *table, int B, int V, hipStream_t s);
+const float *view_table_weights(const void *table, int B, int V);
 hipError_t launch_view_pack(const void *src, void *dst, const void *table, int B, int V, size_t bytes_per_view, hipStream_t s);
 hipError_t launch_view_unpack(const void *src, void *dst, const void *table, int B, int V, size_t bytes_per_view, hipStream_t s);
 

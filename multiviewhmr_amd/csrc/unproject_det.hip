@@ -115,6 +115,27 @@ __global__ void __launch_bounds__(256) k_masked_det_exponent(const unsigned *__r
     kexp[i] = 62 - log2n - e;
 }
 
+// the same under per-view weights, wts (B, V) packed in slot order: the sum's ds is g w_v, so its bound carries the sample's
+// largest weight (without it the int64 sums can wrap); the mean's is g w_v / W <= g, the softmax's g p_v (1 + s_v - out) as unweighted
+__global__ void __launch_bounds__(256) k_weighted_det_exponent(const unsigned *__restrict__ gmax, const unsigned *__restrict__ fmax, int *__restrict__ kexp,
+                                                               long long BC, int method, int C, int V, int log2n, const float *__restrict__ wts)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= BC) return;
+    const unsigned gb = gmax[i], fb = method == AGG_SOFTMAX ? fmax[i] : 0u;
+    if (gb >= 0x7f800000u || fb >= 0x7f800000u) { kexp[i] = kDetPoison; return; }
+    const float *w = wts + (i / C) * V;
+    float wmax = 0.f;
+    for (int v = 0; v < V; ++v) wmax = fmaxf(wmax, w[v]);
+    const double g = (double)__builtin_bit_cast(float, gb), f = (double)__builtin_bit_cast(float, fb);
+    const double bound = method == AGG_SOFTMAX ? g * (1.0 + 2.0 * f) : method == AGG_SUM ? g * (double)wmax : g;
+    if (bound == 0.0) { kexp[i] = 0; return; }
+    if (!(bound < 3.4028234663852886e38)) { kexp[i] = kDetPoison; return; }   // ds itself may overflow fp32 (an infinite weight too)
+    int e;
+    frexp(bound, &e);
+    kexp[i] = 62 - log2n - e;
+}
+
 __device__ __forceinline__ float det_value(unsigned long long acc, int k)
 {
     if (k == kDetPoison) return __builtin_nanf("");
@@ -212,7 +233,10 @@ hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale,
         else hipLaunchKernelGGL(k_det_fmax<float>, g2, dim3(256), 0, s, (const float *)featT, fmax, p.V, p.C, p.C4, HW);
     }
     const int log2n = p.N > 1 ? 64 - __builtin_clzll((unsigned long long)(p.N - 1)) : 0;
-    if (p.view_count)
+    if (p.view_weights)
+        hipLaunchKernelGGL(k_weighted_det_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gmax, fmax, kexp, BC, p.method, p.C, p.V, log2n,
+                           p.view_weights);
+    else if (p.view_count)
         hipLaunchKernelGGL(k_masked_det_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gmax, fmax, kexp, BC, p.method, p.C, log2n,
                            p.view_count);
     else

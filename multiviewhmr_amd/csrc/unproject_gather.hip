@@ -458,6 +458,235 @@ k_masked_bwd_gather_det(const TO *__restrict__ grad_out, const TF *__restrict__ 
     bwd_gather_det_body<TF, TO, METHOD, VT, true>(grad_out, featT, proj, coords, gradI, kexp, Vrt, C, C4, H, W, N, gate, nvs);
 }
 
+// ------------------------------------------------------------------------------------------ per-view confidence weights
+// The gather kernels under per-view weights (include/mvhmr_unproject.h: the *_weighted entry points).  The packed route of
+// the view masks: nvs[b] present views in slots 0 .. nvs[b] - 1, and wts (B, V) their weights in slot order (> 0; 0 behind them).  Copies,
+// not template flags of k_fwd_gather / k_bwd_gather: those kernels' instances keep the code they had.  No weighted max.
+template <typename TF, typename TO, int METHOD, int VT>
+__global__ void __launch_bounds__(256)
+k_fwd_gather_weighted(const TF *__restrict__ featT, const float *__restrict__ proj, const Coords coords,
+                      TO *__restrict__ out, int Vrt, int C, int C4, int H, int W, long long N, int tstride, Gate gate, const int *__restrict__ nvs,
+                      const float *__restrict__ wts)
+{
+    if (gated_off(gate)) return;
+    const int V = VT > 0 ? VT : Vrt;
+    const int nvb = nvs[blockIdx.y];                          // present views of this sample (block-uniform)
+    const float *wb = wts + (long long)blockIdx.y * V;
+    extern __shared__ __align__(16) unsigned char smem[];
+    TapRec *recs = reinterpret_cast<TapRec *>(smem);
+    f32x4 *tile = reinterpret_cast<f32x4 *>(smem + sizeof(TapRec) * kTileVox * V);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, cg = blockIdx.z;
+    for (long long n0 = (long long)blockIdx.x * kTileVox; n0 < N; n0 += (long long)gridDim.x * kTileVox) {   // see k_fwd_gather
+    const long long mapsz = (long long)H * W * C4;
+    const int Q = C4 >> 2;
+
+    build_records(recs, proj, coords, b, V, n0, N, H, W, C4);
+    __syncthreads();
+
+    int q = cg * kGroupQuads + lane;
+    const bool q_active = q < Q;
+    q = q_active ? q : Q - 1;                                // idle lanes shadow the last quad and write nothing
+    const TF *fb = featT + (long long)b * V * mapsz + q * 4;
+
+    for (int jj = 0; jj < kTileVox / 4; ++jj) {
+        const int j = wave * (kTileVox / 4) + jj;
+        f32x4 o;
+        if constexpr (VT > 0) {
+            float s[4][VT], w[VT];
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                w[v] = wb[v];
+                const UTap u = uniform_rec(recs[j * VT + v]);
+                const TF *fv = fb + v * mapsz;
+                // an absent view and an identically zero sample read nothing (k_fwd_gather)
+                if (v >= nvb || (u.w00 == 0.f && u.w01 == 0.f && u.w10 == 0.f && u.w11 == 0.f)) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) s[i][v] = 0.f;
+                    continue;
+                }
+                const f32x4 a = Vec4<TF>::load(fv + u.o00), bb = Vec4<TF>::load(fv + u.o01);
+                const f32x4 c = Vec4<TF>::load(fv + u.o10), d = Vec4<TF>::load(fv + u.o11);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s[i][v] = bilerp(a.v[i], bb.v[i], c.v[i], d.v[i], u.w00, u.w01, u.w10, u.w11);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o.v[i] = weighted_aggregate<METHOD, VT>(s[i], w, nvb);
+        } else {
+            WeightedRunningAgg<METHOD> ra[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ra[i].init();
+            for (int v = 0; v < nvb; ++v) {
+                const UTap u = uniform_rec(recs[j * V + v]);
+                const TF *fv = fb + v * mapsz;
+                const float wv = wb[v];
+                if (u.w00 == 0.f && u.w01 == 0.f && u.w10 == 0.f && u.w11 == 0.f) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) ra[i].push(0.f, wv);
+                    continue;
+                }
+                const f32x4 a = Vec4<TF>::load(fv + u.o00), bb = Vec4<TF>::load(fv + u.o01);
+                const f32x4 c = Vec4<TF>::load(fv + u.o10), d = Vec4<TF>::load(fv + u.o11);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ra[i].push(bilerp(a.v[i], bb.v[i], c.v[i], d.v[i], u.w00, u.w01, u.w10, u.w11), wv);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) o.v[i] = ra[i].result();
+        }
+        if (nvb == 0) o = f32x4{{0.f, 0.f, 0.f, 0.f}};            // a sample without views: a zero volume
+        if (q_active) tile[j * tstride + lane] = o;
+    }
+    __syncthreads();
+
+    const int vl = lane & (kTileVox - 1), half = lane / kTileVox;   // the store phase of k_fwd_gather
+    const long long n = n0 + vl;
+    if (n < N) {
+        for (int qq = wave * 16 + half; qq < wave * 16 + 16; qq += 64 / kTileVox) {
+            const int cq = cg * kGroupQuads + qq;
+            if (cq >= Q) break;
+            const f32x4 t = tile[vl * tstride + qq];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int c = cq * 4 + i;
+                if (c < C) store_streaming(&out[((long long)b * C + c) * N + n], t.v[i]);
+            }
+        }
+    }
+    __syncthreads();
+    }
+}
+
+// the feature backward of both modes: ACC = float adds ds * tap weight with float atomics into the channels-last fp32 gradient
+// (k_bwd_gather), ACC = unsigned long long adds det_fixed(.., K[b][c]) into the int64 one (k_bwd_gather_det; kexp null otherwise)
+template <typename TF, typename TO, int METHOD, int VT, typename ACC>
+__global__ void __launch_bounds__(256)
+k_bwd_gather_weighted(const TO *__restrict__ grad_out, const TF *__restrict__ featT, const float *__restrict__ proj,
+                      const Coords coords, ACC *__restrict__ gradT, const int *__restrict__ kexp, int Vrt, int C, int C4, int H, int W,
+                      long long N, Gate gate, const int *__restrict__ nvs, const float *__restrict__ wts)
+{
+    constexpr bool DET = sizeof(ACC) == 8;
+    if (gated_off(gate)) return;
+    const int V = VT > 0 ? VT : Vrt;
+    const int nvb = nvs[blockIdx.y];                          // present views; none: nothing to scatter
+    if (nvb == 0) return;
+    const float *wb = wts + (long long)blockIdx.y * V;
+    extern __shared__ __align__(16) unsigned char smem[];
+    TapRec *recs = reinterpret_cast<TapRec *>(smem);
+    float *gtile = reinterpret_cast<float *>(smem + sizeof(TapRec) * kTileVox * V);   // [256 ch][kTileVox + 1]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, cg = blockIdx.z;
+    for (long long n0 = (long long)blockIdx.x * kTileVox; n0 < N; n0 += (long long)gridDim.x * kTileVox) {   // see k_fwd_gather
+    const long long mapsz = (long long)H * W * C4;
+
+    build_records(recs, proj, coords, b, V, n0, N, H, W, C4);
+    {   // grad_out tile, coalesced along voxels: the two half-waves load alternate channels
+        const int vl = lane & (kTileVox - 1), half = lane / kTileVox;
+        const long long n = n0 + vl;
+        for (int r = wave * 64 + half; r < wave * 64 + 64; r += 64 / kTileVox) {
+            const int c = cg * kGroupCh + r;
+            float g = 0.f;
+            if (c < C && n < N) g = to_f32<TO>(grad_out[((long long)b * C + c) * N + n]);
+            gtile[r * (kTileVox + 1) + vl] = g;
+        }
+    }
+    __syncthreads();
+
+    int ch[4], kx[4];
+    bool act[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = cg * kGroupCh + i * 64 + lane;
+        act[i] = c < C;
+        ch[i] = act[i] ? c : 0;
+        kx[i] = 0;
+        if constexpr (DET) {
+            kx[i] = act[i] ? kexp[(long long)b * C + ch[i]] : kDetPoison;
+            act[i] = act[i] && kx[i] != kDetPoison;                             // a poisoned channel adds nothing
+        }
+    }
+    const TF *fb = featT + (long long)b * V * mapsz;
+    ACC *gb = gradT + (long long)b * V * mapsz;
+
+    auto sample4 = [&](const UTap &u, int v, float (&sv)[4]) {
+        const TF *fv = fb + v * mapsz;
+        if (u.w00 == 0.f && u.w01 == 0.f && u.w10 == 0.f && u.w11 == 0.f) {        // identically zero: reads nothing (see k_fwd_gather)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sv[i] = 0.f;
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            sv[i] = bilerp(to_f32<TF>(fv[u.o00 + ch[i]]), to_f32<TF>(fv[u.o01 + ch[i]]), to_f32<TF>(fv[u.o10 + ch[i]]),
+                           to_f32<TF>(fv[u.o11 + ch[i]]), u.w00, u.w01, u.w10, u.w11);
+    };
+    auto add = [&](ACC *at, float x, int k) {
+        if constexpr (DET) atomicAdd(at, det_fixed(x, k));
+        else atomicAdd(at, x);
+    };
+    auto scatter4 = [&](const UTap &u, int v, const float (&dsv)[4]) {
+        ACC *gv = gb + v * mapsz;
+        // zero-weight taps (outside the map, or z <= 0) receive nothing -- wave-uniform branches
+        if (u.w00 != 0.f) { for (int i = 0; i < 4; ++i) if (act[i]) add(gv + u.o00 + ch[i], dsv[i] * u.w00, kx[i]); }
+        if (u.w01 != 0.f) { for (int i = 0; i < 4; ++i) if (act[i]) add(gv + u.o01 + ch[i], dsv[i] * u.w01, kx[i]); }
+        if (u.w10 != 0.f) { for (int i = 0; i < 4; ++i) if (act[i]) add(gv + u.o10 + ch[i], dsv[i] * u.w10, kx[i]); }
+        if (u.w11 != 0.f) { for (int i = 0; i < 4; ++i) if (act[i]) add(gv + u.o11 + ch[i], dsv[i] * u.w11, kx[i]); }
+    };
+
+    for (int jj = 0; jj < kTileVox / 4; ++jj) {
+        const int j = wave * (kTileVox / 4) + jj;
+        if (n0 + j >= N) break;
+        float g[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] = gtile[(i * 64 + lane) * (kTileVox + 1) + j];
+
+        if constexpr (VT > 0) {
+            float s[4][VT], ds[4][VT], w[VT];
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                float sv[4] = {0.f, 0.f, 0.f, 0.f};
+                w[v] = wb[v];
+                if (v < nvb) sample4(uniform_rec(recs[j * VT + v]), v, sv);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) s[i][v] = sv[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                float dw[VT];                                                   // (the weights' gradient is the geometry kernel's)
+                weighted_aggregate_grad<METHOD, VT>(s[i], w, g[i], ds[i], dw, nvb);
+            }
+#pragma unroll
+            for (int v = 0; v < VT; ++v) {
+                if (v >= nvb) continue;                                         // an absent view receives nothing
+                const float dsv[4] = {ds[0][v], ds[1][v], ds[2][v], ds[3][v]};
+                scatter4(uniform_rec(recs[j * VT + v]), v, dsv);
+            }
+        } else {
+            // run-time view count: pass 1 accumulates the aggregate, pass 2 re-samples and scatters
+            WeightedRunningAgg<METHOD> ra[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ra[i].init();
+            for (int v = 0; v < nvb; ++v) {
+                float sv[4];
+                sample4(uniform_rec(recs[j * V + v]), v, sv);
+                const float wv = wb[v];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) ra[i].push(sv[i], wv);
+            }
+            for (int v = 0; v < nvb; ++v) {
+                const UTap u = uniform_rec(recs[j * V + v]);
+                float sv[4], dsv[4];
+                sample4(u, v, sv);
+                const float wv = wb[v];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) dsv[i] = ra[i].grad(g[i], sv[i], wv);
+                scatter4(u, v, dsv);
+            }
+        }
+    }
+    __syncthreads();
+    }
+}
+
 // ------------------------------------------------------------------------------------------ layout passes
 // (BV, C, HW) -> (BV, HW, C4): 64 x 64 tiles turned through LDS, both sides coalesced.  VEC: 4 pixels per load and 4 channels per
 // store (16-B / 8-B accesses; HW % 4 == 0 and C4 % 4 == 0, base pointers aligned) -- 4.6 -> 5.8 TB/s for the 302 MB of configs[1].
@@ -599,6 +828,22 @@ static hipError_t fwd_dispatch_v(const TF *featT, const float *proj, const Coord
                            p.view_count);
         return hipGetLastError();
     };
+    auto go_weighted = [&](auto kern) -> hipError_t {
+        hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, featT, proj, coords, out, p.V, p.C, p.C4, p.H, p.W, p.N, tstride, make_gate(p, false),
+                           p.view_count, p.view_weights);
+        return hipGetLastError();
+    };
+    if (p.view_weights) {
+        if constexpr (METHOD == AGG_MAX) return hipErrorNotSupported;   // no weighted max (refused before any launch)
+        else switch (p.V) {
+        case 2: return go_weighted(k_fwd_gather_weighted<TF, TO, METHOD, 2>);
+        case 4: return go_weighted(k_fwd_gather_weighted<TF, TO, METHOD, 4>);
+        case 8: return go_weighted(k_fwd_gather_weighted<TF, TO, METHOD, 8>);
+        default: return go_weighted(k_fwd_gather_weighted<TF, TO, METHOD, 0>);
+        }
+    }
     if (p.view_count) {
         switch (p.V) {
         case 2: return go(k_fwd_gather<TF, TO, METHOD, 2, true>);
@@ -652,6 +897,22 @@ static hipError_t bwd_dispatch_v(const TO *go_, const TF *featT, const float *pr
                            p.view_count);
         return hipGetLastError();
     };
+    auto go_weighted = [&](auto kern) -> hipError_t {
+        hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, gradT, (const int *)nullptr, p.V, p.C, p.C4, p.H, p.W, p.N,
+                           make_gate(p, false), p.view_count, p.view_weights);
+        return hipGetLastError();
+    };
+    if (p.view_weights) {
+        if constexpr (METHOD == AGG_MAX) return hipErrorNotSupported;   // no weighted max (refused before any launch)
+        else switch (p.V) {
+        case 2: return go_weighted(k_bwd_gather_weighted<TF, TO, METHOD, 2, float>);
+        case 4: return go_weighted(k_bwd_gather_weighted<TF, TO, METHOD, 4, float>);
+        case 8: return go_weighted(k_bwd_gather_weighted<TF, TO, METHOD, 8, float>);
+        default: return go_weighted(k_bwd_gather_weighted<TF, TO, METHOD, 0, float>);
+        }
+    }
     if (p.view_count) {
         switch (p.V) {
         case 2: return go(k_bwd_gather<TF, TO, METHOD, 2, true>);
@@ -709,6 +970,22 @@ static hipError_t bwd_det_dispatch_v(const TO *go_, const TF *featT, const float
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, gradI, kexp, p.V, p.C, p.C4, p.H, p.W, p.N, Gate{}, p.view_count);
         return hipGetLastError();
     };
+    auto go_weighted = [&](auto kern) -> hipError_t {
+        hipError_t e = allow_dynamic_lds(reinterpret_cast<const void *>(kern), lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, go_, featT, proj, coords, gradI, kexp, p.V, p.C, p.C4, p.H, p.W, p.N, Gate{}, p.view_count,
+                           p.view_weights);
+        return hipGetLastError();
+    };
+    if (p.view_weights) {
+        if constexpr (METHOD == AGG_MAX) return hipErrorNotSupported;   // no weighted max (refused before any launch)
+        else switch (p.V) {
+        case 2: return go_weighted(k_bwd_gather_weighted<TF, TO, METHOD, 2, unsigned long long>);
+        case 4: return go_weighted(k_bwd_gather_weighted<TF, TO, METHOD, 4, unsigned long long>);
+        case 8: return go_weighted(k_bwd_gather_weighted<TF, TO, METHOD, 8, unsigned long long>);
+        default: return go_weighted(k_bwd_gather_weighted<TF, TO, METHOD, 0, unsigned long long>);
+        }
+    }
     if (p.view_count) {
         switch (p.V) {
         case 2: return go_masked(k_masked_bwd_gather_det<TF, TO, METHOD, 2>);

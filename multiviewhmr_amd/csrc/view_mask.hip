@@ -52,6 +52,39 @@ k_view_table(const uint8_t *__restrict__ mask, const float *__restrict__ proj, T
     t.count[b] = n;
 }
 
+// Per-view confidence weights: a view is present when its mask byte is nonzero (no mask: every view) AND its weight is
+// > 0 -- zero, negative and NaN weights mean absent.  The tables and packed projections as k_view_table's, and the weights packed into
+// slot order behind them (absent slots 0).
+__global__ void __launch_bounds__(64)
+k_view_table_weighted(const uint8_t *__restrict__ mask, const float *__restrict__ weights, const float *__restrict__ proj, TableView t,
+                      float *__restrict__ packed_w, int B, int V)
+{
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    int n = 0;
+    for (int v = 0; v < V; ++v) {
+        const long long bv = (long long)b * V + v;
+        const float w = weights[bv];
+        if ((!mask || mask[bv]) && w > 0.f) {
+            const long long bs = (long long)b * V + n;
+            t.s2v[bs] = v;
+            t.v2s[bv] = n;
+            packed_w[bs] = w;
+            for (int k = 0; k < 12; ++k) t.proj[bs * 12 + k] = proj[bv * 12 + k];
+            ++n;
+        } else {
+            t.v2s[bv] = -1;
+        }
+    }
+    for (int s = n; s < V; ++s) {
+        const long long bs = (long long)b * V + s;
+        t.s2v[bs] = -1;
+        packed_w[bs] = 0.f;
+        for (int k = 0; k < 12; ++k) t.proj[bs * 12 + k] = 0.f;
+    }
+    t.count[b] = n;
+}
+
 // one block row per (sample, slot or view) pair, grid-stride over the T-words of one view.  PACK: dst slot s <- src view s2v[s] (absent
 // slots 0); unpack: dst view v <- src slot v2s[v] (masked views 0).  The index is block-uniform: a zero-filled map reads nothing.
 template <typename T, bool PACK>
@@ -102,6 +135,20 @@ size_t view_table_bytes(int B, int V)
 hipError_t launch_view_table(const uint8_t *mask, const float *proj, void *table, int B, int V, hipStream_t s)
 {
     hipLaunchKernelGGL(k_view_table, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, mask, proj, table_view(table, B, V), B, V);
+    return hipGetLastError();
+}
+
+// the weighted table: k_view_table's regions, then the packed weights (B, V) fp32
+size_t weighted_view_table_bytes(int B, int V) { return view_table_bytes(B, V) + align256((size_t)B * V * sizeof(float)); }
+const float *view_table_weights(const void *table, int B, int V)
+{
+    return reinterpret_cast<const float *>(static_cast<const unsigned char *>(table) + view_table_bytes(B, V));
+}
+
+hipError_t launch_view_table_weighted(const uint8_t *mask, const float *weights, const float *proj, void *table, int B, int V, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_view_table_weighted, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, mask, weights, proj, table_view(table, B, V),
+                       const_cast<float *>(view_table_weights(table, B, V)), B, V);
     return hipGetLastError();
 }
 

@@ -2,7 +2,8 @@
 // mvhmr_native::unprojection[_backward[_geometry]] / unprojection_cuboid[_backward[_geometry]] that multiviewhmr_amd/aggregation.py calls
 // from its torch.library ops and from _FusedAggregate, and of the DLT triangulation (triangulate_dlt[_backward], multiview.py).  Every
 // un-projection op takes a trailing `Tensor? view_mask` (None: the unmasked C entry point), the two feature backwards a trailing
-// `bool deterministic`; the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
+// `bool deterministic`, and all of them behind that `Tensor? view_weights` (per-view confidence weights: the *_weighted entry points; the
+// geometry ops also `Tensor(a!)? grad_weights`, the (B, V) fp32 tensor they write the gradient w.r.t. the weights into); the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
 // tensor checks, descriptor, output and workspace from the caching allocator, the current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -95,6 +96,20 @@ const uint8_t *mask_ptr(const mvhmr_unproject_desc &d, const at::Tensor &feature
     return view_mask->data_ptr<uint8_t>();
 }
 
+// per-view confidence weights (mvhmr_unproject_*_weighted): view_weights (B, V) fp32 on the features' device; null for None
+const float *weights_ptr(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_weights, const char *name = "view_weights (B, V)")
+{
+    if (!view_weights || !view_weights->defined()) return nullptr;
+    check_tensor(*view_weights, features, name, at::kFloat, (int64_t)d.batch * d.views);
+    return view_weights->data_ptr<float>();
+}
+
+// what selects a sample's views: the mask, the weights, both or neither (the C entry point family follows)
+struct ViewArgs {
+    const uint8_t *mask;
+    const float *weights;
+};
+
 // the common tail: workspace, the features' device, the current HIP stream, one C-ABI call.  The workspace comes from the caching
 // allocator through at::empty -- except `unfilled` (the deterministic entry points), straight from the device allocator: under
 // torch.use_deterministic_algorithms(True) at::empty fills new memory (torch.utils.deterministic.fill_uninitialized_memory) --
@@ -144,35 +159,46 @@ struct TensorVolume {
     // gradients w.r.t. proj (B,V,3,4) and coords (B,X,Y,Z,3)
     std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, coords.sizes().vec()}; }
 
-    size_t forward_bytes(const mvhmr_unproject_desc &d, bool masked) const
+    size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
-        return masked ? mvhmr_unproject_forward_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
+        if (v.weights) return mvhmr_unproject_forward_weighted_workspace_bytes(&d);
+        return v.mask ? mvhmr_unproject_forward_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
     }
-    int forward(const mvhmr_unproject_desc &d, const void *features, const float *proj, const uint8_t *mask, void *out, void *ws, size_t n, hipStream_t s) const
+    int forward(const mvhmr_unproject_desc &d, const void *features, const float *proj, const ViewArgs &v, void *out, void *ws, size_t n, hipStream_t s) const
     {
         const float *c = coords.data_ptr<float>();
+        const uint8_t *mask = v.mask;
+        if (v.weights) return mvhmr_unproject_forward_weighted(&d, features, proj, c, mask, v.weights, out, ws, n, s);
         return mask ? mvhmr_unproject_forward_masked(&d, features, proj, c, mask, out, ws, n, s) : mvhmr_unproject_forward(&d, features, proj, c, out, ws, n, s);
     }
-    size_t backward_bytes(const mvhmr_unproject_desc &d, bool masked, bool det) const
+    size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
-        if (masked) return det ? mvhmr_unproject_backward_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_masked_workspace_bytes(&d);
+        if (v.weights) return det ? mvhmr_unproject_backward_deterministic_weighted_workspace_bytes(&d) : mvhmr_unproject_backward_weighted_workspace_bytes(&d);
+        if (v.mask) return det ? mvhmr_unproject_backward_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_masked_workspace_bytes(&d);
         return det ? mvhmr_unproject_backward_deterministic_workspace_bytes(&d) : mvhmr_unproject_backward_workspace_bytes(&d);
     }
-    int backward(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const uint8_t *mask, bool det, void *grad,
+    int backward(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, bool det, void *grad,
                  void *ws, size_t n, hipStream_t s) const
     {
         const float *c = coords.data_ptr<float>();
+        const uint8_t *mask = v.mask;
+        if (v.weights)
+            return (det ? mvhmr_unproject_backward_deterministic_weighted : mvhmr_unproject_backward_weighted)(&d, grad_out, features, proj, c, mask, v.weights,
+                                                                                                                grad, ws, n, s);
         if (mask) return (det ? mvhmr_unproject_backward_deterministic_masked : mvhmr_unproject_backward_masked)(&d, grad_out, features, proj, c, mask, grad, ws, n, s);
         return (det ? mvhmr_unproject_backward_deterministic : mvhmr_unproject_backward)(&d, grad_out, features, proj, c, grad, ws, n, s);
     }
-    size_t geometry_bytes(const mvhmr_unproject_desc &d, bool masked) const
+    size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
-        return masked ? mvhmr_unproject_backward_geometry_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_workspace_bytes(&d);
+        if (v.weights) return mvhmr_unproject_backward_geometry_weighted_workspace_bytes(&d);
+        return v.mask ? mvhmr_unproject_backward_geometry_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_workspace_bytes(&d);
     }
-    int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const uint8_t *mask, float *const *g, void *ws,
-                 size_t n, hipStream_t s) const
+    int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, float *const *g,
+                 float *grad_weights, void *ws, size_t n, hipStream_t s) const
     {
         const float *c = coords.data_ptr<float>();
+        const uint8_t *mask = v.mask;
+        if (v.weights) return mvhmr_unproject_backward_geometry_weighted(&d, grad_out, features, proj, c, mask, v.weights, g[0], g[1], grad_weights, ws, n, s);
         return mask ? mvhmr_unproject_backward_geometry_masked(&d, grad_out, features, proj, c, mask, g[0], g[1], ws, n, s)
                     : mvhmr_unproject_backward_geometry(&d, grad_out, features, proj, c, g[0], g[1], ws, n, s);
     }
@@ -196,39 +222,54 @@ struct CuboidVolume {
     // gradients w.r.t. proj (B,V,3,4), rot (B,3,3) and center (B,3)
     std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, {d.batch, 3, 3}, {d.batch, 3}}; }
 
-    size_t forward_bytes(const mvhmr_unproject_desc &d, bool masked) const
+    size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
-        return masked ? mvhmr_unproject_forward_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
+        if (v.weights) return mvhmr_unproject_forward_cuboid_weighted_workspace_bytes(&d);
+        return v.mask ? mvhmr_unproject_forward_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
     }
-    int forward(const mvhmr_unproject_desc &d, const void *features, const float *proj, const uint8_t *mask, void *out, void *ws, size_t n, hipStream_t s) const
+    int forward(const mvhmr_unproject_desc &d, const void *features, const float *proj, const ViewArgs &v, void *out, void *ws, size_t n, hipStream_t s) const
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
+        const uint8_t *mask = v.mask;
+        if (v.weights)
+            return mvhmr_unproject_forward_cuboid_weighted(&d, features, proj, r, c, position.data(), sides.data(), mask, v.weights, out, ws, n, s);
         return mask ? mvhmr_unproject_forward_cuboid_masked(&d, features, proj, r, c, position.data(), sides.data(), mask, out, ws, n, s)
                     : mvhmr_unproject_forward_cuboid(&d, features, proj, r, c, position.data(), sides.data(), out, ws, n, s);
     }
-    size_t backward_bytes(const mvhmr_unproject_desc &d, bool masked, bool det) const
+    size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
-        if (masked) return det ? mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_masked_workspace_bytes(&d);
+        if (v.weights)
+            return det ? mvhmr_unproject_backward_cuboid_deterministic_weighted_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_weighted_workspace_bytes(&d);
+        if (v.mask) return det ? mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_masked_workspace_bytes(&d);
         return det ? mvhmr_unproject_backward_deterministic_workspace_bytes(&d) : mvhmr_unproject_backward_workspace_bytes(&d);
     }
-    int backward(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const uint8_t *mask, bool det, void *grad,
+    int backward(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, bool det, void *grad,
                  void *ws, size_t n, hipStream_t s) const
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
+        const uint8_t *mask = v.mask;
+        if (v.weights)
+            return (det ? mvhmr_unproject_backward_cuboid_deterministic_weighted : mvhmr_unproject_backward_cuboid_weighted)(
+                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.weights, grad, ws, n, s);
         if (mask)
             return (det ? mvhmr_unproject_backward_cuboid_deterministic_masked : mvhmr_unproject_backward_cuboid_masked)(
                 &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, grad, ws, n, s);
         return (det ? mvhmr_unproject_backward_cuboid_deterministic : mvhmr_unproject_backward_cuboid)(&d, grad_out, features, proj, r, c, position.data(),
                                                                                                      sides.data(), grad, ws, n, s);
     }
-    size_t geometry_bytes(const mvhmr_unproject_desc &d, bool masked) const
+    size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
-        return masked ? mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(&d);
+        if (v.weights) return mvhmr_unproject_backward_geometry_cuboid_weighted_workspace_bytes(&d);
+        return v.mask ? mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(&d);
     }
-    int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const uint8_t *mask, float *const *g, void *ws,
-                 size_t n, hipStream_t s) const
+    int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, float *const *g,
+                 float *grad_weights, void *ws, size_t n, hipStream_t s) const
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
+        const uint8_t *mask = v.mask;
+        if (v.weights)
+            return mvhmr_unproject_backward_geometry_cuboid_weighted(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.weights, g[0],
+                                                                     g[1], g[2], grad_weights, ws, n, s);
         return mask ? mvhmr_unproject_backward_geometry_cuboid_masked(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, g[0], g[1], g[2],
                                                                       ws, n, s)
                     : mvhmr_unproject_backward_geometry_cuboid(&d, grad_out, features, proj, r, c, position.data(), sides.data(), g[0], g[1], g[2], ws, n, s);
@@ -237,14 +278,15 @@ struct CuboidVolume {
 
 // ---- one body per kind of call.  features: the tensor the library reads (planar, channels-last or the quad-planar byte buffer)
 template <typename Volume>
-at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a, const c10::optional<at::Tensor> &view_mask)
+at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a, const c10::optional<at::Tensor> &view_mask,
+                   const c10::optional<at::Tensor> &view_weights)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, nullptr);
-    const uint8_t *mask = mask_ptr(d, features, view_mask);
+    const ViewArgs views{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights)};
     at::Tensor out = at::empty({a.B, a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
-    run(features, vol.forward_bytes(d, mask != nullptr), false, [&](void *ws, size_t n, hipStream_t s) {
-        return vol.forward(d, features.data_ptr(), proj.data_ptr<float>(), mask, out.data_ptr(), ws, n, s);
+    run(features, vol.forward_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
+        return vol.forward(d, features.data_ptr(), proj.data_ptr<float>(), views, out.data_ptr(), ws, n, s);
     });
     return out;
 }
@@ -252,27 +294,32 @@ at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tens
 // deterministic: the feature gradient bitwise reproducible (mvhmr_unproject_backward*_deterministic); the workspace is not filled
 template <typename Volume>
 at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
-                    const c10::optional<at::Tensor> &view_mask, bool deterministic)
+                    const c10::optional<at::Tensor> &view_mask, bool deterministic, const c10::optional<at::Tensor> &view_weights)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out);
-    const uint8_t *mask = mask_ptr(d, features, view_mask);
+    const ViewArgs views{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights)};
     at::Tensor grad = new_feature_grad(d, features);
-    run(features, vol.backward_bytes(d, mask != nullptr, deterministic), deterministic, [&](void *ws, size_t n, hipStream_t s) {
-        return vol.backward(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), mask, deterministic, grad.data_ptr(), ws, n, s);
+    run(features, vol.backward_bytes(d, views, deterministic), deterministic, [&](void *ws, size_t n, hipStream_t s) {
+        return vol.backward(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, deterministic, grad.data_ptr(), ws, n, s);
     });
     return grad;
 }
 
-// the geometry gradients of the form, all fp32, grad_proj first; an output not asked for comes back as an empty tensor
+// the geometry gradients of the form, all fp32, grad_proj first; an output not asked for comes back as an empty tensor.  grad_weights, when
+// given (with view_weights), is written in place: the gradient w.r.t. the weights, which may be the only one asked for
 template <typename Volume>
 std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
-                                          std::initializer_list<bool> want, const c10::optional<at::Tensor> &view_mask)
+                                          std::initializer_list<bool> want, const c10::optional<at::Tensor> &view_mask,
+                                          const c10::optional<at::Tensor> &view_weights, const c10::optional<at::Tensor> &grad_weights)
 {
-    TORCH_CHECK(std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
+    const bool want_weights = grad_weights && grad_weights->defined();
+    TORCH_CHECK(want_weights || std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out);
-    const uint8_t *mask = mask_ptr(d, features, view_mask);
+    const ViewArgs views{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights)};
+    TORCH_CHECK(!want_weights || views.weights, "mvhmr_unproject: grad_weights needs view_weights");
+    float *gw = const_cast<float *>(weights_ptr(d, features, grad_weights, "grad_weights (B, V)"));
     const auto opts = features.options().dtype(at::kFloat);
     const auto shapes = vol.geometry_shapes(d);
     std::vector<at::Tensor> grads;
@@ -282,8 +329,8 @@ std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &g
         grads.push_back(w ? at::empty(shapes[i], opts) : at::empty({0}, opts));
         ptrs.push_back(w ? grads.back().data_ptr<float>() : nullptr);
     }
-    run(features, vol.geometry_bytes(d, mask != nullptr), false, [&](void *ws, size_t n, hipStream_t s) {
-        return vol.geometry(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), mask, ptrs.data(), ws, n, s);
+    run(features, vol.geometry_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
+        return vol.geometry(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, ptrs.data(), gw, ws, n, s);
     });
     return grads;
 }
@@ -293,56 +340,59 @@ using OptTensor = c10::optional<at::Tensor>;
 
 at::Tensor unprojection_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C,
                                int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
-                               const OptTensor &view_mask)
+                               const OptTensor &view_mask, const OptTensor &view_weights)
 {
-    return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask);
+    return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, view_weights);
 }
 
 at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
                                         int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
-                                        int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask, bool deterministic)
+                                        int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask, bool deterministic,
+                                        const OptTensor &view_weights)
 {
     return backward(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask,
-                    deterministic);
+                    deterministic, view_weights);
 }
 
 std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
                                                                           const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H,
                                                                           int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
-                                                                          int64_t variant, bool want_proj, bool want_coords, const OptTensor &view_mask)
+                                                                          int64_t variant, bool want_proj, bool want_coords, const OptTensor &view_mask,
+                                                                          const OptTensor &view_weights, const OptTensor &grad_weights)
 {
     const auto g = backward_geometry(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
-                                     {want_proj, want_coords}, view_mask);
+                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights);
     return {g[0], g[1]};
 }
 
 at::Tensor unprojection_cuboid_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
                                       at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C,
                                       int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
-                                      const OptTensor &view_mask)
+                                      const OptTensor &view_mask, const OptTensor &view_weights)
 {
     return forward(CuboidVolume{rot, center, position, sides, vol}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
-                   view_mask);
+                   view_mask, view_weights);
 }
 
 at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
                                                const at::Tensor &center, at::ArrayRef<double> position, at::ArrayRef<double> sides,
                                                at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
                                                int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask,
-                                               bool deterministic)
+                                               bool deterministic, const OptTensor &view_weights)
 {
     return backward(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
-                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, deterministic);
+                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, deterministic, view_weights);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geometry_native(
     const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
     at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
     int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center,
-    const OptTensor &view_mask)
+    const OptTensor &view_mask, const OptTensor &view_weights, const OptTensor &grad_weights)
 {
     const auto g = backward_geometry(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
-                                     DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, {want_proj, want_rot, want_center}, view_mask);
+                                     DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, {want_proj, want_rot, want_center}, view_mask,
+                                     view_weights, grad_weights);
     return {g[0], g[1], g[2]};
 }
 
@@ -407,18 +457,20 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(c
 #define MVHMR_DESC_ARGS "int B, int V, int C, int H, int W, int method, int feat_dtype, int out_dtype, int layout, int variant"
 #define MVHMR_CUBOID_ARGS "Tensor proj, Tensor rot, Tensor center, float[] position, float[] sides, int[] vol, " MVHMR_DESC_ARGS
 #define MVHMR_MASK_ARG ", Tensor? view_mask=None"
+#define MVHMR_WEIGHTS_ARG ", Tensor? view_weights=None"
+#define MVHMR_GRAD_WEIGHTS_ARG ", Tensor(a!)? grad_weights=None"
 
 TORCH_LIBRARY(mvhmr_native, m)
 {
-    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG ") -> Tensor");
+    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG ") -> Tensor");
     m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG
-          ", bool deterministic=False) -> Tensor");
+          ", bool deterministic=False" MVHMR_WEIGHTS_ARG ") -> Tensor");
     m.def("unprojection_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS
-          ", bool want_proj, bool want_coords" MVHMR_MASK_ARG ") -> (Tensor, Tensor)");
-    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ") -> Tensor");
-    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ", bool deterministic=False) -> Tensor");
+          ", bool want_proj, bool want_coords" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG ") -> (Tensor, Tensor)");
+    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG ") -> Tensor");
+    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ", bool deterministic=False" MVHMR_WEIGHTS_ARG ") -> Tensor");
     m.def("unprojection_cuboid_backward_geometry(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS
-          ", bool want_proj, bool want_rot, bool want_center" MVHMR_MASK_ARG ") -> (Tensor, Tensor, Tensor)");
+          ", bool want_proj, bool want_rot, bool want_center" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG ") -> (Tensor, Tensor, Tensor)");
     m.def("triangulate_dlt(Tensor proj, Tensor points, Tensor? confidences) -> Tensor");
     m.def("triangulate_dlt_backward(Tensor grad_out, Tensor proj, Tensor points, Tensor? confidences) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int");
