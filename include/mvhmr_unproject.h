@@ -391,6 +391,12 @@ int mvhmr_convert_features(const mvhmr_unproject_desc *desc, const void *feature
  * then writes grad_features in the PLANAR layout (n_maps, c_out, Hf, Wf), which is what the conv's own backward consumes.
  *   x (n_maps, c_in, Hf, Wf) fp32, weight (c_out, c_in) fp32 (nn.Conv2d's (c_out, c_in, 1, 1)), bias (c_out) fp32 or null.
  * Shapes: c_in % 16 == 0, c_out % 128 == 0, Hf % 4 == 0, Wf % 32 == 0 (mvhmr_conv1x1_to_quad_supported), else MVHMR_ERR_UNSUPPORTED.
+ * n_maps <= 65535 (the maps are the grid's z extent), else MVHMR_ERR_UNSUPPORTED: split the batch.  Element offsets are 64-bit: a tensor
+ * may hold more than 2^31 elements.
+ * Alignment (this and the three GEMMs below): the kernels use 16-byte loads and stores, so x, weight, bias (when given) and dst here and
+ * in mvhmr_conv1x1_planar, grad_y and x in mvhmr_conv1x1_wgrad[_deterministic], must be 16-byte aligned, else
+ * MVHMR_ERR_INVALID_ARGUMENT (every map and weight row then is, by the shape rules).  Checks run in this order: null pointers,
+ * non-positive extents, alignment (MVHMR_ERR_INVALID_ARGUMENT), then shape and n_maps (MVHMR_ERR_UNSUPPORTED), then the workspace.
  */
 int mvhmr_conv1x1_to_quad(const float *x, const float *weight, const float *bias, void *dst, int32_t n_maps, int32_t c_in,
                           int32_t c_out, int32_t feat_h, int32_t feat_w, void *hip_stream);
@@ -401,6 +407,7 @@ int mvhmr_conv1x1_to_quad_supported(int32_t c_in, int32_t c_out, int32_t feat_h,
  * (+ bias).  With the transposed weight it is the gradient w.r.t. the input of process_feature (autograd through
  * models/aggregation.py:189-191), which the Python binding's fused route uses in backward.
  * Shapes: c_in % 16 == 0, c_out % 128 == 0, pixels % 128 == 0 (mvhmr_conv1x1_planar_supported), else MVHMR_ERR_UNSUPPORTED.
+ * n_maps <= 65535 and 16-byte aligned x, weight, bias, dst as for mvhmr_conv1x1_to_quad.
  */
 int mvhmr_conv1x1_planar(const float *x, const float *weight, const float *bias, float *dst, int32_t n_maps, int32_t c_in,
                          int32_t c_out, int32_t pixels, void *hip_stream);
@@ -412,6 +419,7 @@ int mvhmr_conv1x1_planar_supported(int32_t c_in, int32_t c_out, int32_t pixels);
  * grad_y (n_maps, c_out, pixels), x (n_maps, c_in, pixels) fp32 planar.  grad_weight (c_out, c_in) and grad_bias (c_out, may be
  * NULL) are ADDED INTO with float atomics (zero them first; last-bit run-to-run differences like any split-K reduction).
  * Shapes: c_in % 128 == 0, c_out % 128 == 0, pixels % 32 == 0 (mvhmr_conv1x1_wgrad_supported), else MVHMR_ERR_UNSUPPORTED.
+ * grad_y and x must be 16-byte aligned (MVHMR_ERR_INVALID_ARGUMENT); n_maps has no limit of its own here.
  */
 int mvhmr_conv1x1_wgrad(const float *grad_y, const float *x, float *grad_weight, float *grad_bias, int32_t n_maps, int32_t c_in,
                         int32_t c_out, int32_t pixels, void *hip_stream);

@@ -26,6 +26,7 @@ import torch.nn as nn
 from . import _capi, multiview, volumetric
 
 _METHODS = ("softmax", "sum", "mean", "max")            # aggregation.py:71-85
+_FUSED_MAX_MAPS = 65535                                 # mvhmr_conv1x1_to_quad / _planar: n_maps is the grid's z extent (mvhmr_unproject.h)
 _TYPE_MSG = "Works only with numpy arrays and PyTorch tensors."
 
 
@@ -778,7 +779,9 @@ class VolumeGenerator(nn.Module):
         """The fused conv writes the quad-planar layout, which the un-projection consumes for every geometry (brick kernels as it
         is, gather kernels through one conversion; the device-side gate picks per call).  So only shapes, dtypes and devices
         decide here -- checked on every call, nothing cached: fp32 everywhere, conv parameters on the features' device, a shape the
-        fused GEMM takes and one whose quad-planar copy the un-projection (forward and backward) accepts."""
+        fused GEMM takes and one whose quad-planar copy the un-projection (forward and backward) accepts.  The GEMMs read their operands
+        with 16-byte loads and put the B * V maps in the grid's z extent: memory the route would hand them as it is (a contiguous
+        tensor is not copied) must sit on a 16-byte boundary, and B * V must not exceed _FUSED_MAX_MAPS."""
         if not self.fused_conv or not features.is_cuda or features.dtype != torch.float32 or self.aggregation_method not in _METHODS:
             return False
         if self.volume_dtype not in (None, torch.float32, torch.bfloat16):
@@ -787,10 +790,14 @@ class VolumeGenerator(nn.Module):
         params = [conv.weight] + ([conv.bias] if conv.bias is not None else [])
         if any(t.dtype != torch.float32 or t.device != features.device for t in params):
             return False
+        if any(t.is_contiguous() and t.data_ptr() % 16 != 0 for t in (features, conv.weight)):
+            return False
+        if conv.bias is not None and conv.bias.data_ptr() % 16 != 0:             # (the bias is never copied)
+            return False
         B, V, Cin, Hf, Wf = features.shape
         Cout = conv.out_channels
         L = _capi.lib()
-        if not L.mvhmr_conv1x1_to_quad_supported(Cin, Cout, Hf, Wf):
+        if B * V > _FUSED_MAX_MAPS or not L.mvhmr_conv1x1_to_quad_supported(Cin, Cout, Hf, Wf):
             return False
         meta = torch.empty((B, V, Cout, Hf, Wf), dtype=torch.float32, device="meta")
         desc = _make_desc(meta, (S, S, S), _capi.AGG[self.aggregation_method], self.volume_dtype or torch.float32, _capi.LAYOUT_QUAD, _capi.VARIANT["auto"])

@@ -1163,14 +1163,24 @@ int mvhmr_convert_features(const mvhmr_unproject_desc *desc, const void *feature
     return fail(MVHMR_ERR_INVALID_ARGUMENT, "unknown destination layout %d", dst_layout);
 }
 
+// the 1x1-conv GEMMs read their operands (and write the quad-planar copy) with 16-byte accesses
+static bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }      // (null, an absent bias, counts as aligned)
+static int conv1x1_too_many_maps(int32_t n_maps)
+{
+    return fail(MVHMR_ERR_UNSUPPORTED, "1x1 conv takes at most %d maps per call (got %d): split the batch", kConv1x1MaxMaps, n_maps);
+}
+
 int mvhmr_conv1x1_to_quad(const float *x, const float *weight, const float *bias, void *dst, int32_t n_maps, int32_t c_in, int32_t c_out,
                           int32_t feat_h, int32_t feat_w, void *hip_stream)
 {
     if (!x || !weight || !dst) return fail(MVHMR_ERR_INVALID_ARGUMENT, "x / weight / dst must be non-null");
     if (n_maps < 1 || c_in < 1 || c_out < 1 || feat_h < 1 || feat_w < 1) return fail(MVHMR_ERR_INVALID_ARGUMENT, "every dimension must be >= 1");
+    if (!aligned16(x) || !aligned16(weight) || !aligned16(bias) || !aligned16(dst))
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "x / weight / bias / dst must be 16-byte aligned");
     if (!conv1x1_quad_supported(c_in, c_out, feat_h, feat_w))
         return fail(MVHMR_ERR_UNSUPPORTED, "fused 1x1 conv needs C_in %% 16 == 0, C_out %% 128 == 0, Hf %% 4 == 0, Wf %% 32 == 0 (got %d -> %d, %dx%d)",
                     c_in, c_out, feat_h, feat_w);
+    if (n_maps > kConv1x1MaxMaps) return conv1x1_too_many_maps(n_maps);
     return launched(launch_conv1x1_quad(x, weight, bias, dst, n_maps, c_in, c_out, feat_h, feat_w, static_cast<hipStream_t>(hip_stream)),
                     "fused 1x1 conv");
 }
@@ -1185,8 +1195,11 @@ int mvhmr_conv1x1_planar(const float *x, const float *weight, const float *bias,
 {
     if (!x || !weight || !dst) return fail(MVHMR_ERR_INVALID_ARGUMENT, "null pointer");
     if (n_maps <= 0 || c_in <= 0 || c_out <= 0 || pixels <= 0) return fail(MVHMR_ERR_INVALID_ARGUMENT, "non-positive extent");
+    if (!aligned16(x) || !aligned16(weight) || !aligned16(bias) || !aligned16(dst))
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "x / weight / bias / dst must be 16-byte aligned");
     if (!conv1x1_planar_supported(c_in, c_out, pixels))
         return fail(MVHMR_ERR_UNSUPPORTED, "planar 1x1 conv needs C_in %% 16 == 0, C_out %% 128 == 0, pixels %% 128 == 0 (got %d -> %d, %d)", c_in, c_out, pixels);
+    if (n_maps > kConv1x1MaxMaps) return conv1x1_too_many_maps(n_maps);
     return launched(launch_conv1x1_planar(x, weight, bias, dst, n_maps, c_in, c_out, pixels, static_cast<hipStream_t>(hip_stream)), "planar 1x1 conv");
 }
 
@@ -1200,6 +1213,7 @@ int mvhmr_conv1x1_wgrad(const float *grad_y, const float *x, float *grad_weight,
 {
     if (!grad_y || !x || !grad_weight) return fail(MVHMR_ERR_INVALID_ARGUMENT, "null pointer");
     if (n_maps <= 0 || c_in <= 0 || c_out <= 0 || pixels <= 0) return fail(MVHMR_ERR_INVALID_ARGUMENT, "non-positive extent");
+    if (!aligned16(grad_y) || !aligned16(x)) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_y / x must be 16-byte aligned");
     if (!conv1x1_wgrad_supported(c_in, c_out, pixels))
         return fail(MVHMR_ERR_UNSUPPORTED, "1x1 conv weight gradient needs C_in %% 128 == 0, C_out %% 128 == 0, pixels %% 32 == 0 (got %d -> %d, %d)", c_in, c_out, pixels);
     return launched(launch_conv1x1_wgrad(grad_y, x, grad_weight, grad_bias, n_maps, c_in, c_out, pixels, static_cast<hipStream_t>(hip_stream)),
@@ -1221,6 +1235,7 @@ int mvhmr_conv1x1_wgrad_deterministic(const float *grad_y, const float *x, float
 {
     if (!grad_y || !x || !grad_weight) return fail(MVHMR_ERR_INVALID_ARGUMENT, "null pointer");
     if (n_maps <= 0 || c_in <= 0 || c_out <= 0 || pixels <= 0) return fail(MVHMR_ERR_INVALID_ARGUMENT, "non-positive extent");
+    if (!aligned16(grad_y) || !aligned16(x)) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_y / x must be 16-byte aligned");
     if (!conv1x1_wgrad_supported(c_in, c_out, pixels))
         return fail(MVHMR_ERR_UNSUPPORTED, "1x1 conv weight gradient needs C_in %% 128 == 0, C_out %% 128 == 0, pixels %% 32 == 0 (got %d -> %d, %d)", c_in, c_out, pixels);
     const int rc = check_ws(workspace, workspace_bytes, conv1x1_wgrad_det_workspace_bytes(n_maps, c_in, c_out, pixels));

@@ -144,7 +144,7 @@ bool conv1x1_planar_supported(int Cin, int Cout, int HW) { return Cin % kTK == 0
 hipError_t launch_conv1x1_quad(const float *x, const float *w, const float *bias, void *dst, int BV, int Cin, int Cout, int H, int W,
                                hipStream_t s)
 {
-    if (!conv1x1_quad_supported(Cin, Cout, H, W)) return hipErrorNotSupported;
+    if (!conv1x1_quad_supported(Cin, Cout, H, W) || BV > kConv1x1MaxMaps) return hipErrorNotSupported;
     const dim3 grid((W / 32) * (H / 4), Cout / kTM, BV);
     hipLaunchKernelGGL(k_conv1x1_quad<true>, grid, dim3(256), 0, s, x, w, bias, (float4 *)dst, Cin, Cout, H, W);
     return hipGetLastError();
@@ -153,7 +153,7 @@ hipError_t launch_conv1x1_quad(const float *x, const float *w, const float *bias
 // y[bv, co, p] = sum_ci w[co, ci] * x[bv, ci, p] (+ bias[co]), everything planar fp32
 hipError_t launch_conv1x1_planar(const float *x, const float *w, const float *bias, float *dst, int BV, int Cin, int Cout, int HW, hipStream_t s)
 {
-    if (!conv1x1_planar_supported(Cin, Cout, HW)) return hipErrorNotSupported;
+    if (!conv1x1_planar_supported(Cin, Cout, HW) || BV > kConv1x1MaxMaps) return hipErrorNotSupported;
     const dim3 grid(HW / kTN, Cout / kTM, BV);
     hipLaunchKernelGGL(k_conv1x1_quad<false>, grid, dim3(256), 0, s, x, w, bias, (float4 *)dst, Cin, Cout, 1, HW);
     return hipGetLastError();

@@ -123,6 +123,9 @@ hipError_t launch_conv1x1_wgrad(const float *gy, const float *x, float *dW, floa
 // deterministic form: per-slice partial slabs in `ws` (conv1x1_wgrad_det_workspace_bytes), summed in a fixed order; dW / db are written
 size_t conv1x1_wgrad_det_workspace_bytes(int BV, int Cin, int Cout, int HW);
 hipError_t launch_conv1x1_wgrad_det(const float *gy, const float *x, float *dW, float *db, void *ws, int BV, int Cin, int Cout, int HW, hipStream_t s);
+// the two below put the map index in the grid's z extent: BV <= kConv1x1MaxMaps, else hipErrorNotSupported.  All four GEMMs read x, w,
+// bias and gy (and write the quad-planar dst) with 16-byte accesses: the C ABI checks the pointers
+constexpr int kConv1x1MaxMaps = 65535;
 hipError_t launch_conv1x1_planar(const float *x, const float *w, const float *bias, float *dst, int BV, int Cin, int Cout, int HW, hipStream_t s);
 hipError_t launch_conv1x1_quad(const float *x, const float *w, const float *bias, void *dst, int BV, int Cin, int Cout, int H, int W,
                                hipStream_t s);
