@@ -37,7 +37,9 @@ extern "C" {
                                  mvhmr_triangulate_dlt_backward, mvhmr_unproject_backward_deterministic[_workspace_bytes],
                                  mvhmr_unproject_backward_cuboid_deterministic[_workspace_bytes], mvhmr_conv1x1_wgrad_deterministic[_workspace_bytes],
                                  the *_masked entry points and their *_masked_workspace_bytes queries (per-sample view masks), the
-                                 *_weighted entry points and their *_weighted_workspace_bytes queries (per-view confidence weights) */
+                                 *_weighted entry points and their *_weighted_workspace_bytes queries (per-view confidence weights), the
+                                 *_visible entry points, their *_visible_workspace_bytes queries and mvhmr_unproject_visibility[_cuboid]
+                                 (visibility-aware aggregation) */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -365,6 +367,64 @@ int mvhmr_unproject_backward_geometry_cuboid_weighted(const mvhmr_unproject_desc
                                                       const uint8_t *view_mask, const float *view_weights, float *grad_proj, float *grad_rot,
                                                       float *grad_center, float *grad_weights, void *workspace, size_t workspace_bytes,
                                                       void *hip_stream);
+
+/*
+ * Visibility-aware aggregation (additive within ABI 4): the *_visible entry points are the *_masked ones -- same arguments,
+ * view_mask (B,V) uint8 on the DEVICE and nullable (NULL = every view present) -- with every VOXEL aggregating only the views that see it.
+ * With ix, iy, z the fp32 pixel position and depth the kernels compute for (voxel n, view v), view v SEES n iff
+ *     z > 0  and  0 <= ix <= Wf - 1  and  0 <= iy <= Hf - 1
+ * both ends inclusive; NaN anywhere, or z == 0, is not seen.  A seen view's bilinear footprint lies wholly inside the map; a view whose
+ * footprint is only partly inside (-1 < ix < 0 ...) is NOT seen, although the plain call gives it a non-zero sample.  S(b,n) = the
+ * present views that see n; with s_v the per-view sample:
+ *     sum      out = sum_S s_v                 mean  out = sum_S s_v / |S|
+ *     max      out = max_S s_v                 softmax  out = sum_S p_v s_v, p the softmax over S
+ * |S| = 0 gives out = 0 and exact-zero gradients for that voxel; a view outside S is not read for that voxel (non-finite feature values
+ * only unseen voxel-views would tap never reach the output) and receives exact zeros.  S is piecewise constant in the geometry, so the
+ * geometry gradients are the plain call's chain rule restricted to v in S.  The deterministic backward bounds the mean's fixed-point scale
+ * by max |grad_out| alone (a voxel may be seen by one view).  Limits, layouts, storage pairings, variants (quad-planar layouts and
+ * MVHMR_VARIANT_BRICK refused with MVHMR_ERR_UNSUPPORTED; AUTO runs the gather family) as the masked calls.  No view_weights yet.
+ * Workspace: the *_visible_workspace_bytes queries, never less than the masked ones; without a mask nothing is packed or copied.
+ *
+ * mvhmr_unproject_visibility[_cuboid] writes the sets themselves: bits (B,X,Y,Z) int32 on the device, bit v set iff view v is present
+ * (view_mask nullable) and sees the voxel.  desc->channels, dtypes and method are not used; no workspace; one kernel on hip_stream.
+ */
+size_t mvhmr_unproject_forward_visible_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_forward_cuboid_visible_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_visible_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_visible_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_deterministic_visible_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_deterministic_visible_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_visible_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_cuboid_visible_workspace_bytes(const mvhmr_unproject_desc *desc);
+int mvhmr_unproject_forward_visible(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords, const uint8_t
+                                    *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_forward_cuboid_visible(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float
+                                           *center, const double position[3], const double sides[3], const uint8_t *view_mask, void *out, void
+                                           *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float
+                                     *coords, const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void
+                                     *hip_stream);
+int mvhmr_unproject_backward_cuboid_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const
+                                            float *rot, const float *center, const double position[3], const double sides[3], const uint8_t
+                                            *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_deterministic_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                   const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace, size_t
+                                                   workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_deterministic_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float
+                                                          *proj, const float *rot, const float *center, const double position[3], const double
+                                                          sides[3], const uint8_t *view_mask, void *grad_features, void *workspace, size_t
+                                                          workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const
+                                              float *coords, const uint8_t *view_mask, float *grad_proj, float *grad_coords, void *workspace, size_t
+                                              workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_cuboid_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                     const float *rot, const float *center, const double position[3], const double sides[3], const
+                                                     uint8_t *view_mask, float *grad_proj, float *grad_rot, float *grad_center, void *workspace,
+                                                     size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_visibility(const mvhmr_unproject_desc *desc, const float *proj, const float *coords, const uint8_t *view_mask, int32_t *bits, void
+                               *hip_stream);
+int mvhmr_unproject_visibility_cuboid(const mvhmr_unproject_desc *desc, const float *proj, const float *rot, const float *center, const double
+                                      position[3], const double sides[3], const uint8_t *view_mask, int32_t *bits, void *hip_stream);
 
 /*
  * Layout pass on its own: features (B,V,C,Hf,Wf) -> dst in `dst_layout` (MVHMR_LAYOUT_BVHWC with the channel

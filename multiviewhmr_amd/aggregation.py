@@ -154,7 +154,9 @@ def _op_defined(name):
 # mask byte is nonzero and its weight > 0; DESIGN.md 5.9 -- the geometry backward differentiates w.r.t. them too), the placing arguments,
 # then method, out_dtype, variant.  The cuboid families feed the same kernels from the cuboid recipe
 # (mvhmr_unproject_*_cuboid) instead of a coordinate tensor.  The masked families (mvhmr_unproject_*_masked) read planar or channels-last
-# features, never a quad-planar copy, and run the gather kernels with a per-sample view count.
+# features, never a quad-planar copy, and run the gather kernels with a per-sample view count.  The visible families
+# (mvhmr_unproject_*_visible) are masked families -- view_mask is all ones when the caller gave none -- in which every voxel aggregates only
+# the views that see it.
 _CUBOID_ARGS = ("float[] position", "float[] sides", "int[] vol")
 _FAMILIES = {
     "unprojection": (("coords",), (), False),
@@ -163,14 +165,16 @@ _FAMILIES = {
     "unprojection_cuboid_masked": (("rot", "center"), _CUBOID_ARGS, True),
     "unprojection_weighted": (("coords",), (), True, True),
     "unprojection_cuboid_weighted": (("rot", "center"), _CUBOID_ARGS, True, True),
+    "unprojection_visible": (("coords",), (), True, False, True),
+    "unprojection_cuboid_visible": (("rot", "center"), _CUBOID_ARGS, True, False, True),
 }
 
 
 class _Family:
     """the implementations of one family's ops, each taking the ops' arguments positionally"""
 
-    def __init__(self, name, places, extras, masked, weighted=False):
-        self.name, self.masked, self.weighted = name, masked, weighted
+    def __init__(self, name, places, extras, masked, weighted=False, visible=False):
+        self.name, self.masked, self.weighted, self.visible = name, masked, weighted, visible
         self.native = "unprojection_cuboid" if extras else "unprojection"       # the extension's op: view_mask / view_weights are trailing arguments there
         self.geo = ("proj",) + places                                           # the geometry tensors, behind features
         self.tensors = ("features",) + self.geo + (("view_mask",) if masked else ()) + (("view_weights",) if weighted else ())
@@ -205,12 +209,12 @@ class _Family:
 
     def forward(self, *args):
         lead, (mask, weights) = self.native_args(args)
-        return getattr(_native(), self.native)(*lead, mask, weights)
+        return getattr(_native(), self.native)(*lead, mask, weights, self.visible)
 
     def backward(self, deterministic, grad_out, *args):
         """gradient w.r.t. features (the geometry's is backward_geometry)"""
         lead, (mask, weights) = self.native_args(args)
-        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights)
+        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible)
 
     def backward_geometry(self, grad_out, *args):
         """planar features go through the library's channels-last pass, channels-last ones are read as they are; the gradient w.r.t.
@@ -219,7 +223,7 @@ class _Family:
         want = self.split(args)[5]
         op = getattr(_native(), self.native + "_backward_geometry")
         if not self.weighted:
-            return tuple(op(grad_out.contiguous(), *lead, *want, mask))
+            return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, self.visible))
         gw = weights.new_empty(weights.shape if want[-1] else (0,))
         if not any(want[:-1]):                             # the weights' gradient alone: the extension's outputs stay empty
             op(grad_out.contiguous(), *lead, *want[:-1], mask, weights, gw)
@@ -310,7 +314,7 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
 
 
 def unprojection(features, proj_matricies, coord_volumes, aggregation_method='softmax', *, out_dtype=None,
-                 variant='auto', view_mask=None, view_weights=None):
+                 variant='auto', view_mask=None, view_weights=None, visible_only=False):
     """Fused project -> bilinear-sample -> cross-view aggregate (reference: models/aggregation.py:20-87).
 
     features        (B, V, C, Hf, Wf) float32 (or float16, this package's storage mode) on a HIP device;
@@ -331,6 +335,12 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
                     NaN is absent exactly as under view_mask (with a mask too: present = mask and w > 0); over the present views sum is
                     sum w_v s_v, mean that over sum w_v, softmax weighs e^{s_v} by w_v; 'max' raises ValueError.  Differentiable (the
                     gradient comes back in the caller's dtype and device); runs the gather kernels; DESIGN.md 5.9.
+    visible_only    keyword-only, default False.  True: every VOXEL aggregates only the views that see it -- depth > 0 and the projection
+                    inside the feature map, 0 <= ix <= Wf - 1 and 0 <= iy <= Hf - 1 -- instead of letting the others contribute zeros (the
+                    reference's quirk Q2): mean divides by the number of seeing views, softmax and max range over them, a voxel no view
+                    sees is 0.  Unseen views are not read for that voxel and get zero gradients there; `view_visibility` returns the sets.
+                    Differentiable like the plain call, composes with view_mask; with view_weights it raises ValueError (not built yet);
+                    runs the gather kernels ('brick' is refused); DESIGN.md 5.10.
     """
     def volume_shape(B):
         if coord_volumes.dim() != 5 or coord_volumes.shape[0] != B or coord_volumes.shape[4] != 3:
@@ -341,6 +351,7 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
         _check_view_mask(view_mask, features)
     if view_weights is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_view_weights(view_weights, features, aggregation_method)
+    _check_visible_only(visible_only, view_weights)
     out_dtype, _, empty = _check_call(features, proj_matricies, (coord_volumes,), volume_shape, aggregation_method, variant, out_dtype,
                                       same_device=True)
     if empty is not None:
@@ -348,6 +359,9 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
     # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
     proj = proj_matricies.to(torch.float32).contiguous()
     coords = coord_volumes.to(torch.float32).contiguous()
+    if visible_only:
+        return torch.ops.mvhmr.unprojection_visible(features, proj, coords, _weighted_mask(view_mask, features), _capi.AGG[aggregation_method],
+                                                    _dtype_code(out_dtype), _capi.VARIANT[variant])
     if view_weights is not None:
         return torch.ops.mvhmr.unprojection_weighted(features, proj, coords, _weighted_mask(view_mask, features), _weights_fp32(view_weights, features),
                                                      _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
@@ -366,6 +380,13 @@ def _check_view_mask(view_mask, features):
         raise TypeError("unprojection: view_mask must be bool or an integer dtype, got %s" % view_mask.dtype)
     if tuple(view_mask.shape) != tuple(features.shape[:2]):
         raise RuntimeError("unprojection: view_mask must be %s, got %s" % (tuple(features.shape[:2]), tuple(view_mask.shape)))
+
+
+def _check_visible_only(visible_only, view_weights):
+    """visibility-aware aggregation does not take per-view weights yet"""
+    if visible_only and view_weights is not None:
+        raise ValueError("unprojection: visible_only=True with view_weights is not supported yet (the next step of DESIGN.md 5.10): pass a view_mask, "
+                         "or drop one of the two")
 
 
 def _mask_bytes(view_mask, features):
@@ -445,14 +466,14 @@ _register_dlt_op()
 
 
 def unprojection_cuboid(features, proj_matricies, rotations, centers, position, sides, volume_shape,
-                        aggregation_method='softmax', *, out_dtype=None, variant='auto', view_mask=None, view_weights=None):
+                        aggregation_method='softmax', *, out_dtype=None, variant='auto', view_mask=None, view_weights=None, visible_only=False):
     """`unprojection` for the volumes VolumeGenerator builds (aggregation.py:138-187), without the coordinate tensor: voxel centres
     are rot[b] @ (position + sides / (S - 1) * (i,j,k) - center[b]) + center[b], evaluated inside the kernels (bit-equal to
     mvhmr_build_coord_volumes followed by `unprojection`).
 
     rotations (B,3,3) and centers (B,3): float32 tensors on features.device; position, sides: 3 numbers each (cuboid corner and
     edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers (and view_weights).
-    view_mask, view_weights: as for `unprojection`."""
+    view_mask, view_weights, visible_only: as for `unprojection`."""
     def checked_shape(B):
         if tuple(rotations.shape) != (B, 3, 3) or tuple(centers.shape) != (B, 3):
             raise RuntimeError("unprojection: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
@@ -463,6 +484,7 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
         _check_view_mask(view_mask, features)
     if view_weights is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_view_weights(view_weights, features, aggregation_method)
+    _check_visible_only(visible_only, view_weights)
     out_dtype, vol, empty = _check_call(features, proj_matricies, (rotations, centers), checked_shape, aggregation_method, variant,
                                         out_dtype, same_device=False)
     if empty is not None:
@@ -472,6 +494,10 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     proj = proj_matricies.to(device=dev, dtype=torch.float32).contiguous()
     rot = rotations.to(device=dev, dtype=torch.float32).contiguous()
     cen = centers.to(device=dev, dtype=torch.float32).contiguous()
+    if visible_only:
+        return torch.ops.mvhmr.unprojection_cuboid_visible(features, proj, rot, cen, _weighted_mask(view_mask, features), [float(x) for x in position],
+                                                           [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method],
+                                                           _dtype_code(out_dtype), _capi.VARIANT[variant])
     if view_weights is not None:
         return torch.ops.mvhmr.unprojection_cuboid_weighted(features, proj, rot, cen, _weighted_mask(view_mask, features),
                                                             _weights_fp32(view_weights, features), [float(x) for x in position],
@@ -483,6 +509,58 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
                                                           _dtype_code(out_dtype), _capi.VARIANT[variant])
     return torch.ops.mvhmr.unprojection_cuboid(features, proj, rot, cen, [float(x) for x in position], [float(x) for x in sides], list(vol),
                                                _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
+
+
+def _visibility_args(proj_matricies, feature_shape, view_mask):
+    """the checks view_visibility and view_visibility_cuboid share -> (proj fp32 contiguous, Hf, Wf, mask bytes or None)"""
+    if not torch.is_tensor(proj_matricies):
+        raise TypeError(_TYPE_MSG)
+    if proj_matricies.dim() != 4 or tuple(proj_matricies.shape[2:]) != (3, 4):
+        raise RuntimeError("view_visibility: proj_matricies must be (B, V, 3, 4), got %s" % (tuple(proj_matricies.shape),))
+    if not proj_matricies.is_cuda:
+        raise RuntimeError("view_visibility: proj_matricies live on %s; this implementation runs only on a HIP device" % proj_matricies.device)
+    Hf, Wf = (int(x) for x in feature_shape)
+    if view_mask is not None:
+        _check_view_mask(view_mask, proj_matricies)                          # (only its (B, V) leading shape is read)
+    proj = proj_matricies.detach().to(torch.float32).contiguous()
+    return proj, Hf, Wf, None if view_mask is None else _mask_bytes(view_mask, proj)
+
+
+def view_visibility(proj_matricies, coord_volumes, feature_shape, view_mask=None):
+    """Which views see which voxel, by the rule of `unprojection(..., visible_only=True)` and from the same arithmetic.
+
+    proj_matricies (B, V, 3, 4) and coord_volumes (B, X, Y, Z, 3) on a HIP device, feature_shape = (Hf, Wf), view_mask as for `unprojection`.
+    Returns a (B, X, Y, Z) int32 tensor: bit v is set iff view v is present and sees the voxel (depth > 0, 0 <= ix <= Wf - 1, 0 <= iy <= Hf - 1).
+    Not differentiable.  What a caller masks a loss with, or feeds to the network as a per-voxel view count."""
+    proj, Hf, Wf, mask = _visibility_args(proj_matricies, feature_shape, view_mask)
+    if not torch.is_tensor(coord_volumes):
+        raise TypeError(_TYPE_MSG)
+    if coord_volumes.dim() != 5 or coord_volumes.shape[0] != proj.shape[0] or coord_volumes.shape[4] != 3:
+        raise RuntimeError("view_visibility: coord_volumes must be (%d, X, Y, Z, 3), got %s" % (proj.shape[0], tuple(coord_volumes.shape)))
+    if coord_volumes.device != proj.device:
+        raise RuntimeError("view_visibility: expected all tensors on %s, got coord_volumes on %s" % (proj.device, coord_volumes.device))
+    if 0 in coord_volumes.shape or proj.shape[1] == 0:
+        return torch.zeros(tuple(coord_volumes.shape[:4]), dtype=torch.int32, device=proj.device)
+    _native()                                            # loads the extension: its visibility ops are mvhmr_visibility::
+    return torch.ops.mvhmr_visibility.view_visibility(proj, coord_volumes.detach().to(torch.float32).contiguous(), Hf, Wf, mask)
+
+
+def view_visibility_cuboid(proj_matricies, rotations, centers, position, sides, volume_shape, feature_shape, view_mask=None):
+    """`view_visibility` for the volumes of `unprojection_cuboid` (same placing arguments): bit-equal to it on the coordinate tensor."""
+    proj, Hf, Wf, mask = _visibility_args(proj_matricies, feature_shape, view_mask)
+    B = proj.shape[0]
+    if not torch.is_tensor(rotations) or not torch.is_tensor(centers):
+        raise TypeError(_TYPE_MSG)
+    if tuple(rotations.shape) != (B, 3, 3) or tuple(centers.shape) != (B, 3):
+        raise RuntimeError("view_visibility: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
+                           % (B, B, tuple(rotations.shape), tuple(centers.shape)))
+    vol = [int(v) for v in volume_shape]
+    if 0 in vol or 0 in proj.shape:
+        return torch.zeros((B,) + tuple(vol), dtype=torch.int32, device=proj.device)
+    rot = rotations.detach().to(device=proj.device, dtype=torch.float32).contiguous()
+    cen = centers.detach().to(device=proj.device, dtype=torch.float32).contiguous()
+    _native()
+    return torch.ops.mvhmr_visibility.view_visibility_cuboid(proj, rot, cen, [float(x) for x in position], [float(x) for x in sides], vol, Hf, Wf, mask)
 
 
 # --------------------------------------------------------------------------------------- caller side
@@ -642,7 +720,7 @@ class VolumeGenerator(nn.Module):
 
     def __init__(self, volume_size=64, input_channels=256, output_channels=32, cuboid_side=2500.0,
                  aggregation_method='softmax', use_triangulation=False, kind='mpii', device='cuda',
-                 dataset='human36m', volume_dtype=None, **kwargs):
+                 dataset='human36m', volume_dtype=None, visible_only=False, **kwargs):
         # **kwargs swallows unknown keywords exactly like the reference (quirk Q5: build_volume_generator
         # passes volume_aggregation_method=, so aggregation_method keeps its default)
         super().__init__()
@@ -654,6 +732,7 @@ class VolumeGenerator(nn.Module):
         self.kind = kind
         self.dataset = dataset
         self.volume_dtype = volume_dtype  # extension: None = float32 like the reference; torch.bfloat16 / float16 for a half-precision consumer
+        self.visible_only = bool(visible_only)  # extension: every voxel aggregates only the views that see it
         self.fused_conv = True            # 1x1 conv + layout pass as one MFMA GEMM wherever its shapes allow (see _fused_path_applies)
         self.to(device)
 
@@ -759,7 +838,8 @@ class VolumeGenerator(nn.Module):
         rots = rots.to(device=device, dtype=torch.float32).contiguous()
         centers = centers.to(device=device, dtype=torch.float32).contiguous()
 
-        if view_mask is None and view_weights is None and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask or weights do not take)
+        _check_visible_only(self.visible_only, view_weights)
+        if view_mask is None and view_weights is None and not self.visible_only and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask, weights or visible_only do not take)
             # 1x1 conv and layout pass in one MFMA GEMM, its output only ever exists in the layout the brick forward stages
             conv = self.process_feature[0]
             return _FusedAggregate.apply(features, conv.weight, conv.bias, proj, rots, centers, tuple(cub.position), tuple(cub.sides),
@@ -772,6 +852,8 @@ class VolumeGenerator(nn.Module):
         masked = {} if view_mask is None else {"view_mask": view_mask}       # (an unmasked batch calls exactly as before)
         if view_weights is not None:
             masked["view_weights"] = view_weights
+        if self.visible_only:
+            masked["visible_only"] = True
         return unprojection_cuboid(features, proj, rots, centers, cub.position, cub.sides, (S, S, S),
                                    aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **masked)
 
@@ -804,6 +886,14 @@ class VolumeGenerator(nn.Module):
         return L.mvhmr_unproject_selected_variant(ctypes.byref(desc)) > 0 and L.mvhmr_unproject_backward_supported(ctypes.byref(desc)) == 1
 
 
+def _cfg_visible_only(cfg):
+    """MODEL.AGGREGATION.VISIBLE_ONLY, an extension key the reference's cfg tree does not have: absent (however the tree says so) = False"""
+    try:
+        return bool(cfg.MODEL.AGGREGATION.VISIBLE_ONLY)
+    except (AttributeError, KeyError):
+        return False
+
+
 def build_volume_generator(cfg):
     """cfg is the reference's yacs tree (cfg/defaults.py:18-30,89-90); same wiring as aggregation.py:198-208."""
     input_channels = cfg.MODEL.BACKBONE.DECONV_FILTERS[-1] if cfg.MODEL.BACKBONE.DECONV_LAYERS != 0 else 2048
@@ -814,4 +904,5 @@ def build_volume_generator(cfg):
                            use_triangulation=cfg.MODEL.AGGREGATION.USE_TRIANGULATION,
                            kind=cfg.DATASET.KIND,
                            dataset=cfg.DATASET.TYPE,
-                           volume_aggregation_method=cfg.MODEL.AGGREGATION.METHOD)
+                           volume_aggregation_method=cfg.MODEL.AGGREGATION.METHOD,
+                           visible_only=_cfg_visible_only(cfg))

@@ -281,26 +281,43 @@ int weights_refused(const mvhmr_unproject_desc *desc)
     if (desc->method == MVHMR_AGG_MAX) return fail(MVHMR_ERR_UNSUPPORTED, "aggregation method max has no weighted form: pass a view mask instead of view weights");
     return MVHMR_OK;
 }
+// ---- visibility-aware aggregation (include/mvhmr_unproject.h): every voxel aggregates only the views that see it.  The
+// route of the masks: the gather family with the per-tap scatter backward and the geometry kernels, which launch their *_seen kernels
+// (Problem::visible); with a mask the views are packed exactly as for a masked call, without one nothing is packed or copied.  Refused
+// where a mask is.
+int visible_refused(const mvhmr_unproject_desc *desc)
+{
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "visibility-aware aggregation needs planar or channels-last features (quad-planar copies: pass the planar features)");
+    if (desc->variant == MVHMR_VARIANT_BRICK)
+        return fail(MVHMR_ERR_UNSUPPORTED, "visibility-aware aggregation runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
+    return MVHMR_OK;
+}
 // what selects the packed route of a call, and whether the descriptor can take it
 struct Views {
     const uint8_t *mask;
     const float *weights;
+    bool visible = false;                       // the *_visible entry points (no weights there); a null mask packs nothing
     bool packed() const { return mask || weights; }
 };
 int views_refused(const mvhmr_unproject_desc *desc, const Views &w)
 {
     int rc = MVHMR_OK;
+    if (w.visible && (rc = visible_refused(desc)) != MVHMR_OK) return rc;
     if (w.mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
     return w.weights ? weights_refused(desc) : MVHMR_OK;
 }
-// the three kinds of plan: every view, a mask, weights (with or without a mask)
-enum class Pack { None, Masked, Weighted };
-Pack pack_of(const Views &w) { return w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None; }
+// the kinds of plan: every view, a mask, weights (with or without a mask), the seeing views of every voxel (with or without a mask)
+enum class Pack { None, Masked, Weighted, Visible };
+Pack pack_of(const Views &w) { return w.visible ? Pack::Visible : w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None; }
+// the plan whose workspace a plan's total also covers: a weighted or visible call's serves the masked one, a masked call's the unmasked one
+Pack pack_below(Pack pack) { return pack == Pack::Masked ? Pack::None : Pack::Masked; }
 // the descriptor and problem of the packed call; view_count is set once the table exists (pack_views)
-void mask_route(mvhmr_unproject_desc *desc, Problem *p)
+void mask_route(mvhmr_unproject_desc *desc, Problem *p, Pack pack)
 {
     desc->variant = MVHMR_VARIANT_GATHER;
     p->masked = 1;
+    p->visible = pack == Pack::Visible;
 }
 size_t masked_view_bytes(const Problem &p) { return (size_t)p.C * p.H * p.W * feat_elem(p); }   // one view, planar or channels-last (C4 == C)
 
@@ -359,7 +376,7 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pac
     f.desc = *desc;
     f.p = p;
     if (pack != Pack::None) {
-        mask_route(&f.desc, &f.p);
+        mask_route(&f.desc, &f.p, pack);
         f.head = plan_mask_head(a, p, 1, pack == Pack::Weighted);
     }
     const mvhmr_unproject_desc *d = &f.desc;
@@ -376,7 +393,7 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pac
         f.staged = a.take(brick_workspace_bytes(f.p));
     }
     // (a weighted call's workspace also serves the masked one, a masked call's the unmasked one)
-    f.total = pack == Pack::None ? a.top : max_size(a.top, plan_forward(desc, p, pack == Pack::Weighted ? Pack::Masked : Pack::None).total);
+    f.total = pack == Pack::None ? a.top : max_size(a.top, plan_forward(desc, p, pack_below(pack)).total);
     return f;
 }
 
@@ -447,7 +464,7 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
     b.desc = *desc;
     b.p = p;
     if (pack != Pack::None) {
-        mask_route(&b.desc, &b.p);
+        mask_route(&b.desc, &b.p, pack);
         b.head = plan_mask_head(a, p, 2, pack == Pack::Weighted);
     }
     if (det) {
@@ -459,7 +476,7 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
     } else {
         place_default_backward(b, a);
     }
-    b.total = pack == Pack::None ? a.top : max_size(a.top, plan_backward(desc, p, det, pack == Pack::Weighted ? Pack::Masked : Pack::None).total);
+    b.total = pack == Pack::None ? a.top : max_size(a.top, plan_backward(desc, p, det, pack_below(pack)).total);
     return b;
 }
 
@@ -483,7 +500,7 @@ GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, b
     g.desc = *desc;
     g.p = p;
     if (pack != Pack::None) {
-        mask_route(&g.desc, &g.p);
+        mask_route(&g.desc, &g.p, pack);
         g.head = plan_mask_head(a, p, 1, pack == Pack::Weighted);
         g.packed_grad_proj = a.take(align_up((size_t)p.B * p.V * 12 * sizeof(float)));
     }
@@ -494,7 +511,7 @@ GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, b
     if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) g.staged = a.take(featT_bytes(p));
     g.part = a.take(align_up(geom_partial_bytes(p)));
     if (cuboid) g.pose_part = a.take(align_up(pose_partial_bytes(p)));
-    g.total = pack == Pack::None ? a.top : max_size(a.top, plan_geometry(desc, p, cuboid, pack == Pack::Weighted ? Pack::Masked : Pack::None).total);
+    g.total = pack == Pack::None ? a.top : max_size(a.top, plan_geometry(desc, p, cuboid, pack_below(pack)).total);
     return g;
 }
 
@@ -708,7 +725,7 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
     void *scale = at(c.workspace, b.scale);
     rc = clear_gradient(acc, p, sizeof(long long), s);
     if (rc != MVHMR_OK) return rc;
-    rc = launched(launch_det_scale(c.grad_out, feat, scale, p, s, brick), "deterministic scale pass");
+    rc = launched(launch_det_scale(c.grad_out, feat, scale, p, s, brick, c.proj, &coords), "deterministic scale pass");
     if (rc != MVHMR_OK) return rc;
     const int *kexp = det_exponents(scale, p);
     if (brick) {
@@ -813,10 +830,23 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     return launched(launch_view_unpack(gw, grad_weights, at(workspace, g.head.table), p.B, p.V, sizeof(float), s), "view unpack");
 }
 
+// ---- the visibility bits themselves: no features, no workspace, one kernel
+int run_visibility(const mvhmr_unproject_desc *desc, const VolumeSource &v, const float *proj, const uint8_t *view_mask, int32_t *bits, void *hip_stream)
+{
+    Problem p;
+    Coords coords;
+    int rc = open_call(desc, v, &p, &coords);
+    if (rc != MVHMR_OK) return rc;
+    if (!proj || !bits) return fail(MVHMR_ERR_INVALID_ARGUMENT, "proj / bits must be non-null");
+    if ((rc = visible_refused(desc)) != MVHMR_OK) return rc;
+    return launched(launch_view_visibility(proj, coords, view_mask, bits, p, static_cast<hipStream_t>(hip_stream)), "view visibility");
+}
+
 // the workspace queries: a descriptor the call would refuse outright needs none
 bool pack_refused(const mvhmr_unproject_desc *desc, Pack pack)
 {
-    return (pack == Pack::Masked && mask_refused(desc) != MVHMR_OK) || (pack == Pack::Weighted && weights_refused(desc) != MVHMR_OK);
+    return (pack == Pack::Masked && mask_refused(desc) != MVHMR_OK) || (pack == Pack::Weighted && weights_refused(desc) != MVHMR_OK) ||
+           (pack == Pack::Visible && visible_refused(desc) != MVHMR_OK);
 }
 size_t forward_need(const mvhmr_unproject_desc *desc, Pack pack)
 {
@@ -1111,6 +1141,79 @@ int mvhmr_unproject_backward_geometry_cuboid_weighted(const mvhmr_unproject_desc
 {
     return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, view_weights}, grad_proj, nullptr,
                         grad_rot, grad_center, grad_weights, workspace, workspace_bytes, hip_stream);
+}
+
+// ---- visibility-aware aggregation: the _masked entry points (view_mask may be null) with every voxel aggregating only the views that see it
+size_t mvhmr_unproject_forward_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Visible); }
+size_t mvhmr_unproject_forward_cuboid_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Visible); }
+size_t mvhmr_unproject_backward_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Visible); }
+size_t mvhmr_unproject_backward_cuboid_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Visible); }
+size_t mvhmr_unproject_backward_deterministic_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Visible); }
+size_t mvhmr_unproject_backward_cuboid_deterministic_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Visible); }
+size_t mvhmr_unproject_backward_geometry_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Visible); }
+size_t mvhmr_unproject_backward_geometry_cuboid_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Visible); }
+
+int mvhmr_unproject_forward_visible(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, nullptr, true}, out, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_forward_cuboid_visible(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, nullptr, true}, out, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, true}, false, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, true}, false, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_deterministic_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, true}, true, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_deterministic_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, true}, true, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords, const uint8_t *view_mask, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, true}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
+                        workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_cuboid_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3], const uint8_t *view_mask, float *grad_proj,
+        float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, true}, grad_proj, nullptr, grad_rot,
+                        grad_center, nullptr, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_visibility(const mvhmr_unproject_desc *desc, const float *proj, const float *coords, const uint8_t *view_mask, int32_t *bits,
+                               void *hip_stream)
+{
+    return run_visibility(desc, tensor_volume(coords), proj, view_mask, bits, hip_stream);
+}
+
+int mvhmr_unproject_visibility_cuboid(const mvhmr_unproject_desc *desc, const float *proj, const float *rot, const float *center,
+                                      const double position[3], const double sides[3], const uint8_t *view_mask, int32_t *bits, void *hip_stream)
+{
+    return run_visibility(desc, cuboid_volume(rot, center, position, sides), proj, view_mask, bits, hip_stream);
 }
 
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)

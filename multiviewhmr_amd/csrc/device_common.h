@@ -113,6 +113,23 @@ __device__ __forceinline__ Taps make_taps(const float *__restrict__ P, float X0,
     return t;
 }
 
+// Visibility: the view SEES the voxel iff z > 0, 0 <= ix <= W - 1 and 0 <= iy <= H - 1, with ix, iy, z the very values make_taps
+// computes (the same operations in the same order: a caller of both gets one copy of the arithmetic and bit-equal positions).  Both ends are
+// inclusive; NaN anywhere, or z == 0, is not seen.  A seen view's bilinear footprint lies wholly inside the map.
+__device__ __forceinline__ bool view_sees(const float *__restrict__ P, float X0, float X1, float X2, int H, int W)
+{
+    const float a = __fmaf_rn(P[3], 1.f, __fmaf_rn(P[2], X2, __fmaf_rn(P[1], X1, __fmul_rn(P[0], X0))));
+    const float b = __fmaf_rn(P[7], 1.f, __fmaf_rn(P[6], X2, __fmaf_rn(P[5], X1, __fmul_rn(P[4], X0))));
+    const float z = __fmaf_rn(P[11], 1.f, __fmaf_rn(P[10], X2, __fmaf_rn(P[9], X1, __fmul_rn(P[8], X0))));
+    if (!(z > 0.f)) return false;
+    const float u = __fdiv_rn(a, z), v = __fdiv_rn(b, z);
+    const float gx = __fmul_rn(2.f, __fsub_rn(__fdiv_rn(u, (float)H), 0.5f));      // quirk Q1, as make_taps
+    const float gy = __fmul_rn(2.f, __fsub_rn(__fdiv_rn(v, (float)W), 0.5f));
+    const float ix = __fmul_rn(__fmul_rn(__fadd_rn(gx, 1.f), 0.5f), (float)(W - 1));
+    const float iy = __fmul_rn(__fmul_rn(__fadd_rn(gy, 1.f), 0.5f), (float)(H - 1));
+    return ix >= 0.f && ix <= (float)(W - 1) && iy >= 0.f && iy <= (float)(H - 1);
+}
+
 __device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v11, float w00, float w01, float w10, float w11)
 {
     return __fmaf_rn(v11, w11, __fmaf_rn(v10, w10, __fmaf_rn(v01, w01, __fmul_rn(v00, w00))));
@@ -318,6 +335,43 @@ __device__ __forceinline__ void masked_aggregate_grad(float (&s)[V], float g, fl
         aggregate_grad<METHOD, V>(s, g, ds);
 #pragma unroll
         for (int v = 1; v < V; ++v) ds[v] = v < nv ? ds[v] : 0.f;
+    }
+}
+
+// Visibility-aware aggregation: bit v of `bits` says whether slot v takes part for THIS voxel (wave-uniform); any slot,
+// slot 0 included, may be absent.  The model of masked_aggregate with a bit test where that has v < nv; no bit set gives 0.
+template <int METHOD, int V>
+__device__ __forceinline__ float seen_aggregate(float (&s)[V], unsigned bits)
+{
+    if (bits == 0u) return 0.f;
+    if constexpr (METHOD == AGG_SUM || METHOD == AGG_MEAN) {
+        float r = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) r = (bits >> v & 1u) ? __fadd_rn(r, s[v]) : r;
+        return METHOD == AGG_MEAN ? __fdiv_rn(r, (float)__builtin_popcount(bits)) : r;
+    } else {
+#pragma unroll
+        for (int v = 0; v < V; ++v) s[v] = (bits >> v & 1u) ? s[v] : kMaskedSample;
+        return aggregate<METHOD, V>(s);
+    }
+}
+// the absent slots get ds = 0 exactly (their -FLT_MAX samples must not reach a product); the mean's ds is g / |S|, so |ds| <= |g|
+template <int METHOD, int V>
+__device__ __forceinline__ void seen_aggregate_grad(float (&s)[V], float g, float (&ds)[V], unsigned bits)
+{
+    if constexpr (METHOD == AGG_SUM) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) ds[v] = (bits >> v & 1u) ? g : 0.f;
+    } else if constexpr (METHOD == AGG_MEAN) {
+        const float gv = bits ? __fdiv_rn(g, (float)__builtin_popcount(bits)) : 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) ds[v] = (bits >> v & 1u) ? gv : 0.f;
+    } else {
+#pragma unroll
+        for (int v = 0; v < V; ++v) s[v] = (bits >> v & 1u) ? s[v] : kMaskedSample;
+        aggregate_grad<METHOD, V>(s, g, ds);
+#pragma unroll
+        for (int v = 0; v < V; ++v) ds[v] = (bits >> v & 1u) ? ds[v] : 0.f;
     }
 }
 

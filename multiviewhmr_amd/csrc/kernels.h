@@ -29,6 +29,9 @@ struct Problem {
     const float *view_weights = nullptr;
     // the view-mask route (set before the table exists, for the workspace queries): the gather family with the per-tap scatter backward
     int masked = 0;
+    // Visibility-aware aggregation: every voxel aggregates only the views that see it.  The gather and geometry launchers
+    // hand such a problem to their *_seen kernels (unproject_visible.hip, unproject_visible_geom.hip); view_count, when set, bounds the slots.
+    int visible = 0;
 };
 
 inline Gate make_gate(const Problem &p, bool wants_brick) { return Gate{p.gate_count, p.gate_limit, wants_brick ? 1 : 0}; }
@@ -61,7 +64,9 @@ hipError_t launch_bwd_gather(const void *grad_out, const void *featT, const floa
 // channels-last feature copy; k_bwd_gather_det adds int64 fixed point into gradI (zeroed, channels-last (B,V,HW,C4)); the conversion passes
 // write the caller's planar or channels-last gradient (NaN for a poisoned (b, c))
 size_t det_scale_bytes(const Problem &p);
-hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale, const Problem &p, hipStream_t s, bool quad = false);   // feat: channels-last copy, or the quad-planar one (quad)
+// (a visible problem's softmax bound ranges over the pixels its seeing voxel-views tap: it needs proj and coords, and det_scale_bytes has the marks)
+hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale, const Problem &p, hipStream_t s, bool quad = false,   // feat: channels-last copy, or the quad-planar one (quad)
+                            const float *proj = nullptr, const Coords *coords = nullptr);
 const int *det_exponents(const void *scale, const Problem &p);
 hipError_t launch_bwd_gather_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
                                  const int *kexp, const Problem &p, hipStream_t s);
@@ -155,6 +160,19 @@ size_t pose_partial_bytes(const Problem &p);
 hipError_t launch_bwd_geom_cuboid(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
                                   float *pose_part, float *grad_rot, float *grad_center, const Problem &p, hipStream_t s, float *wpart = nullptr,
                                   float *grad_weights = nullptr);
+
+// visibility-aware aggregation (unproject_visible.hip; Problem::visible): the gather forward, the per-tap scatter backward of both modes
+// (launch_fwd_gather / launch_bwd_gather / launch_bwd_gather_det call these for visible problems), and the bitmask itself -- bits (B, N)
+// int32, bit v = view v is present (mask (B, V) bytes, null: all) and sees the voxel
+hipError_t launch_fwd_gather_seen(const void *featT, const float *proj, const Coords &coords, void *out, const Problem &p, hipStream_t s);
+hipError_t launch_bwd_gather_seen(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *gradT, const Problem &p,
+                                  hipStream_t s);
+hipError_t launch_bwd_gather_seen_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
+                                      const int *kexp, const Problem &p, hipStream_t s);
+hipError_t launch_view_visibility(const float *proj, const Coords &coords, const uint8_t *mask, int *bits, const Problem &p, hipStream_t s);
+// (the seen instances of k_bwd_geom live in unproject_visible_geom.hip; launch_bwd_geom[_cuboid] call this for visible problems)
+hipError_t launch_bwd_geom_seen_kernel(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part,
+                                       float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
 
 // view masks (view_mask.hip): from mask (B,V) bytes, one thread per sample writes n_b (B ints), slot -> view and view -> slot (-1: masked)
 // tables (B,V ints each) and the projections packed into slot order (absent slots zero); then per-(sample, slot) copies of `bytes_per_view`

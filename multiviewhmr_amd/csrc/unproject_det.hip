@@ -55,6 +55,48 @@ __global__ void __launch_bounds__(256) k_det_fmax(const TF *__restrict__ featT, 
     }
 }
 
+// Visibility-aware softmax: a view that does not see a voxel is not read for it, so the bound may range only over the pixels
+// a seeing voxel-view taps -- a non-finite value elsewhere must neither poison the (b, c) nor widen its scale.  k_det_mark_seen sets one byte
+// per tapped pixel of every (b, slot) map (thread per (voxel, slot): view_sees and make_taps, the very test and taps k_bwd_gather_seen uses;
+// every writer stores the same 1, so the order plays no part), k_det_fmax_seen is k_det_fmax over the marked pixels.
+__global__ void __launch_bounds__(256) k_det_mark_seen(const float *__restrict__ proj, const Coords coords, unsigned char *__restrict__ marks, int V,
+                                                       int H, int W, long long N, const int *__restrict__ nvs)
+{
+    const long long bv = blockIdx.y;
+    const int b = (int)(bv / V), v = (int)(bv % V);
+    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N || (nvs && v >= nvs[b])) return;                                   // slots behind the present views are absent
+    float X0, X1, X2;
+    voxel_xyz(coords, b, N, n, X0, X1, X2);
+    const float *P = proj + bv * 12;
+    if (!view_sees(P, X0, X1, X2, H, W)) return;
+    const Taps t = make_taps(P, X0, X1, X2, H, W);                                // clamped to the map whatever the position
+    unsigned char *m = marks + bv * (long long)H * W;
+    m[t.y0 * W + t.x0] = 1;
+    m[t.y0 * W + t.x1] = 1;
+    m[t.y1 * W + t.x0] = 1;
+    m[t.y1 * W + t.x1] = 1;
+}
+
+template <typename TF>
+__global__ void __launch_bounds__(256) k_det_fmax_seen(const TF *__restrict__ featT, const unsigned char *__restrict__ marks, unsigned *__restrict__ fmax,
+                                                       int V, int C, int C4, int HW)
+{
+    const long long bv = blockIdx.y;
+    const int b = (int)(bv / V), p0 = blockIdx.x * kDetPix, p1 = p0 + kDetPix < HW ? p0 + kDetPix : HW;
+    const TF *f = featT + bv * (long long)HW * C4;
+    const unsigned char *mk = marks + bv * (long long)HW;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        unsigned m = 0;
+        for (int p = p0; p < p1; ++p) {
+            if (!mk[p]) continue;                                                 // block-uniform
+            const unsigned a = abs_bits(to_f32<TF>(f[(long long)p * C4 + c]));
+            m = a > m ? a : m;
+        }
+        if (m) atomicMax(fmax + (long long)b * C + c, m);
+    }
+}
+
 // the same from the column-major quad-planar fp32 copy (BV, C4/4, W, H, 4) the brick kernels stage: block (pixel chunk, bv * nqv + q), lanes
 // 4 apart hold the same channel
 template <int UNUSED = 0>
@@ -205,9 +247,14 @@ k_det_quad_to_planar(const unsigned long long *__restrict__ src, const int *__re
         for (int r = threadIdx.x / BW; r < nc * H; r += 512 / BW) d[(long long)r * W + xl] = from_f32<TF>(tile[r * TS + xl]);
 }
 
-size_t det_scale_bytes(const Problem &p) { return (size_t)p.B * p.C * 3 * sizeof(int); }
+// gmax, fmax, K: three words per (b, c); a visible problem's tap marks (one byte per pixel of every (b, slot) map) lie behind them
+size_t det_scale_bytes(const Problem &p)
+{
+    return (size_t)p.B * p.C * 3 * sizeof(int) + (p.visible ? (size_t)p.B * p.V * p.H * p.W : 0);
+}
 
-hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale, const Problem &p, hipStream_t s, bool quad)
+hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale, const Problem &p, hipStream_t s, bool quad, const float *proj,
+                            const Coords *coords)
 {
     const void *featT = feat;
     const long long BC = (long long)p.B * p.C;
@@ -222,7 +269,18 @@ hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale,
     if (p.out_bf16) hipLaunchKernelGGL(k_det_gmax<bf16_t>, g1, dim3(256), 0, s, (const bf16_t *)grad_out, gmax, p.N);
     else if (p.out_f16) hipLaunchKernelGGL(k_det_gmax<__half>, g1, dim3(256), 0, s, (const __half *)grad_out, gmax, p.N);
     else hipLaunchKernelGGL(k_det_gmax<float>, g1, dim3(256), 0, s, (const float *)grad_out, gmax, p.N);
-    if (p.method == AGG_SOFTMAX && quad) {
+    if (p.method == AGG_SOFTMAX && p.visible) {
+        if (quad || !proj || !coords) return hipErrorInvalidValue;               // the gather family only
+        const int HW = p.H * p.W;
+        unsigned char *marks = reinterpret_cast<unsigned char *>(kexp + BC);
+        e = hipMemsetAsync(marks, 0, (size_t)p.B * p.V * HW, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_det_mark_seen, dim3((unsigned)((p.N + 255) / 256), (unsigned)(p.B * p.V)), dim3(256), 0, s, proj, *coords, marks, p.V, p.H,
+                           p.W, p.N, p.view_count);
+        const dim3 g2((unsigned)((HW + kDetPix - 1) / kDetPix), (unsigned)(p.B * p.V));
+        if (p.feat_f16) hipLaunchKernelGGL(k_det_fmax_seen<__half>, g2, dim3(256), 0, s, (const __half *)featT, marks, fmax, p.V, p.C, p.C4, HW);
+        else hipLaunchKernelGGL(k_det_fmax_seen<float>, g2, dim3(256), 0, s, (const float *)featT, marks, fmax, p.V, p.C, p.C4, HW);
+    } else if (p.method == AGG_SOFTMAX && quad) {
         const int HW = p.H * p.W, nqv = p.C4 / 4;
         const dim3 g2((unsigned)((HW + 4 * kDetPix - 1) / (4 * kDetPix)), (unsigned)((long long)p.B * p.V * nqv));
         hipLaunchKernelGGL(k_det_fmax_quad<>, g2, dim3(256), 0, s, (const float4 *)feat, fmax, p.V, p.C, nqv, HW);
@@ -233,7 +291,11 @@ hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale,
         else hipLaunchKernelGGL(k_det_fmax<float>, g2, dim3(256), 0, s, (const float *)featT, fmax, p.V, p.C, p.C4, HW);
     }
     const int log2n = p.N > 1 ? 64 - __builtin_clzll((unsigned long long)(p.N - 1)) : 0;
-    if (p.view_weights)
+    if (p.visible)
+        // visibility-aware aggregation: a voxel may be seen by ONE view, so the mean's |ds| = |g| / |S| is bounded by |g| alone
+        // -- not g / V, not g / n_b: k_det_exponent with a divisor of 1
+        hipLaunchKernelGGL(k_det_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gmax, fmax, kexp, BC, p.method, 1, log2n);
+    else if (p.view_weights)
         hipLaunchKernelGGL(k_weighted_det_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gmax, fmax, kexp, BC, p.method, p.C, p.V, log2n,
                            p.view_weights);
     else if (p.view_count)

@@ -378,6 +378,7 @@ static hipError_t geom_dispatch(const void *grad_out, const void *featT, const f
                                 float *pose_part, float *wpart, const Problem &p, hipStream_t s)
 {
     if (p.view_weights) return launch_bwd_geom_weighted_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, wpart, POSE, p, s);
+    if (p.visible) return launch_bwd_geom_seen_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, POSE, p, s);
     if (p.out_bf16)
         return p.feat_f16 ? hipErrorNotSupported
                           : geom_dispatch_m<float, bf16_t, POSE>((const bf16_t *)grad_out, (const float *)featT, proj, coords, part, grad_coords, pose_part, p, s);

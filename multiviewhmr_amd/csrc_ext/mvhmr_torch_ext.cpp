@@ -3,7 +3,9 @@
 // from its torch.library ops and from _FusedAggregate, and of the DLT triangulation (triangulate_dlt[_backward], multiview.py).  Every
 // un-projection op takes a trailing `Tensor? view_mask` (None: the unmasked C entry point), the two feature backwards a trailing
 // `bool deterministic`, and all of them behind that `Tensor? view_weights` (per-view confidence weights: the *_weighted entry points; the
-// geometry ops also `Tensor(a!)? grad_weights`, the (B, V) fp32 tensor they write the gradient w.r.t. the weights into); the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
+// geometry ops also `Tensor(a!)? grad_weights`, the (B, V) fp32 tensor they write the gradient w.r.t. the weights into) and last `bool visible_only`
+// (visibility-aware aggregation: the *_visible entry points, view_mask nullable, no weights); mvhmr_visibility::view_visibility[_cuboid] return the
+// (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
 // tensor checks, descriptor, output and workspace from the caching allocator, the current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -108,7 +110,16 @@ const float *weights_ptr(const mvhmr_unproject_desc &d, const at::Tensor &featur
 struct ViewArgs {
     const uint8_t *mask;
     const float *weights;
+    bool visible = false;                                       // the *_visible entry points: every voxel aggregates the views that see it
 };
+
+ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_mask,
+                   const c10::optional<at::Tensor> &view_weights, bool visible_only)
+{
+    const ViewArgs v{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights), visible_only};
+    TORCH_CHECK(!(v.visible && v.weights), "mvhmr_unproject: visible_only does not take view_weights");
+    return v;
+}
 
 // the common tail: workspace, the features' device, the current HIP stream, one C-ABI call.  The workspace comes from the caching
 // allocator through at::empty -- except `unfilled` (the deterministic entry points), straight from the device allocator: under
@@ -156,11 +167,16 @@ struct TensorVolume {
     {
         check_inputs(d, features, proj, &coords, nullptr, nullptr, grad_out);
     }
+    int visibility(const mvhmr_unproject_desc &d, const float *proj, const uint8_t *mask, int32_t *bits, hipStream_t s) const
+    {
+        return mvhmr_unproject_visibility(&d, proj, coords.data_ptr<float>(), mask, bits, s);
+    }
     // gradients w.r.t. proj (B,V,3,4) and coords (B,X,Y,Z,3)
     std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, coords.sizes().vec()}; }
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.visible) return mvhmr_unproject_forward_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_forward_weighted_workspace_bytes(&d);
         return v.mask ? mvhmr_unproject_forward_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
     }
@@ -168,11 +184,13 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.visible) return mvhmr_unproject_forward_visible(&d, features, proj, c, mask, out, ws, n, s);
         if (v.weights) return mvhmr_unproject_forward_weighted(&d, features, proj, c, mask, v.weights, out, ws, n, s);
         return mask ? mvhmr_unproject_forward_masked(&d, features, proj, c, mask, out, ws, n, s) : mvhmr_unproject_forward(&d, features, proj, c, out, ws, n, s);
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.visible) return det ? mvhmr_unproject_backward_deterministic_visible_workspace_bytes(&d) : mvhmr_unproject_backward_visible_workspace_bytes(&d);
         if (v.weights) return det ? mvhmr_unproject_backward_deterministic_weighted_workspace_bytes(&d) : mvhmr_unproject_backward_weighted_workspace_bytes(&d);
         if (v.mask) return det ? mvhmr_unproject_backward_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_masked_workspace_bytes(&d);
         return det ? mvhmr_unproject_backward_deterministic_workspace_bytes(&d) : mvhmr_unproject_backward_workspace_bytes(&d);
@@ -182,6 +200,7 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.visible) return (det ? mvhmr_unproject_backward_deterministic_visible : mvhmr_unproject_backward_visible)(&d, grad_out, features, proj, c, mask, grad, ws, n, s);
         if (v.weights)
             return (det ? mvhmr_unproject_backward_deterministic_weighted : mvhmr_unproject_backward_weighted)(&d, grad_out, features, proj, c, mask, v.weights,
                                                                                                                 grad, ws, n, s);
@@ -190,6 +209,7 @@ struct TensorVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.visible) return mvhmr_unproject_backward_geometry_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_backward_geometry_weighted_workspace_bytes(&d);
         return v.mask ? mvhmr_unproject_backward_geometry_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_workspace_bytes(&d);
     }
@@ -198,6 +218,7 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.visible) return mvhmr_unproject_backward_geometry_visible(&d, grad_out, features, proj, c, mask, g[0], g[1], ws, n, s);
         if (v.weights) return mvhmr_unproject_backward_geometry_weighted(&d, grad_out, features, proj, c, mask, v.weights, g[0], g[1], grad_weights, ws, n, s);
         return mask ? mvhmr_unproject_backward_geometry_masked(&d, grad_out, features, proj, c, mask, g[0], g[1], ws, n, s)
                     : mvhmr_unproject_backward_geometry(&d, grad_out, features, proj, c, g[0], g[1], ws, n, s);
@@ -219,11 +240,16 @@ struct CuboidVolume {
     {
         check_inputs(d, features, proj, nullptr, &rot, &center, grad_out);
     }
+    int visibility(const mvhmr_unproject_desc &d, const float *proj, const uint8_t *mask, int32_t *bits, hipStream_t s) const
+    {
+        return mvhmr_unproject_visibility_cuboid(&d, proj, rot.data_ptr<float>(), center.data_ptr<float>(), position.data(), sides.data(), mask, bits, s);
+    }
     // gradients w.r.t. proj (B,V,3,4), rot (B,3,3) and center (B,3)
     std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, {d.batch, 3, 3}, {d.batch, 3}}; }
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.visible) return mvhmr_unproject_forward_cuboid_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_forward_cuboid_weighted_workspace_bytes(&d);
         return v.mask ? mvhmr_unproject_forward_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
     }
@@ -231,6 +257,7 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.visible) return mvhmr_unproject_forward_cuboid_visible(&d, features, proj, r, c, position.data(), sides.data(), mask, out, ws, n, s);
         if (v.weights)
             return mvhmr_unproject_forward_cuboid_weighted(&d, features, proj, r, c, position.data(), sides.data(), mask, v.weights, out, ws, n, s);
         return mask ? mvhmr_unproject_forward_cuboid_masked(&d, features, proj, r, c, position.data(), sides.data(), mask, out, ws, n, s)
@@ -238,6 +265,8 @@ struct CuboidVolume {
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.visible)
+            return det ? mvhmr_unproject_backward_cuboid_deterministic_visible_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_visible_workspace_bytes(&d);
         if (v.weights)
             return det ? mvhmr_unproject_backward_cuboid_deterministic_weighted_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_weighted_workspace_bytes(&d);
         if (v.mask) return det ? mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_masked_workspace_bytes(&d);
@@ -248,6 +277,9 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.visible)
+            return (det ? mvhmr_unproject_backward_cuboid_deterministic_visible : mvhmr_unproject_backward_cuboid_visible)(
+                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, grad, ws, n, s);
         if (v.weights)
             return (det ? mvhmr_unproject_backward_cuboid_deterministic_weighted : mvhmr_unproject_backward_cuboid_weighted)(
                 &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.weights, grad, ws, n, s);
@@ -259,6 +291,7 @@ struct CuboidVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.visible) return mvhmr_unproject_backward_geometry_cuboid_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_backward_geometry_cuboid_weighted_workspace_bytes(&d);
         return v.mask ? mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(&d);
     }
@@ -267,6 +300,9 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.visible)
+            return mvhmr_unproject_backward_geometry_cuboid_visible(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, g[0], g[1], g[2],
+                                                                    ws, n, s);
         if (v.weights)
             return mvhmr_unproject_backward_geometry_cuboid_weighted(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.weights, g[0],
                                                                      g[1], g[2], grad_weights, ws, n, s);
@@ -279,11 +315,11 @@ struct CuboidVolume {
 // ---- one body per kind of call.  features: the tensor the library reads (planar, channels-last or the quad-planar byte buffer)
 template <typename Volume>
 at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a, const c10::optional<at::Tensor> &view_mask,
-                   const c10::optional<at::Tensor> &view_weights)
+                   const c10::optional<at::Tensor> &view_weights, bool visible_only)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, nullptr);
-    const ViewArgs views{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights)};
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only);
     at::Tensor out = at::empty({a.B, a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
     run(features, vol.forward_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
         return vol.forward(d, features.data_ptr(), proj.data_ptr<float>(), views, out.data_ptr(), ws, n, s);
@@ -294,11 +330,11 @@ at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tens
 // deterministic: the feature gradient bitwise reproducible (mvhmr_unproject_backward*_deterministic); the workspace is not filled
 template <typename Volume>
 at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
-                    const c10::optional<at::Tensor> &view_mask, bool deterministic, const c10::optional<at::Tensor> &view_weights)
+                    const c10::optional<at::Tensor> &view_mask, bool deterministic, const c10::optional<at::Tensor> &view_weights, bool visible_only)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out);
-    const ViewArgs views{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights)};
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only);
     at::Tensor grad = new_feature_grad(d, features);
     run(features, vol.backward_bytes(d, views, deterministic), deterministic, [&](void *ws, size_t n, hipStream_t s) {
         return vol.backward(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, deterministic, grad.data_ptr(), ws, n, s);
@@ -311,13 +347,13 @@ at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Ten
 template <typename Volume>
 std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
                                           std::initializer_list<bool> want, const c10::optional<at::Tensor> &view_mask,
-                                          const c10::optional<at::Tensor> &view_weights, const c10::optional<at::Tensor> &grad_weights)
+                                          const c10::optional<at::Tensor> &view_weights, const c10::optional<at::Tensor> &grad_weights, bool visible_only)
 {
     const bool want_weights = grad_weights && grad_weights->defined();
     TORCH_CHECK(want_weights || std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out);
-    const ViewArgs views{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights)};
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only);
     TORCH_CHECK(!want_weights || views.weights, "mvhmr_unproject: grad_weights needs view_weights");
     float *gw = const_cast<float *>(weights_ptr(d, features, grad_weights, "grad_weights (B, V)"));
     const auto opts = features.options().dtype(at::kFloat);
@@ -335,64 +371,97 @@ std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &g
     return grads;
 }
 
-// ---- the six ops
+// the (B, X, Y, Z) int32 bitmask of the views that are present and see each voxel: proj is the tensor every other one is checked against
+template <typename Volume>
+at::Tensor visibility(const Volume &vol, const at::Tensor &proj, const mvhmr_unproject_desc &d, const c10::optional<at::Tensor> &view_mask)
+{
+    TORCH_CHECK(proj.is_cuda() && proj.is_contiguous() && proj.scalar_type() == at::kFloat && proj.numel() == (int64_t)d.batch * d.views * 12,
+                "mvhmr_unproject: proj_matricies must be a contiguous fp32 (B, V, 3, 4) tensor on a HIP device");
+    const uint8_t *mask = mask_ptr(d, proj, view_mask);
+    c10::DeviceGuard guard(proj.device());
+    at::Tensor bits = at::empty({d.batch, d.vol_x, d.vol_y, d.vol_z}, proj.options().dtype(at::kInt));
+    const int status = vol.visibility(d, proj.data_ptr<float>(), mask, bits.data_ptr<int32_t>(), c10::hip::getCurrentHIPStream(proj.device().index()).stream());
+    TORCH_CHECK(status == MVHMR_OK, "mvhmr_unproject: ", mvhmr_last_error());
+    return bits;
+}
+
+// ---- the ops
 using OptTensor = c10::optional<at::Tensor>;
+
+at::Tensor view_visibility_native(const at::Tensor &proj, const at::Tensor &coords, int64_t H, int64_t W, const OptTensor &view_mask)
+{
+    const int64_t B = proj.size(0), V = proj.size(1);
+    const mvhmr_unproject_desc d = coords_desc(coords, B, V, 1, H, W, MVHMR_AGG_SUM, MVHMR_F32, MVHMR_F32, MVHMR_LAYOUT_BVCHW, MVHMR_VARIANT_AUTO);
+    check_tensor(coords, proj, "coord_volumes (B, X, Y, Z, 3)", at::kFloat, B * d.vol_x * d.vol_y * d.vol_z * 3);
+    return visibility(TensorVolume{coords}, proj, d, view_mask);
+}
+
+at::Tensor view_visibility_cuboid_native(const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center, at::ArrayRef<double> position,
+                                         at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t H, int64_t W, const OptTensor &view_mask)
+{
+    const int64_t B = proj.size(0), V = proj.size(1);
+    const mvhmr_unproject_desc d = cuboid_desc(position, sides, vol, B, V, 1, H, W, MVHMR_AGG_SUM, MVHMR_F32, MVHMR_F32, MVHMR_LAYOUT_BVCHW, MVHMR_VARIANT_AUTO);
+    check_tensor(rot, proj, "rot (B, 3, 3)", at::kFloat, B * 9);
+    check_tensor(center, proj, "center (B, 3)", at::kFloat, B * 3);
+    return visibility(CuboidVolume{rot, center, position, sides, vol}, proj, d, view_mask);
+}
 
 at::Tensor unprojection_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C,
                                int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
-                               const OptTensor &view_mask, const OptTensor &view_weights)
+                               const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only)
 {
-    return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, view_weights);
+    return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, view_weights,
+                   visible_only);
 }
 
 at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
                                         int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
                                         int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask, bool deterministic,
-                                        const OptTensor &view_weights)
+                                        const OptTensor &view_weights, bool visible_only)
 {
     return backward(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask,
-                    deterministic, view_weights);
+                    deterministic, view_weights, visible_only);
 }
 
 std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
                                                                           const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H,
                                                                           int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
                                                                           int64_t variant, bool want_proj, bool want_coords, const OptTensor &view_mask,
-                                                                          const OptTensor &view_weights, const OptTensor &grad_weights)
+                                                                          const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only)
 {
     const auto g = backward_geometry(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
-                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights);
+                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights, visible_only);
     return {g[0], g[1]};
 }
 
 at::Tensor unprojection_cuboid_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
                                       at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C,
                                       int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
-                                      const OptTensor &view_mask, const OptTensor &view_weights)
+                                      const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only)
 {
     return forward(CuboidVolume{rot, center, position, sides, vol}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
-                   view_mask, view_weights);
+                   view_mask, view_weights, visible_only);
 }
 
 at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
                                                const at::Tensor &center, at::ArrayRef<double> position, at::ArrayRef<double> sides,
                                                at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
                                                int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask,
-                                               bool deterministic, const OptTensor &view_weights)
+                                               bool deterministic, const OptTensor &view_weights, bool visible_only)
 {
     return backward(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
-                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, deterministic, view_weights);
+                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, deterministic, view_weights, visible_only);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geometry_native(
     const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
     at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
     int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center,
-    const OptTensor &view_mask, const OptTensor &view_weights, const OptTensor &grad_weights)
+    const OptTensor &view_mask, const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only)
 {
     const auto g = backward_geometry(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
                                      DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, {want_proj, want_rot, want_center}, view_mask,
-                                     view_weights, grad_weights);
+                                     view_weights, grad_weights, visible_only);
     return {g[0], g[1], g[2]};
 }
 
@@ -459,18 +528,19 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(c
 #define MVHMR_MASK_ARG ", Tensor? view_mask=None"
 #define MVHMR_WEIGHTS_ARG ", Tensor? view_weights=None"
 #define MVHMR_GRAD_WEIGHTS_ARG ", Tensor(a!)? grad_weights=None"
+#define MVHMR_VISIBLE_ARG ", bool visible_only=False"
 
 TORCH_LIBRARY(mvhmr_native, m)
 {
-    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG ") -> Tensor");
+    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> Tensor");
     m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG
-          ", bool deterministic=False" MVHMR_WEIGHTS_ARG ") -> Tensor");
+          ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> Tensor");
     m.def("unprojection_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS
-          ", bool want_proj, bool want_coords" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG ") -> (Tensor, Tensor)");
-    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG ") -> Tensor");
-    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ", bool deterministic=False" MVHMR_WEIGHTS_ARG ") -> Tensor");
+          ", bool want_proj, bool want_coords" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> (Tensor, Tensor)");
+    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> Tensor");
+    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> Tensor");
     m.def("unprojection_cuboid_backward_geometry(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS
-          ", bool want_proj, bool want_rot, bool want_center" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG ") -> (Tensor, Tensor, Tensor)");
+          ", bool want_proj, bool want_rot, bool want_center" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> (Tensor, Tensor, Tensor)");
     m.def("triangulate_dlt(Tensor proj, Tensor points, Tensor? confidences) -> Tensor");
     m.def("triangulate_dlt_backward(Tensor grad_out, Tensor proj, Tensor points, Tensor? confidences) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int");
@@ -486,6 +556,19 @@ TORCH_LIBRARY_IMPL(mvhmr_native, CUDA, m)
     m.impl("unprojection_cuboid_backward_geometry", &unprojection_cuboid_backward_geometry_native);
     m.impl("triangulate_dlt", &triangulate_dlt_native);
     m.impl("triangulate_dlt_backward", &triangulate_dlt_backward_native);
+}
+
+// the visibility bits are no un-projection: a namespace of their own, mvhmr_native holds the six un-projection ops and the DLT
+TORCH_LIBRARY(mvhmr_visibility, m)
+{
+    m.def("view_visibility(Tensor proj, Tensor coords, int H, int W, Tensor? view_mask=None) -> Tensor");
+    m.def("view_visibility_cuboid(Tensor proj, Tensor rot, Tensor center, float[] position, float[] sides, int[] vol, int H, int W, Tensor? view_mask=None) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(mvhmr_visibility, CUDA, m)
+{
+    m.impl("view_visibility", &view_visibility_native);
+    m.impl("view_visibility_cuboid", &view_visibility_cuboid_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)
