@@ -427,6 +427,64 @@ int mvhmr_unproject_visibility_cuboid(const mvhmr_unproject_desc *desc, const fl
                                       position[3], const double sides[3], const uint8_t *view_mask, int32_t *bits, void *hip_stream);
 
 /*
+ * Per-pixel view confidence maps: the *_confidence entry points are the *_visible ones with `view_confidence` behind
+ * `view_mask` and the seeing test as the flag `visible` (0: off).  view_confidence (B,V,Hf,Wf) fp32 planar on the device: one map per view at
+ * feature resolution, or NULL -- then the call is exactly the masked call (visible == 0) or the visible call (visible != 0).
+ *
+ * For voxel n of sample b and view v take ix, iy, z, the four taps and their weights exactly as the features' sample s_v does (same rounding
+ * order, quirk Q1, zero padding).  c_v is the map of (b, v) sampled with the same taps and weights by the same fused multiply-adds: one more
+ * channel.  Present set S(b, n) = { v : view_mask[b][v] != 0 (if given) and c_v > 0 [and view v sees the voxel, if visible] }.  The test is
+ * c_v > 0: a sample that is zero, negative or NaN makes the view absent for that voxel, and so does z <= 0 or a footprint wholly outside the
+ * map (c_v = 0 there: quirk Q2 does not apply to a confidence call).  An absent view's features are not read for that voxel and it receives
+ * exact-zero gradients.  With W = sum_S c_v, everything in fp32:
+ *     method    out                                        ds_v (v in S)              dc_v (v in S), per channel
+ *     sum       sum_S c_v s_v                              g c_v                      g s_v
+ *     mean      sum_S c_v s_v / W                          g c_v / W                  g (s_v - out) / W
+ *     softmax   sum_S p_v s_v,                             g p_v (1 + s_v - out)      g (p_v / c_v) (s_v - out)
+ *               p_v = c_v e^(s_v - m) / sum_S c_u e^(s_u - m), m = max_S s
+ *     max       refused: MVHMR_ERR_UNSUPPORTED, as for view_weights
+ * An empty S gives out = 0 and exact-zero gradients for that voxel.  Per-view scalar weights are the case of a constant map, a mask the case
+ * of an all-zero map; mean and softmax do not change when all maps of a sample are scaled by one positive constant.
+ *
+ * Gradients.  grad_features: the four taps times ds_v.  The geometry calls gain grad_confidence (B,V,Hf,Wf) fp32 [write]: for every voxel the
+ * sum over channels of dc_v, scattered to the map by the same four tap weights; nullable, every element written when given (zeros for views a
+ * mask drops), it may be the only output, all outputs null is MVHMR_ERR_INVALID_ARGUMENT, and grad_confidence without view_confidence is
+ * MVHMR_ERR_INVALID_ARGUMENT.  It is bitwise reproducible in every mode (fixed-order sums, then int64 fixed point with one power-of-two
+ * exponent per (b, v) taken from the measured largest |sum_channels dc_v|; a (b, v) whose largest value is not finite comes back NaN).
+ * grad_proj, grad_coords, grad_rot, grad_center: the plain call's chain rule over v in S (S is piecewise constant; out is continuous where
+ * c_v -> 0+) with one more term per view, (sum_channels dc_v) * grad c_v(ix, iy), the confidence sample's own position derivative.
+ * The deterministic feature backward bounds the sum's fixed-point scale by max |grad_out| times the sample's largest confidence pixel, the
+ * mean's and the softmax's as the visible calls do.
+ * Limits, layouts, storage pairings, variants as the masked calls: quad-planar layouts and MVHMR_VARIANT_BRICK are refused with
+ * MVHMR_ERR_UNSUPPORTED, AUTO runs the gather family.  Workspace: the *_confidence_workspace_bytes queries, never less than the masked or
+ * visible ones; without a mask nothing is packed or copied, with one the maps are packed in slot order together with the features.
+ */
+size_t mvhmr_unproject_forward_confidence_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_forward_cuboid_confidence_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_confidence_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_confidence_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_deterministic_confidence_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_deterministic_confidence_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_confidence_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_cuboid_confidence_workspace_bytes(const mvhmr_unproject_desc *desc);
+int mvhmr_unproject_forward_confidence(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_deterministic_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, const float *view_confidence, int visible, float *grad_proj, float *grad_coords, float *grad_confidence, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_forward_cuboid_confidence(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_deterministic_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_cuboid_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, const float *view_confidence, int visible, float *grad_proj, float *grad_rot, float *grad_center, float *grad_confidence, void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/*
  * Layout pass on its own: features (B,V,C,Hf,Wf) -> dst in `dst_layout` (MVHMR_LAYOUT_BVHWC with the channel
  * count rounded up to a multiple of 4 and zero padded, or MVHMR_LAYOUT_QUAD), desc->feat_dtype.
  * desc->feat_layout names the SOURCE: MVHMR_LAYOUT_BVCHW (also assumed for MVHMR_LAYOUT_QUAD descriptors, as before), or

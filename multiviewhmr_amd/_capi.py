@@ -31,8 +31,8 @@ EXPORTS = (
     "mvhmr_unproject_backward_cuboid_deterministic", "mvhmr_conv1x1_wgrad_deterministic_workspace_bytes", "mvhmr_conv1x1_wgrad_deterministic",
 ) + tuple("mvhmr_unproject_%s_%s%s" % (n, tag, w) for n in ("forward", "forward_cuboid", "backward", "backward_cuboid", "backward_deterministic",
                                                            "backward_cuboid_deterministic", "backward_geometry", "backward_geometry_cuboid")
-          for w in ("", "_workspace_bytes")       # per-sample view masks, per-view confidence weights, visibility-aware aggregation
-          for tag in ("masked", "weighted", "visible")) + ("mvhmr_unproject_visibility", "mvhmr_unproject_visibility_cuboid")
+          for w in ("", "_workspace_bytes")       # per-sample view masks, per-view confidence weights, visibility-aware aggregation, per-pixel confidence maps
+          for tag in ("masked", "weighted", "visible", "confidence")) + ("mvhmr_unproject_visibility", "mvhmr_unproject_visibility_cuboid")
 
 
 class Desc(ctypes.Structure):
@@ -155,6 +155,18 @@ def lib():
         fn = getattr(L, "mvhmr_unproject_visibility" + vol)
         fn.restype = ctypes.c_int
         fn.argtypes = [dp, vp] + place + [vp, vp, vp]
+    # the *_confidence family: the *_visible signatures with view_confidence and the flag `visible` behind view_mask, the geometry calls also
+    # with grad_confidence
+    for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
+        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
+                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
+                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 4 if vol else 3)):
+            fn = getattr(L, "mvhmr_unproject_%s_confidence" % name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = lead + place + [vp, vp, ctypes.c_int] + [vp] * outs + [vp, sz, vp]
+            q = getattr(L, "mvhmr_unproject_%s_confidence_workspace_bytes" % name)
+            q.restype = sz
+            q.argtypes = [dp]
     if L.mvhmr_abi_version() != ABI_VERSION:
         raise RuntimeError("libmvhmr_unproject.so speaks ABI %d, this binding %d: rebuild" %
                            (L.mvhmr_abi_version(), ABI_VERSION))

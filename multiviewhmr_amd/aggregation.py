@@ -156,7 +156,10 @@ def _op_defined(name):
 # (mvhmr_unproject_*_cuboid) instead of a coordinate tensor.  The masked families (mvhmr_unproject_*_masked) read planar or channels-last
 # features, never a quad-planar copy, and run the gather kernels with a per-sample view count.  The visible families
 # (mvhmr_unproject_*_visible) are masked families -- view_mask is all ones when the caller gave none -- in which every voxel aggregates only
-# the views that see it.
+# the views that see it.  The confidence families (mvhmr_unproject_*_confidence) are masked families too, with
+# view_confidence (B, V, Hf, Wf) fp32 behind view_mask: per-pixel confidence maps sampled like one more channel; the geometry
+# backward differentiates w.r.t. them as well; their *_visible twins add the seeing test.  Their view_mask is `Tensor?`: None is the null
+# mask of the C entry points, with which nothing is packed or copied.
 _CUBOID_ARGS = ("float[] position", "float[] sides", "int[] vol")
 _FAMILIES = {
     "unprojection": (("coords",), (), False),
@@ -167,31 +170,38 @@ _FAMILIES = {
     "unprojection_cuboid_weighted": (("rot", "center"), _CUBOID_ARGS, True, True),
     "unprojection_visible": (("coords",), (), True, False, True),
     "unprojection_cuboid_visible": (("rot", "center"), _CUBOID_ARGS, True, False, True),
+    "unprojection_confidence": (("coords",), (), True, False, False, True),
+    "unprojection_cuboid_confidence": (("rot", "center"), _CUBOID_ARGS, True, False, False, True),
+    "unprojection_confidence_visible": (("coords",), (), True, False, True, True),
+    "unprojection_cuboid_confidence_visible": (("rot", "center"), _CUBOID_ARGS, True, False, True, True),
 }
 
 
 class _Family:
     """the implementations of one family's ops, each taking the ops' arguments positionally"""
 
-    def __init__(self, name, places, extras, masked, weighted=False, visible=False):
-        self.name, self.masked, self.weighted, self.visible = name, masked, weighted, visible
+    def __init__(self, name, places, extras, masked, weighted=False, visible=False, confidence=False):
+        self.name, self.masked, self.weighted, self.visible, self.confidence = name, masked, weighted, visible, confidence
         self.native = "unprojection_cuboid" if extras else "unprojection"       # the extension's op: view_mask / view_weights are trailing arguments there
         self.geo = ("proj",) + places                                           # the geometry tensors, behind features
-        self.tensors = ("features",) + self.geo + (("view_mask",) if masked else ()) + (("view_weights",) if weighted else ())
-        self.grads = self.geo + (("view_weights",) if weighted else ())         # what the geometry backward differentiates
+        self.tensors = (("features",) + self.geo + (("view_mask",) if masked else ()) + (("view_weights",) if weighted else ())
+                        + (("view_confidence",) if confidence else ()))
+        self.grads = self.geo + (("view_weights",) if weighted else ()) + (("view_confidence",) if confidence else ())   # what the geometry backward differentiates
         self.extras = extras
         self.n_inputs = len(self.tensors) + len(extras) + 3
 
     def schema(self):
-        return ", ".join(["Tensor " + t for t in self.tensors] + list(self.extras) + ["int method", "int out_dtype", "int variant"])
+        # (a confidence family's view_mask is optional: None reaches the C entry point as a null mask, and nothing is packed or copied)
+        kind = lambda t: "Tensor? " if self.confidence and t == "view_mask" else "Tensor "  # noqa: E731
+        return ", ".join([kind(t) + t for t in self.tensors] + list(self.extras) + ["int method", "int out_dtype", "int variant"])
 
     def split(self, args):
-        """-> features, (proj, *placing tensors), (view_mask or None, view_weights or None), placing arguments, (method, out_dtype, variant),
-        want_* flags (default True)"""
+        """-> features, (proj, *placing tensors), (view_mask or None, view_weights or None, view_confidence or None), placing arguments,
+        (method, out_dtype, variant), want_* flags (default True)"""
         n, k = len(self.tensors), len(self.tensors) + len(self.extras)
         g = 1 + len(self.geo)
         want = tuple(args[k + 3:])
-        views = (args[g] if self.masked else None, args[g + 1] if self.weighted else None)
+        views = (args[g] if self.masked else None, args[g + 1] if self.weighted else None, args[g + 1] if self.confidence else None)
         return (args[0], tuple(args[1:g]), views, tuple(args[n:k]), tuple(args[k:k + 3]), want + (True,) * (len(self.grads) - len(want)))
 
     def volume(self, geo, extra):
@@ -199,7 +209,7 @@ class _Family:
 
     def native_args(self, args, geometry=False):
         """the extension's leading arguments (the view the library reads, proj, placing tensors and arguments, descriptor fields), then
-        (view_mask, view_weights)"""
+        (view_mask, view_weights, view_confidence)"""
         features, geo, views, extra, (method, out_dtype, variant), _ = self.split(args)
         layout = None
         if self.masked or geometry:
@@ -208,20 +218,27 @@ class _Family:
         return (read,) + geo + extra + desc, views
 
     def forward(self, *args):
-        lead, (mask, weights) = self.native_args(args)
-        return getattr(_native(), self.native)(*lead, mask, weights, self.visible)
+        lead, (mask, weights, conf) = self.native_args(args)
+        return getattr(_native(), self.native)(*lead, mask, weights, self.visible, conf)
 
     def backward(self, deterministic, grad_out, *args):
         """gradient w.r.t. features (the geometry's is backward_geometry)"""
-        lead, (mask, weights) = self.native_args(args)
-        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible)
+        lead, (mask, weights, conf) = self.native_args(args)
+        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible, conf)
 
     def backward_geometry(self, grad_out, *args):
         """planar features go through the library's channels-last pass, channels-last ones are read as they are; the gradient w.r.t.
-        view_weights (weighted families, last) is written by the extension into the tensor handed to it"""
-        lead, (mask, weights) = self.native_args(args, geometry=True)
+        view_weights or view_confidence (weighted and confidence families, last) is written by the extension into the tensor handed to it"""
+        lead, (mask, weights, conf) = self.native_args(args, geometry=True)
         want = self.split(args)[5]
         op = getattr(_native(), self.native + "_backward_geometry")
+        if self.confidence:
+            gc = conf.new_empty(conf.shape if want[-1] else (0,))
+            tail = (mask, None, None, self.visible, conf, gc if want[-1] else None)
+            if not any(want[:-1]):                         # the maps' gradient alone: the extension's outputs stay empty
+                op(grad_out.contiguous(), *lead, *want[:-1], *tail)
+                return tuple(conf.new_empty((0,)) for _ in self.geo) + (gc,)
+            return tuple(op(grad_out.contiguous(), *lead, *want[:-1], *tail)) + (gc,)
         if not self.weighted:
             return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, self.visible))
         gw = weights.new_empty(weights.shape if want[-1] else (0,))
@@ -239,7 +256,7 @@ class _Family:
 
     def fake_backward_geometry(self, grad_out, *args):
         _, geo, views, _, _, want = self.split(args)
-        diff = geo + ((views[1],) if self.weighted else ())
+        diff = geo + ((views[1],) if self.weighted else ()) + ((views[2],) if self.confidence else ())
         return tuple(t.new_empty(t.shape if w else (0,), dtype=torch.float32) for t, w in zip(diff, want))
 
     def setup_context(self, ctx, inputs, output):
@@ -250,7 +267,7 @@ class _Family:
         ops, saved = torch.ops.mvhmr, ctx.saved_tensors
         op = getattr(ops, self.name + ("_backward_deterministic" if torch.are_deterministic_algorithms_enabled() else "_backward"))
         g = op(grad_out, *saved, *ctx.args) if ctx.needs_input_grad[0] else None
-        at = [1 + i for i in range(len(self.geo))] + ([len(self.tensors) - 1] if self.weighted else [])   # the differentiable inputs behind features
+        at = [1 + i for i in range(len(self.geo))] + ([len(self.tensors) - 1] if self.weighted or self.confidence else [])   # the differentiable inputs behind features
         want = tuple(ctx.needs_input_grad[i] for i in at)
         grads = [g] + [None] * (self.n_inputs - 1)
         if any(want):                                      # a features-only backward launches nothing more
@@ -314,7 +331,7 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
 
 
 def unprojection(features, proj_matricies, coord_volumes, aggregation_method='softmax', *, out_dtype=None,
-                 variant='auto', view_mask=None, view_weights=None, visible_only=False):
+                 variant='auto', view_mask=None, view_weights=None, visible_only=False, view_confidence=None):
     """Fused project -> bilinear-sample -> cross-view aggregate (reference: models/aggregation.py:20-87).
 
     features        (B, V, C, Hf, Wf) float32 (or float16, this package's storage mode) on a HIP device;
@@ -341,6 +358,13 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
                     sees is 0.  Unseen views are not read for that voxel and get zero gradients there; `view_visibility` returns the sets.
                     Differentiable like the plain call, composes with view_mask; with view_weights it raises ValueError (not built yet);
                     runs the gather kernels ('brick' is refused); DESIGN.md 5.10.
+    view_confidence (B, V, Hf, Wf) floating tensor, any device (keyword-only; None = none): one confidence map per view, at feature
+                    resolution, bilinearly sampled at the voxel with the very taps of the view's features (one more channel).  Every voxel
+                    aggregates its views weighted by that sample c: over the views with c > 0 sum is sum c_v s_v, mean that over sum c_v,
+                    softmax weighs e^{s_v} by c_v; a view whose c is zero, negative or NaN for a voxel -- one behind the camera or projecting
+                    wholly outside the map included -- is absent for that voxel: not read, zero gradients.  Differentiable (the gradient comes
+                    back in the caller's dtype and device, and enters the geometry gradients); composes with view_mask and visible_only;
+                    'max' and view_weights raise ValueError (multiply the maps by the weights); runs the gather kernels; DESIGN.md 5.11.
     """
     def volume_shape(B):
         if coord_volumes.dim() != 5 or coord_volumes.shape[0] != B or coord_volumes.shape[4] != 3:
@@ -352,6 +376,8 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
     if view_weights is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_view_weights(view_weights, features, aggregation_method)
     _check_visible_only(visible_only, view_weights)
+    if view_confidence is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_view_confidence(view_confidence, features, aggregation_method, view_weights)
     out_dtype, _, empty = _check_call(features, proj_matricies, (coord_volumes,), volume_shape, aggregation_method, variant, out_dtype,
                                       same_device=True)
     if empty is not None:
@@ -359,6 +385,10 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
     # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
     proj = proj_matricies.to(torch.float32).contiguous()
     coords = coord_volumes.to(torch.float32).contiguous()
+    if view_confidence is not None:
+        op = torch.ops.mvhmr.unprojection_confidence_visible if visible_only else torch.ops.mvhmr.unprojection_confidence
+        return op(features, proj, coords, None if view_mask is None else _mask_bytes(view_mask, features), _weights_fp32(view_confidence, features),
+                  _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
     if visible_only:
         return torch.ops.mvhmr.unprojection_visible(features, proj, coords, _weighted_mask(view_mask, features), _capi.AGG[aggregation_method],
                                                     _dtype_code(out_dtype), _capi.VARIANT[variant])
@@ -404,6 +434,23 @@ def _check_view_weights(view_weights, features, aggregation_method):
         raise RuntimeError("unprojection: view_weights must be %s, got %s" % (tuple(features.shape[:2]), tuple(view_weights.shape)))
     if aggregation_method == "max":
         raise ValueError("unprojection: aggregation_method 'max' has no weighted form (pass a view_mask, not view_weights)")
+
+
+def _check_view_confidence(view_confidence, features, aggregation_method, view_weights=None):
+    """view_confidence (B, V, Hf, Wf) of a floating dtype, any device: raises TypeError / RuntimeError as _check_view_weights does, ValueError for
+    'max' and together with view_weights"""
+    if not torch.is_tensor(view_confidence):
+        raise TypeError("unprojection: view_confidence must be a (B, V, Hf, Wf) floating tensor, got %s" % type(view_confidence).__name__)
+    if not view_confidence.dtype.is_floating_point:
+        raise TypeError("unprojection: view_confidence must be a floating dtype, got %s" % view_confidence.dtype)
+    want = tuple(features.shape[:2]) + tuple(features.shape[3:])
+    if tuple(view_confidence.shape) != want:
+        raise RuntimeError("unprojection: view_confidence must be %s, got %s" % (want, tuple(view_confidence.shape)))
+    if aggregation_method == "max":
+        raise ValueError("unprojection: aggregation_method 'max' has no weighted form (pass a view_mask, not view_confidence)")
+    if view_weights is not None:
+        raise ValueError("unprojection: view_weights together with view_confidence is not taken: multiply the maps by the weights "
+                         "(view_confidence * view_weights[:, :, None, None]), which is exactly equivalent and differentiable through torch")
 
 
 def _weights_fp32(view_weights, features):
@@ -466,14 +513,15 @@ _register_dlt_op()
 
 
 def unprojection_cuboid(features, proj_matricies, rotations, centers, position, sides, volume_shape,
-                        aggregation_method='softmax', *, out_dtype=None, variant='auto', view_mask=None, view_weights=None, visible_only=False):
+                        aggregation_method='softmax', *, out_dtype=None, variant='auto', view_mask=None, view_weights=None, visible_only=False,
+                        view_confidence=None):
     """`unprojection` for the volumes VolumeGenerator builds (aggregation.py:138-187), without the coordinate tensor: voxel centres
     are rot[b] @ (position + sides / (S - 1) * (i,j,k) - center[b]) + center[b], evaluated inside the kernels (bit-equal to
     mvhmr_build_coord_volumes followed by `unprojection`).
 
     rotations (B,3,3) and centers (B,3): float32 tensors on features.device; position, sides: 3 numbers each (cuboid corner and
     edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers (and view_weights).
-    view_mask, view_weights, visible_only: as for `unprojection`."""
+    view_mask, view_weights, visible_only, view_confidence: as for `unprojection`."""
     def checked_shape(B):
         if tuple(rotations.shape) != (B, 3, 3) or tuple(centers.shape) != (B, 3):
             raise RuntimeError("unprojection: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
@@ -485,6 +533,8 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     if view_weights is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_view_weights(view_weights, features, aggregation_method)
     _check_visible_only(visible_only, view_weights)
+    if view_confidence is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_view_confidence(view_confidence, features, aggregation_method, view_weights)
     out_dtype, vol, empty = _check_call(features, proj_matricies, (rotations, centers), checked_shape, aggregation_method, variant,
                                         out_dtype, same_device=False)
     if empty is not None:
@@ -494,6 +544,11 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     proj = proj_matricies.to(device=dev, dtype=torch.float32).contiguous()
     rot = rotations.to(device=dev, dtype=torch.float32).contiguous()
     cen = centers.to(device=dev, dtype=torch.float32).contiguous()
+    if view_confidence is not None:
+        op = torch.ops.mvhmr.unprojection_cuboid_confidence_visible if visible_only else torch.ops.mvhmr.unprojection_cuboid_confidence
+        return op(features, proj, rot, cen, None if view_mask is None else _mask_bytes(view_mask, features), _weights_fp32(view_confidence, features),
+                  [float(x) for x in position], [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method], _dtype_code(out_dtype),
+                  _capi.VARIANT[variant])
     if visible_only:
         return torch.ops.mvhmr.unprojection_cuboid_visible(features, proj, rot, cen, _weighted_mask(view_mask, features), [float(x) for x in position],
                                                            [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method],
@@ -828,6 +883,10 @@ class VolumeGenerator(nn.Module):
         view_weights = batch.get('view_weights')                            # optional (B, V): per-view confidences
         if view_weights is not None:
             _check_view_weights(view_weights, proj, self.aggregation_method)
+        view_confidence = batch.get('view_confidence')                      # optional (B, V, Hf, Wf): per-pixel confidence maps
+        if view_confidence is not None:
+            meta = torch.empty((batch_size, n_views, 1) + features_shape, device="meta")
+            _check_view_confidence(view_confidence, meta, self.aggregation_method, view_weights)
         if view_weights is not None:
             rots, centers = self.volume_pose(batch, proj_org, images_shape, view_mask, view_weights)
         else:
@@ -839,7 +898,7 @@ class VolumeGenerator(nn.Module):
         centers = centers.to(device=device, dtype=torch.float32).contiguous()
 
         _check_visible_only(self.visible_only, view_weights)
-        if view_mask is None and view_weights is None and not self.visible_only and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask, weights or visible_only do not take)
+        if view_mask is None and view_weights is None and view_confidence is None and not self.visible_only and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask, weights, confidence maps or visible_only do not take)
             # 1x1 conv and layout pass in one MFMA GEMM, its output only ever exists in the layout the brick forward stages
             conv = self.process_feature[0]
             return _FusedAggregate.apply(features, conv.weight, conv.bias, proj, rots, centers, tuple(cub.position), tuple(cub.sides),
@@ -854,6 +913,8 @@ class VolumeGenerator(nn.Module):
             masked["view_weights"] = view_weights
         if self.visible_only:
             masked["visible_only"] = True
+        if view_confidence is not None:
+            masked["view_confidence"] = view_confidence
         return unprojection_cuboid(features, proj, rots, centers, cub.position, cub.sides, (S, S, S),
                                    aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **masked)
 

@@ -293,23 +293,42 @@ int visible_refused(const mvhmr_unproject_desc *desc)
         return fail(MVHMR_ERR_UNSUPPORTED, "visibility-aware aggregation runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
     return MVHMR_OK;
 }
+// ---- per-pixel view confidence maps (include/mvhmr_unproject.h): the route of the visible calls -- the gather family with the
+// per-tap scatter backward and the geometry kernels, which launch their *_conf kernels (Problem::confidence); with a mask the maps are packed
+// in slot order together with the features, without one nothing is packed or copied.  Refused where weights are.
+int confidence_refused(const mvhmr_unproject_desc *desc)
+{
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "view confidence maps need planar or channels-last features (quad-planar copies: pass the planar features)");
+    if (desc->variant == MVHMR_VARIANT_BRICK)
+        return fail(MVHMR_ERR_UNSUPPORTED, "view confidence maps run the gather kernels: MVHMR_VARIANT_BRICK is not served");
+    if (desc->method == MVHMR_AGG_MAX)
+        return fail(MVHMR_ERR_UNSUPPORTED, "aggregation method max has no weighted form: pass a view mask instead of view confidence maps");
+    return MVHMR_OK;
+}
 // what selects the packed route of a call, and whether the descriptor can take it
 struct Views {
     const uint8_t *mask;
     const float *weights;
     bool visible = false;                       // the *_visible entry points (no weights there); a null mask packs nothing
+    const float *confidence = nullptr;          // the *_confidence entry points (no weights there; `visible` composes); a null mask packs nothing
     bool packed() const { return mask || weights; }
 };
 int views_refused(const mvhmr_unproject_desc *desc, const Views &w)
 {
     int rc = MVHMR_OK;
     if (w.visible && (rc = visible_refused(desc)) != MVHMR_OK) return rc;
+    if (w.confidence && (rc = confidence_refused(desc)) != MVHMR_OK) return rc;
     if (w.mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
     return w.weights ? weights_refused(desc) : MVHMR_OK;
 }
-// the kinds of plan: every view, a mask, weights (with or without a mask), the seeing views of every voxel (with or without a mask)
-enum class Pack { None, Masked, Weighted, Visible };
-Pack pack_of(const Views &w) { return w.visible ? Pack::Visible : w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None; }
+// the kinds of plan: every view, a mask, weights (with or without a mask), the seeing views of every voxel (with or without a mask),
+// confidence maps (with or without a mask, with or without the seeing test)
+enum class Pack { None, Masked, Weighted, Visible, Confidence };
+Pack pack_of(const Views &w)
+{
+    return w.confidence ? Pack::Confidence : w.visible ? Pack::Visible : w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None;
+}
 // the plan whose workspace a plan's total also covers: a weighted or visible call's serves the masked one, a masked call's the unmasked one
 Pack pack_below(Pack pack) { return pack == Pack::Masked ? Pack::None : Pack::Masked; }
 // the descriptor and problem of the packed call; view_count is set once the table exists (pack_views)
@@ -317,8 +336,17 @@ void mask_route(mvhmr_unproject_desc *desc, Problem *p, Pack pack)
 {
     desc->variant = MVHMR_VARIANT_GATHER;
     p->masked = 1;
-    p->visible = pack == Pack::Visible;
+    p->visible = pack == Pack::Visible;          // (a confidence call's flag is set from the call's own: confidence_route)
+    p->conf = pack == Pack::Confidence;
 }
+// a confidence call reads the caller's maps (no mask) or the packed ones (pack_views), and composes with the seeing test
+void confidence_route(Problem &p, const Views &w)
+{
+    if (!w.confidence) return;
+    p.visible = w.visible;
+    if (!p.confidence) p.confidence = w.confidence;
+}
+size_t conf_map_bytes(const Problem &p) { return (size_t)p.H * p.W * sizeof(float); }                   // one view's confidence map
 size_t masked_view_bytes(const Problem &p) { return (size_t)p.C * p.H * p.W * feat_elem(p); }   // one view, planar or channels-last (C4 == C)
 
 // ---- workspace plans.  One plan per kind of call says which route runs and where every region of the workspace lies; it is computed
@@ -334,13 +362,15 @@ unsigned char *at(void *workspace, size_t offset) { return offset == kNoRegion ?
 // a masked call's head: table + packed features (+ the packed gradient); the unmasked route's regions lie behind it
 struct MaskHead {
     size_t table = kNoRegion, feat = kNoRegion, grad = kNoRegion;
+    size_t conf = kNoRegion;                    // a confidence call's maps packed in slot order
 };
-MaskHead plan_mask_head(Arena &a, const Problem &p, int copies, bool weighted = false)
+MaskHead plan_mask_head(Arena &a, const Problem &p, int copies, Pack pack)
 {
     MaskHead h;
-    h.table = a.take(align_up(weighted ? weighted_view_table_bytes(p.B, p.V) : view_table_bytes(p.B, p.V)));
+    h.table = a.take(align_up(pack == Pack::Weighted ? weighted_view_table_bytes(p.B, p.V) : view_table_bytes(p.B, p.V)));
     h.feat = a.take(align_up((size_t)p.B * p.V * masked_view_bytes(p)));
     if (copies > 1) h.grad = a.take(align_up((size_t)p.B * p.V * masked_view_bytes(p)));
+    if (pack == Pack::Confidence) h.conf = a.take(align_up((size_t)p.B * p.V * conf_map_bytes(p)));
     return h;
 }
 // builds the table, packs the features; from here on the call reads the packed features and projections
@@ -353,6 +383,11 @@ int pack_views(const MaskHead &h, const Views &w, void *workspace, const void **
     if (w.weights) p.view_weights = view_table_weights(table, p.B, p.V);
     rc = launched(launch_view_pack(*features, at(workspace, h.feat), table, p.B, p.V, masked_view_bytes(p), s), "view pack");
     if (rc != MVHMR_OK) return rc;
+    if (w.confidence) {
+        rc = launched(launch_view_pack(w.confidence, at(workspace, h.conf), table, p.B, p.V, conf_map_bytes(p), s), "confidence pack");
+        if (rc != MVHMR_OK) return rc;
+        p.confidence = reinterpret_cast<const float *>(at(workspace, h.conf));
+    }
     p.view_count = view_table_counts(table);
     *features = at(workspace, h.feat);
     *proj = view_table_proj(table, p.B, p.V);
@@ -377,7 +412,7 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pac
     f.p = p;
     if (pack != Pack::None) {
         mask_route(&f.desc, &f.p, pack);
-        f.head = plan_mask_head(a, p, 1, pack == Pack::Weighted);
+        f.head = plan_mask_head(a, p, 1, pack);
     }
     const mvhmr_unproject_desc *d = &f.desc;
     const bool brick = pick_variant(d, f.p) == MVHMR_VARIANT_BRICK;
@@ -394,6 +429,7 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pac
     }
     // (a weighted call's workspace also serves the masked one, a masked call's the unmasked one)
     f.total = pack == Pack::None ? a.top : max_size(a.top, plan_forward(desc, p, pack_below(pack)).total);
+    if (pack == Pack::Confidence) f.total = max_size(f.total, plan_forward(desc, p, Pack::Visible).total);      // (a null map is the visible call)
     return f;
 }
 
@@ -465,7 +501,7 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
     b.p = p;
     if (pack != Pack::None) {
         mask_route(&b.desc, &b.p, pack);
-        b.head = plan_mask_head(a, p, 2, pack == Pack::Weighted);
+        b.head = plan_mask_head(a, p, 2, pack);
     }
     if (det) {
         BackwardPlan dflt = b;
@@ -477,6 +513,7 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
         place_default_backward(b, a);
     }
     b.total = pack == Pack::None ? a.top : max_size(a.top, plan_backward(desc, p, det, pack_below(pack)).total);
+    if (pack == Pack::Confidence) b.total = max_size(b.total, plan_backward(desc, p, det, Pack::Visible).total);
     return b;
 }
 
@@ -491,6 +528,8 @@ struct GeometryPlan {
     size_t part = kNoRegion, pose_part = kNoRegion;
     size_t packed_grad_weights = kNoRegion;     // weighted: grad_weights (B,V) in slot order, unpacked at the end; weight_part: its fp32 partials
     size_t weight_part = kNoRegion;
+    // confidence: grad_confidence (B,V,Hf,Wf) in slot order, the (B,V,N) fp32 stream of sum_channels dc, the int64 map and the (B,V) maxima
+    size_t packed_grad_conf = kNoRegion, conf_stream = kNoRegion, conf_acc = kNoRegion, conf_max = kNoRegion;
     size_t total = 0;
 };
 GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, bool cuboid, Pack pack)
@@ -501,17 +540,24 @@ GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, b
     g.p = p;
     if (pack != Pack::None) {
         mask_route(&g.desc, &g.p, pack);
-        g.head = plan_mask_head(a, p, 1, pack == Pack::Weighted);
+        g.head = plan_mask_head(a, p, 1, pack);
         g.packed_grad_proj = a.take(align_up((size_t)p.B * p.V * 12 * sizeof(float)));
     }
     if (pack == Pack::Weighted) {
         g.packed_grad_weights = a.take(align_up((size_t)p.B * p.V * sizeof(float)));
         g.weight_part = a.take(align_up(geom_weight_partial_bytes(p)));
     }
+    if (pack == Pack::Confidence) {
+        g.packed_grad_conf = a.take(align_up((size_t)p.B * p.V * conf_map_bytes(p)));
+        g.conf_stream = a.take(align_up(conf_grad_stream_bytes(p)));
+        g.conf_acc = a.take(align_up(conf_grad_acc_bytes(p)));
+        g.conf_max = a.take(align_up(conf_grad_max_bytes(p)));
+    }
     if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) g.staged = a.take(featT_bytes(p));
     g.part = a.take(align_up(geom_partial_bytes(p)));
     if (cuboid) g.pose_part = a.take(align_up(pose_partial_bytes(p)));
     g.total = pack == Pack::None ? a.top : max_size(a.top, plan_geometry(desc, p, cuboid, pack_below(pack)).total);
+    if (pack == Pack::Confidence) g.total = max_size(g.total, plan_geometry(desc, p, cuboid, Pack::Visible).total);
     return g;
 }
 
@@ -580,6 +626,7 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
     rc = check_ws(workspace, workspace_bytes, f.total);
     if (rc != MVHMR_OK) return rc;
     if (views.packed() && (rc = pack_views(f.head, views, workspace, &features, &proj, p, s)) != MVHMR_OK) return rc;
+    confidence_route(p, views);
     // planar input whose staged copy this call makes itself: scaled by log2(e) when the kernel that reads it wants that
     if (desc->feat_layout == MVHMR_LAYOUT_BVCHW && brick_fwd_prescales(p)) p.feat_log2e = 1;
 
@@ -761,6 +808,7 @@ int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     const bool packed = views.packed();
     if (packed && (rc = pack_views(b.head, views, workspace, &features, &proj, b.p, s)) != MVHMR_OK) return rc;
+    confidence_route(b.p, views);
     // a masked or weighted call's gradient comes in slot order and is unpacked into view order, absent views zero-filled
     void *grad = packed ? at(workspace, b.head.grad) : grad_features;
     const BackwardArgs c{grad_out, features, proj, &coords, grad, workspace, s};
@@ -772,7 +820,7 @@ int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
 // ---- geometry backward
 int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
                  const Views &views, float *grad_proj, float *grad_coords, float *grad_rot, float *grad_center, float *grad_weights, void *workspace,
-                 size_t workspace_bytes, void *hip_stream)
+                 size_t workspace_bytes, void *hip_stream, float *grad_confidence = nullptr)
 {
     const bool mask = views.packed();
     Problem p0;
@@ -787,12 +835,15 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     rc = make_coords(v, p0, &coords);
     if (rc != MVHMR_OK) return rc;
     if (grad_weights && !views.weights) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_weights without view_weights: nothing to differentiate");
-    if (!v.cuboid && !grad_proj && !grad_coords && !grad_weights)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, views.weights ? "grad_proj, grad_coords and grad_weights are all null: nothing to compute"
-                                                              : "grad_proj and grad_coords are both null: nothing to compute");
-    if (v.cuboid && !grad_proj && !grad_rot && !grad_center && !grad_weights)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, views.weights ? "grad_proj, grad_rot, grad_center and grad_weights are all null: nothing to compute"
-                                                              : "grad_proj, grad_rot and grad_center are all null: nothing to compute");
+    if (grad_confidence && !views.confidence) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_confidence without view_confidence: nothing to differentiate");
+    if (!v.cuboid && !grad_proj && !grad_coords && !grad_weights && !grad_confidence)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, views.weights      ? "grad_proj, grad_coords and grad_weights are all null: nothing to compute"
+                                                : views.confidence ? "grad_proj, grad_coords and grad_confidence are all null: nothing to compute"
+                                                                   : "grad_proj and grad_coords are both null: nothing to compute");
+    if (v.cuboid && !grad_proj && !grad_rot && !grad_center && !grad_weights && !grad_confidence)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, views.weights      ? "grad_proj, grad_rot, grad_center and grad_weights are all null: nothing to compute"
+                                                : views.confidence ? "grad_proj, grad_rot, grad_center and grad_confidence are all null: nothing to compute"
+                                                                   : "grad_proj, grad_rot and grad_center are all null: nothing to compute");
     if (!data) return fail(MVHMR_ERR_INVALID_ARGUMENT, no_data);
     if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
@@ -805,6 +856,10 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     const Problem &p = g.p;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (mask && (rc = pack_views(g.head, views, workspace, &features, &proj, g.p, s)) != MVHMR_OK) return rc;
+    confidence_route(g.p, views);
+    // grad_confidence: the kernel's stream of sum_channels dc, then launch_conf_grad (slot order behind the head with a mask, unpacked at the end)
+    float *gc = mask && grad_confidence ? reinterpret_cast<float *>(at(workspace, g.packed_grad_conf)) : grad_confidence;
+    if (grad_confidence) g.p.conf_stream = reinterpret_cast<float *>(at(workspace, g.conf_stream));
     // a masked call's grad_proj comes in slot order behind the head and is unpacked; the other gradients are per sample
     float *gp = mask && grad_proj ? reinterpret_cast<float *>(at(workspace, g.packed_grad_proj)) : grad_proj;
     void *staged = at(workspace, g.staged);
@@ -823,7 +878,12 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     } else {
         rc = launched(launch_bwd_geom(grad_out, featT, proj, coords, part, gp, grad_coords, p, s, wpart, gw), "geometry backward");
     }
+    if (rc == MVHMR_OK && grad_confidence)
+        rc = launched(launch_conf_grad(p.conf_stream, proj, coords, reinterpret_cast<unsigned long long *>(at(workspace, g.conf_acc)),
+                                       reinterpret_cast<unsigned *>(at(workspace, g.conf_max)), gc, p, s), "confidence gradient");
     if (rc != MVHMR_OK || !mask) return rc;
+    if (grad_confidence && (rc = launched(launch_view_unpack(gc, grad_confidence, at(workspace, g.head.table), p.B, p.V, conf_map_bytes(p), s), "view unpack")) != MVHMR_OK)
+        return rc;
     if (grad_proj && (rc = launched(launch_view_unpack(gp, grad_proj, at(workspace, g.head.table), p.B, p.V, 12 * sizeof(float), s), "view unpack")) != MVHMR_OK)
         return rc;
     if (!grad_weights) return rc;
@@ -846,7 +906,7 @@ int run_visibility(const mvhmr_unproject_desc *desc, const VolumeSource &v, cons
 bool pack_refused(const mvhmr_unproject_desc *desc, Pack pack)
 {
     return (pack == Pack::Masked && mask_refused(desc) != MVHMR_OK) || (pack == Pack::Weighted && weights_refused(desc) != MVHMR_OK) ||
-           (pack == Pack::Visible && visible_refused(desc) != MVHMR_OK);
+           (pack == Pack::Visible && visible_refused(desc) != MVHMR_OK) || (pack == Pack::Confidence && confidence_refused(desc) != MVHMR_OK);
 }
 size_t forward_need(const mvhmr_unproject_desc *desc, Pack pack)
 {
@@ -1214,6 +1274,65 @@ int mvhmr_unproject_visibility_cuboid(const mvhmr_unproject_desc *desc, const fl
                                       const double position[3], const double sides[3], const uint8_t *view_mask, int32_t *bits, void *hip_stream)
 {
     return run_visibility(desc, cuboid_volume(rot, center, position, sides), proj, view_mask, bits, hip_stream);
+}
+
+// ---- per-pixel view confidence maps: the _visible entry points with `view_confidence` (B,V,Hf,Wf) fp32 beside `view_mask` (either may be
+// null) and the seeing test as a flag; the geometry calls also write grad_confidence
+size_t mvhmr_unproject_forward_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Confidence); }
+size_t mvhmr_unproject_forward_cuboid_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Confidence); }
+size_t mvhmr_unproject_backward_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Confidence); }
+size_t mvhmr_unproject_backward_cuboid_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Confidence); }
+size_t mvhmr_unproject_backward_deterministic_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Confidence); }
+size_t mvhmr_unproject_backward_cuboid_deterministic_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Confidence); }
+size_t mvhmr_unproject_backward_geometry_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Confidence); }
+size_t mvhmr_unproject_backward_geometry_cuboid_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Confidence); }
+
+int mvhmr_unproject_forward_confidence(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, out, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, false, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_deterministic_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, true, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, const float *view_confidence, int visible, float *grad_proj, float *grad_coords, float *grad_confidence, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, grad_proj, grad_coords, nullptr, nullptr, nullptr, workspace, workspace_bytes, hip_stream, grad_confidence);
+}
+
+int mvhmr_unproject_forward_cuboid_confidence(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, out, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, false, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_deterministic_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, true, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_cuboid_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, const float *view_confidence, int visible, float *grad_proj, float *grad_rot, float *grad_center, float *grad_confidence, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, grad_proj, nullptr, grad_rot, grad_center, nullptr, workspace, workspace_bytes, hip_stream, grad_confidence);
 }
 
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)

@@ -451,6 +451,83 @@ __device__ __forceinline__ void weighted_aggregate_grad(const float (&s)[V], con
     }
 }
 
+// Per-pixel view confidence: the table of 5.9 with per-VOXEL weights and a per-voxel present set.  c[v] is the confidence
+// map of view v sampled at this voxel, bit v of `bits` (wave-uniform) says whether slot v takes part -- the caller sets it only where
+// c[v] > 0, so W > 0 and den > 0 whenever a bit is set; any slot may be absent.  No bit set gives 0 and exact-zero gradients.
+template <int METHOD, int V>
+__device__ __forceinline__ float conf_aggregate(const float (&s)[V], const float (&c)[V], unsigned bits)
+{
+    static_assert(METHOD != AGG_MAX, "max has no weighted form");
+    if (bits == 0u) return 0.f;
+    if constexpr (METHOD == AGG_SUM || METHOD == AGG_MEAN) {
+        float r = 0.f, W = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            r = (bits >> v & 1u) ? fmaf(c[v], s[v], r) : r;
+            W = (bits >> v & 1u) ? W + c[v] : W;
+        }
+        return METHOD == AGG_MEAN ? __fdiv_rn(r, W) : r;
+    } else {
+        float m = -INFINITY;
+#pragma unroll
+        for (int v = 0; v < V; ++v) m = (bits >> v & 1u) ? fmaxf(m, s[v]) : m;
+        float den = 0.f, num = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float e = (bits >> v & 1u) ? c[v] * __builtin_amdgcn_exp2f((s[v] - m) * 1.4426950408889634f) : 0.f;
+            den += e;
+            num = (bits >> v & 1u) ? fmaf(e, s[v], num) : num;
+        }
+        return __fdiv_rn(num, den);                                             // den >= the maximum's confidence > 0
+    }
+}
+
+// g * d(conf_aggregate)/d(s_v) into ds[v] and g * d(conf_aggregate)/d(c_v) into dc[v]; absent slots get exact zeros (their samples are
+// never multiplied: the caller may hand anything there)
+template <int METHOD, int V>
+__device__ __forceinline__ void conf_aggregate_grad(const float (&s)[V], const float (&c)[V], float g, float (&ds)[V], float (&dc)[V], unsigned bits)
+{
+    static_assert(METHOD != AGG_MAX, "max has no weighted form");
+    if constexpr (METHOD == AGG_SUM) {
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            ds[v] = (bits >> v & 1u) ? g * c[v] : 0.f;
+            dc[v] = (bits >> v & 1u) ? g * s[v] : 0.f;
+        }
+    } else if constexpr (METHOD == AGG_MEAN) {
+        float r = 0.f, W = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            r = (bits >> v & 1u) ? fmaf(c[v], s[v], r) : r;
+            W = (bits >> v & 1u) ? W + c[v] : W;
+        }
+        const float gW = bits ? __fdiv_rn(g, W) : 0.f, o = bits ? __fdiv_rn(r, W) : 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            ds[v] = (bits >> v & 1u) ? gW * c[v] : 0.f;
+            dc[v] = (bits >> v & 1u) ? gW * (s[v] - o) : 0.f;
+        }
+    } else {
+        float m = -INFINITY;
+#pragma unroll
+        for (int v = 0; v < V; ++v) m = (bits >> v & 1u) ? fmaxf(m, s[v]) : m;
+        float e[V], den = 0.f, num = 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            e[v] = (bits >> v & 1u) ? __builtin_amdgcn_exp2f((s[v] - m) * 1.4426950408889634f) : 0.f;     // p_v / c_v, before the division
+            den = (bits >> v & 1u) ? fmaf(c[v], e[v], den) : den;
+            num = (bits >> v & 1u) ? fmaf(c[v] * e[v], s[v], num) : num;
+        }
+        const float gr = bits ? __fdiv_rn(g, den) : 0.f, o = bits ? __fdiv_rn(num, den) : 0.f;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const float q = gr * e[v];                                          // g p_v / c_v
+            ds[v] = (bits >> v & 1u) ? q * c[v] * (1.f + s[v] - o) : 0.f;
+            dc[v] = (bits >> v & 1u) ? q * (s[v] - o) : 0.f;
+        }
+    }
+}
+
 // Running form for a view count only known at run time (V > 8): one pass, same result up to rounding.
 template <int METHOD>
 struct RunningAgg {

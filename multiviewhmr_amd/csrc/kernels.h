@@ -32,6 +32,14 @@ struct Problem {
     // Visibility-aware aggregation: every voxel aggregates only the views that see it.  The gather and geometry launchers
     // hand such a problem to their *_seen kernels (unproject_visible.hip, unproject_visible_geom.hip); view_count, when set, bounds the slots.
     int visible = 0;
+    // Per-pixel view confidence: the maps (device, (B, V, Hf, Wf) fp32, in slot order when view_count is set), sampled like one
+    // more channel; a view takes part for a voxel iff its sample is > 0 (and, with `visible`, it sees the voxel).  Null = none; the gather and
+    // geometry launchers hand such a problem to their *_conf kernels (unproject_confidence.hip, unproject_confidence_geom.hip).  `conf` marks
+    // the route before the pointer exists (the workspace queries); conf_stream, when set, receives the geometry kernel's (B, V, N) fp32 stream
+    // of sum_channels dc (conf_grad_stream_bytes), from which launch_conf_grad builds grad_confidence.
+    const float *confidence = nullptr;
+    int conf = 0;
+    float *conf_stream = nullptr;
 };
 
 inline Gate make_gate(const Problem &p, bool wants_brick) { return Gate{p.gate_count, p.gate_limit, wants_brick ? 1 : 0}; }
@@ -172,6 +180,27 @@ hipError_t launch_bwd_gather_seen_det(const void *grad_out, const void *featT, c
 hipError_t launch_view_visibility(const float *proj, const Coords &coords, const uint8_t *mask, int *bits, const Problem &p, hipStream_t s);
 // (the seen instances of k_bwd_geom live in unproject_visible_geom.hip; launch_bwd_geom[_cuboid] call this for visible problems)
 hipError_t launch_bwd_geom_seen_kernel(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part,
+                                       float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
+
+// per-pixel view confidence (unproject_confidence.hip; Problem::confidence): the gather forward and the per-tap scatter backward of both modes
+// (launch_fwd_gather / launch_bwd_gather / launch_bwd_gather_det call these for confidence problems), the deterministic scale pass
+// (launch_det_scale calls it; its regions lie behind det_scale_bytes' three words per (b, c): conf_det_scale_extra_bytes), and grad_confidence
+// (B, V, Hf, Wf) fp32 from the geometry kernel's stream: bitwise reproducible, integer atomics only, every element written
+hipError_t launch_fwd_gather_conf(const void *featT, const float *proj, const Coords &coords, void *out, const Problem &p, hipStream_t s);
+hipError_t launch_bwd_gather_conf(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *gradT, const Problem &p,
+                                  hipStream_t s);
+hipError_t launch_bwd_gather_conf_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
+                                      const int *kexp, const Problem &p, hipStream_t s);
+size_t conf_det_scale_extra_bytes(const Problem &p);
+hipError_t launch_det_scale_conf(const void *grad_out, const void *featT, void *scale, const Problem &p, hipStream_t s, const float *proj,
+                                 const Coords *coords);
+size_t conf_grad_stream_bytes(const Problem &p);
+size_t conf_grad_acc_bytes(const Problem &p);
+size_t conf_grad_max_bytes(const Problem &p);
+hipError_t launch_conf_grad(const float *stream, const float *proj, const Coords &coords, unsigned long long *acc, unsigned *smax, float *grad_conf,
+                            const Problem &p, hipStream_t s);
+// (the confidence instances of k_bwd_geom live in unproject_confidence_geom.hip; launch_bwd_geom[_cuboid] call this for confidence problems)
+hipError_t launch_bwd_geom_conf_kernel(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part,
                                        float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
 
 // view masks (view_mask.hip): from mask (B,V) bytes, one thread per sample writes n_b (B ints), slot -> view and view -> slot (-1: masked)

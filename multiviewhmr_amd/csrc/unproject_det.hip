@@ -250,12 +250,14 @@ k_det_quad_to_planar(const unsigned long long *__restrict__ src, const int *__re
 // gmax, fmax, K: three words per (b, c); a visible problem's tap marks (one byte per pixel of every (b, slot) map) lie behind them
 size_t det_scale_bytes(const Problem &p)
 {
+    if (p.conf) return (size_t)p.B * p.C * 3 * sizeof(int) + conf_det_scale_extra_bytes(p);     // (per-pixel view confidence: unproject_confidence.hip)
     return (size_t)p.B * p.C * 3 * sizeof(int) + (p.visible ? (size_t)p.B * p.V * p.H * p.W : 0);
 }
 
 hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale, const Problem &p, hipStream_t s, bool quad, const float *proj,
                             const Coords *coords)
 {
+    if (p.confidence) return quad ? hipErrorInvalidValue : launch_det_scale_conf(grad_out, feat, scale, p, s, proj, coords);
     const void *featT = feat;
     const long long BC = (long long)p.B * p.C;
     unsigned *gmax = static_cast<unsigned *>(scale), *fmax = gmax + BC;

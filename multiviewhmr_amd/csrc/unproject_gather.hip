@@ -876,6 +876,7 @@ static hipError_t fwd_dispatch_m(const TF *featT, const float *proj, const Coord
 hipError_t launch_fwd_gather(const void *featT, const float *proj, const Coords &coords, void *out, const Problem &p,
                              hipStream_t s)
 {
+    if (p.confidence) return launch_fwd_gather_conf(featT, proj, coords, out, p, s);    // per-pixel view confidence: unproject_confidence.hip
     if (p.visible) return launch_fwd_gather_seen(featT, proj, coords, out, p, s);      // visibility-aware aggregation: unproject_visible.hip
     if (p.out_bf16) return p.feat_f16 ? hipErrorNotSupported : fwd_dispatch_m((const float *)featT, proj, coords, (bf16_t *)out, p, s);
     if (!p.feat_f16 && !p.out_f16) return fwd_dispatch_m((const float *)featT, proj, coords, (float *)out, p, s);
@@ -946,6 +947,7 @@ static hipError_t bwd_dispatch_m(const TO *go_, const TF *featT, const float *pr
 hipError_t launch_bwd_gather(const void *grad_out, const void *featT, const float *proj, const Coords &coords,
                              float *gradT, const Problem &p, hipStream_t s)
 {
+    if (p.confidence) return launch_bwd_gather_conf(grad_out, featT, proj, coords, gradT, p, s);
     if (p.visible) return launch_bwd_gather_seen(grad_out, featT, proj, coords, gradT, p, s);
     if (p.out_bf16) return p.feat_f16 ? hipErrorNotSupported : bwd_dispatch_m((const bf16_t *)grad_out, (const float *)featT, proj, coords, gradT, p, s);
     if (!p.feat_f16 && !p.out_f16) return bwd_dispatch_m((const float *)grad_out, (const float *)featT, proj, coords, gradT, p, s);
@@ -1020,6 +1022,7 @@ static hipError_t bwd_det_dispatch_m(const TO *go_, const TF *featT, const float
 hipError_t launch_bwd_gather_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
                                  const int *kexp, const Problem &p, hipStream_t s)
 {
+    if (p.confidence) return launch_bwd_gather_conf_det(grad_out, featT, proj, coords, gradI, kexp, p, s);
     if (p.visible) return launch_bwd_gather_seen_det(grad_out, featT, proj, coords, gradI, kexp, p, s);
     if (p.out_bf16) return p.feat_f16 ? hipErrorNotSupported : bwd_det_dispatch_m((const bf16_t *)grad_out, (const float *)featT, proj, coords, gradI, kexp, p, s);
     if (!p.feat_f16 && !p.out_f16) return bwd_det_dispatch_m((const float *)grad_out, (const float *)featT, proj, coords, gradI, kexp, p, s);

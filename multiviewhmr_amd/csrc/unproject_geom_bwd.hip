@@ -378,6 +378,7 @@ static hipError_t geom_dispatch(const void *grad_out, const void *featT, const f
                                 float *pose_part, float *wpart, const Problem &p, hipStream_t s)
 {
     if (p.view_weights) return launch_bwd_geom_weighted_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, wpart, POSE, p, s);
+    if (p.confidence) return launch_bwd_geom_conf_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, POSE, p, s);
     if (p.visible) return launch_bwd_geom_seen_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, POSE, p, s);
     if (p.out_bf16)
         return p.feat_f16 ? hipErrorNotSupported
@@ -417,7 +418,7 @@ hipError_t launch_bwd_geom_cuboid(const void *grad_out, const void *featT, const
                                   float *grad_weights)
 {
     const bool pose = grad_rot || grad_center;
-    if (p.V < 1 || p.V > kMaxViews || coords.ptr || (grad_proj && !part) || (pose && !pose_part) || (!grad_proj && !pose && !grad_weights) ||
+    if (p.V < 1 || p.V > kMaxViews || coords.ptr || (grad_proj && !part) || (pose && !pose_part) || (!grad_proj && !pose && !grad_weights && !p.conf_stream) ||
         (grad_weights && (!wpart || !p.view_weights)))
         return hipErrorInvalidValue;
     float *wp = grad_weights ? wpart : nullptr;

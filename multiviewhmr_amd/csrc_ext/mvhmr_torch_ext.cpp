@@ -4,7 +4,9 @@
 // un-projection op takes a trailing `Tensor? view_mask` (None: the unmasked C entry point), the two feature backwards a trailing
 // `bool deterministic`, and all of them behind that `Tensor? view_weights` (per-view confidence weights: the *_weighted entry points; the
 // geometry ops also `Tensor(a!)? grad_weights`, the (B, V) fp32 tensor they write the gradient w.r.t. the weights into) and last `bool visible_only`
-// (visibility-aware aggregation: the *_visible entry points, view_mask nullable, no weights); mvhmr_visibility::view_visibility[_cuboid] return the
+// (visibility-aware aggregation: the *_visible entry points, view_mask nullable, no weights), then `Tensor? view_confidence` (per-pixel confidence maps
+// (B, V, Hf, Wf) fp32: the *_confidence entry points, which take visible_only as a flag; the geometry ops also `Tensor(b!)? grad_confidence`, the tensor they
+// write the gradient w.r.t. the maps into); mvhmr_visibility::view_visibility[_cuboid] return the
 // (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
 // tensor checks, descriptor, output and workspace from the caching allocator, the current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
@@ -111,13 +113,24 @@ struct ViewArgs {
     const uint8_t *mask;
     const float *weights;
     bool visible = false;                                       // the *_visible entry points: every voxel aggregates the views that see it
+    const float *confidence = nullptr;                          // the *_confidence entry points: per-pixel confidence maps (visible is their flag)
 };
 
-ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_mask,
-                   const c10::optional<at::Tensor> &view_weights, bool visible_only)
+// per-pixel confidence maps (mvhmr_unproject_*_confidence): (B, V, Hf, Wf) fp32 on the features' device; null for None
+const float *confidence_ptr(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &t, const char *name)
 {
-    const ViewArgs v{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights), visible_only};
+    if (!t || !t->defined()) return nullptr;
+    check_tensor(*t, features, name, at::kFloat, (int64_t)d.batch * d.views * d.feat_h * d.feat_w);
+    return t->data_ptr<float>();
+}
+
+ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_mask,
+                   const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence)
+{
+    const ViewArgs v{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights), visible_only,
+                     confidence_ptr(d, features, view_confidence, "view_confidence (B, V, Hf, Wf)")};
     TORCH_CHECK(!(v.visible && v.weights), "mvhmr_unproject: visible_only does not take view_weights");
+    TORCH_CHECK(!(v.confidence && v.weights), "mvhmr_unproject: view_confidence does not take view_weights");
     return v;
 }
 
@@ -176,6 +189,7 @@ struct TensorVolume {
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.confidence) return mvhmr_unproject_forward_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_forward_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_forward_weighted_workspace_bytes(&d);
         return v.mask ? mvhmr_unproject_forward_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
@@ -184,12 +198,14 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.confidence) return mvhmr_unproject_forward_confidence(&d, features, proj, c, mask, v.confidence, v.visible, out, ws, n, s);
         if (v.visible) return mvhmr_unproject_forward_visible(&d, features, proj, c, mask, out, ws, n, s);
         if (v.weights) return mvhmr_unproject_forward_weighted(&d, features, proj, c, mask, v.weights, out, ws, n, s);
         return mask ? mvhmr_unproject_forward_masked(&d, features, proj, c, mask, out, ws, n, s) : mvhmr_unproject_forward(&d, features, proj, c, out, ws, n, s);
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.confidence) return det ? mvhmr_unproject_backward_deterministic_confidence_workspace_bytes(&d) : mvhmr_unproject_backward_confidence_workspace_bytes(&d);
         if (v.visible) return det ? mvhmr_unproject_backward_deterministic_visible_workspace_bytes(&d) : mvhmr_unproject_backward_visible_workspace_bytes(&d);
         if (v.weights) return det ? mvhmr_unproject_backward_deterministic_weighted_workspace_bytes(&d) : mvhmr_unproject_backward_weighted_workspace_bytes(&d);
         if (v.mask) return det ? mvhmr_unproject_backward_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_masked_workspace_bytes(&d);
@@ -200,6 +216,9 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.confidence)
+            return (det ? mvhmr_unproject_backward_deterministic_confidence : mvhmr_unproject_backward_confidence)(&d, grad_out, features, proj, c, mask, v.confidence,
+                                                                                                                    v.visible, grad, ws, n, s);
         if (v.visible) return (det ? mvhmr_unproject_backward_deterministic_visible : mvhmr_unproject_backward_visible)(&d, grad_out, features, proj, c, mask, grad, ws, n, s);
         if (v.weights)
             return (det ? mvhmr_unproject_backward_deterministic_weighted : mvhmr_unproject_backward_weighted)(&d, grad_out, features, proj, c, mask, v.weights,
@@ -209,15 +228,18 @@ struct TensorVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.confidence) return mvhmr_unproject_backward_geometry_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_backward_geometry_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_backward_geometry_weighted_workspace_bytes(&d);
         return v.mask ? mvhmr_unproject_backward_geometry_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_workspace_bytes(&d);
     }
     int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, float *const *g,
-                 float *grad_weights, void *ws, size_t n, hipStream_t s) const
+                 float *grad_weights, float *grad_confidence, void *ws, size_t n, hipStream_t s) const
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.confidence)
+            return mvhmr_unproject_backward_geometry_confidence(&d, grad_out, features, proj, c, mask, v.confidence, v.visible, g[0], g[1], grad_confidence, ws, n, s);
         if (v.visible) return mvhmr_unproject_backward_geometry_visible(&d, grad_out, features, proj, c, mask, g[0], g[1], ws, n, s);
         if (v.weights) return mvhmr_unproject_backward_geometry_weighted(&d, grad_out, features, proj, c, mask, v.weights, g[0], g[1], grad_weights, ws, n, s);
         return mask ? mvhmr_unproject_backward_geometry_masked(&d, grad_out, features, proj, c, mask, g[0], g[1], ws, n, s)
@@ -249,6 +271,7 @@ struct CuboidVolume {
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.confidence) return mvhmr_unproject_forward_cuboid_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_forward_cuboid_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_forward_cuboid_weighted_workspace_bytes(&d);
         return v.mask ? mvhmr_unproject_forward_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
@@ -257,6 +280,8 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.confidence)
+            return mvhmr_unproject_forward_cuboid_confidence(&d, features, proj, r, c, position.data(), sides.data(), mask, v.confidence, v.visible, out, ws, n, s);
         if (v.visible) return mvhmr_unproject_forward_cuboid_visible(&d, features, proj, r, c, position.data(), sides.data(), mask, out, ws, n, s);
         if (v.weights)
             return mvhmr_unproject_forward_cuboid_weighted(&d, features, proj, r, c, position.data(), sides.data(), mask, v.weights, out, ws, n, s);
@@ -265,6 +290,8 @@ struct CuboidVolume {
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.confidence)
+            return det ? mvhmr_unproject_backward_cuboid_deterministic_confidence_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_confidence_workspace_bytes(&d);
         if (v.visible)
             return det ? mvhmr_unproject_backward_cuboid_deterministic_visible_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_visible_workspace_bytes(&d);
         if (v.weights)
@@ -277,6 +304,9 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.confidence)
+            return (det ? mvhmr_unproject_backward_cuboid_deterministic_confidence : mvhmr_unproject_backward_cuboid_confidence)(
+                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.confidence, v.visible, grad, ws, n, s);
         if (v.visible)
             return (det ? mvhmr_unproject_backward_cuboid_deterministic_visible : mvhmr_unproject_backward_cuboid_visible)(
                 &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, grad, ws, n, s);
@@ -291,15 +321,19 @@ struct CuboidVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.confidence) return mvhmr_unproject_backward_geometry_cuboid_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_backward_geometry_cuboid_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_backward_geometry_cuboid_weighted_workspace_bytes(&d);
         return v.mask ? mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(&d);
     }
     int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, float *const *g,
-                 float *grad_weights, void *ws, size_t n, hipStream_t s) const
+                 float *grad_weights, float *grad_confidence, void *ws, size_t n, hipStream_t s) const
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.confidence)
+            return mvhmr_unproject_backward_geometry_cuboid_confidence(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.confidence,
+                                                                       v.visible, g[0], g[1], g[2], grad_confidence, ws, n, s);
         if (v.visible)
             return mvhmr_unproject_backward_geometry_cuboid_visible(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, g[0], g[1], g[2],
                                                                     ws, n, s);
@@ -315,11 +349,11 @@ struct CuboidVolume {
 // ---- one body per kind of call.  features: the tensor the library reads (planar, channels-last or the quad-planar byte buffer)
 template <typename Volume>
 at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a, const c10::optional<at::Tensor> &view_mask,
-                   const c10::optional<at::Tensor> &view_weights, bool visible_only)
+                   const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, nullptr);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only);
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence);
     at::Tensor out = at::empty({a.B, a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
     run(features, vol.forward_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
         return vol.forward(d, features.data_ptr(), proj.data_ptr<float>(), views, out.data_ptr(), ws, n, s);
@@ -330,11 +364,12 @@ at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tens
 // deterministic: the feature gradient bitwise reproducible (mvhmr_unproject_backward*_deterministic); the workspace is not filled
 template <typename Volume>
 at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
-                    const c10::optional<at::Tensor> &view_mask, bool deterministic, const c10::optional<at::Tensor> &view_weights, bool visible_only)
+                    const c10::optional<at::Tensor> &view_mask, bool deterministic, const c10::optional<at::Tensor> &view_weights, bool visible_only,
+                    const c10::optional<at::Tensor> &view_confidence)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only);
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence);
     at::Tensor grad = new_feature_grad(d, features);
     run(features, vol.backward_bytes(d, views, deterministic), deterministic, [&](void *ws, size_t n, hipStream_t s) {
         return vol.backward(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, deterministic, grad.data_ptr(), ws, n, s);
@@ -347,15 +382,19 @@ at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Ten
 template <typename Volume>
 std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
                                           std::initializer_list<bool> want, const c10::optional<at::Tensor> &view_mask,
-                                          const c10::optional<at::Tensor> &view_weights, const c10::optional<at::Tensor> &grad_weights, bool visible_only)
+                                          const c10::optional<at::Tensor> &view_weights, const c10::optional<at::Tensor> &grad_weights, bool visible_only,
+                                          const c10::optional<at::Tensor> &view_confidence, const c10::optional<at::Tensor> &grad_confidence)
 {
     const bool want_weights = grad_weights && grad_weights->defined();
-    TORCH_CHECK(want_weights || std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
+    const bool want_conf = grad_confidence && grad_confidence->defined();
+    TORCH_CHECK(want_weights || want_conf || std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only);
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence);
     TORCH_CHECK(!want_weights || views.weights, "mvhmr_unproject: grad_weights needs view_weights");
+    TORCH_CHECK(!want_conf || views.confidence, "mvhmr_unproject: grad_confidence needs view_confidence");
     float *gw = const_cast<float *>(weights_ptr(d, features, grad_weights, "grad_weights (B, V)"));
+    float *gc = const_cast<float *>(confidence_ptr(d, features, grad_confidence, "grad_confidence (B, V, Hf, Wf)"));
     const auto opts = features.options().dtype(at::kFloat);
     const auto shapes = vol.geometry_shapes(d);
     std::vector<at::Tensor> grads;
@@ -366,7 +405,7 @@ std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &g
         ptrs.push_back(w ? grads.back().data_ptr<float>() : nullptr);
     }
     run(features, vol.geometry_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
-        return vol.geometry(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, ptrs.data(), gw, ws, n, s);
+        return vol.geometry(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, ptrs.data(), gw, gc, ws, n, s);
     });
     return grads;
 }
@@ -408,60 +447,62 @@ at::Tensor view_visibility_cuboid_native(const at::Tensor &proj, const at::Tenso
 
 at::Tensor unprojection_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C,
                                int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
-                               const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only)
+                               const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence)
 {
     return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, view_weights,
-                   visible_only);
+                   visible_only, view_confidence);
 }
 
 at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
                                         int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
                                         int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask, bool deterministic,
-                                        const OptTensor &view_weights, bool visible_only)
+                                        const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence)
 {
     return backward(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask,
-                    deterministic, view_weights, visible_only);
+                    deterministic, view_weights, visible_only, view_confidence);
 }
 
 std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
                                                                           const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H,
                                                                           int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
                                                                           int64_t variant, bool want_proj, bool want_coords, const OptTensor &view_mask,
-                                                                          const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only)
+                                                                          const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only,
+                                                                          const OptTensor &view_confidence, const OptTensor &grad_confidence)
 {
     const auto g = backward_geometry(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
-                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights, visible_only);
+                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights, visible_only, view_confidence, grad_confidence);
     return {g[0], g[1]};
 }
 
 at::Tensor unprojection_cuboid_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
                                       at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C,
                                       int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
-                                      const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only)
+                                      const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence)
 {
     return forward(CuboidVolume{rot, center, position, sides, vol}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
-                   view_mask, view_weights, visible_only);
+                   view_mask, view_weights, visible_only, view_confidence);
 }
 
 at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
                                                const at::Tensor &center, at::ArrayRef<double> position, at::ArrayRef<double> sides,
                                                at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
                                                int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask,
-                                               bool deterministic, const OptTensor &view_weights, bool visible_only)
+                                               bool deterministic, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence)
 {
     return backward(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
-                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, deterministic, view_weights, visible_only);
+                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, deterministic, view_weights, visible_only, view_confidence);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geometry_native(
     const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
     at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
     int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center,
-    const OptTensor &view_mask, const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only)
+    const OptTensor &view_mask, const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only, const OptTensor &view_confidence,
+    const OptTensor &grad_confidence)
 {
     const auto g = backward_geometry(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
                                      DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, {want_proj, want_rot, want_center}, view_mask,
-                                     view_weights, grad_weights, visible_only);
+                                     view_weights, grad_weights, visible_only, view_confidence, grad_confidence);
     return {g[0], g[1], g[2]};
 }
 
@@ -529,18 +570,20 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(c
 #define MVHMR_WEIGHTS_ARG ", Tensor? view_weights=None"
 #define MVHMR_GRAD_WEIGHTS_ARG ", Tensor(a!)? grad_weights=None"
 #define MVHMR_VISIBLE_ARG ", bool visible_only=False"
+#define MVHMR_CONF_ARG ", Tensor? view_confidence=None"
+#define MVHMR_GRAD_CONF_ARG ", Tensor(b!)? grad_confidence=None"
 
 TORCH_LIBRARY(mvhmr_native, m)
 {
-    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> Tensor");
+    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG ") -> Tensor");
     m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG
-          ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> Tensor");
+          ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG ") -> Tensor");
     m.def("unprojection_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS
-          ", bool want_proj, bool want_coords" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> (Tensor, Tensor)");
-    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> Tensor");
-    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> Tensor");
+          ", bool want_proj, bool want_coords" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_GRAD_CONF_ARG ") -> (Tensor, Tensor)");
+    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG ") -> Tensor");
+    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG ") -> Tensor");
     m.def("unprojection_cuboid_backward_geometry(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS
-          ", bool want_proj, bool want_rot, bool want_center" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG ") -> (Tensor, Tensor, Tensor)");
+          ", bool want_proj, bool want_rot, bool want_center" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_GRAD_CONF_ARG ") -> (Tensor, Tensor, Tensor)");
     m.def("triangulate_dlt(Tensor proj, Tensor points, Tensor? confidences) -> Tensor");
     m.def("triangulate_dlt_backward(Tensor grad_out, Tensor proj, Tensor points, Tensor? confidences) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int");
