@@ -485,6 +485,66 @@ int mvhmr_unproject_backward_geometry_cuboid_confidence(const mvhmr_unproject_de
         const uint8_t *view_mask, const float *view_confidence, int visible, float *grad_proj, float *grad_rot, float *grad_center, float *grad_confidence, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
+ * Shared feature maps (additive within ABI 4): `volumes` (M) volumes are un-projected from the desc->batch (B) feature
+ * samples through feature_index, M int32 on the device.  Volume m is the plain un-projection of features[feature_index[m]] under
+ * proj[feature_index[m]] onto coords[m] (tensor form: coords (M,X,Y,Z,3)) or the cuboid of rot[m], center[m] (cuboid form: rot (M,3,3),
+ * center (M,3); position and sides shared).  The index may repeat a sample, skip one and come in any order.  The descriptor keeps its
+ * meaning: desc->batch is B, the number of FEATURE samples; features and proj are (B, ...), out and grad_out are (M,C,X,Y,Z).
+ *   grad_features (B, ...): sample b receives the sum over the volumes that name it; every element is written, a sample no volume names
+ *       gets exact zeros.  Deterministic form: one exponent per feature sample and channel, whose bound counts the volumes that name it.
+ *   grad_proj (B,V,3,4): summed over the same volumes, float64, volumes in ascending order then their blocks in order (bitwise
+ *       reproducible); a sample no volume names gets zeros.  grad_coords (M,X,Y,Z,3), grad_rot (M,3,3), grad_center (M,3): per volume.
+ * An entry outside [0, B) is "no sample": that volume is exact zeros, contributes to no gradient (its own geometry gradients are zeros),
+ * and nothing is read through it.  Nothing is inspected on the host: no synchronisation, the calls stay graph-capturable.
+ * Routing and refusals are those of the *_masked calls: the gather kernels (MVHMR_VARIANT_AUTO runs them), planar or channels-last
+ * features; MVHMR_VARIANT_BRICK and the quad-planar layouts -> MVHMR_ERR_UNSUPPORTED.  1 <= volumes (MVHMR_ERR_INVALID_ARGUMENT) <= 65535
+ * (MVHMR_ERR_UNSUPPORTED: the volume index is the grid's y extent).  A null feature_index needs volumes == batch
+ * (MVHMR_ERR_INVALID_ARGUMENT) and is the plain call with MVHMR_VARIANT_GATHER.  view_mask, view_weights, view_confidence and visible are
+ * the view selections of the families above; they do not compose with the index yet: each must be null / 0, else MVHMR_ERR_UNSUPPORTED with
+ * its own text.
+ * Workspace: the *_shared_workspace_bytes queries take `volumes` too.  Every feature-sized region (channels-last copy, gradient
+ * accumulator) is sized by B; only the geometry calls' partials grow with M.  Each total also covers the plain call's.
+ */
+size_t mvhmr_unproject_forward_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes);
+size_t mvhmr_unproject_forward_cuboid_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes);
+size_t mvhmr_unproject_backward_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes);
+size_t mvhmr_unproject_backward_cuboid_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes);
+size_t mvhmr_unproject_backward_deterministic_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes);
+size_t mvhmr_unproject_backward_cuboid_deterministic_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes);
+size_t mvhmr_unproject_backward_geometry_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes);
+size_t mvhmr_unproject_backward_geometry_cuboid_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes);
+int mvhmr_unproject_forward_shared(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+        int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible,
+        void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_forward_cuboid_shared(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center,
+        const double position[3], const double sides[3],
+        int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible,
+        void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible,
+        void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot,
+        const float *center, const double position[3], const double sides[3],
+        int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible,
+        void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_deterministic_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords,
+        int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible,
+        void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_deterministic_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3],
+        int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible,
+        void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords,
+        int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible,
+        float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_cuboid_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3],
+        int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible,
+        float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/*
  * Layout pass on its own: features (B,V,C,Hf,Wf) -> dst in `dst_layout` (MVHMR_LAYOUT_BVHWC with the channel
  * count rounded up to a multiple of 4 and zero padded, or MVHMR_LAYOUT_QUAD), desc->feat_dtype.
  * desc->feat_layout names the SOURCE: MVHMR_LAYOUT_BVCHW (also assumed for MVHMR_LAYOUT_QUAD descriptors, as before), or

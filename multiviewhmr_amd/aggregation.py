@@ -159,7 +159,9 @@ def _op_defined(name):
 # the views that see it.  The confidence families (mvhmr_unproject_*_confidence) are masked families too, with
 # view_confidence (B, V, Hf, Wf) fp32 behind view_mask: per-pixel confidence maps sampled like one more channel; the geometry
 # backward differentiates w.r.t. them as well; their *_visible twins add the seeing test.  Their view_mask is `Tensor?`: None is the null
-# mask of the C entry points, with which nothing is packed or copied.
+# mask of the C entry points, with which nothing is packed or copied.  The shared families (mvhmr_unproject_*_shared) take
+# feature_index (M,) int32 on the features' device behind the placing tensors, which then hold M entries: volume m reads sample
+# feature_index[m]; the forward returns M volumes, the feature gradient has B samples; the index is not differentiable.
 _CUBOID_ARGS = ("float[] position", "float[] sides", "int[] vol")
 _FAMILIES = {
     "unprojection": (("coords",), (), False),
@@ -174,18 +176,20 @@ _FAMILIES = {
     "unprojection_cuboid_confidence": (("rot", "center"), _CUBOID_ARGS, True, False, False, True),
     "unprojection_confidence_visible": (("coords",), (), True, False, True, True),
     "unprojection_cuboid_confidence_visible": (("rot", "center"), _CUBOID_ARGS, True, False, True, True),
+    "unprojection_shared": (("coords",), (), False, False, False, False, True),
+    "unprojection_cuboid_shared": (("rot", "center"), _CUBOID_ARGS, False, False, False, False, True),
 }
 
 
 class _Family:
     """the implementations of one family's ops, each taking the ops' arguments positionally"""
 
-    def __init__(self, name, places, extras, masked, weighted=False, visible=False, confidence=False):
-        self.name, self.masked, self.weighted, self.visible, self.confidence = name, masked, weighted, visible, confidence
+    def __init__(self, name, places, extras, masked, weighted=False, visible=False, confidence=False, shared=False):
+        self.name, self.masked, self.weighted, self.visible, self.confidence, self.shared = name, masked, weighted, visible, confidence, shared
         self.native = "unprojection_cuboid" if extras else "unprojection"       # the extension's op: view_mask / view_weights are trailing arguments there
         self.geo = ("proj",) + places                                           # the geometry tensors, behind features
         self.tensors = (("features",) + self.geo + (("view_mask",) if masked else ()) + (("view_weights",) if weighted else ())
-                        + (("view_confidence",) if confidence else ()))
+                        + (("view_confidence",) if confidence else ()) + (("feature_index",) if shared else ()))
         self.grads = self.geo + (("view_weights",) if weighted else ()) + (("view_confidence",) if confidence else ())   # what the geometry backward differentiates
         self.extras = extras
         self.n_inputs = len(self.tensors) + len(extras) + 3
@@ -204,6 +208,10 @@ class _Family:
         views = (args[g] if self.masked else None, args[g + 1] if self.weighted else None, args[g + 1] if self.confidence else None)
         return (args[0], tuple(args[1:g]), views, tuple(args[n:k]), tuple(args[k:k + 3]), want + (True,) * (len(self.grads) - len(want)))
 
+    def index(self, args):
+        """a shared family's feature_index (behind the geometry tensors), else None"""
+        return args[1 + len(self.geo)] if self.shared else None
+
     def volume(self, geo, extra):
         return tuple(extra[2]) if extra else tuple(geo[1].shape[1:4])
 
@@ -212,19 +220,19 @@ class _Family:
         (view_mask, view_weights, view_confidence)"""
         features, geo, views, extra, (method, out_dtype, variant), _ = self.split(args)
         layout = None
-        if self.masked or geometry:
+        if self.masked or self.shared or geometry:
             features, layout = _geometry_read_layout(features)
         read, desc = _native_args(features, self.volume(geo, extra), method, out_dtype, variant, layout)
         return (read,) + geo + extra + desc, views
 
     def forward(self, *args):
         lead, (mask, weights, conf) = self.native_args(args)
-        return getattr(_native(), self.native)(*lead, mask, weights, self.visible, conf)
+        return getattr(_native(), self.native)(*lead, mask, weights, self.visible, conf, self.index(args))
 
     def backward(self, deterministic, grad_out, *args):
         """gradient w.r.t. features (the geometry's is backward_geometry)"""
         lead, (mask, weights, conf) = self.native_args(args)
-        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible, conf)
+        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible, conf, self.index(args))
 
     def backward_geometry(self, grad_out, *args):
         """planar features go through the library's channels-last pass, channels-last ones are read as they are; the gradient w.r.t.
@@ -240,7 +248,7 @@ class _Family:
                 return tuple(conf.new_empty((0,)) for _ in self.geo) + (gc,)
             return tuple(op(grad_out.contiguous(), *lead, *want[:-1], *tail)) + (gc,)
         if not self.weighted:
-            return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, self.visible))
+            return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, self.visible, None, None, self.index(args)))
         gw = weights.new_empty(weights.shape if want[-1] else (0,))
         if not any(want[:-1]):                             # the weights' gradient alone: the extension's outputs stay empty
             op(grad_out.contiguous(), *lead, *want[:-1], mask, weights, gw)
@@ -249,7 +257,8 @@ class _Family:
 
     def fake_forward(self, *args):
         features, geo, _, extra, (_, out_dtype, _), _ = self.split(args)
-        return features.new_empty((features.shape[0], features.shape[2]) + self.volume(geo, extra), dtype=_DTYPES[out_dtype])
+        volumes = self.index(args).shape[0] if self.shared else features.shape[0]
+        return features.new_empty((volumes, features.shape[2]) + self.volume(geo, extra), dtype=_DTYPES[out_dtype])
 
     def fake_backward(self, grad_out, features, *args):
         return torch.empty_like(features)
@@ -331,7 +340,7 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
 
 
 def unprojection(features, proj_matricies, coord_volumes, aggregation_method='softmax', *, out_dtype=None,
-                 variant='auto', view_mask=None, view_weights=None, visible_only=False, view_confidence=None):
+                 variant='auto', view_mask=None, view_weights=None, visible_only=False, view_confidence=None, feature_index=None):
     """Fused project -> bilinear-sample -> cross-view aggregate (reference: models/aggregation.py:20-87).
 
     features        (B, V, C, Hf, Wf) float32 (or float16, this package's storage mode) on a HIP device;
@@ -365,11 +374,23 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
                     wholly outside the map included -- is absent for that voxel: not read, zero gradients.  Differentiable (the gradient comes
                     back in the caller's dtype and device, and enters the geometry gradients); composes with view_mask and visible_only;
                     'max' and view_weights raise ValueError (multiply the maps by the weights); runs the gather kernels; DESIGN.md 5.11.
+    feature_index   (M,) integer tensor, any device (keyword-only; None = volume b reads sample b): M volumes share the B feature samples.
+                    coord_volumes is then (M, X, Y, Z, 3) and out[m] the plain un-projection of features[idx[m]] under proj_matricies[idx[m]]
+                    onto coord_volumes[m]; the result is (M, C, X, Y, Z).  The index may repeat a sample, skip one and come in any order;
+                    nothing is duplicated.  features.grad and proj_matricies.grad sum over the volumes that name a sample (an unnamed sample
+                    gets exact zeros), coord_volumes.grad is per volume.  A CPU index is checked (IndexError outside [0, B)); a device index is
+                    not inspected -- no synchronisation, graph-capturable -- and an entry outside [0, B) gives a zero volume that contributes
+                    to no gradient.  M > 65535 raises ValueError, M = 0 gives an empty result.  With view_mask, view_weights, visible_only or
+                    view_confidence it raises ValueError (not built yet).  Runs the gather kernels ('brick' is refused); DESIGN.md 5.12.
     """
     def volume_shape(B):
-        if coord_volumes.dim() != 5 or coord_volumes.shape[0] != B or coord_volumes.shape[4] != 3:
-            raise RuntimeError("unprojection: coord_volumes must be (%d, X, Y, Z, 3), got %s" % (B, tuple(coord_volumes.shape)))
+        n = B if feature_index is None else feature_index.shape[0]
+        if coord_volumes.dim() != 5 or coord_volumes.shape[0] != n or coord_volumes.shape[4] != 3:
+            raise RuntimeError("unprojection: coord_volumes must be (%d, X, Y, Z, 3), got %s" % (n, tuple(coord_volumes.shape)))
         return tuple(coord_volumes.shape[1:4])
+
+    if feature_index is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_feature_index(feature_index, features, view_mask, view_weights, visible_only, view_confidence)
 
     if view_mask is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_view_mask(view_mask, features)
@@ -380,11 +401,16 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
         _check_view_confidence(view_confidence, features, aggregation_method, view_weights)
     out_dtype, _, empty = _check_call(features, proj_matricies, (coord_volumes,), volume_shape, aggregation_method, variant, out_dtype,
                                       same_device=True)
+    if feature_index is not None and (empty is not None or feature_index.shape[0] == 0):
+        return features.new_zeros((feature_index.shape[0], features.shape[2]) + tuple(coord_volumes.shape[1:4]), dtype=out_dtype)
     if empty is not None:
         return empty
     # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
     proj = proj_matricies.to(torch.float32).contiguous()
     coords = coord_volumes.to(torch.float32).contiguous()
+    if feature_index is not None:
+        return torch.ops.mvhmr.unprojection_shared(features, proj, coords, _index_int32(feature_index, features), _capi.AGG[aggregation_method],
+                                                   _dtype_code(out_dtype), _capi.VARIANT[variant])
     if view_confidence is not None:
         op = torch.ops.mvhmr.unprojection_confidence_visible if visible_only else torch.ops.mvhmr.unprojection_confidence
         return op(features, proj, coords, None if view_mask is None else _mask_bytes(view_mask, features), _weights_fp32(view_confidence, features),
@@ -410,6 +436,37 @@ def _check_view_mask(view_mask, features):
         raise TypeError("unprojection: view_mask must be bool or an integer dtype, got %s" % view_mask.dtype)
     if tuple(view_mask.shape) != tuple(features.shape[:2]):
         raise RuntimeError("unprojection: view_mask must be %s, got %s" % (tuple(features.shape[:2]), tuple(view_mask.shape)))
+
+
+_MAX_VOLUMES = 65535                                    # the *_shared entry points: the volume index is the grid's y extent (mvhmr_unproject.h)
+
+
+def _check_feature_index(feature_index, features, view_mask=None, view_weights=None, visible_only=False, view_confidence=None):
+    """feature_index (M,) of an integer dtype, any device: raises TypeError / RuntimeError as _check_view_mask does, IndexError for a CPU entry
+    outside [0, B) (a device index is not inspected: no synchronisation), ValueError for M > 65535 and beside a view selection"""
+    if not torch.is_tensor(feature_index):
+        raise TypeError("unprojection: feature_index must be an (M,) tensor of integers, got %s" % type(feature_index).__name__)
+    if feature_index.dtype.is_floating_point or feature_index.dtype.is_complex or feature_index.dtype == torch.bool:
+        raise TypeError("unprojection: feature_index must be an integer dtype, got %s" % feature_index.dtype)
+    if feature_index.dim() != 1:
+        raise RuntimeError("unprojection: feature_index must be (M,), got %s" % (tuple(feature_index.shape),))
+    for given, what in ((view_mask is not None, "view_mask"), (view_weights is not None, "view_weights"), (bool(visible_only), "visible_only=True"),
+                        (view_confidence is not None, "view_confidence")):
+        if given:
+            raise ValueError("unprojection: feature_index with %s is not built yet (the next step of DESIGN.md 5.12): un-project those samples "
+                             "on their own" % what)
+    if feature_index.shape[0] > _MAX_VOLUMES:
+        raise ValueError("unprojection: feature_index names %d volumes, at most %d per call: split the call" % (feature_index.shape[0], _MAX_VOLUMES))
+    B = features.shape[0]
+    if not feature_index.is_cuda and feature_index.device.type != "meta" and feature_index.numel():
+        lo, hi = int(feature_index.min()), int(feature_index.max())
+        if lo < 0 or hi >= B:
+            raise IndexError("unprojection: feature_index entry %d is outside [0, %d)" % (lo if lo < 0 else hi, B))
+
+
+def _index_int32(feature_index, features):
+    """the checked index as the library reads it: contiguous int32 on features.device (a device tensor is cast there: no synchronisation)"""
+    return feature_index.to(device=features.device, dtype=torch.int32).contiguous()
 
 
 def _check_visible_only(visible_only, view_weights):
@@ -514,19 +571,24 @@ _register_dlt_op()
 
 def unprojection_cuboid(features, proj_matricies, rotations, centers, position, sides, volume_shape,
                         aggregation_method='softmax', *, out_dtype=None, variant='auto', view_mask=None, view_weights=None, visible_only=False,
-                        view_confidence=None):
+                        view_confidence=None, feature_index=None):
     """`unprojection` for the volumes VolumeGenerator builds (aggregation.py:138-187), without the coordinate tensor: voxel centres
     are rot[b] @ (position + sides / (S - 1) * (i,j,k) - center[b]) + center[b], evaluated inside the kernels (bit-equal to
     mvhmr_build_coord_volumes followed by `unprojection`).
 
     rotations (B,3,3) and centers (B,3): float32 tensors on features.device; position, sides: 3 numbers each (cuboid corner and
     edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers (and view_weights).
-    view_mask, view_weights, visible_only, view_confidence: as for `unprojection`."""
+    view_mask, view_weights, visible_only, view_confidence, feature_index: as for `unprojection`; with feature_index (M,) rotations are
+    (M,3,3) and centers (M,3) -- one pose per volume, position / sides / volume_shape shared -- and their gradients are per volume."""
     def checked_shape(B):
-        if tuple(rotations.shape) != (B, 3, 3) or tuple(centers.shape) != (B, 3):
+        n = B if feature_index is None else feature_index.shape[0]
+        if tuple(rotations.shape) != (n, 3, 3) or tuple(centers.shape) != (n, 3):
             raise RuntimeError("unprojection: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
-                               % (B, B, tuple(rotations.shape), tuple(centers.shape)))
+                               % (n, n, tuple(rotations.shape), tuple(centers.shape)))
         return tuple(int(v) for v in volume_shape)
+
+    if feature_index is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_feature_index(feature_index, features, view_mask, view_weights, visible_only, view_confidence)
 
     if view_mask is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_view_mask(view_mask, features)
@@ -537,6 +599,8 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
         _check_view_confidence(view_confidence, features, aggregation_method, view_weights)
     out_dtype, vol, empty = _check_call(features, proj_matricies, (rotations, centers), checked_shape, aggregation_method, variant,
                                         out_dtype, same_device=False)
+    if feature_index is not None and (empty is not None or feature_index.shape[0] == 0):
+        return features.new_zeros((feature_index.shape[0], features.shape[2]) + vol, dtype=out_dtype)
     if empty is not None:
         return empty
     dev = features.device                               # the cuboid's few numbers move to the features' device
@@ -544,6 +608,10 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     proj = proj_matricies.to(device=dev, dtype=torch.float32).contiguous()
     rot = rotations.to(device=dev, dtype=torch.float32).contiguous()
     cen = centers.to(device=dev, dtype=torch.float32).contiguous()
+    if feature_index is not None:
+        return torch.ops.mvhmr.unprojection_cuboid_shared(features, proj, rot, cen, _index_int32(feature_index, features), [float(x) for x in position],
+                                                          [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method], _dtype_code(out_dtype),
+                                                          _capi.VARIANT[variant])
     if view_confidence is not None:
         op = torch.ops.mvhmr.unprojection_cuboid_confidence_visible if visible_only else torch.ops.mvhmr.unprojection_cuboid_confidence
         return op(features, proj, rot, cen, None if view_mask is None else _mask_bytes(view_mask, features), _weights_fp32(view_confidence, features),
@@ -804,7 +872,7 @@ class VolumeGenerator(nn.Module):
             return [0, 0, 1]
         raise ValueError("Unknown kind: {}".format(self.kind))  # the reference fails with UnboundLocalError here
 
-    def volume_pose(self, batch, proj_matricies_org, images_shape, view_mask=None, view_weights=None):
+    def volume_pose(self, batch, proj_matricies_org, images_shape, view_mask=None, view_weights=None, feature_index=None):
         """Per-sample rotation (B,3,3) and pivot (B,3), float32 numpy/tensor (aggregation.py:163-181).
 
         Training draws theta ~ U(0, 2 pi) from the GLOBAL numpy stream, one draw per sample in order
@@ -812,8 +880,10 @@ class VolumeGenerator(nn.Module):
         image centre when use_triangulation is set -- a function of proj_matricies_org that carries its gradient (the reference
         triangulates from the caller's proj_matricies with torch.svd).  With a view mask (B, V) the pivot is the weighted DLT with the mask as
         the confidences, on projections whose masked rows are zeroed first (0 * NaN is not 0); fewer than two present views is undefined.
-        With view_weights (B, V) the confidences are the effective weights (mask ? w : 0 where w > 0, else 0), which carry their gradient."""
-        batch_size = proj_matricies_org.shape[0]
+        With view_weights (B, V) the confidences are the effective weights (mask ? w : 0 where w > 0, else 0), which carry their gradient.
+        With a feature_index (M,) there is one pose per VOLUME: M draws of theta in order (the identity index consumes the stream as no index
+        does), keypoints_3d holds M entries, and the per-sample DLT pivots are gathered by the index with torch indexing (differentiable)."""
+        batch_size = proj_matricies_org.shape[0] if feature_index is None else feature_index.shape[0]
         axis = self.rotation_axis()
         if self.training:
             # one draw per sample, in order, from the GLOBAL numpy stream (Q6): a sized draw consumes the same stream
@@ -839,6 +909,8 @@ class VolumeGenerator(nn.Module):
                 P = torch.where(present[:, :, None, None], proj_matricies_org, torch.zeros((), dtype=proj_matricies_org.dtype,
                                                                                           device=proj_matricies_org.device))
                 centers = multiview.triangulate_points_from_multiple_views_linear_batch(P, images_center, conf)
+            if feature_index is not None:
+                centers = centers[feature_index.to(device=centers.device, dtype=torch.long)]
         else:
             kp = batch['keypoints_3d']
             if torch.is_tensor(kp):                                          # already a (B, 17, 3|4) tensor (any device)
@@ -887,7 +959,12 @@ class VolumeGenerator(nn.Module):
         if view_confidence is not None:
             meta = torch.empty((batch_size, n_views, 1) + features_shape, device="meta")
             _check_view_confidence(view_confidence, meta, self.aggregation_method, view_weights)
-        if view_weights is not None:
+        feature_index = batch.get('feature_index')                          # optional (M,): M volumes share the samples' feature maps
+        if feature_index is not None:
+            meta = torch.empty((batch_size, n_views, 1) + features_shape, device="meta")
+            _check_feature_index(feature_index, meta, view_mask, view_weights, self.visible_only, view_confidence)
+            rots, centers = self.volume_pose(batch, proj_org, images_shape, feature_index=feature_index)
+        elif view_weights is not None:
             rots, centers = self.volume_pose(batch, proj_org, images_shape, view_mask, view_weights)
         else:
             rots, centers = (self.volume_pose(batch, proj_org, images_shape) if view_mask is None
@@ -898,7 +975,7 @@ class VolumeGenerator(nn.Module):
         centers = centers.to(device=device, dtype=torch.float32).contiguous()
 
         _check_visible_only(self.visible_only, view_weights)
-        if view_mask is None and view_weights is None and view_confidence is None and not self.visible_only and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask, weights, confidence maps or visible_only do not take)
+        if view_mask is None and view_weights is None and view_confidence is None and feature_index is None and not self.visible_only and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask, weights, confidence maps or visible_only do not take)
             # 1x1 conv and layout pass in one MFMA GEMM, its output only ever exists in the layout the brick forward stages
             conv = self.process_feature[0]
             return _FusedAggregate.apply(features, conv.weight, conv.bias, proj, rots, centers, tuple(cub.position), tuple(cub.sides),
@@ -915,6 +992,8 @@ class VolumeGenerator(nn.Module):
             masked["visible_only"] = True
         if view_confidence is not None:
             masked["view_confidence"] = view_confidence
+        if feature_index is not None:
+            masked["feature_index"] = feature_index                           # -> (M, C, S, S, S)
         return unprojection_cuboid(features, proj, rots, centers, cub.position, cub.sides, (S, S, S),
                                    aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **masked)
 

@@ -306,6 +306,40 @@ int confidence_refused(const mvhmr_unproject_desc *desc)
         return fail(MVHMR_ERR_UNSUPPORTED, "aggregation method max has no weighted form: pass a view mask instead of view confidence maps");
     return MVHMR_OK;
 }
+// ---- shared feature maps (include/mvhmr_unproject.h): `volumes` volumes read the desc->batch feature samples through a device
+// index.  The route of the masked calls without their head -- nothing is packed or copied: the gather family with the per-tap scatter backward
+// and the geometry kernels, which launch their *_shared kernels (Problem::feature_index).  Every feature-sized region stays sized by the
+// batch; only the geometry partials are per volume.  Refused where a mask is; the view selections (mask, weights, seeing test, confidence
+// maps) do not compose with the index yet and are refused each with its own text.  A null index with volumes == batch is the plain gather call.
+struct SharedIndex {
+    int32_t volumes;
+    const int32_t *index;
+    const uint8_t *mask;
+    const float *weights, *confidence;
+    int visible;
+};
+// the checks that need no index: what the workspace queries ask too
+int shared_shape_refused(const mvhmr_unproject_desc *desc, int32_t volumes)
+{
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "shared feature maps need planar or channels-last features (quad-planar copies: pass the planar features)");
+    if (desc->variant == MVHMR_VARIANT_BRICK) return fail(MVHMR_ERR_UNSUPPORTED, "shared feature maps run the gather kernels: MVHMR_VARIANT_BRICK is not served");
+    if (volumes < 1) return fail(MVHMR_ERR_INVALID_ARGUMENT, "volumes must be >= 1 (got %d)", volumes);
+    if (volumes > kSharedMaxVolumes)
+        return fail(MVHMR_ERR_UNSUPPORTED, "at most %d volumes per call (the volume index is the grid's y extent; got %d): split the call", kSharedMaxVolumes, volumes);
+    return MVHMR_OK;
+}
+int shared_refused(const mvhmr_unproject_desc *desc, const SharedIndex &sh)
+{
+    if (sh.mask) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with a view mask is not built yet: un-project the masked samples on their own");
+    if (sh.weights) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with view weights is not built yet: un-project the weighted samples on their own");
+    if (sh.visible) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with visibility-aware aggregation is not built yet: un-project those samples on their own");
+    if (sh.confidence) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with view confidence maps is not built yet: un-project those samples on their own");
+    if (const int rc = shared_shape_refused(desc, sh.volumes)) return rc;
+    if (!sh.index && sh.volumes != desc->batch)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "a null feature_index is the plain call: volumes (%d) must equal batch (%d)", sh.volumes, desc->batch);
+    return MVHMR_OK;
+}
 // what selects the packed route of a call, and whether the descriptor can take it
 struct Views {
     const uint8_t *mask;
@@ -323,14 +357,14 @@ int views_refused(const mvhmr_unproject_desc *desc, const Views &w)
     return w.weights ? weights_refused(desc) : MVHMR_OK;
 }
 // the kinds of plan: every view, a mask, weights (with or without a mask), the seeing views of every voxel (with or without a mask),
-// confidence maps (with or without a mask, with or without the seeing test)
-enum class Pack { None, Masked, Weighted, Visible, Confidence };
+// confidence maps (with or without a mask, with or without the seeing test); Shared: shared feature maps (no head: nothing is packed)
+enum class Pack { None, Masked, Weighted, Visible, Confidence, Shared };
 Pack pack_of(const Views &w)
 {
     return w.confidence ? Pack::Confidence : w.visible ? Pack::Visible : w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None;
 }
 // the plan whose workspace a plan's total also covers: a weighted or visible call's serves the masked one, a masked call's the unmasked one
-Pack pack_below(Pack pack) { return pack == Pack::Masked ? Pack::None : Pack::Masked; }
+Pack pack_below(Pack pack) { return pack == Pack::Masked || pack == Pack::Shared ? Pack::None : Pack::Masked; }
 // the descriptor and problem of the packed call; view_count is set once the table exists (pack_views)
 void mask_route(mvhmr_unproject_desc *desc, Problem *p, Pack pack)
 {
@@ -345,6 +379,28 @@ void confidence_route(Problem &p, const Views &w)
     if (!w.confidence) return;
     p.visible = w.visible;
     if (!p.confidence) p.confidence = w.confidence;
+}
+// a shared call: the index and the volume count ride in the problem (the plans read the count: the geometry partials are per volume); a null
+// index with volumes == batch is the plain call with the gather variant (Problem::volumes stays 0)
+Pack shared_pack(const SharedIndex *sh) { return sh && sh->index ? Pack::Shared : Pack::None; }
+void shared_route(const SharedIndex *sh, mvhmr_unproject_desc *dq, const mvhmr_unproject_desc **desc, Problem *p)
+{
+    if (!sh) return;
+    if (sh->index) {
+        p->feature_index = sh->index;
+        p->volumes = sh->volumes;
+        return;
+    }
+    *dq = **desc;
+    dq->variant = MVHMR_VARIANT_GATHER;
+    *desc = dq;
+}
+// the plain call with the gather variant: what a null index runs, and a workspace every shared plan's total covers
+mvhmr_unproject_desc gather_twin(const mvhmr_unproject_desc *desc)
+{
+    mvhmr_unproject_desc d = *desc;
+    d.variant = MVHMR_VARIANT_GATHER;
+    return d;
 }
 size_t conf_map_bytes(const Problem &p) { return (size_t)p.H * p.W * sizeof(float); }                   // one view's confidence map
 size_t masked_view_bytes(const Problem &p) { return (size_t)p.C * p.H * p.W * feat_elem(p); }   // one view, planar or channels-last (C4 == C)
@@ -412,7 +468,7 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pac
     f.p = p;
     if (pack != Pack::None) {
         mask_route(&f.desc, &f.p, pack);
-        f.head = plan_mask_head(a, p, 1, pack);
+        if (pack != Pack::Shared) f.head = plan_mask_head(a, p, 1, pack);
     }
     const mvhmr_unproject_desc *d = &f.desc;
     const bool brick = pick_variant(d, f.p) == MVHMR_VARIANT_BRICK;
@@ -430,6 +486,10 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pac
     // (a weighted call's workspace also serves the masked one, a masked call's the unmasked one)
     f.total = pack == Pack::None ? a.top : max_size(a.top, plan_forward(desc, p, pack_below(pack)).total);
     if (pack == Pack::Confidence) f.total = max_size(f.total, plan_forward(desc, p, Pack::Visible).total);      // (a null map is the visible call)
+    if (pack == Pack::Shared) {                                                                                 // (a null index is the plain gather call)
+        const mvhmr_unproject_desc dg = gather_twin(desc);
+        f.total = max_size(f.total, plan_forward(&dg, p, Pack::None).total);
+    }
     return f;
 }
 
@@ -491,7 +551,8 @@ void place_det_backward(BackwardPlan &b, Arena &a)
     b.route = brick ? Bwd::DetBrick : Bwd::DetGather;
     if (d->feat_layout != (brick ? MVHMR_LAYOUT_QUAD : MVHMR_LAYOUT_BVHWC)) b.staged = a.take(brick ? brick_workspace_bytes(p) : featT_bytes(p));
     b.acc = a.take(det_acc_bytes(p));
-    b.scale = a.take(align_up(det_scale_bytes(p)));
+    // (shared feature maps: the per-sample exponent table and the histogram cnt of the volumes that name each sample)
+    b.scale = a.take(align_up(p.volumes ? shared_det_scale_bytes(p) : det_scale_bytes(p)));
 }
 BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, bool det, Pack pack)
 {
@@ -501,7 +562,7 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
     b.p = p;
     if (pack != Pack::None) {
         mask_route(&b.desc, &b.p, pack);
-        b.head = plan_mask_head(a, p, 2, pack);
+        if (pack != Pack::Shared) b.head = plan_mask_head(a, p, 2, pack);
     }
     if (det) {
         BackwardPlan dflt = b;
@@ -514,6 +575,10 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
     }
     b.total = pack == Pack::None ? a.top : max_size(a.top, plan_backward(desc, p, det, pack_below(pack)).total);
     if (pack == Pack::Confidence) b.total = max_size(b.total, plan_backward(desc, p, det, Pack::Visible).total);
+    if (pack == Pack::Shared) {
+        const mvhmr_unproject_desc dg = gather_twin(desc);
+        b.total = max_size(b.total, plan_backward(&dg, p, det, Pack::None).total);
+    }
     return b;
 }
 
@@ -540,6 +605,8 @@ GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, b
     g.p = p;
     if (pack != Pack::None) {
         mask_route(&g.desc, &g.p, pack);
+    }
+    if (pack != Pack::None && pack != Pack::Shared) {
         g.head = plan_mask_head(a, p, 1, pack);
         g.packed_grad_proj = a.take(align_up((size_t)p.B * p.V * 12 * sizeof(float)));
     }
@@ -554,8 +621,9 @@ GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, b
         g.conf_max = a.take(align_up(conf_grad_max_bytes(p)));
     }
     if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) g.staged = a.take(featT_bytes(p));
-    g.part = a.take(align_up(geom_partial_bytes(p)));
-    if (cuboid) g.pose_part = a.take(align_up(pose_partial_bytes(p)));
+    // (shared feature maps: the partials are the only per-volume regions)
+    g.part = a.take(align_up(pack == Pack::Shared ? shared_geom_partial_bytes(p) : geom_partial_bytes(p)));
+    if (cuboid) g.pose_part = a.take(align_up(pack == Pack::Shared ? shared_pose_partial_bytes(p) : pose_partial_bytes(p)));
     g.total = pack == Pack::None ? a.top : max_size(a.top, plan_geometry(desc, p, cuboid, pack_below(pack)).total);
     if (pack == Pack::Confidence) g.total = max_size(g.total, plan_geometry(desc, p, cuboid, Pack::Visible).total);
     return g;
@@ -597,7 +665,7 @@ int query_variant(const mvhmr_unproject_desc *desc, const VolumeSource &v, const
 
 // ---- forward
 int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *features, const float *proj, const Views &views, void *out,
-                void *workspace, size_t workspace_bytes, void *hip_stream)
+                void *workspace, size_t workspace_bytes, void *hip_stream, const SharedIndex *shared = nullptr)
 {
     Problem p0;
     Coords coords;
@@ -605,8 +673,10 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
     if (rc != MVHMR_OK) return rc;
     if (!features || !proj || !out) return fail(MVHMR_ERR_INVALID_ARGUMENT, "features / proj / out must be non-null");
     if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
+    if (shared && (rc = shared_refused(desc, *shared)) != MVHMR_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     mvhmr_unproject_desc dq;
+    shared_route(shared, &dq, &desc, &p0);
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) {
         // the quad-planar copy times log2(e): only the wave-specialised softmax forward reads it (mvhmr_preferred_layout says when)
         if (!brick_fwd_prescales(p0) || desc->variant == MVHMR_VARIANT_GATHER)
@@ -618,7 +688,7 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
         desc = &dq;
         p0.feat_log2e = 1;
     }
-    ForwardPlan f = plan_forward(desc, p0, pack_of(views));
+    ForwardPlan f = plan_forward(desc, p0, shared ? shared_pack(shared) : pack_of(views));
     desc = &f.desc;
     Problem &p = f.p;
     rc = variant_conflict(desc, p, pick_variant(desc, p));
@@ -657,6 +727,7 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
             rc = stage_channels_last(desc, features, staged, p, s);
             if (rc != MVHMR_OK) return rc;
         }
+        if (p.feature_index) return launched(launch_fwd_gather_shared(staged ? staged : features, proj, coords, out, p, s), "shared gather forward");
         return launched(launch_fwd_gather(staged ? staged : features, proj, coords, out, p, s), "gather forward");
     }
     return fail(MVHMR_ERR_INVALID_ARGUMENT, "unknown forward route");
@@ -741,7 +812,8 @@ int launch_backward_default(BackwardPlan &b, const BackwardArgs &c)
         float *gradT = acc ? acc : static_cast<float *>(c.grad_features);      // in place: fp32 channels-last grad_features is the accumulator
         rc = clear_gradient(gradT, p, sizeof(float), s);
         if (rc != MVHMR_OK) return rc;
-        rc = launched(launch_bwd_gather(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "gather backward");
+        rc = p.feature_index ? launched(launch_bwd_gather_shared(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "shared gather backward")
+                             : launched(launch_bwd_gather(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "gather backward");
         if (rc != MVHMR_OK || !acc) return rc;
         if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_grad_to_planar(gradT, c.grad_features, p, s), "gradient layout pass");   // planar gradient for planar and quad-planar features alike
         return launched(launch_grad_cast(gradT, c.grad_features, p, s), "gradient cast");
@@ -772,7 +844,8 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
     void *scale = at(c.workspace, b.scale);
     rc = clear_gradient(acc, p, sizeof(long long), s);
     if (rc != MVHMR_OK) return rc;
-    rc = launched(launch_det_scale(c.grad_out, feat, scale, p, s, brick, c.proj, &coords), "deterministic scale pass");
+    rc = p.feature_index ? launched(launch_det_scale_shared(c.grad_out, feat, scale, p, s), "deterministic scale pass")
+                         : launched(launch_det_scale(c.grad_out, feat, scale, p, s, brick, c.proj, &coords), "deterministic scale pass");
     if (rc != MVHMR_OK) return rc;
     const int *kexp = det_exponents(scale, p);
     if (brick) {
@@ -780,14 +853,16 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
         if (rc != MVHMR_OK) return rc;
         return launched(launch_det_quad_to_planar(acc, kexp, c.grad_features, p, s), "gradient layout pass");
     }
-    rc = launched(launch_bwd_gather_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic gather backward");
+    rc = p.feature_index ? launched(launch_bwd_gather_shared_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic shared gather backward")
+                         : launched(launch_bwd_gather_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic gather backward");
     if (rc != MVHMR_OK) return rc;
     if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_det_grad_to_planar(acc, kexp, c.grad_features, p, s), "gradient layout pass");
     return launched(launch_det_grad_cast(acc, kexp, c.grad_features, p, s), "gradient cast");
 }
 
 int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
-                 const Views &views, bool det, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+                 const Views &views, bool det, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream,
+                 const SharedIndex *shared = nullptr)
 {
     Problem p0;
     Coords coords;
@@ -796,11 +871,14 @@ int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     if (!grad_out || !features || !proj || !grad_features)
         return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
     if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
+    if (shared && (rc = shared_refused(desc, *shared)) != MVHMR_OK) return rc;
+    mvhmr_unproject_desc dq;
+    shared_route(shared, &dq, &desc, &p0);
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
         return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p0) && !quad_to_channels_last_supported(p0))
         return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
-    BackwardPlan b = plan_backward(desc, p0, det, pack_of(views));
+    BackwardPlan b = plan_backward(desc, p0, det, shared ? shared_pack(shared) : pack_of(views));
     rc = check_ws(workspace, workspace_bytes, b.total);
     if (rc != MVHMR_OK) return rc;
     if (b.desc.variant == MVHMR_VARIANT_BRICK && !bwd_uses_brick(&b.desc, b.p))
@@ -820,7 +898,7 @@ int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
 // ---- geometry backward
 int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
                  const Views &views, float *grad_proj, float *grad_coords, float *grad_rot, float *grad_center, float *grad_weights, void *workspace,
-                 size_t workspace_bytes, void *hip_stream, float *grad_confidence = nullptr)
+                 size_t workspace_bytes, void *hip_stream, float *grad_confidence = nullptr, const SharedIndex *shared = nullptr)
 {
     const bool mask = views.packed();
     Problem p0;
@@ -846,11 +924,14 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
                                                                    : "grad_proj, grad_rot and grad_center are all null: nothing to compute");
     if (!data) return fail(MVHMR_ERR_INVALID_ARGUMENT, no_data);
     if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
+    if (shared && (rc = shared_refused(desc, *shared)) != MVHMR_OK) return rc;
+    mvhmr_unproject_desc dq;
+    shared_route(shared, &dq, &desc, &p0);
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
         return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p0))
         return fail(MVHMR_ERR_UNSUPPORTED, "quad-planar features of this shape cannot be converted to channels-last (C %% 4 == 0, C <= 4092, B * V <= 65535)");
-    GeometryPlan g = plan_geometry(desc, p0, v.cuboid, pack_of(views));
+    GeometryPlan g = plan_geometry(desc, p0, v.cuboid, shared ? shared_pack(shared) : pack_of(views));
     rc = check_ws(workspace, workspace_bytes, g.total);
     if (rc != MVHMR_OK) return rc;
     const Problem &p = g.p;
@@ -872,6 +953,12 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     // grad_weights likewise: fp32 partials, summed into slot order, unpacked (absent views zero-filled)
     float *gw = grad_weights ? reinterpret_cast<float *>(at(workspace, g.packed_grad_weights)) : nullptr;
     float *wpart = grad_weights ? reinterpret_cast<float *>(at(workspace, g.weight_part)) : nullptr;
+    if (p.feature_index) {
+        // shared feature maps: grad_coords / grad_rot / grad_center are per volume, grad_proj is summed over the volumes that name each sample
+        float *pose_part = (grad_rot || grad_center) ? reinterpret_cast<float *>(at(workspace, g.pose_part)) : nullptr;
+        return v.cuboid ? launched(launch_bwd_geom_cuboid_shared(grad_out, featT, proj, coords, part, gp, pose_part, grad_rot, grad_center, p, s), "shared cuboid geometry backward")
+                        : launched(launch_bwd_geom_shared(grad_out, featT, proj, coords, part, gp, grad_coords, p, s), "shared geometry backward");
+    }
     if (v.cuboid) {
         float *pose_part = (grad_rot || grad_center) ? reinterpret_cast<float *>(at(workspace, g.pose_part)) : nullptr;
         rc = launched(launch_bwd_geom_cuboid(grad_out, featT, proj, coords, part, gp, pose_part, grad_rot, grad_center, p, s, wpart, gw), "cuboid geometry backward");
@@ -925,6 +1012,31 @@ size_t geometry_need(const mvhmr_unproject_desc *desc, bool cuboid, Pack pack)
     Problem p;
     if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E || pack_refused(desc, pack)) return 0;
     return plan_geometry(desc, p, cuboid, pack).total;
+}
+
+// the *_shared queries: the checks of the call that do not need a pointer, then the plan's total (a null index is not known here: the
+// total covers it)
+bool shared_query_refused(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_shape_refused(desc, volumes) != MVHMR_OK; }
+size_t shared_forward_need(const mvhmr_unproject_desc *desc, int32_t volumes)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || shared_query_refused(desc, volumes)) return 0;
+    p.volumes = volumes;
+    return plan_forward(desc, p, Pack::Shared).total;
+}
+size_t shared_backward_need(const mvhmr_unproject_desc *desc, int32_t volumes, bool det)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || shared_query_refused(desc, volumes)) return 0;
+    p.volumes = volumes;
+    return plan_backward(desc, p, det, Pack::Shared).total;
+}
+size_t shared_geometry_need(const mvhmr_unproject_desc *desc, int32_t volumes, bool cuboid)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || shared_query_refused(desc, volumes)) return 0;
+    p.volumes = volumes;
+    return plan_geometry(desc, p, cuboid, Pack::Shared).total;
 }
 
 }  // namespace
@@ -1333,6 +1445,83 @@ int mvhmr_unproject_backward_geometry_cuboid_confidence(const mvhmr_unproject_de
         const uint8_t *view_mask, const float *view_confidence, int visible, float *grad_proj, float *grad_rot, float *grad_center, float *grad_confidence, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, grad_proj, nullptr, grad_rot, grad_center, nullptr, workspace, workspace_bytes, hip_stream, grad_confidence);
+}
+
+// ---- shared feature maps: the plain entry points with `volumes` and `feature_index` behind what places the volume, then the view selections
+// of the other families (view_mask, view_weights, view_confidence, visible), which do not compose with the index yet: each must be null / 0
+size_t mvhmr_unproject_forward_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_forward_need(desc, volumes); }
+size_t mvhmr_unproject_forward_cuboid_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_forward_need(desc, volumes); }
+size_t mvhmr_unproject_backward_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_backward_need(desc, volumes, false); }
+size_t mvhmr_unproject_backward_cuboid_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_backward_need(desc, volumes, false); }
+size_t mvhmr_unproject_backward_deterministic_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_backward_need(desc, volumes, true); }
+size_t mvhmr_unproject_backward_cuboid_deterministic_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_backward_need(desc, volumes, true); }
+size_t mvhmr_unproject_backward_geometry_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_geometry_need(desc, volumes, false); }
+size_t mvhmr_unproject_backward_geometry_cuboid_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_geometry_need(desc, volumes, true); }
+
+#define MVHMR_SHARED_ARGS int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible
+#define MVHMR_SHARED_INDEX const SharedIndex sh{volumes, feature_index, view_mask, view_weights, view_confidence, visible}
+
+int mvhmr_unproject_forward_shared(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords, MVHMR_SHARED_ARGS,
+        void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_SHARED_INDEX;
+    return run_forward(desc, tensor_volume(coords), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream, &sh);
+}
+
+int mvhmr_unproject_forward_cuboid_shared(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center,
+        const double position[3], const double sides[3], MVHMR_SHARED_ARGS, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_SHARED_INDEX;
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream, &sh);
+}
+
+int mvhmr_unproject_backward_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        MVHMR_SHARED_ARGS, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_SHARED_INDEX;
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace, workspace_bytes, hip_stream, &sh);
+}
+
+int mvhmr_unproject_backward_cuboid_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot,
+        const float *center, const double position[3], const double sides[3], MVHMR_SHARED_ARGS, void *grad_features, void *workspace, size_t workspace_bytes,
+        void *hip_stream)
+{
+    MVHMR_SHARED_INDEX;
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace,
+                        workspace_bytes, hip_stream, &sh);
+}
+
+int mvhmr_unproject_backward_deterministic_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords, MVHMR_SHARED_ARGS, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_SHARED_INDEX;
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace, workspace_bytes, hip_stream, &sh);
+}
+
+int mvhmr_unproject_backward_cuboid_deterministic_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3], MVHMR_SHARED_ARGS, void *grad_features, void *workspace,
+        size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_SHARED_INDEX;
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace,
+                        workspace_bytes, hip_stream, &sh);
+}
+
+int mvhmr_unproject_backward_geometry_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords, MVHMR_SHARED_ARGS, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_SHARED_INDEX;
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
+                        workspace, workspace_bytes, hip_stream, nullptr, &sh);
+}
+
+int mvhmr_unproject_backward_geometry_cuboid_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3], MVHMR_SHARED_ARGS, float *grad_proj, float *grad_rot,
+        float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_SHARED_INDEX;
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, nullptr, grad_rot,
+                        grad_center, nullptr, workspace, workspace_bytes, hip_stream, nullptr, &sh);
 }
 
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)

@@ -40,6 +40,12 @@ struct Problem {
     const float *confidence = nullptr;
     int conf = 0;
     float *conf_stream = nullptr;
+    // Shared feature maps: `volumes` (M) volumes read the B feature samples through feature_index (device, M ints): volume m
+    // un-projects features[feature_index[m]] under proj[feature_index[m]] onto coordinates / pose / output m; an entry outside [0, B) is "no
+    // sample" (a zero volume that contributes to no gradient).  Null = volume b reads sample b (volumes is not read).  The host route hands
+    // such a problem to the *_shared kernels (unproject_shared.hip, unproject_shared_geom.hip); B stays the number of FEATURE samples.
+    const int *feature_index = nullptr;
+    int volumes = 0;
 };
 
 inline Gate make_gate(const Problem &p, bool wants_brick) { return Gate{p.gate_count, p.gate_limit, wants_brick ? 1 : 0}; }
@@ -202,6 +208,26 @@ hipError_t launch_conf_grad(const float *stream, const float *proj, const Coords
 // (the confidence instances of k_bwd_geom live in unproject_confidence_geom.hip; launch_bwd_geom[_cuboid] call this for confidence problems)
 hipError_t launch_bwd_geom_conf_kernel(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part,
                                        float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
+
+// shared feature maps (unproject_shared.hip, unproject_shared_geom.hip; Problem::feature_index / volumes): the gather forward, the per-tap scatter
+// backward of both modes, the deterministic scale pass -- one exponent per FEATURE sample and channel whose bound carries cnt[b], the number of
+// volumes that name b (shared_det_scale_bytes: det_scale_bytes' three words per (b, c), det_exponents finds K, then the B-word histogram) --
+// and the geometry backward, whose grad_proj and pose partials are per VOLUME (shared_geom_partial_bytes / shared_pose_partial_bytes) and are
+// summed per (b, v) over the volumes that name b in ascending order.  The volume index is the grid's y extent.
+constexpr int kSharedMaxVolumes = 65535;
+hipError_t launch_fwd_gather_shared(const void *featT, const float *proj, const Coords &coords, void *out, const Problem &p, hipStream_t s);
+hipError_t launch_bwd_gather_shared(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *gradT, const Problem &p,
+                                    hipStream_t s);
+hipError_t launch_bwd_gather_shared_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
+                                        const int *kexp, const Problem &p, hipStream_t s);
+size_t shared_det_scale_bytes(const Problem &p);
+hipError_t launch_det_scale_shared(const void *grad_out, const void *featT, void *scale, const Problem &p, hipStream_t s);
+size_t shared_geom_partial_bytes(const Problem &p);
+size_t shared_pose_partial_bytes(const Problem &p);
+hipError_t launch_bwd_geom_shared(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
+                                  float *grad_coords, const Problem &p, hipStream_t s);
+hipError_t launch_bwd_geom_cuboid_shared(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
+                                         float *pose_part, float *grad_rot, float *grad_center, const Problem &p, hipStream_t s);
 
 // view masks (view_mask.hip): from mask (B,V) bytes, one thread per sample writes n_b (B ints), slot -> view and view -> slot (-1: masked)
 // tables (B,V ints each) and the projections packed into slot order (absent slots zero); then per-(sample, slot) copies of `bytes_per_view`

@@ -6,7 +6,8 @@
 // geometry ops also `Tensor(a!)? grad_weights`, the (B, V) fp32 tensor they write the gradient w.r.t. the weights into) and last `bool visible_only`
 // (visibility-aware aggregation: the *_visible entry points, view_mask nullable, no weights), then `Tensor? view_confidence` (per-pixel confidence maps
 // (B, V, Hf, Wf) fp32: the *_confidence entry points, which take visible_only as a flag; the geometry ops also `Tensor(b!)? grad_confidence`, the tensor they
-// write the gradient w.r.t. the maps into); mvhmr_visibility::view_visibility[_cuboid] return the
+// write the gradient w.r.t. the maps into), and last of all `Tensor? feature_index` (shared feature maps: the *_shared entry points; (M,) int32, the volumes'
+// tensors then hold M entries); mvhmr_visibility::view_visibility[_cuboid] return the
 // (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
 // tensor checks, descriptor, output and workspace from the caching allocator, the current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
@@ -31,10 +32,12 @@ mvhmr_unproject_desc make_desc(int64_t B, int64_t V, int64_t C, int64_t H, int64
     return d;
 }
 
+// M: the number of volumes (B without a feature_index)
 mvhmr_unproject_desc coords_desc(const at::Tensor &coords, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
-                                 int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant)
+                                 int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, int64_t M = -1)
 {
-    TORCH_CHECK(coords.dim() == 5 && coords.size(0) == B && coords.size(4) == 3, "mvhmr_unproject: coord_volumes must be fp32 (B, X, Y, Z, 3)");
+    TORCH_CHECK(coords.dim() == 5 && coords.size(0) == (M < 0 ? B : M) && coords.size(4) == 3, "mvhmr_unproject: coord_volumes must be fp32 (",
+                M < 0 || M == B ? "B" : "M", ", X, Y, Z, 3) with ", M < 0 ? B : M, " volumes");
     return make_desc(B, V, C, H, W, coords.size(1), coords.size(2), coords.size(3), method, feat_dtype, out_dtype, layout, variant);
 }
 
@@ -61,10 +64,12 @@ void check_tensor(const at::Tensor &t, const at::Tensor &features, const char *n
 
 // The C ABI trusts its descriptor (plain pointers carry no sizes): every tensor is checked against it HERE, before anything is launched.
 // coords (tensor ops) or rot + center (cuboid ops) describe the volume; grad_out is undefined for a forward.
+// M volumes: the tensors that place the volume and grad_out are per volume (M == B without a feature_index)
 void check_inputs(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *coords,
-                  const at::Tensor *rot, const at::Tensor *center, const at::Tensor *grad_out)
+                  const at::Tensor *rot, const at::Tensor *center, const at::Tensor *grad_out, int64_t M)
 {
     const int64_t B = d.batch, V = d.views, C = d.channels, H = d.feat_h, W = d.feat_w;
+    const bool shared = M != B;                                 // (the messages name the leading extent the tensor is checked against)
     TORCH_CHECK(features.is_cuda() && features.is_contiguous(), "mvhmr_unproject: features must be a contiguous tensor on a HIP device");
     TORCH_CHECK(B >= 1 && V >= 1 && C >= 1 && H >= 1 && W >= 1, "mvhmr_unproject: every dimension must be >= 1");
     TORCH_CHECK(d.feat_dtype == MVHMR_F32 || d.feat_dtype == MVHMR_F16, "mvhmr_unproject: features are fp32 or fp16");
@@ -76,13 +81,13 @@ void check_inputs(const mvhmr_unproject_desc &d, const at::Tensor &features, con
     TORCH_CHECK(quad || features.element_size() == (d.feat_dtype == MVHMR_F16 ? 2 : 4), "mvhmr_unproject: feature dtype and descriptor disagree");
     check_tensor(proj, features, "proj_matricies (B, V, 3, 4)", at::kFloat, B * V * 12);
     if (coords)
-        check_tensor(*coords, features, "coord_volumes (B, X, Y, Z, 3)", at::kFloat, B * d.vol_x * d.vol_y * d.vol_z * 3);
+        check_tensor(*coords, features, shared ? "coord_volumes (M, X, Y, Z, 3)" : "coord_volumes (B, X, Y, Z, 3)", at::kFloat, M * d.vol_x * d.vol_y * d.vol_z * 3);
     if (rot)
-        check_tensor(*rot, features, "rot (B, 3, 3)", at::kFloat, B * 9);
+        check_tensor(*rot, features, shared ? "rot (M, 3, 3)" : "rot (B, 3, 3)", at::kFloat, M * 9);
     if (center)
-        check_tensor(*center, features, "center (B, 3)", at::kFloat, B * 3);
+        check_tensor(*center, features, shared ? "center (M, 3)" : "center (B, 3)", at::kFloat, M * 3);
     if (grad_out)
-        check_tensor(*grad_out, features, "grad_out (B, C, X, Y, Z)", scalar_of(d.out_dtype), B * C * d.vol_x * d.vol_y * d.vol_z);
+        check_tensor(*grad_out, features, shared ? "grad_out (M, C, X, Y, Z)" : "grad_out (B, C, X, Y, Z)", scalar_of(d.out_dtype), M * C * d.vol_x * d.vol_y * d.vol_z);
 }
 
 
@@ -114,7 +119,15 @@ struct ViewArgs {
     const float *weights;
     bool visible = false;                                       // the *_visible entry points: every voxel aggregates the views that see it
     const float *confidence = nullptr;                          // the *_confidence entry points: per-pixel confidence maps (visible is their flag)
+    const int32_t *index = nullptr;                             // the *_shared entry points: `volumes` volumes read the samples through feature_index
+    int32_t volumes = 0;                                        // (the library refuses the selections above beside an index, each with its own text)
 };
+
+// shared feature maps (mvhmr_unproject_*_shared): feature_index (M,) int32 on the features' device; null for None
+int64_t volumes_of(const c10::optional<at::Tensor> &feature_index, int64_t B)
+{
+    return feature_index && feature_index->defined() ? feature_index->numel() : B;
+}
 
 // per-pixel confidence maps (mvhmr_unproject_*_confidence): (B, V, Hf, Wf) fp32 on the features' device; null for None
 const float *confidence_ptr(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &t, const char *name)
@@ -125,10 +138,18 @@ const float *confidence_ptr(const mvhmr_unproject_desc &d, const at::Tensor &fea
 }
 
 ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_mask,
-                   const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence)
+                   const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence,
+                   const c10::optional<at::Tensor> &feature_index)
 {
-    const ViewArgs v{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights), visible_only,
-                     confidence_ptr(d, features, view_confidence, "view_confidence (B, V, Hf, Wf)")};
+    ViewArgs v{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights), visible_only,
+               confidence_ptr(d, features, view_confidence, "view_confidence (B, V, Hf, Wf)")};
+    if (feature_index && feature_index->defined()) {
+        TORCH_CHECK(feature_index->dim() == 1 && feature_index->numel() >= 1 && feature_index->numel() <= INT32_MAX,
+                    "mvhmr_unproject: feature_index must be a non-empty (M,) tensor");
+        check_tensor(*feature_index, features, "feature_index (M,)", at::kInt, feature_index->numel());
+        v.index = feature_index->data_ptr<int32_t>();
+        v.volumes = (int32_t)feature_index->numel();
+    }
     TORCH_CHECK(!(v.visible && v.weights), "mvhmr_unproject: visible_only does not take view_weights");
     TORCH_CHECK(!(v.confidence && v.weights), "mvhmr_unproject: view_confidence does not take view_weights");
     return v;
@@ -164,6 +185,7 @@ at::Tensor new_feature_grad(const mvhmr_unproject_desc &d, const at::Tensor &fea
 // the descriptor's fields as the ops take them: B..W the logical feature shape
 struct DescArgs {
     int64_t B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant;
+    int64_t M;                                                  // volumes: B, or the length of the feature_index
 };
 
 // ---- what places the volume.  Each form knows its descriptor, its tensors' checks, the shapes of its geometry gradients and its C
@@ -174,11 +196,11 @@ struct TensorVolume {
 
     mvhmr_unproject_desc desc(const DescArgs &a) const
     {
-        return coords_desc(coords, a.B, a.V, a.C, a.H, a.W, a.method, a.feat_dtype, a.out_dtype, a.layout, a.variant);
+        return coords_desc(coords, a.B, a.V, a.C, a.H, a.W, a.method, a.feat_dtype, a.out_dtype, a.layout, a.variant, a.M);
     }
-    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out) const
+    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out, int64_t M) const
     {
-        check_inputs(d, features, proj, &coords, nullptr, nullptr, grad_out);
+        check_inputs(d, features, proj, &coords, nullptr, nullptr, grad_out, M);
     }
     int visibility(const mvhmr_unproject_desc &d, const float *proj, const uint8_t *mask, int32_t *bits, hipStream_t s) const
     {
@@ -189,6 +211,7 @@ struct TensorVolume {
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.index) return mvhmr_unproject_forward_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_forward_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_forward_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_forward_weighted_workspace_bytes(&d);
@@ -198,6 +221,7 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.index) return mvhmr_unproject_forward_shared(&d, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, out, ws, n, s);
         if (v.confidence) return mvhmr_unproject_forward_confidence(&d, features, proj, c, mask, v.confidence, v.visible, out, ws, n, s);
         if (v.visible) return mvhmr_unproject_forward_visible(&d, features, proj, c, mask, out, ws, n, s);
         if (v.weights) return mvhmr_unproject_forward_weighted(&d, features, proj, c, mask, v.weights, out, ws, n, s);
@@ -205,6 +229,7 @@ struct TensorVolume {
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.index) return det ? mvhmr_unproject_backward_deterministic_shared_workspace_bytes(&d, v.volumes) : mvhmr_unproject_backward_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return det ? mvhmr_unproject_backward_deterministic_confidence_workspace_bytes(&d) : mvhmr_unproject_backward_confidence_workspace_bytes(&d);
         if (v.visible) return det ? mvhmr_unproject_backward_deterministic_visible_workspace_bytes(&d) : mvhmr_unproject_backward_visible_workspace_bytes(&d);
         if (v.weights) return det ? mvhmr_unproject_backward_deterministic_weighted_workspace_bytes(&d) : mvhmr_unproject_backward_weighted_workspace_bytes(&d);
@@ -216,6 +241,8 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.index)
+            return (det ? mvhmr_unproject_backward_deterministic_shared : mvhmr_unproject_backward_shared)(&d, grad_out, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, grad, ws, n, s);
         if (v.confidence)
             return (det ? mvhmr_unproject_backward_deterministic_confidence : mvhmr_unproject_backward_confidence)(&d, grad_out, features, proj, c, mask, v.confidence,
                                                                                                                     v.visible, grad, ws, n, s);
@@ -228,6 +255,7 @@ struct TensorVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.index) return mvhmr_unproject_backward_geometry_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_backward_geometry_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_backward_geometry_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_backward_geometry_weighted_workspace_bytes(&d);
@@ -238,6 +266,7 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.index) return mvhmr_unproject_backward_geometry_shared(&d, grad_out, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, g[0], g[1], ws, n, s);
         if (v.confidence)
             return mvhmr_unproject_backward_geometry_confidence(&d, grad_out, features, proj, c, mask, v.confidence, v.visible, g[0], g[1], grad_confidence, ws, n, s);
         if (v.visible) return mvhmr_unproject_backward_geometry_visible(&d, grad_out, features, proj, c, mask, g[0], g[1], ws, n, s);
@@ -258,19 +287,20 @@ struct CuboidVolume {
     {
         return cuboid_desc(position, sides, vol, a.B, a.V, a.C, a.H, a.W, a.method, a.feat_dtype, a.out_dtype, a.layout, a.variant);
     }
-    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out) const
+    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out, int64_t M) const
     {
-        check_inputs(d, features, proj, nullptr, &rot, &center, grad_out);
+        check_inputs(d, features, proj, nullptr, &rot, &center, grad_out, M);
     }
     int visibility(const mvhmr_unproject_desc &d, const float *proj, const uint8_t *mask, int32_t *bits, hipStream_t s) const
     {
         return mvhmr_unproject_visibility_cuboid(&d, proj, rot.data_ptr<float>(), center.data_ptr<float>(), position.data(), sides.data(), mask, bits, s);
     }
-    // gradients w.r.t. proj (B,V,3,4), rot (B,3,3) and center (B,3)
-    std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, {d.batch, 3, 3}, {d.batch, 3}}; }
+    // gradients w.r.t. proj (B,V,3,4), rot (B,3,3) and center (B,3) -- (M,3,3) and (M,3) under a feature_index
+    std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, rot.sizes().vec(), center.sizes().vec()}; }
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.index) return mvhmr_unproject_forward_cuboid_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_forward_cuboid_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_forward_cuboid_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_forward_cuboid_weighted_workspace_bytes(&d);
@@ -280,6 +310,7 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.index) return mvhmr_unproject_forward_cuboid_shared(&d, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, out, ws, n, s);
         if (v.confidence)
             return mvhmr_unproject_forward_cuboid_confidence(&d, features, proj, r, c, position.data(), sides.data(), mask, v.confidence, v.visible, out, ws, n, s);
         if (v.visible) return mvhmr_unproject_forward_cuboid_visible(&d, features, proj, r, c, position.data(), sides.data(), mask, out, ws, n, s);
@@ -290,6 +321,8 @@ struct CuboidVolume {
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.index)
+            return det ? mvhmr_unproject_backward_cuboid_deterministic_shared_workspace_bytes(&d, v.volumes) : mvhmr_unproject_backward_cuboid_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence)
             return det ? mvhmr_unproject_backward_cuboid_deterministic_confidence_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_confidence_workspace_bytes(&d);
         if (v.visible)
@@ -304,6 +337,9 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.index)
+            return (det ? mvhmr_unproject_backward_cuboid_deterministic_shared : mvhmr_unproject_backward_cuboid_shared)(
+                &d, grad_out, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, grad, ws, n, s);
         if (v.confidence)
             return (det ? mvhmr_unproject_backward_cuboid_deterministic_confidence : mvhmr_unproject_backward_cuboid_confidence)(
                 &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.confidence, v.visible, grad, ws, n, s);
@@ -321,6 +357,7 @@ struct CuboidVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.index) return mvhmr_unproject_backward_geometry_cuboid_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_backward_geometry_cuboid_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_backward_geometry_cuboid_visible_workspace_bytes(&d);
         if (v.weights) return mvhmr_unproject_backward_geometry_cuboid_weighted_workspace_bytes(&d);
@@ -331,6 +368,8 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.index)
+            return mvhmr_unproject_backward_geometry_cuboid_shared(&d, grad_out, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, g[0], g[1], g[2], ws, n, s);
         if (v.confidence)
             return mvhmr_unproject_backward_geometry_cuboid_confidence(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.confidence,
                                                                        v.visible, g[0], g[1], g[2], grad_confidence, ws, n, s);
@@ -349,12 +388,13 @@ struct CuboidVolume {
 // ---- one body per kind of call.  features: the tensor the library reads (planar, channels-last or the quad-planar byte buffer)
 template <typename Volume>
 at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a, const c10::optional<at::Tensor> &view_mask,
-                   const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence)
+                   const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence,
+                   const c10::optional<at::Tensor> &feature_index)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
-    vol.check(d, features, proj, nullptr);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence);
-    at::Tensor out = at::empty({a.B, a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
+    vol.check(d, features, proj, nullptr, a.M);
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index);
+    at::Tensor out = at::empty({a.M, a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
     run(features, vol.forward_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
         return vol.forward(d, features.data_ptr(), proj.data_ptr<float>(), views, out.data_ptr(), ws, n, s);
     });
@@ -365,11 +405,11 @@ at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tens
 template <typename Volume>
 at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
                     const c10::optional<at::Tensor> &view_mask, bool deterministic, const c10::optional<at::Tensor> &view_weights, bool visible_only,
-                    const c10::optional<at::Tensor> &view_confidence)
+                    const c10::optional<at::Tensor> &view_confidence, const c10::optional<at::Tensor> &feature_index)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
-    vol.check(d, features, proj, &grad_out);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence);
+    vol.check(d, features, proj, &grad_out, a.M);
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index);
     at::Tensor grad = new_feature_grad(d, features);
     run(features, vol.backward_bytes(d, views, deterministic), deterministic, [&](void *ws, size_t n, hipStream_t s) {
         return vol.backward(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, deterministic, grad.data_ptr(), ws, n, s);
@@ -383,14 +423,15 @@ template <typename Volume>
 std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
                                           std::initializer_list<bool> want, const c10::optional<at::Tensor> &view_mask,
                                           const c10::optional<at::Tensor> &view_weights, const c10::optional<at::Tensor> &grad_weights, bool visible_only,
-                                          const c10::optional<at::Tensor> &view_confidence, const c10::optional<at::Tensor> &grad_confidence)
+                                          const c10::optional<at::Tensor> &view_confidence, const c10::optional<at::Tensor> &grad_confidence,
+                                          const c10::optional<at::Tensor> &feature_index)
 {
     const bool want_weights = grad_weights && grad_weights->defined();
     const bool want_conf = grad_confidence && grad_confidence->defined();
     TORCH_CHECK(want_weights || want_conf || std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
     const mvhmr_unproject_desc d = vol.desc(a);
-    vol.check(d, features, proj, &grad_out);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence);
+    vol.check(d, features, proj, &grad_out, a.M);
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index);
     TORCH_CHECK(!want_weights || views.weights, "mvhmr_unproject: grad_weights needs view_weights");
     TORCH_CHECK(!want_conf || views.confidence, "mvhmr_unproject: grad_confidence needs view_confidence");
     float *gw = const_cast<float *>(weights_ptr(d, features, grad_weights, "grad_weights (B, V)"));
@@ -447,19 +488,20 @@ at::Tensor view_visibility_cuboid_native(const at::Tensor &proj, const at::Tenso
 
 at::Tensor unprojection_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C,
                                int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
-                               const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence)
+                               const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence,
+                               const OptTensor &feature_index)
 {
-    return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, view_weights,
-                   visible_only, view_confidence);
+    return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask, view_weights,
+                   visible_only, view_confidence, feature_index);
 }
 
 at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
                                         int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
                                         int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask, bool deterministic,
-                                        const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence)
+                                        const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence, const OptTensor &feature_index)
 {
-    return backward(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask,
-                    deterministic, view_weights, visible_only, view_confidence);
+    return backward(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask,
+                    deterministic, view_weights, visible_only, view_confidence, feature_index);
 }
 
 std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
@@ -467,30 +509,33 @@ std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const a
                                                                           int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout,
                                                                           int64_t variant, bool want_proj, bool want_coords, const OptTensor &view_mask,
                                                                           const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only,
-                                                                          const OptTensor &view_confidence, const OptTensor &grad_confidence)
+                                                                          const OptTensor &view_confidence, const OptTensor &grad_confidence,
+                                                                          const OptTensor &feature_index)
 {
-    const auto g = backward_geometry(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
-                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights, visible_only, view_confidence, grad_confidence);
+    const auto g = backward_geometry(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)},
+                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index);
     return {g[0], g[1]};
 }
 
 at::Tensor unprojection_cuboid_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot, const at::Tensor &center,
                                       at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C,
                                       int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
-                                      const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence)
+                                      const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence,
+                                      const OptTensor &feature_index)
 {
-    return forward(CuboidVolume{rot, center, position, sides, vol}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant},
-                   view_mask, view_weights, visible_only, view_confidence);
+    return forward(CuboidVolume{rot, center, position, sides, vol}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)},
+                   view_mask, view_weights, visible_only, view_confidence, feature_index);
 }
 
 at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
                                                const at::Tensor &center, at::ArrayRef<double> position, at::ArrayRef<double> sides,
                                                at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
                                                int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask,
-                                               bool deterministic, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence)
+                                               bool deterministic, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence,
+                                               const OptTensor &feature_index)
 {
     return backward(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
-                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, view_mask, deterministic, view_weights, visible_only, view_confidence);
+                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask, deterministic, view_weights, visible_only, view_confidence, feature_index);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geometry_native(
@@ -498,11 +543,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geom
     at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
     int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center,
     const OptTensor &view_mask, const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only, const OptTensor &view_confidence,
-    const OptTensor &grad_confidence)
+    const OptTensor &grad_confidence, const OptTensor &feature_index)
 {
     const auto g = backward_geometry(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
-                                     DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant}, {want_proj, want_rot, want_center}, view_mask,
-                                     view_weights, grad_weights, visible_only, view_confidence, grad_confidence);
+                                     DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, {want_proj, want_rot, want_center}, view_mask,
+                                     view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index);
     return {g[0], g[1], g[2]};
 }
 
@@ -572,18 +617,19 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(c
 #define MVHMR_VISIBLE_ARG ", bool visible_only=False"
 #define MVHMR_CONF_ARG ", Tensor? view_confidence=None"
 #define MVHMR_GRAD_CONF_ARG ", Tensor(b!)? grad_confidence=None"
+#define MVHMR_INDEX_ARG ", Tensor? feature_index=None"
 
 TORCH_LIBRARY(mvhmr_native, m)
 {
-    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG ") -> Tensor");
+    m.def("unprojection(Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_INDEX_ARG ") -> Tensor");
     m.def("unprojection_backward(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS MVHMR_MASK_ARG
-          ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG ") -> Tensor");
+          ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_INDEX_ARG ") -> Tensor");
     m.def("unprojection_backward_geometry(Tensor grad_out, Tensor features, Tensor proj, Tensor coords, " MVHMR_DESC_ARGS
-          ", bool want_proj, bool want_coords" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_GRAD_CONF_ARG ") -> (Tensor, Tensor)");
-    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG ") -> Tensor");
-    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG ") -> Tensor");
+          ", bool want_proj, bool want_coords" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_GRAD_CONF_ARG MVHMR_INDEX_ARG ") -> (Tensor, Tensor)");
+    m.def("unprojection_cuboid(Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_INDEX_ARG ") -> Tensor");
+    m.def("unprojection_cuboid_backward(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS MVHMR_MASK_ARG ", bool deterministic=False" MVHMR_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_INDEX_ARG ") -> Tensor");
     m.def("unprojection_cuboid_backward_geometry(Tensor grad_out, Tensor features, " MVHMR_CUBOID_ARGS
-          ", bool want_proj, bool want_rot, bool want_center" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_GRAD_CONF_ARG ") -> (Tensor, Tensor, Tensor)");
+          ", bool want_proj, bool want_rot, bool want_center" MVHMR_MASK_ARG MVHMR_WEIGHTS_ARG MVHMR_GRAD_WEIGHTS_ARG MVHMR_VISIBLE_ARG MVHMR_CONF_ARG MVHMR_GRAD_CONF_ARG MVHMR_INDEX_ARG ") -> (Tensor, Tensor, Tensor)");
     m.def("triangulate_dlt(Tensor proj, Tensor points, Tensor? confidences) -> Tensor");
     m.def("triangulate_dlt_backward(Tensor grad_out, Tensor proj, Tensor points, Tensor? confidences) -> (Tensor, Tensor, Tensor)");
     m.def("abi_version() -> int");

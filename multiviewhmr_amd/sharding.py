@@ -29,14 +29,26 @@ def shard_batch(features, proj_matricies, coord_volumes, world_size=None, rank=N
 
 def shard_batch_dict(batch, world_size=None, rank=None):
     """Slice the reference's `batch` dict (data/data_utils.py:25-27): images (B,V,H,W,3), cameras[v][b], keypoints_3d[b], and the optional
-    view_mask (B,V), view_weights (B,V) and view_confidence (B,V,Hf,Wf)."""
+    view_mask (B,V), view_weights (B,V) and view_confidence (B,V,Hf,Wf).  With an optional feature_index (M,) (shared feature maps) the
+    volumes follow their samples: see below; without one nothing changes."""
     world_size = dist.get_world_size() if world_size is None else world_size
     rank = dist.get_rank() if rank is None else rank
-    lo, hi = shard_bounds(len(batch['keypoints_3d']), world_size, rank)
+    index = batch.get('feature_index')
+    # with a feature_index (M,) the volumes, not the samples, own keypoints_3d: the sample count comes from the images
+    lo, hi = shard_bounds(len(batch['keypoints_3d']) if index is None else batch['images'].shape[0], world_size, rank)
     out = dict(batch)
     out['images'] = batch['images'][lo:hi]
     out['cameras'] = [row[lo:hi] for row in batch['cameras']]
-    out['keypoints_3d'] = batch['keypoints_3d'][lo:hi]
+    if index is None:
+        out['keypoints_3d'] = batch['keypoints_3d'][lo:hi]
+    else:
+        # shared feature maps (DESIGN.md 5.12): the rank keeps the volumes whose sample it owns, in their order, their index rebased by -lo
+        # and their keypoints_3d selected by the same volumes (none: M = 0)
+        index = torch.as_tensor(index)
+        keep = torch.nonzero((index >= lo) & (index < hi)).flatten()
+        out['feature_index'] = index[keep] - lo
+        kp = batch['keypoints_3d']
+        out['keypoints_3d'] = kp[keep.to(kp.device)] if torch.is_tensor(kp) else [kp[int(m)] for m in keep]
     if batch.get('view_mask') is not None:             # per-sample view mask (B, V): sliced with its samples
         out['view_mask'] = batch['view_mask'][lo:hi]
     if batch.get('view_weights') is not None:          # per-view confidence weights (B, V): likewise
