@@ -55,7 +55,7 @@ __device__ __attribute__((noinline)) void fwd_groups_slow(const float4 *fk, TO *
             float r;
             if constexpr (METHOD == AGG_MEAN) r = __fdiv_rn(aggregate<AGG_SUM, VT>(s[i]), (float)nv);
             else r = aggregate<METHOD, VT>(s[i]);
-            (oq + i * N)[vox] = from_f32<TO>(r);
+            (oq + i * N)[vox] = from_f32<TO>(__fadd_rn(r, 0.f));                 // + 0.f: as in fwd_global_voxel (clamped taps of zero weight)
         }
     }
 }

@@ -244,7 +244,9 @@ __device__ __attribute__((noinline)) void fwd_global_voxel(const float4 *fk, TO 
             float r;
             if constexpr (METHOD == AGG_MEAN) r = __fdiv_rn(aggregate<AGG_SUM, VT>(s[i]), (float)nv);
             else r = aggregate<METHOD, VT>(s[i]);
-            if (q * 4 + i < C) (oq + i * N)[vox] = from_f32<TO>(r);
+            // + 0.f: a voxel all of whose taps lie outside every map sums 0 * (clamped border pixel) terms, which is -0.0 where those pixels
+            // are negative; the reference (and the LDS path, whose outside taps read the zero slots) gives +0.0 there
+            if (q * 4 + i < C) (oq + i * N)[vox] = from_f32<TO>(__fadd_rn(r, 0.f));
         }
     }
 }
@@ -667,7 +669,7 @@ k_fwd_brick(const float4 *__restrict__ featK, const float *__restrict__ proj, co
                         float r;
                         if constexpr (METHOD == AGG_MEAN) r = __fdiv_rn(aggregate<AGG_SUM, VT>(s[i]), mean_fix);
                         else r = aggregate<METHOD, VT>(s[i]);
-                        (oq + i * N)[vox[u]] = from_f32<TO>(r);
+                        (oq + i * N)[vox[u]] = from_f32<TO>(__fadd_rn(r, 0.f));   // + 0.f: as in fwd_global_voxel (clamped taps of zero weight)
                     }
                 }
             }
