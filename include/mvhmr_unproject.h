@@ -545,6 +545,60 @@ int mvhmr_unproject_backward_geometry_cuboid_shared(const mvhmr_unproject_desc *
         float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
+ * Lens distortion (additive within ABI 4): the voxels are projected THROUGH a Brown-Conrady lens model, so the features may
+ * come from raw, un-rectified images.  lens is (B,V,10) fp32 on the device, one record per (sample, view):
+ *     fx, fy, cx, cy          the intrinsics that went into proj[b,v] (feature level; skew is taken as zero)
+ *     k1, k2, p1, p2, k3      the distortion coefficients in OpenCV's order (the model of projectPoints, factors of two included)
+ *     r2max                   the fold-back guard
+ * With u = a / z, v = b / z the pin-hole pixel position of a voxel, every operation one separately rounded fp32 operation in this order:
+ *     xn = (u - cx) / fx   yn = (v - cy) / fy   xx = xn*xn   yy = yn*yn   xy = xn*yn   r2 = xx + yy
+ *     !(r2 <= r2max): the view gives this voxel an exactly zero sample, as z <= 0 does (nothing read, zero gradients; NaN compares false)
+ *     rad = 1 + r2*(k1 + r2*(k2 + r2*k3))
+ *     xd = (xn*rad + (2*p1)*xy) + p2*(r2 + 2*xx)          yd = (yn*rad + p1*(r2 + 2*yy)) + (2*p2)*xy
+ *     u' = fx*xd + cx      v' = fy*yd + cy
+ * and u', v' take the place of u, v in everything that follows (grid normalisation, border tests, taps, weights).  A view whose five
+ * coefficients are all +0.0 or -0.0 takes the plain path: its samples and gradients are bit-equal to the plain MVHMR_VARIANT_GATHER call
+ * whatever its intrinsics say.  The gradients w.r.t. features, proj and coords / rot / center go through the lens (the geometry backward
+ * multiplies by the 2x2 Jacobian of the step); the lens itself is not differentiated.
+ * Routing: the gather kernels (MVHMR_VARIANT_AUTO runs them), planar or channels-last features, every storage mode of the plain gather
+ * call; the feature backward takes the plane route wherever the plain MVHMR_VARIANT_GATHER call does.  MVHMR_VARIANT_BRICK and the
+ * quad-planar layouts -> MVHMR_ERR_UNSUPPORTED ("lens distortion runs the gather kernels").  A null lens is the plain call with
+ * MVHMR_VARIANT_GATHER.  view_mask, view_weights, view_confidence, visible and feature_index are the selections of the families above; they
+ * do not compose with the lens yet: each must be null / 0, else MVHMR_ERR_UNSUPPORTED with its own text.
+ * Workspace: no region is added; each *_lens_workspace_bytes total is the plain MVHMR_VARIANT_GATHER call's and covers the plain call's.
+ */
+size_t mvhmr_unproject_forward_lens_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_forward_cuboid_lens_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_lens_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_lens_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_deterministic_lens_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_deterministic_lens_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_lens_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_cuboid_lens_workspace_bytes(const mvhmr_unproject_desc *desc);
+int mvhmr_unproject_forward_lens(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+        const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,        void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_forward_cuboid_lens(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center,
+        const double position[3], const double sides[3],
+        const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,        void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,        void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot,
+        const float *center, const double position[3], const double sides[3],
+        const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,        void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_deterministic_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords,
+        const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,        void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_deterministic_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3],
+        const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,        void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords,
+        const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,        float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_cuboid_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3],
+        const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,        float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream);
+
+/*
  * Layout pass on its own: features (B,V,C,Hf,Wf) -> dst in `dst_layout` (MVHMR_LAYOUT_BVHWC with the channel
  * count rounded up to a multiple of 4 and zero padded, or MVHMR_LAYOUT_QUAD), desc->feat_dtype.
  * desc->feat_layout names the SOURCE: MVHMR_LAYOUT_BVCHW (also assumed for MVHMR_LAYOUT_QUAD descriptors, as before), or

@@ -31,8 +31,8 @@ EXPORTS = (
     "mvhmr_unproject_backward_cuboid_deterministic", "mvhmr_conv1x1_wgrad_deterministic_workspace_bytes", "mvhmr_conv1x1_wgrad_deterministic",
 ) + tuple("mvhmr_unproject_%s_%s%s" % (n, tag, w) for n in ("forward", "forward_cuboid", "backward", "backward_cuboid", "backward_deterministic",
                                                            "backward_cuboid_deterministic", "backward_geometry", "backward_geometry_cuboid")
-          for w in ("", "_workspace_bytes")       # per-sample view masks, per-view confidence weights, visibility-aware aggregation, per-pixel confidence maps, shared feature maps
-          for tag in ("masked", "weighted", "visible", "confidence", "shared")) + ("mvhmr_unproject_visibility", "mvhmr_unproject_visibility_cuboid")
+          for w in ("", "_workspace_bytes")       # per-sample view masks, per-view confidence weights, visibility-aware aggregation, per-pixel confidence maps, shared feature maps, lens distortion
+          for tag in ("masked", "weighted", "visible", "confidence", "shared", "lens")) + ("mvhmr_unproject_visibility", "mvhmr_unproject_visibility_cuboid")
 
 
 class Desc(ctypes.Structure):
@@ -179,6 +179,18 @@ def lib():
             q = getattr(L, "mvhmr_unproject_%s_shared_workspace_bytes" % name)
             q.restype = sz
             q.argtypes = [dp, i32]
+    # the *_lens family: the plain signatures with lens and the (refused) selections view_mask, view_weights, view_confidence, visible,
+    # feature_index behind what places the volume
+    for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
+        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
+                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
+                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 3 if vol else 2)):
+            fn = getattr(L, "mvhmr_unproject_%s_lens" % name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = lead + place + [vp, vp, vp, vp, ctypes.c_int, vp] + [vp] * outs + [vp, sz, vp]
+            q = getattr(L, "mvhmr_unproject_%s_lens_workspace_bytes" % name)
+            q.restype = sz
+            q.argtypes = [dp]
     if L.mvhmr_abi_version() != ABI_VERSION:
         raise RuntimeError("libmvhmr_unproject.so speaks ABI %d, this binding %d: rebuild" %
                            (L.mvhmr_abi_version(), ABI_VERSION))

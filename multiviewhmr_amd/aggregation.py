@@ -161,7 +161,10 @@ def _op_defined(name):
 # backward differentiates w.r.t. them as well; their *_visible twins add the seeing test.  Their view_mask is `Tensor?`: None is the null
 # mask of the C entry points, with which nothing is packed or copied.  The shared families (mvhmr_unproject_*_shared) take
 # feature_index (M,) int32 on the features' device behind the placing tensors, which then hold M entries: volume m reads sample
-# feature_index[m]; the forward returns M volumes, the feature gradient has B samples; the index is not differentiable.
+# feature_index[m]; the forward returns M volumes, the feature gradient has B samples; the index is not differentiable.  The lens families
+# (mvhmr_unproject_*_lens) take lens (B, V, 10) fp32 on the features' device behind the placing tensors: the voxels are
+# projected through the records; features are read as the plain families read them (the feature backward takes the plane route wherever the
+# plain gather call does); the lens is not differentiable.
 _CUBOID_ARGS = ("float[] position", "float[] sides", "int[] vol")
 _FAMILIES = {
     "unprojection": (("coords",), (), False),
@@ -178,18 +181,21 @@ _FAMILIES = {
     "unprojection_cuboid_confidence_visible": (("rot", "center"), _CUBOID_ARGS, True, False, True, True),
     "unprojection_shared": (("coords",), (), False, False, False, False, True),
     "unprojection_cuboid_shared": (("rot", "center"), _CUBOID_ARGS, False, False, False, False, True),
+    "unprojection_lens": (("coords",), (), False, False, False, False, False, True),
+    "unprojection_cuboid_lens": (("rot", "center"), _CUBOID_ARGS, False, False, False, False, False, True),
 }
 
 
 class _Family:
     """the implementations of one family's ops, each taking the ops' arguments positionally"""
 
-    def __init__(self, name, places, extras, masked, weighted=False, visible=False, confidence=False, shared=False):
+    def __init__(self, name, places, extras, masked, weighted=False, visible=False, confidence=False, shared=False, lens=False):
         self.name, self.masked, self.weighted, self.visible, self.confidence, self.shared = name, masked, weighted, visible, confidence, shared
+        self.lens = lens
         self.native = "unprojection_cuboid" if extras else "unprojection"       # the extension's op: view_mask / view_weights are trailing arguments there
         self.geo = ("proj",) + places                                           # the geometry tensors, behind features
         self.tensors = (("features",) + self.geo + (("view_mask",) if masked else ()) + (("view_weights",) if weighted else ())
-                        + (("view_confidence",) if confidence else ()) + (("feature_index",) if shared else ()))
+                        + (("view_confidence",) if confidence else ()) + (("feature_index",) if shared else ()) + (("lens",) if lens else ()))
         self.grads = self.geo + (("view_weights",) if weighted else ()) + (("view_confidence",) if confidence else ())   # what the geometry backward differentiates
         self.extras = extras
         self.n_inputs = len(self.tensors) + len(extras) + 3
@@ -212,6 +218,10 @@ class _Family:
         """a shared family's feature_index (behind the geometry tensors), else None"""
         return args[1 + len(self.geo)] if self.shared else None
 
+    def lens_of(self, args):
+        """a lens family's records (behind the geometry tensors), else None"""
+        return args[1 + len(self.geo)] if self.lens else None
+
     def volume(self, geo, extra):
         return tuple(extra[2]) if extra else tuple(geo[1].shape[1:4])
 
@@ -227,12 +237,12 @@ class _Family:
 
     def forward(self, *args):
         lead, (mask, weights, conf) = self.native_args(args)
-        return getattr(_native(), self.native)(*lead, mask, weights, self.visible, conf, self.index(args))
+        return getattr(_native(), self.native)(*lead, mask, weights, self.visible, conf, self.index(args), self.lens_of(args))
 
     def backward(self, deterministic, grad_out, *args):
         """gradient w.r.t. features (the geometry's is backward_geometry)"""
         lead, (mask, weights, conf) = self.native_args(args)
-        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible, conf, self.index(args))
+        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible, conf, self.index(args), self.lens_of(args))
 
     def backward_geometry(self, grad_out, *args):
         """planar features go through the library's channels-last pass, channels-last ones are read as they are; the gradient w.r.t.
@@ -248,7 +258,7 @@ class _Family:
                 return tuple(conf.new_empty((0,)) for _ in self.geo) + (gc,)
             return tuple(op(grad_out.contiguous(), *lead, *want[:-1], *tail)) + (gc,)
         if not self.weighted:
-            return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, self.visible, None, None, self.index(args)))
+            return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, self.visible, None, None, self.index(args), self.lens_of(args)))
         gw = weights.new_empty(weights.shape if want[-1] else (0,))
         if not any(want[:-1]):                             # the weights' gradient alone: the extension's outputs stay empty
             op(grad_out.contiguous(), *lead, *want[:-1], mask, weights, gw)
@@ -340,7 +350,7 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
 
 
 def unprojection(features, proj_matricies, coord_volumes, aggregation_method='softmax', *, out_dtype=None,
-                 variant='auto', view_mask=None, view_weights=None, visible_only=False, view_confidence=None, feature_index=None):
+                 variant='auto', view_mask=None, view_weights=None, visible_only=False, view_confidence=None, feature_index=None, lens=None):
     """Fused project -> bilinear-sample -> cross-view aggregate (reference: models/aggregation.py:20-87).
 
     features        (B, V, C, Hf, Wf) float32 (or float16, this package's storage mode) on a HIP device;
@@ -382,6 +392,15 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
                     not inspected -- no synchronisation, graph-capturable -- and an entry outside [0, B) gives a zero volume that contributes
                     to no gradient.  M > 65535 raises ValueError, M = 0 gives an empty result.  With view_mask, view_weights, visible_only or
                     view_confidence it raises ValueError (not built yet).  Runs the gather kernels ('brick' is refused); DESIGN.md 5.12.
+    lens            (B, V, 10) floating tensor, any device (keyword-only; None = pin-hole cameras): per (sample, view) the record
+                    (fx, fy, cx, cy, k1, k2, p1, p2, k3, r2max) -- the intrinsics that went into proj_matricies[b, v] (feature level, zero
+                    skew), the Brown-Conrady coefficients in OpenCV's order and the fold-back guard; `feature_level_lens` builds it from the
+                    cameras.  The voxels are projected THROUGH the lens (OpenCV's projectPoints model, each step one rounded fp32 operation),
+                    so `features` may come from raw, un-rectified images.  A ray with r2 > r2max gives an exactly zero sample, as one behind
+                    the camera does; a view whose five coefficients are zero is bit-equal to the plain variant='gather' call.  Differentiable
+                    w.r.t. features, proj_matricies and coord_volumes through the lens; the lens itself is not (requires_grad raises
+                    ValueError).  With view_mask, view_weights, visible_only, view_confidence or feature_index it raises ValueError (not built
+                    yet).  Runs the gather kernels ('auto' too; 'brick' is refused); DESIGN.md 5.13.
     """
     def volume_shape(B):
         n = B if feature_index is None else feature_index.shape[0]
@@ -389,6 +408,8 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
             raise RuntimeError("unprojection: coord_volumes must be (%d, X, Y, Z, 3), got %s" % (n, tuple(coord_volumes.shape)))
         return tuple(coord_volumes.shape[1:4])
 
+    if lens is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_lens(lens, features, view_mask, view_weights, visible_only, view_confidence, feature_index)
     if feature_index is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_feature_index(feature_index, features, view_mask, view_weights, visible_only, view_confidence)
 
@@ -408,6 +429,9 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
     # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
     proj = proj_matricies.to(torch.float32).contiguous()
     coords = coord_volumes.to(torch.float32).contiguous()
+    if lens is not None:
+        return torch.ops.mvhmr.unprojection_lens(features, proj, coords, _lens_fp32(lens, features), _capi.AGG[aggregation_method],
+                                                 _dtype_code(out_dtype), _lens_variant(variant))
     if feature_index is not None:
         return torch.ops.mvhmr.unprojection_shared(features, proj, coords, _index_int32(feature_index, features), _capi.AGG[aggregation_method],
                                                    _dtype_code(out_dtype), _capi.VARIANT[variant])
@@ -436,6 +460,33 @@ def _check_view_mask(view_mask, features):
         raise TypeError("unprojection: view_mask must be bool or an integer dtype, got %s" % view_mask.dtype)
     if tuple(view_mask.shape) != tuple(features.shape[:2]):
         raise RuntimeError("unprojection: view_mask must be %s, got %s" % (tuple(features.shape[:2]), tuple(view_mask.shape)))
+
+
+def _check_lens(lens, features, view_mask=None, view_weights=None, visible_only=False, view_confidence=None, feature_index=None):
+    """lens (B, V, 10) of a floating dtype, any device: raises TypeError / RuntimeError as _check_view_weights does, ValueError when it requires
+    grad and beside a view selection or a feature_index"""
+    if not torch.is_tensor(lens):
+        raise TypeError("unprojection: lens must be a (B, V, 10) floating tensor, got %s" % type(lens).__name__)
+    if not lens.dtype.is_floating_point:
+        raise TypeError("unprojection: lens must be a floating dtype, got %s" % lens.dtype)
+    if tuple(lens.shape) != tuple(features.shape[:2]) + (10,):
+        raise RuntimeError("unprojection: lens must be (B, V, 10) = %s, got %s" % (tuple(features.shape[:2]) + (10,), tuple(lens.shape)))
+    if lens.requires_grad:
+        raise ValueError("unprojection: lens is not differentiable in this version (DESIGN.md 5.13): pass lens.detach()")
+    for given, what in ((view_mask is not None, "view_mask"), (view_weights is not None, "view_weights"), (bool(visible_only), "visible_only=True"),
+                        (view_confidence is not None, "view_confidence"), (feature_index is not None, "feature_index")):
+        if given:
+            raise ValueError("unprojection: lens with %s is not built yet (the next step of DESIGN.md 5.13)" % what)
+
+
+def _lens_fp32(lens, features):
+    """the checked records as the library reads them: contiguous fp32 on features.device (a device tensor is cast there: no synchronisation)"""
+    return lens.to(device=features.device, dtype=torch.float32).contiguous()
+
+
+def _lens_variant(variant):
+    """a lens call runs the gather family: 'auto' is 'gather' ('brick' reaches the library, which refuses it)"""
+    return _capi.VARIANT["gather" if variant == "auto" else variant]
 
 
 _MAX_VOLUMES = 65535                                    # the *_shared entry points: the volume index is the grid's y extent (mvhmr_unproject.h)
@@ -571,14 +622,14 @@ _register_dlt_op()
 
 def unprojection_cuboid(features, proj_matricies, rotations, centers, position, sides, volume_shape,
                         aggregation_method='softmax', *, out_dtype=None, variant='auto', view_mask=None, view_weights=None, visible_only=False,
-                        view_confidence=None, feature_index=None):
+                        view_confidence=None, feature_index=None, lens=None):
     """`unprojection` for the volumes VolumeGenerator builds (aggregation.py:138-187), without the coordinate tensor: voxel centres
     are rot[b] @ (position + sides / (S - 1) * (i,j,k) - center[b]) + center[b], evaluated inside the kernels (bit-equal to
     mvhmr_build_coord_volumes followed by `unprojection`).
 
     rotations (B,3,3) and centers (B,3): float32 tensors on features.device; position, sides: 3 numbers each (cuboid corner and
     edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers (and view_weights).
-    view_mask, view_weights, visible_only, view_confidence, feature_index: as for `unprojection`; with feature_index (M,) rotations are
+    view_mask, view_weights, visible_only, view_confidence, feature_index, lens: as for `unprojection`; with feature_index (M,) rotations are
     (M,3,3) and centers (M,3) -- one pose per volume, position / sides / volume_shape shared -- and their gradients are per volume."""
     def checked_shape(B):
         n = B if feature_index is None else feature_index.shape[0]
@@ -587,6 +638,8 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
                                % (n, n, tuple(rotations.shape), tuple(centers.shape)))
         return tuple(int(v) for v in volume_shape)
 
+    if lens is not None and torch.is_tensor(features) and features.dim() == 5:
+        _check_lens(lens, features, view_mask, view_weights, visible_only, view_confidence, feature_index)
     if feature_index is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_feature_index(feature_index, features, view_mask, view_weights, visible_only, view_confidence)
 
@@ -608,6 +661,10 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     proj = proj_matricies.to(device=dev, dtype=torch.float32).contiguous()
     rot = rotations.to(device=dev, dtype=torch.float32).contiguous()
     cen = centers.to(device=dev, dtype=torch.float32).contiguous()
+    if lens is not None:
+        return torch.ops.mvhmr.unprojection_cuboid_lens(features, proj, rot, cen, _lens_fp32(lens, features), [float(x) for x in position],
+                                                        [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method], _dtype_code(out_dtype),
+                                                        _lens_variant(variant))
     if feature_index is not None:
         return torch.ops.mvhmr.unprojection_cuboid_shared(features, proj, rot, cen, _index_int32(feature_index, features), [float(x) for x in position],
                                                           [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method], _dtype_code(out_dtype),
@@ -711,6 +768,56 @@ def feature_level_projections(cameras, images_shape, features_shape):
     P = P + K[..., :, 1:2] * Rt[..., 1:2, :]
     P = P + K[..., :, 2:3] * Rt[..., 2:3, :]
     return P.astype(np.float32)
+
+
+def lens_r2max(k1, k2, k3):
+    """The fold-back guard of a Brown-Conrady lens: the smallest positive root rho of 1 + 3 k1 rho + 5 k2 rho^2 + 7 k3 rho^3, i.e. of
+    d(r rad(r^2)) / dr = 0 with rho = r^2 -- beyond it the radial map is no longer monotonic and far rays fold back into the frame.
+    float64 numpy.roots, returned as float32 (rounded towards zero, so the guard never lets a folded ray through); FLT_MAX when there is no
+    positive real root."""
+    flt_max = float(np.finfo(np.float32).max)
+    coeffs = [7.0 * float(k3), 5.0 * float(k2), 3.0 * float(k1), 1.0]
+    while len(coeffs) > 1 and coeffs[0] == 0.0:
+        coeffs = coeffs[1:]
+    if len(coeffs) == 1:
+        return np.float32(flt_max)
+    roots = np.roots(np.array(coeffs, dtype=np.float64))
+    real = [float(r.real) for r in roots if abs(r.imag) <= 1e-12 * max(1.0, abs(r.real)) and r.real > 0]
+    if not real or min(real) >= flt_max:
+        return np.float32(flt_max)
+    rho = np.float32(min(real))
+    return rho if float(rho) <= min(real) else np.nextafter(rho, np.float32(0))
+
+
+def feature_level_lens(cameras, images_shape, features_shape):
+    """(B, V, 10) float32 numpy: the lens records `unprojection(lens=)` reads, for the cameras `feature_level_projections` reads.
+
+    Per camera (fx, fy, cx, cy, k1, k2, p1, p2, k3, r2max): the intrinsics are K after the same float64 scaling feature_level_projections
+    applies (update_after_resize, quirk Q3 included), so they are the ones inside the projection matrix by construction; the coefficients
+    are the camera's `dist` (OpenCV order; None = zeros: a pin-hole view, which takes the plain path); r2max = lens_r2max(k1, k2, k3).
+    A camera with skew (K[0, 1] != 0) raises ValueError: the lens step takes the skew as zero."""
+    height, width = images_shape
+    new_width, new_height = features_shape
+    sx, sy = new_width / width, new_height / height
+    V, B = len(cameras), len(cameras[0])
+    out = np.zeros((B, V, 10), dtype=np.float32)
+    for b in range(B):
+        for v in range(V):
+            cam = cameras[v][b]
+            K = np.array(cam.K, dtype=np.float64)
+            if K[0, 1] != 0.0:
+                raise ValueError("feature_level_lens: camera (view %d, sample %d) has skew %r; the lens step takes the skew as zero" % (v, b, K[0, 1]))
+            dist = getattr(cam, "dist", None)
+            d = np.zeros(5, dtype=np.float64)
+            if dist is not None:
+                flat = np.asarray(dist, dtype=np.float64).flatten()
+                if flat.size not in (4, 5):
+                    raise ValueError("feature_level_lens: dist must hold 4 or 5 coefficients (k1, k2, p1, p2[, k3]), got %d" % flat.size)
+                d[:flat.size] = flat
+            out[b, v, :4] = (K[0, 0] * sx, K[1, 1] * sy, K[0, 2] * sx, K[1, 2] * sy)      # float64 products, one rounding to float32
+            out[b, v, 4:9] = d
+            out[b, v, 9] = lens_r2max(*out[b, v, [4, 5, 8]])                                # of the coefficients as the kernels read them
+    return out
 
 
 class _FusedAggregate(torch.autograd.Function):
@@ -839,11 +946,17 @@ def feature_level_projections_device(packed, images_shape, features_shape):
 
 
 class VolumeGenerator(nn.Module):
-    """1x1 conv on the per-view feature maps + un-projection into a voxel volume (aggregation.py:90-195)."""
+    """1x1 conv on the per-view feature maps + un-projection into a voxel volume (aggregation.py:90-195).
+
+    lens_distortion (extension, default False; cfg key MODEL.AGGREGATION.LENS_DISTORTION): un-project THROUGH the cameras' lens distortion
+    (DESIGN.md 5.13), so that the backbone may run on raw, un-rectified crops.  forward then reads batch['lens'] (B, V, 10) when given, else
+    builds it from batch['cameras'] (feature_level_lens), and runs the gather family (the fused conv route is skipped).  The
+    use_triangulation pivot is unchanged: it triangulates the image centres, which sit next to the principal points, where the lens
+    displacement is of second order in the normalised radius (radially even third), far below the cuboid's voxel pitch."""
 
     def __init__(self, volume_size=64, input_channels=256, output_channels=32, cuboid_side=2500.0,
                  aggregation_method='softmax', use_triangulation=False, kind='mpii', device='cuda',
-                 dataset='human36m', volume_dtype=None, visible_only=False, **kwargs):
+                 dataset='human36m', volume_dtype=None, visible_only=False, lens_distortion=False, **kwargs):
         # **kwargs swallows unknown keywords exactly like the reference (quirk Q5: build_volume_generator
         # passes volume_aggregation_method=, so aggregation_method keeps its default)
         super().__init__()
@@ -856,6 +969,7 @@ class VolumeGenerator(nn.Module):
         self.dataset = dataset
         self.volume_dtype = volume_dtype  # extension: None = float32 like the reference; torch.bfloat16 / float16 for a half-precision consumer
         self.visible_only = bool(visible_only)  # extension: every voxel aggregates only the views that see it
+        self.lens_distortion = bool(lens_distortion)  # extension: un-project through the cameras' lens distortion (the class docstring)
         self.fused_conv = True            # 1x1 conv + layout pass as one MFMA GEMM wherever its shapes allow (see _fused_path_applies)
         self.to(device)
 
@@ -975,7 +1089,14 @@ class VolumeGenerator(nn.Module):
         centers = centers.to(device=device, dtype=torch.float32).contiguous()
 
         _check_visible_only(self.visible_only, view_weights)
-        if view_mask is None and view_weights is None and view_confidence is None and feature_index is None and not self.visible_only and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask, weights, confidence maps or visible_only do not take)
+        lens = None
+        if self.lens_distortion:
+            lens = batch.get('lens')                                          # optional (B, V, 10): the lens records
+            if lens is None:
+                lens = torch.from_numpy(feature_level_lens(batch['cameras'], images_shape, features_shape))
+            meta = torch.empty((batch_size, n_views, 1) + features_shape, device="meta")
+            _check_lens(lens, meta, view_mask, view_weights, self.visible_only, view_confidence, feature_index)
+        if lens is None and view_mask is None and view_weights is None and view_confidence is None and feature_index is None and not self.visible_only and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask, weights, confidence maps or visible_only do not take)
             # 1x1 conv and layout pass in one MFMA GEMM, its output only ever exists in the layout the brick forward stages
             conv = self.process_feature[0]
             return _FusedAggregate.apply(features, conv.weight, conv.bias, proj, rots, centers, tuple(cub.position), tuple(cub.sides),
@@ -994,6 +1115,8 @@ class VolumeGenerator(nn.Module):
             masked["view_confidence"] = view_confidence
         if feature_index is not None:
             masked["feature_index"] = feature_index                           # -> (M, C, S, S, S)
+        if lens is not None:
+            masked["lens"] = lens                                             # (the gather family: the fused conv's quad-planar copy is not taken)
         return unprojection_cuboid(features, proj, rots, centers, cub.position, cub.sides, (S, S, S),
                                    aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **masked)
 
@@ -1034,6 +1157,14 @@ def _cfg_visible_only(cfg):
         return False
 
 
+def _cfg_lens_distortion(cfg):
+    """MODEL.AGGREGATION.LENS_DISTORTION, an extension key the reference's cfg tree does not have: absent (however the tree says so) = False"""
+    try:
+        return bool(cfg.MODEL.AGGREGATION.LENS_DISTORTION)
+    except (AttributeError, KeyError):
+        return False
+
+
 def build_volume_generator(cfg):
     """cfg is the reference's yacs tree (cfg/defaults.py:18-30,89-90); same wiring as aggregation.py:198-208."""
     input_channels = cfg.MODEL.BACKBONE.DECONV_FILTERS[-1] if cfg.MODEL.BACKBONE.DECONV_LAYERS != 0 else 2048
@@ -1045,4 +1176,5 @@ def build_volume_generator(cfg):
                            kind=cfg.DATASET.KIND,
                            dataset=cfg.DATASET.TYPE,
                            volume_aggregation_method=cfg.MODEL.AGGREGATION.METHOD,
-                           visible_only=_cfg_visible_only(cfg))
+                           visible_only=_cfg_visible_only(cfg),
+                           lens_distortion=_cfg_lens_distortion(cfg))

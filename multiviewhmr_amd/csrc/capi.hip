@@ -340,6 +340,36 @@ int shared_refused(const mvhmr_unproject_desc *desc, const SharedIndex &sh)
         return fail(MVHMR_ERR_INVALID_ARGUMENT, "a null feature_index is the plain call: volumes (%d) must equal batch (%d)", sh.volumes, desc->batch);
     return MVHMR_OK;
 }
+// ---- lens distortion (include/mvhmr_unproject.h): one Brown-Conrady record per (sample, view) through which the voxels are
+// projected.  The plain gather route with the gather variant -- forward, the plane backward wherever the plain gather call takes it (its tap
+// table is built through the records), else the per-tap scatter, both modes, and the geometry kernels -- whose launchers hand a problem with
+// Problem::lens to the *_lens kernels.  Nothing is packed or copied, no region is added.  The brick variant and the quad-planar layouts are
+// refused (a brick's window is bounded by the projective image of its corners, which does not hold under distortion); the view selections and
+// the feature index do not compose with the lens yet and are refused each with its own text.  A null lens is the plain gather call.
+struct LensArgs {
+    const float *lens;
+    const uint8_t *mask;
+    const float *weights, *confidence;
+    int visible;
+    const int32_t *index;
+};
+// the checks that need no pointer: what the workspace queries ask too
+int lens_shape_refused(const mvhmr_unproject_desc *desc)
+{
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion runs the gather kernels: it needs planar or channels-last features (quad-planar copies: pass the planar features)");
+    if (desc->variant == MVHMR_VARIANT_BRICK) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
+    return MVHMR_OK;
+}
+int lens_refused(const mvhmr_unproject_desc *desc, const LensArgs &la)
+{
+    if (la.mask) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with a view mask is not built yet: un-project the masked samples without a lens");
+    if (la.weights) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with view weights is not built yet: un-project the weighted samples without a lens");
+    if (la.visible) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with visibility-aware aggregation is not built yet: the seeing test is pin-hole");
+    if (la.confidence) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with view confidence maps is not built yet: un-project those samples without a lens");
+    if (la.index) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with a feature_index is not built yet: un-project the shared samples without a lens");
+    return lens_shape_refused(desc);
+}
 // what selects the packed route of a call, and whether the descriptor can take it
 struct Views {
     const uint8_t *mask;
@@ -357,8 +387,9 @@ int views_refused(const mvhmr_unproject_desc *desc, const Views &w)
     return w.weights ? weights_refused(desc) : MVHMR_OK;
 }
 // the kinds of plan: every view, a mask, weights (with or without a mask), the seeing views of every voxel (with or without a mask),
-// confidence maps (with or without a mask, with or without the seeing test); Shared: shared feature maps (no head: nothing is packed)
-enum class Pack { None, Masked, Weighted, Visible, Confidence, Shared };
+// confidence maps (with or without a mask, with or without the seeing test); Shared: shared feature maps (no head: nothing is packed);
+// Lens: lens distortion (no head either: the plain plan of the gather variant)
+enum class Pack { None, Masked, Weighted, Visible, Confidence, Shared, Lens };
 Pack pack_of(const Views &w)
 {
     return w.confidence ? Pack::Confidence : w.visible ? Pack::Visible : w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None;
@@ -466,7 +497,9 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pac
     Arena a;
     f.desc = *desc;
     f.p = p;
-    if (pack != Pack::None) {
+    if (pack == Pack::Lens) {
+        f.desc.variant = MVHMR_VARIANT_GATHER;
+    } else if (pack != Pack::None) {
         mask_route(&f.desc, &f.p, pack);
         if (pack != Pack::Shared) f.head = plan_mask_head(a, p, 1, pack);
     }
@@ -484,6 +517,10 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pac
         f.staged = a.take(brick_workspace_bytes(f.p));
     }
     // (a weighted call's workspace also serves the masked one, a masked call's the unmasked one)
+    if (pack == Pack::Lens) {                                                                                   // (also covers the plain call as the descriptor has it)
+        f.total = max_size(a.top, plan_forward(desc, p, Pack::None).total);
+        return f;
+    }
     f.total = pack == Pack::None ? a.top : max_size(a.top, plan_forward(desc, p, pack_below(pack)).total);
     if (pack == Pack::Confidence) f.total = max_size(f.total, plan_forward(desc, p, Pack::Visible).total);      // (a null map is the visible call)
     if (pack == Pack::Shared) {                                                                                 // (a null index is the plain gather call)
@@ -560,7 +597,9 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
     Arena a;
     b.desc = *desc;
     b.p = p;
-    if (pack != Pack::None) {
+    if (pack == Pack::Lens) {
+        b.desc.variant = MVHMR_VARIANT_GATHER;
+    } else if (pack != Pack::None) {
         mask_route(&b.desc, &b.p, pack);
         if (pack != Pack::Shared) b.head = plan_mask_head(a, p, 2, pack);
     }
@@ -572,6 +611,10 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
         a.top = max_size(a.top, da.top);
     } else {
         place_default_backward(b, a);
+    }
+    if (pack == Pack::Lens) {
+        b.total = max_size(a.top, plan_backward(desc, p, det, Pack::None).total);
+        return b;
     }
     b.total = pack == Pack::None ? a.top : max_size(a.top, plan_backward(desc, p, det, pack_below(pack)).total);
     if (pack == Pack::Confidence) b.total = max_size(b.total, plan_backward(desc, p, det, Pack::Visible).total);
@@ -603,6 +646,7 @@ GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, b
     Arena a;
     g.desc = *desc;
     g.p = p;
+    if (pack == Pack::Lens) pack = Pack::None;             // (desc->variant plays no part: the plain plan)
     if (pack != Pack::None) {
         mask_route(&g.desc, &g.p, pack);
     }
@@ -665,7 +709,7 @@ int query_variant(const mvhmr_unproject_desc *desc, const VolumeSource &v, const
 
 // ---- forward
 int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *features, const float *proj, const Views &views, void *out,
-                void *workspace, size_t workspace_bytes, void *hip_stream, const SharedIndex *shared = nullptr)
+                void *workspace, size_t workspace_bytes, void *hip_stream, const SharedIndex *shared = nullptr, const LensArgs *lens = nullptr)
 {
     Problem p0;
     Coords coords;
@@ -674,6 +718,8 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
     if (!features || !proj || !out) return fail(MVHMR_ERR_INVALID_ARGUMENT, "features / proj / out must be non-null");
     if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
     if (shared && (rc = shared_refused(desc, *shared)) != MVHMR_OK) return rc;
+    if (lens && (rc = lens_refused(desc, *lens)) != MVHMR_OK) return rc;
+    if (lens) p0.lens = lens->lens;                           // (null: the plain gather call)
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     mvhmr_unproject_desc dq;
     shared_route(shared, &dq, &desc, &p0);
@@ -688,7 +734,7 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
         desc = &dq;
         p0.feat_log2e = 1;
     }
-    ForwardPlan f = plan_forward(desc, p0, shared ? shared_pack(shared) : pack_of(views));
+    ForwardPlan f = plan_forward(desc, p0, lens ? Pack::Lens : shared ? shared_pack(shared) : pack_of(views));
     desc = &f.desc;
     Problem &p = f.p;
     rc = variant_conflict(desc, p, pick_variant(desc, p));
@@ -728,6 +774,7 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
             if (rc != MVHMR_OK) return rc;
         }
         if (p.feature_index) return launched(launch_fwd_gather_shared(staged ? staged : features, proj, coords, out, p, s), "shared gather forward");
+        if (p.lens) return launched(launch_fwd_gather_lens(staged ? staged : features, proj, coords, out, p, s), "lens gather forward");
         return launched(launch_fwd_gather(staged ? staged : features, proj, coords, out, p, s), "gather forward");
     }
     return fail(MVHMR_ERR_INVALID_ARGUMENT, "unknown forward route");
@@ -813,6 +860,7 @@ int launch_backward_default(BackwardPlan &b, const BackwardArgs &c)
         rc = clear_gradient(gradT, p, sizeof(float), s);
         if (rc != MVHMR_OK) return rc;
         rc = p.feature_index ? launched(launch_bwd_gather_shared(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "shared gather backward")
+             : p.lens        ? launched(launch_bwd_gather_lens(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "lens gather backward")
                              : launched(launch_bwd_gather(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "gather backward");
         if (rc != MVHMR_OK || !acc) return rc;
         if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_grad_to_planar(gradT, c.grad_features, p, s), "gradient layout pass");   // planar gradient for planar and quad-planar features alike
@@ -854,6 +902,7 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
         return launched(launch_det_quad_to_planar(acc, kexp, c.grad_features, p, s), "gradient layout pass");
     }
     rc = p.feature_index ? launched(launch_bwd_gather_shared_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic shared gather backward")
+         : p.lens        ? launched(launch_bwd_gather_lens_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic lens gather backward")
                          : launched(launch_bwd_gather_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic gather backward");
     if (rc != MVHMR_OK) return rc;
     if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_det_grad_to_planar(acc, kexp, c.grad_features, p, s), "gradient layout pass");
@@ -862,7 +911,7 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
 
 int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
                  const Views &views, bool det, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream,
-                 const SharedIndex *shared = nullptr)
+                 const SharedIndex *shared = nullptr, const LensArgs *lens = nullptr)
 {
     Problem p0;
     Coords coords;
@@ -872,13 +921,15 @@ int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
         return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
     if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
     if (shared && (rc = shared_refused(desc, *shared)) != MVHMR_OK) return rc;
+    if (lens && (rc = lens_refused(desc, *lens)) != MVHMR_OK) return rc;
+    if (lens) p0.lens = lens->lens;
     mvhmr_unproject_desc dq;
     shared_route(shared, &dq, &desc, &p0);
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
         return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p0) && !quad_to_channels_last_supported(p0))
         return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
-    BackwardPlan b = plan_backward(desc, p0, det, shared ? shared_pack(shared) : pack_of(views));
+    BackwardPlan b = plan_backward(desc, p0, det, lens ? Pack::Lens : shared ? shared_pack(shared) : pack_of(views));
     rc = check_ws(workspace, workspace_bytes, b.total);
     if (rc != MVHMR_OK) return rc;
     if (b.desc.variant == MVHMR_VARIANT_BRICK && !bwd_uses_brick(&b.desc, b.p))
@@ -898,7 +949,8 @@ int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
 // ---- geometry backward
 int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
                  const Views &views, float *grad_proj, float *grad_coords, float *grad_rot, float *grad_center, float *grad_weights, void *workspace,
-                 size_t workspace_bytes, void *hip_stream, float *grad_confidence = nullptr, const SharedIndex *shared = nullptr)
+                 size_t workspace_bytes, void *hip_stream, float *grad_confidence = nullptr, const SharedIndex *shared = nullptr,
+                 const LensArgs *lens = nullptr)
 {
     const bool mask = views.packed();
     Problem p0;
@@ -925,13 +977,15 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     if (!data) return fail(MVHMR_ERR_INVALID_ARGUMENT, no_data);
     if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
     if (shared && (rc = shared_refused(desc, *shared)) != MVHMR_OK) return rc;
+    if (lens && (rc = lens_refused(desc, *lens)) != MVHMR_OK) return rc;
+    if (lens) p0.lens = lens->lens;
     mvhmr_unproject_desc dq;
     shared_route(shared, &dq, &desc, &p0);
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
         return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p0))
         return fail(MVHMR_ERR_UNSUPPORTED, "quad-planar features of this shape cannot be converted to channels-last (C %% 4 == 0, C <= 4092, B * V <= 65535)");
-    GeometryPlan g = plan_geometry(desc, p0, v.cuboid, shared ? shared_pack(shared) : pack_of(views));
+    GeometryPlan g = plan_geometry(desc, p0, v.cuboid, lens ? Pack::Lens : shared ? shared_pack(shared) : pack_of(views));
     rc = check_ws(workspace, workspace_bytes, g.total);
     if (rc != MVHMR_OK) return rc;
     const Problem &p = g.p;
@@ -1037,6 +1091,26 @@ size_t shared_geometry_need(const mvhmr_unproject_desc *desc, int32_t volumes, b
     if (check_desc(desc, &p) != MVHMR_OK || shared_query_refused(desc, volumes)) return 0;
     p.volumes = volumes;
     return plan_geometry(desc, p, cuboid, Pack::Shared).total;
+}
+
+// the *_lens queries: the checks of the call that need no pointer, then the plan's total (a null lens is not known here: the total covers it)
+size_t lens_forward_need(const mvhmr_unproject_desc *desc)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || lens_shape_refused(desc) != MVHMR_OK) return 0;
+    return plan_forward(desc, p, Pack::Lens).total;
+}
+size_t lens_backward_need(const mvhmr_unproject_desc *desc, bool det)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || lens_shape_refused(desc) != MVHMR_OK) return 0;
+    return plan_backward(desc, p, det, Pack::Lens).total;
+}
+size_t lens_geometry_need(const mvhmr_unproject_desc *desc, bool cuboid)
+{
+    Problem p;
+    if (check_desc(desc, &p) != MVHMR_OK || lens_shape_refused(desc) != MVHMR_OK) return 0;
+    return plan_geometry(desc, p, cuboid, Pack::Lens).total;
 }
 
 }  // namespace
@@ -1522,6 +1596,86 @@ int mvhmr_unproject_backward_geometry_cuboid_shared(const mvhmr_unproject_desc *
     MVHMR_SHARED_INDEX;
     return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, nullptr, grad_rot,
                         grad_center, nullptr, workspace, workspace_bytes, hip_stream, nullptr, &sh);
+}
+
+// ---- lens distortion: the plain entry points with `lens` behind what places the volume, then the view selections of the other families and the
+// feature index, which do not compose with the lens yet: each must be null / 0
+size_t mvhmr_unproject_forward_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_forward_need(desc); }
+size_t mvhmr_unproject_forward_cuboid_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_forward_need(desc); }
+size_t mvhmr_unproject_backward_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_backward_need(desc, false); }
+size_t mvhmr_unproject_backward_cuboid_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_backward_need(desc, false); }
+size_t mvhmr_unproject_backward_deterministic_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_backward_need(desc, true); }
+size_t mvhmr_unproject_backward_cuboid_deterministic_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_backward_need(desc, true); }
+size_t mvhmr_unproject_backward_geometry_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_geometry_need(desc, false); }
+size_t mvhmr_unproject_backward_geometry_cuboid_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_geometry_need(desc, true); }
+
+#define MVHMR_LENS_ARGS const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index
+#define MVHMR_LENS_RECORDS const LensArgs la{lens, view_mask, view_weights, view_confidence, visible, feature_index}
+
+int mvhmr_unproject_forward_lens(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords, MVHMR_LENS_ARGS,
+        void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_LENS_RECORDS;
+    return run_forward(desc, tensor_volume(coords), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream, nullptr, &la);
+}
+
+int mvhmr_unproject_forward_cuboid_lens(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center,
+        const double position[3], const double sides[3], MVHMR_LENS_ARGS, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_LENS_RECORDS;
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream,
+                       nullptr, &la);
+}
+
+int mvhmr_unproject_backward_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        MVHMR_LENS_ARGS, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_LENS_RECORDS;
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace, workspace_bytes, hip_stream,
+                        nullptr, &la);
+}
+
+int mvhmr_unproject_backward_cuboid_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot,
+        const float *center, const double position[3], const double sides[3], MVHMR_LENS_ARGS, void *grad_features, void *workspace, size_t workspace_bytes,
+        void *hip_stream)
+{
+    MVHMR_LENS_RECORDS;
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace,
+                        workspace_bytes, hip_stream, nullptr, &la);
+}
+
+int mvhmr_unproject_backward_deterministic_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords, MVHMR_LENS_ARGS, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_LENS_RECORDS;
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace, workspace_bytes, hip_stream,
+                        nullptr, &la);
+}
+
+int mvhmr_unproject_backward_cuboid_deterministic_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3], MVHMR_LENS_ARGS, void *grad_features, void *workspace,
+        size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_LENS_RECORDS;
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace,
+                        workspace_bytes, hip_stream, nullptr, &la);
+}
+
+int mvhmr_unproject_backward_geometry_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords, MVHMR_LENS_ARGS, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_LENS_RECORDS;
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
+                        workspace, workspace_bytes, hip_stream, nullptr, nullptr, &la);
+}
+
+int mvhmr_unproject_backward_geometry_cuboid_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3], MVHMR_LENS_ARGS, float *grad_proj, float *grad_rot,
+        float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    MVHMR_LENS_RECORDS;
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, nullptr, grad_rot,
+                        grad_center, nullptr, workspace, workspace_bytes, hip_stream, nullptr, nullptr, &la);
 }
 
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)

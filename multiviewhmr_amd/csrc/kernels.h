@@ -46,6 +46,10 @@ struct Problem {
     // such a problem to the *_shared kernels (unproject_shared.hip, unproject_shared_geom.hip); B stays the number of FEATURE samples.
     const int *feature_index = nullptr;
     int volumes = 0;
+    // Lens distortion: one Brown-Conrady record per (sample, view) (device, (B, V, 10) fp32: fx, fy, cx, cy, k1, k2, p1, p2,
+    // k3, r2max; lens.h) through which the voxels are projected.  Null = pin-hole cameras.  The host route hands such a problem to the *_lens
+    // kernels (unproject_lens.hip, unproject_lens_geom.hip); the plane backward builds its tap table through the records and runs as it is.
+    const float *lens = nullptr;
 };
 
 inline Gate make_gate(const Problem &p, bool wants_brick) { return Gate{p.gate_count, p.gate_limit, wants_brick ? 1 : 0}; }
@@ -228,6 +232,18 @@ hipError_t launch_bwd_geom_shared(const void *grad_out, const void *featT, const
                                   float *grad_coords, const Problem &p, hipStream_t s);
 hipError_t launch_bwd_geom_cuboid_shared(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
                                          float *pose_part, float *grad_rot, float *grad_center, const Problem &p, hipStream_t s);
+
+// lens distortion (unproject_lens.hip, unproject_lens_geom.hip; Problem::lens): the gather forward, the per-tap scatter backward of both modes (the
+// deterministic scale pass is the plain one: its bound does not depend on where the taps land), the plane backward's tap table (launch_bwd_plane
+// calls it for a lens problem; tabW is its float4 table) and the lens instances of k_bwd_geom (launch_bwd_geom[_cuboid] call this for them)
+hipError_t launch_fwd_gather_lens(const void *featT, const float *proj, const Coords &coords, void *out, const Problem &p, hipStream_t s);
+hipError_t launch_bwd_gather_lens(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *gradT, const Problem &p,
+                                  hipStream_t s);
+hipError_t launch_bwd_gather_lens_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
+                                      const int *kexp, const Problem &p, hipStream_t s);
+hipError_t launch_plane_taps_lens(const float *proj, const Coords &coords, void *tabW, int *tabX, int *cmax, const Problem &p, hipStream_t s);
+hipError_t launch_bwd_geom_lens_kernel(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part,
+                                       float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
 
 // view masks (view_mask.hip): from mask (B,V) bytes, one thread per sample writes n_b (B ints), slot -> view and view -> slot (-1: masked)
 // tables (B,V ints each) and the projections packed into slot order (absent slots zero); then per-(sample, slot) copies of `bytes_per_view`

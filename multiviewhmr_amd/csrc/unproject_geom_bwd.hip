@@ -380,6 +380,7 @@ static hipError_t geom_dispatch(const void *grad_out, const void *featT, const f
     if (p.view_weights) return launch_bwd_geom_weighted_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, wpart, POSE, p, s);
     if (p.confidence) return launch_bwd_geom_conf_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, POSE, p, s);
     if (p.visible) return launch_bwd_geom_seen_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, POSE, p, s);
+    if (p.lens) return launch_bwd_geom_lens_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, POSE, p, s);     // lens distortion: unproject_lens_geom.hip
     if (p.out_bf16)
         return p.feat_f16 ? hipErrorNotSupported
                           : geom_dispatch_m<float, bf16_t, POSE>((const bf16_t *)grad_out, (const float *)featT, proj, coords, part, grad_coords, pose_part, p, s);

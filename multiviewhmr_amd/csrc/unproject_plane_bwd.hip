@@ -473,9 +473,14 @@ hipError_t launch_bwd_plane(const void *featK, const void *grad_out, const float
     float4 *dsW = reinterpret_cast<float4 *>(t3);
     int *dsMax = reinterpret_cast<int *>(t3 + align256(bvn * (size_t)slab * sizeof(float4)));
     const Gate gate = make_gate(p, false);
-    hipLaunchKernelGGL(k_plane_taps, dim3((unsigned)(p.B * p.V)), dim3(1024), (size_t)(p.H * p.W + 1) * sizeof(int), s, proj, coords, tabW, tabX, cmax,
-                       p.V, p.H, p.W, p.N, gate);
-    hipError_t e = hipGetLastError();
+    hipError_t e;
+    if (p.lens) {
+        e = launch_plane_taps_lens(proj, coords, tabW, tabX, cmax, p, s);           // the same table through the lens records (unproject_lens.hip)
+    } else {
+        hipLaunchKernelGGL(k_plane_taps, dim3((unsigned)(p.B * p.V)), dim3(1024), (size_t)(p.H * p.W + 1) * sizeof(int), s, proj, coords, tabW, tabX, cmax,
+                           p.V, p.H, p.W, p.N, gate);
+        e = hipGetLastError();
+    }
     if (e != hipSuccess) return e;
     const float4 *fk = static_cast<const float4 *>(featK);
     // per slab of quads: the Jacobian pass (grad_out's storage type), then the planes (the gradient's storage type)

@@ -7,7 +7,7 @@
 // (visibility-aware aggregation: the *_visible entry points, view_mask nullable, no weights), then `Tensor? view_confidence` (per-pixel confidence maps
 // (B, V, Hf, Wf) fp32: the *_confidence entry points, which take visible_only as a flag; the geometry ops also `Tensor(b!)? grad_confidence`, the tensor they
 // write the gradient w.r.t. the maps into), and last of all `Tensor? feature_index` (shared feature maps: the *_shared entry points; (M,) int32, the volumes'
-// tensors then hold M entries); mvhmr_visibility::view_visibility[_cuboid] return the
+// tensors then hold M entries) and `Tensor? lens` (lens distortion: the *_lens entry points; (B, V, 10) fp32 records); mvhmr_visibility::view_visibility[_cuboid] return the
 // (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
 // tensor checks, descriptor, output and workspace from the caching allocator, the current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
@@ -121,6 +121,7 @@ struct ViewArgs {
     const float *confidence = nullptr;                          // the *_confidence entry points: per-pixel confidence maps (visible is their flag)
     const int32_t *index = nullptr;                             // the *_shared entry points: `volumes` volumes read the samples through feature_index
     int32_t volumes = 0;                                        // (the library refuses the selections above beside an index, each with its own text)
+    const float *lens = nullptr;                                // the *_lens entry points: (B, V, 10) lens records (the library refuses everything above beside them)
 };
 
 // shared feature maps (mvhmr_unproject_*_shared): feature_index (M,) int32 on the features' device; null for None
@@ -139,7 +140,7 @@ const float *confidence_ptr(const mvhmr_unproject_desc &d, const at::Tensor &fea
 
 ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_mask,
                    const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence,
-                   const c10::optional<at::Tensor> &feature_index)
+                   const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens)
 {
     ViewArgs v{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights), visible_only,
                confidence_ptr(d, features, view_confidence, "view_confidence (B, V, Hf, Wf)")};
@@ -149,6 +150,10 @@ ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, co
         check_tensor(*feature_index, features, "feature_index (M,)", at::kInt, feature_index->numel());
         v.index = feature_index->data_ptr<int32_t>();
         v.volumes = (int32_t)feature_index->numel();
+    }
+    if (lens && lens->defined()) {
+        check_tensor(*lens, features, "lens (B, V, 10)", at::kFloat, (int64_t)d.batch * d.views * 10);
+        v.lens = lens->data_ptr<float>();
     }
     TORCH_CHECK(!(v.visible && v.weights), "mvhmr_unproject: visible_only does not take view_weights");
     TORCH_CHECK(!(v.confidence && v.weights), "mvhmr_unproject: view_confidence does not take view_weights");
@@ -211,6 +216,7 @@ struct TensorVolume {
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.lens) return mvhmr_unproject_forward_lens_workspace_bytes(&d);
         if (v.index) return mvhmr_unproject_forward_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_forward_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_forward_visible_workspace_bytes(&d);
@@ -221,6 +227,7 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.lens) return mvhmr_unproject_forward_lens(&d, features, proj, c, v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, out, ws, n, s);
         if (v.index) return mvhmr_unproject_forward_shared(&d, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, out, ws, n, s);
         if (v.confidence) return mvhmr_unproject_forward_confidence(&d, features, proj, c, mask, v.confidence, v.visible, out, ws, n, s);
         if (v.visible) return mvhmr_unproject_forward_visible(&d, features, proj, c, mask, out, ws, n, s);
@@ -229,6 +236,7 @@ struct TensorVolume {
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.lens) return det ? mvhmr_unproject_backward_deterministic_lens_workspace_bytes(&d) : mvhmr_unproject_backward_lens_workspace_bytes(&d);
         if (v.index) return det ? mvhmr_unproject_backward_deterministic_shared_workspace_bytes(&d, v.volumes) : mvhmr_unproject_backward_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return det ? mvhmr_unproject_backward_deterministic_confidence_workspace_bytes(&d) : mvhmr_unproject_backward_confidence_workspace_bytes(&d);
         if (v.visible) return det ? mvhmr_unproject_backward_deterministic_visible_workspace_bytes(&d) : mvhmr_unproject_backward_visible_workspace_bytes(&d);
@@ -241,6 +249,8 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.lens)
+            return (det ? mvhmr_unproject_backward_deterministic_lens : mvhmr_unproject_backward_lens)(&d, grad_out, features, proj, c, v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, grad, ws, n, s);
         if (v.index)
             return (det ? mvhmr_unproject_backward_deterministic_shared : mvhmr_unproject_backward_shared)(&d, grad_out, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, grad, ws, n, s);
         if (v.confidence)
@@ -255,6 +265,7 @@ struct TensorVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.lens) return mvhmr_unproject_backward_geometry_lens_workspace_bytes(&d);
         if (v.index) return mvhmr_unproject_backward_geometry_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_backward_geometry_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_backward_geometry_visible_workspace_bytes(&d);
@@ -266,6 +277,7 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.lens) return mvhmr_unproject_backward_geometry_lens(&d, grad_out, features, proj, c, v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, g[0], g[1], ws, n, s);
         if (v.index) return mvhmr_unproject_backward_geometry_shared(&d, grad_out, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, g[0], g[1], ws, n, s);
         if (v.confidence)
             return mvhmr_unproject_backward_geometry_confidence(&d, grad_out, features, proj, c, mask, v.confidence, v.visible, g[0], g[1], grad_confidence, ws, n, s);
@@ -300,6 +312,7 @@ struct CuboidVolume {
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.lens) return mvhmr_unproject_forward_cuboid_lens_workspace_bytes(&d);
         if (v.index) return mvhmr_unproject_forward_cuboid_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_forward_cuboid_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_forward_cuboid_visible_workspace_bytes(&d);
@@ -310,6 +323,8 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.lens)
+            return mvhmr_unproject_forward_cuboid_lens(&d, features, proj, r, c, position.data(), sides.data(), v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, out, ws, n, s);
         if (v.index) return mvhmr_unproject_forward_cuboid_shared(&d, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, out, ws, n, s);
         if (v.confidence)
             return mvhmr_unproject_forward_cuboid_confidence(&d, features, proj, r, c, position.data(), sides.data(), mask, v.confidence, v.visible, out, ws, n, s);
@@ -321,6 +336,7 @@ struct CuboidVolume {
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.lens) return det ? mvhmr_unproject_backward_cuboid_deterministic_lens_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_lens_workspace_bytes(&d);
         if (v.index)
             return det ? mvhmr_unproject_backward_cuboid_deterministic_shared_workspace_bytes(&d, v.volumes) : mvhmr_unproject_backward_cuboid_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence)
@@ -337,6 +353,9 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.lens)
+            return (det ? mvhmr_unproject_backward_cuboid_deterministic_lens : mvhmr_unproject_backward_cuboid_lens)(
+                &d, grad_out, features, proj, r, c, position.data(), sides.data(), v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, grad, ws, n, s);
         if (v.index)
             return (det ? mvhmr_unproject_backward_cuboid_deterministic_shared : mvhmr_unproject_backward_cuboid_shared)(
                 &d, grad_out, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, grad, ws, n, s);
@@ -357,6 +376,7 @@ struct CuboidVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.lens) return mvhmr_unproject_backward_geometry_cuboid_lens_workspace_bytes(&d);
         if (v.index) return mvhmr_unproject_backward_geometry_cuboid_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_backward_geometry_cuboid_confidence_workspace_bytes(&d);
         if (v.visible) return mvhmr_unproject_backward_geometry_cuboid_visible_workspace_bytes(&d);
@@ -368,6 +388,8 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.lens)
+            return mvhmr_unproject_backward_geometry_cuboid_lens(&d, grad_out, features, proj, r, c, position.data(), sides.data(), v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, g[0], g[1], g[2], ws, n, s);
         if (v.index)
             return mvhmr_unproject_backward_geometry_cuboid_shared(&d, grad_out, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, g[0], g[1], g[2], ws, n, s);
         if (v.confidence)
@@ -389,11 +411,11 @@ struct CuboidVolume {
 template <typename Volume>
 at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a, const c10::optional<at::Tensor> &view_mask,
                    const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence,
-                   const c10::optional<at::Tensor> &feature_index)
+                   const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, nullptr, a.M);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index);
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens);
     at::Tensor out = at::empty({a.M, a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
     run(features, vol.forward_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
         return vol.forward(d, features.data_ptr(), proj.data_ptr<float>(), views, out.data_ptr(), ws, n, s);
@@ -405,11 +427,12 @@ at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tens
 template <typename Volume>
 at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
                     const c10::optional<at::Tensor> &view_mask, bool deterministic, const c10::optional<at::Tensor> &view_weights, bool visible_only,
-                    const c10::optional<at::Tensor> &view_confidence, const c10::optional<at::Tensor> &feature_index)
+                    const c10::optional<at::Tensor> &view_confidence, const c10::optional<at::Tensor> &feature_index,
+                    const c10::optional<at::Tensor> &lens)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out, a.M);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index);
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens);
     at::Tensor grad = new_feature_grad(d, features);
     run(features, vol.backward_bytes(d, views, deterministic), deterministic, [&](void *ws, size_t n, hipStream_t s) {
         return vol.backward(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, deterministic, grad.data_ptr(), ws, n, s);
@@ -424,14 +447,14 @@ std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &g
                                           std::initializer_list<bool> want, const c10::optional<at::Tensor> &view_mask,
                                           const c10::optional<at::Tensor> &view_weights, const c10::optional<at::Tensor> &grad_weights, bool visible_only,
                                           const c10::optional<at::Tensor> &view_confidence, const c10::optional<at::Tensor> &grad_confidence,
-                                          const c10::optional<at::Tensor> &feature_index)
+                                          const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens)
 {
     const bool want_weights = grad_weights && grad_weights->defined();
     const bool want_conf = grad_confidence && grad_confidence->defined();
     TORCH_CHECK(want_weights || want_conf || std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out, a.M);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index);
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens);
     TORCH_CHECK(!want_weights || views.weights, "mvhmr_unproject: grad_weights needs view_weights");
     TORCH_CHECK(!want_conf || views.confidence, "mvhmr_unproject: grad_confidence needs view_confidence");
     float *gw = const_cast<float *>(weights_ptr(d, features, grad_weights, "grad_weights (B, V)"));
@@ -489,19 +512,19 @@ at::Tensor view_visibility_cuboid_native(const at::Tensor &proj, const at::Tenso
 at::Tensor unprojection_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C,
                                int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
                                const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence,
-                               const OptTensor &feature_index)
+                               const OptTensor &feature_index, const OptTensor &lens)
 {
     return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask, view_weights,
-                   visible_only, view_confidence, feature_index);
+                   visible_only, view_confidence, feature_index, lens);
 }
 
 at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
                                         int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
                                         int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask, bool deterministic,
-                                        const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence, const OptTensor &feature_index)
+                                        const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence, const OptTensor &feature_index, const OptTensor &lens)
 {
     return backward(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask,
-                    deterministic, view_weights, visible_only, view_confidence, feature_index);
+                    deterministic, view_weights, visible_only, view_confidence, feature_index, lens);
 }
 
 std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
@@ -510,10 +533,10 @@ std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const a
                                                                           int64_t variant, bool want_proj, bool want_coords, const OptTensor &view_mask,
                                                                           const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only,
                                                                           const OptTensor &view_confidence, const OptTensor &grad_confidence,
-                                                                          const OptTensor &feature_index)
+                                                                          const OptTensor &feature_index, const OptTensor &lens)
 {
     const auto g = backward_geometry(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)},
-                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index);
+                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index, lens);
     return {g[0], g[1]};
 }
 
@@ -521,10 +544,10 @@ at::Tensor unprojection_cuboid_native(const at::Tensor &features, const at::Tens
                                       at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C,
                                       int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
                                       const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence,
-                                      const OptTensor &feature_index)
+                                      const OptTensor &feature_index, const OptTensor &lens)
 {
     return forward(CuboidVolume{rot, center, position, sides, vol}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)},
-                   view_mask, view_weights, visible_only, view_confidence, feature_index);
+                   view_mask, view_weights, visible_only, view_confidence, feature_index, lens);
 }
 
 at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
@@ -532,10 +555,10 @@ at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const
                                                at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
                                                int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask,
                                                bool deterministic, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence,
-                                               const OptTensor &feature_index)
+                                               const OptTensor &feature_index, const OptTensor &lens)
 {
     return backward(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
-                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask, deterministic, view_weights, visible_only, view_confidence, feature_index);
+                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask, deterministic, view_weights, visible_only, view_confidence, feature_index, lens);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geometry_native(
@@ -543,11 +566,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geom
     at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
     int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center,
     const OptTensor &view_mask, const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only, const OptTensor &view_confidence,
-    const OptTensor &grad_confidence, const OptTensor &feature_index)
+    const OptTensor &grad_confidence, const OptTensor &feature_index, const OptTensor &lens)
 {
     const auto g = backward_geometry(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
                                      DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, {want_proj, want_rot, want_center}, view_mask,
-                                     view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index);
+                                     view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index, lens);
     return {g[0], g[1], g[2]};
 }
 
@@ -617,7 +640,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(c
 #define MVHMR_VISIBLE_ARG ", bool visible_only=False"
 #define MVHMR_CONF_ARG ", Tensor? view_confidence=None"
 #define MVHMR_GRAD_CONF_ARG ", Tensor(b!)? grad_confidence=None"
-#define MVHMR_INDEX_ARG ", Tensor? feature_index=None"
+#define MVHMR_INDEX_ARG ", Tensor? feature_index=None, Tensor? lens=None"
 
 TORCH_LIBRARY(mvhmr_native, m)
 {

@@ -29,7 +29,7 @@ def shard_batch(features, proj_matricies, coord_volumes, world_size=None, rank=N
 
 def shard_batch_dict(batch, world_size=None, rank=None):
     """Slice the reference's `batch` dict (data/data_utils.py:25-27): images (B,V,H,W,3), cameras[v][b], keypoints_3d[b], and the optional
-    view_mask (B,V), view_weights (B,V) and view_confidence (B,V,Hf,Wf).  With an optional feature_index (M,) (shared feature maps) the
+    view_mask (B,V), view_weights (B,V), view_confidence (B,V,Hf,Wf) and lens (B,V,10).  With an optional feature_index (M,) (shared feature maps) the
     volumes follow their samples: see below; without one nothing changes."""
     world_size = dist.get_world_size() if world_size is None else world_size
     rank = dist.get_rank() if rank is None else rank
@@ -55,6 +55,8 @@ def shard_batch_dict(batch, world_size=None, rank=None):
         out['view_weights'] = batch['view_weights'][lo:hi]
     if batch.get('view_confidence') is not None:       # per-pixel confidence maps (B, V, Hf, Wf): likewise
         out['view_confidence'] = batch['view_confidence'][lo:hi]
+    if batch.get('lens') is not None:                  # lens records (B, V, 10): likewise
+        out['lens'] = batch['lens'][lo:hi]
     return out
 
 
