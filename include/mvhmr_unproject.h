@@ -427,6 +427,57 @@ int mvhmr_unproject_visibility_cuboid(const mvhmr_unproject_desc *desc, const fl
                                       position[3], const double sides[3], const uint8_t *view_mask, int32_t *bits, void *hip_stream);
 
 /*
+ * Cross-view variance (additive within ABI 4): the *_moments entry points are the *_visible ones with two arguments behind
+ * `view_mask` (nullable as there): `visible` (0: every present view takes part, a view behind the camera or outside the map with its sample
+ * of zero, as in the plain mean; non-zero: the present views that see the voxel, the seeing test of the *_visible calls) and `moments`.
+ * With S the participating views of one (voxel, channel), n = |S| and s_v the per-view samples, in fp32 and in view order:
+ *     mu  = (sum_S s_v) / n                 var = (sum_S (s_v - mu)^2) / n       (population variance around the ROUNDED mu)
+ * var >= 0, var = 0 exactly for n = 1, mu = var = 0 for n = 0 (exact-zero gradients there).  MVHMR_MOMENTS_VAR: out / grad_out hold C
+ * channels, the variance.  MVHMR_MOMENTS_MEANVAR: 2C channels, [0, C) the mean -- the bits of the *_visible / *_masked mean call with the
+ * gather variant -- and [C, 2C) the variance -- the bits of MVHMR_MOMENTS_VAR.  Any other value is MVHMR_ERR_INVALID_ARGUMENT.
+ * desc->method names the moment the variance is taken around and must be MVHMR_AGG_MEAN (anything else: MVHMR_ERR_UNSUPPORTED).
+ * Gradient: ds_v = (2 g_v / n) (s_v - mu) + g_m / n for v in S with g_m, g_v the halves of grad_out (g_m = 0 for MVHMR_MOMENTS_VAR), exactly 0
+ * outside S; the geometry gradients are the existing chain rule driven by these.  The deterministic backward bounds its fixed-point scale
+ * by max |g_m| + 4 max |g_v| Fmax per (b, c), Fmax the largest |feature| a participating view taps.  Limits, layouts, storage pairings,
+ * variants (quad-planar layouts and MVHMR_VARIANT_BRICK refused with MVHMR_ERR_UNSUPPORTED; AUTO runs the gather family) as the visible calls.
+ * Workspace: the *_moments_workspace_bytes queries, never less than the visible ones; without a mask nothing is packed or copied.
+ */
+typedef enum mvhmr_moments_t {
+    MVHMR_MOMENTS_VAR = 1,
+    MVHMR_MOMENTS_MEANVAR = 2
+} mvhmr_moments_t;
+size_t mvhmr_unproject_forward_moments_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_forward_cuboid_moments_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_moments_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_moments_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_deterministic_moments_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_cuboid_deterministic_moments_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_moments_workspace_bytes(const mvhmr_unproject_desc *desc);
+size_t mvhmr_unproject_backward_geometry_cuboid_moments_workspace_bytes(const mvhmr_unproject_desc *desc);
+int mvhmr_unproject_forward_moments(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords, const uint8_t *view_mask, int32_t visible, int32_t moments, void *out, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_forward_cuboid_moments(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float
+                                           *center, const double position[3], const double sides[3], const uint8_t *view_mask, int32_t visible, int32_t moments, void *out, void
+                                           *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float
+                                     *coords, const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void
+                                     *hip_stream);
+int mvhmr_unproject_backward_cuboid_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const
+                                            float *rot, const float *center, const double position[3], const double sides[3], const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_deterministic_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                   const float *coords, const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t
+                                                   workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_cuboid_deterministic_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float
+                                                          *proj, const float *rot, const float *center, const double position[3], const double
+                                                          sides[3], const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t
+                                                          workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const
+                                              float *coords, const uint8_t *view_mask, int32_t visible, int32_t moments, float *grad_proj, float *grad_coords, void *workspace, size_t
+                                              workspace_bytes, void *hip_stream);
+int mvhmr_unproject_backward_geometry_cuboid_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+                                                     const float *rot, const float *center, const double position[3], const double sides[3], const uint8_t *view_mask, int32_t visible, int32_t moments, float *grad_proj, float *grad_rot, float *grad_center, void *workspace,
+                                                     size_t workspace_bytes, void *hip_stream);
+
+/*
  * Per-pixel view confidence maps: the *_confidence entry points are the *_visible ones with `view_confidence` behind
  * `view_mask` and the seeing test as the flag `visible` (0: off).  view_confidence (B,V,Hf,Wf) fp32 planar on the device: one map per view at
  * feature resolution, or NULL -- then the call is exactly the masked call (visible == 0) or the visible call (visible != 0).

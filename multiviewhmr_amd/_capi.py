@@ -14,6 +14,7 @@ AGG = {"softmax": 0, "sum": 1, "mean": 2, "max": 3}
 F32, F16, BF16 = 0, 1, 2
 LAYOUT_BVCHW, LAYOUT_BVHWC, LAYOUT_QUAD, LAYOUT_QUAD_LOG2E = 0, 1, 2, 3
 VARIANT = {"auto": 0, "gather": 1, "brick": 2}
+MOMENTS_VAR, MOMENTS_MEANVAR = 1, 2                       # mvhmr_moments_t: the cross-view variance alone / behind the mean
 
 EXPORTS = (
     "mvhmr_abi_version", "mvhmr_status_string", "mvhmr_last_error",
@@ -31,8 +32,8 @@ EXPORTS = (
     "mvhmr_unproject_backward_cuboid_deterministic", "mvhmr_conv1x1_wgrad_deterministic_workspace_bytes", "mvhmr_conv1x1_wgrad_deterministic",
 ) + tuple("mvhmr_unproject_%s_%s%s" % (n, tag, w) for n in ("forward", "forward_cuboid", "backward", "backward_cuboid", "backward_deterministic",
                                                            "backward_cuboid_deterministic", "backward_geometry", "backward_geometry_cuboid")
-          for w in ("", "_workspace_bytes")       # per-sample view masks, per-view confidence weights, visibility-aware aggregation, per-pixel confidence maps, shared feature maps, lens distortion
-          for tag in ("masked", "weighted", "visible", "confidence", "shared", "lens")) + ("mvhmr_unproject_visibility", "mvhmr_unproject_visibility_cuboid")
+          for w in ("", "_workspace_bytes")       # per-sample view masks, per-view confidence weights, visibility-aware aggregation, per-pixel confidence maps, shared feature maps, lens distortion, cross-view variance
+          for tag in ("masked", "weighted", "visible", "confidence", "shared", "lens", "moments")) + ("mvhmr_unproject_visibility", "mvhmr_unproject_visibility_cuboid")
 
 
 class Desc(ctypes.Structure):
@@ -189,6 +190,17 @@ def lib():
             fn.restype = ctypes.c_int
             fn.argtypes = lead + place + [vp, vp, vp, vp, ctypes.c_int, vp] + [vp] * outs + [vp, sz, vp]
             q = getattr(L, "mvhmr_unproject_%s_lens_workspace_bytes" % name)
+            q.restype = sz
+            q.argtypes = [dp]
+    # the *_moments family: the *_visible signatures with the flag `visible` and `moments` (MOMENTS_VAR / MOMENTS_MEANVAR) behind view_mask
+    for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
+        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
+                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
+                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 3 if vol else 2)):
+            fn = getattr(L, "mvhmr_unproject_%s_moments" % name)
+            fn.restype = ctypes.c_int
+            fn.argtypes = lead + place + [vp, i32, i32] + [vp] * outs + [vp, sz, vp]
+            q = getattr(L, "mvhmr_unproject_%s_moments_workspace_bytes" % name)
             q.restype = sz
             q.argtypes = [dp]
     if L.mvhmr_abi_version() != ABI_VERSION:

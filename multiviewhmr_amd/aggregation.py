@@ -26,6 +26,7 @@ import torch.nn as nn
 from . import _capi, multiview, volumetric
 
 _METHODS = ("softmax", "sum", "mean", "max")            # aggregation.py:71-85
+_MOMENTS = {"var": 1, "meanvar": 2}                       # extension: the cross-view variance, alone or behind the mean (mvhmr_moments_t)
 _FUSED_MAX_MAPS = 65535                                 # mvhmr_conv1x1_to_quad / _planar: n_maps is the grid's z extent (mvhmr_unproject.h)
 _TYPE_MSG = "Works only with numpy arrays and PyTorch tensors."
 
@@ -237,12 +238,12 @@ class _Family:
 
     def forward(self, *args):
         lead, (mask, weights, conf) = self.native_args(args)
-        return getattr(_native(), self.native)(*lead, mask, weights, self.visible, conf, self.index(args), self.lens_of(args))
+        return getattr(_native(), self.native)(*lead, mask, weights, self.visible, conf, feature_index=self.index(args), lens=self.lens_of(args))
 
     def backward(self, deterministic, grad_out, *args):
         """gradient w.r.t. features (the geometry's is backward_geometry)"""
         lead, (mask, weights, conf) = self.native_args(args)
-        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible, conf, self.index(args), self.lens_of(args))
+        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible, conf, feature_index=self.index(args), lens=self.lens_of(args))
 
     def backward_geometry(self, grad_out, *args):
         """planar features go through the library's channels-last pass, channels-last ones are read as they are; the gradient w.r.t.
@@ -258,7 +259,7 @@ class _Family:
                 return tuple(conf.new_empty((0,)) for _ in self.geo) + (gc,)
             return tuple(op(grad_out.contiguous(), *lead, *want[:-1], *tail)) + (gc,)
         if not self.weighted:
-            return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, self.visible, None, None, self.index(args), self.lens_of(args)))
+            return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, self.visible, None, None, feature_index=self.index(args), lens=self.lens_of(args)))
         gw = weights.new_empty(weights.shape if want[-1] else (0,))
         if not any(want[:-1]):                             # the weights' gradient alone: the extension's outputs stay empty
             op(grad_out.contiguous(), *lead, *want[:-1], mask, weights, gw)
@@ -312,7 +313,53 @@ class _Family:
         torch.library.register_autograd(name, self.autograd, setup_context=self.setup_context)
 
 
+class _MomentsFamily(_Family):
+    """mvhmr::unprojection_moments / mvhmr::unprojection_cuboid_moments (the *_moments entry points; DESIGN.md 5.14): a masked family whose
+    view_mask is `Tensor?` (None: the null mask, nothing is packed or copied), with `bool visible_only` and `int moments` (1: the variance, C
+    channels; 2: the mean and the variance, 2C channels) behind the placing arguments.  `method` is the moment the variance is taken around:
+    mean.  The feature gradient has the features' C channels; the geometry backward is the family's usual one."""
+
+    def __init__(self, name, places, extras):
+        super().__init__(name, places, extras, True)
+        self.place_extras = extras
+        self.extras = tuple(extras) + ("bool visible_only", "int moments")
+        self.n_inputs = len(self.tensors) + len(self.extras) + 3
+
+    def schema(self):
+        kind = lambda t: "Tensor? " if t == "view_mask" else "Tensor "  # noqa: E731
+        return ", ".join([kind(t) + t for t in self.tensors] + list(self.extras) + ["int method", "int out_dtype", "int variant"])
+
+    def native_args(self, args, geometry=False):
+        """-> the extension's leading arguments, view_mask, visible_only, moments"""
+        features, geo, views, extra, (method, out_dtype, variant), _ = self.split(args)
+        features, layout = _geometry_read_layout(features)
+        place, visible, moments = tuple(extra[:-2]), bool(extra[-2]), int(extra[-1])
+        read, desc = _native_args(features, self.volume(geo, place), method, out_dtype, variant, layout)
+        return (read,) + geo + place + desc, views[0], visible, moments
+
+    def forward(self, *args):
+        lead, mask, visible, moments = self.native_args(args)
+        return getattr(_native(), self.native)(*lead, mask, None, visible, None, moments)
+
+    def backward(self, deterministic, grad_out, *args):
+        lead, mask, visible, moments = self.native_args(args)
+        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, None, visible, None, moments)
+
+    def backward_geometry(self, grad_out, *args):
+        lead, mask, visible, moments = self.native_args(args, geometry=True)
+        want = self.split(args)[5]
+        op = getattr(_native(), self.native + "_backward_geometry")
+        return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, visible, None, None, moments))
+
+    def fake_forward(self, *args):
+        features, geo, _, extra, (_, out_dtype, _), _ = self.split(args)
+        halves = 2 if int(extra[-1]) == _MOMENTS["meanvar"] else 1
+        return features.new_empty((features.shape[0], halves * features.shape[2]) + self.volume(geo, tuple(extra[:-2])), dtype=_DTYPES[out_dtype])
+
+
 _OPS = {name: _Family(name, *spec) for name, spec in _FAMILIES.items()}
+_OPS["unprojection_moments"] = _MomentsFamily("unprojection_moments", ("coords",), ())
+_OPS["unprojection_cuboid_moments"] = _MomentsFamily("unprojection_cuboid_moments", ("rot", "center"), _CUBOID_ARGS)
 for _family in _OPS.values():
     _family.register()
 _op_backward = functools.partial(_OPS["unprojection"].backward, False)          # (grad_out, features, proj, coords, method, out_dtype, variant)
@@ -325,7 +372,7 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
     for t in (features, proj_matricies) + volume:
         if not torch.is_tensor(t):
             raise TypeError(_TYPE_MSG)                       # utils/multiview.py:110
-    if aggregation_method not in _METHODS:
+    if aggregation_method not in _METHODS and aggregation_method not in _MOMENTS:
         raise ValueError("Unknown aggregation_method: {}".format(aggregation_method))
     if variant not in _capi.VARIANT:
         raise ValueError("Unknown kernel variant: {}".format(variant))
@@ -345,7 +392,8 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
         out_dtype = torch.float16 if features.dtype == torch.float16 else torch.float32
     if features.numel() == 0 or 0 in vol:
         # empty batch / empty volume: the reference's zero-initialised volume comes back (aggregation.py:25-28), nothing to launch
-        return out_dtype, vol, torch.zeros((B, features.shape[2]) + vol, dtype=out_dtype, device=features.device)
+        channels = features.shape[2] * (2 if aggregation_method == "meanvar" else 1)
+        return out_dtype, vol, torch.zeros((B, channels) + vol, dtype=out_dtype, device=features.device)
     return out_dtype, vol, None
 
 
@@ -357,7 +405,13 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
                     a channels-last-strided tensor (physically (B,V,Hf,Wf,C)) is consumed without a layout pass
     proj_matricies  (B, V, 3, 4)  -- feature-resolution projection matrices
     coord_volumes   (B, X, Y, Z, 3) -- voxel centres in world units
-    aggregation_method  'softmax' | 'sum' | 'mean' | 'max'; anything else -> ValueError (aggregation.py:85)
+    aggregation_method  'softmax' | 'sum' | 'mean' | 'max'; anything else -> ValueError (aggregation.py:85) -- except the extensions
+                    'var' and 'meanvar' (DESIGN.md 5.14): the population variance of the participating views' samples, (B, C, X, Y, Z),
+                    and torch.cat([mean, var], 1), (B, 2C, X, Y, Z).  The participating views are all of them (a view behind the camera
+                    or outside the map with its sample of zero, as in 'mean'), the present ones under view_mask, the present ones that
+                    see the voxel under visible_only=True; one view gives variance 0, none gives zeros.  The mean half carries the bits of
+                    the 'mean' call with variant='gather'.  Differentiable like the plain call; runs the gather kernels ('brick' is
+                    refused); with view_weights, view_confidence, feature_index or lens it raises ValueError (not built yet).
     returns         a new (B, C, X, Y, Z) tensor on features.device, float32 like the reference (aggregation.py:25)
                     unless out_dtype is given (float16 features default to a float16 volume; float32 features may ask for a
                     bfloat16 volume -- what a half-precision consumer reads -- and then take a bfloat16 grad_out)
@@ -408,6 +462,7 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
             raise RuntimeError("unprojection: coord_volumes must be (%d, X, Y, Z, 3), got %s" % (n, tuple(coord_volumes.shape)))
         return tuple(coord_volumes.shape[1:4])
 
+    _check_moments(aggregation_method, view_weights, view_confidence, feature_index, lens)
     if lens is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_lens(lens, features, view_mask, view_weights, visible_only, view_confidence, feature_index)
     if feature_index is not None and torch.is_tensor(features) and features.dim() == 5:
@@ -429,6 +484,10 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
     # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
     proj = proj_matricies.to(torch.float32).contiguous()
     coords = coord_volumes.to(torch.float32).contiguous()
+    if aggregation_method in _MOMENTS:
+        return torch.ops.mvhmr.unprojection_moments(features, proj, coords, None if view_mask is None else _mask_bytes(view_mask, features),
+                                                    bool(visible_only), _MOMENTS[aggregation_method], _capi.AGG["mean"], _dtype_code(out_dtype),
+                                                    _capi.VARIANT[variant])
     if lens is not None:
         return torch.ops.mvhmr.unprojection_lens(features, proj, coords, _lens_fp32(lens, features), _capi.AGG[aggregation_method],
                                                  _dtype_code(out_dtype), _lens_variant(variant))
@@ -450,6 +509,17 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
         return torch.ops.mvhmr.unprojection_masked(features, proj, coords, mask, _capi.AGG[aggregation_method], _dtype_code(out_dtype),
                                                    _capi.VARIANT[variant])
     return torch.ops.mvhmr.unprojection(features, proj, coords, _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
+
+
+def _check_moments(aggregation_method, view_weights=None, view_confidence=None, feature_index=None, lens=None):
+    """'var' / 'meanvar'  take a view mask and visible_only; the other view selections do not compose with them yet"""
+    if not isinstance(aggregation_method, str) or aggregation_method not in _MOMENTS:
+        return
+    for given, what in ((view_weights is not None, "view_weights"), (view_confidence is not None, "view_confidence"),
+                        (feature_index is not None, "feature_index"), (lens is not None, "lens")):
+        if given:
+            raise ValueError("unprojection: aggregation_method='%s' with %s is not built yet (the next step of DESIGN.md 5.14): "
+                             "pass a view_mask and / or visible_only=True" % (aggregation_method, what))
 
 
 def _check_view_mask(view_mask, features):
@@ -638,6 +708,7 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
                                % (n, n, tuple(rotations.shape), tuple(centers.shape)))
         return tuple(int(v) for v in volume_shape)
 
+    _check_moments(aggregation_method, view_weights, view_confidence, feature_index, lens)
     if lens is not None and torch.is_tensor(features) and features.dim() == 5:
         _check_lens(lens, features, view_mask, view_weights, visible_only, view_confidence, feature_index)
     if feature_index is not None and torch.is_tensor(features) and features.dim() == 5:
@@ -661,6 +732,10 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     proj = proj_matricies.to(device=dev, dtype=torch.float32).contiguous()
     rot = rotations.to(device=dev, dtype=torch.float32).contiguous()
     cen = centers.to(device=dev, dtype=torch.float32).contiguous()
+    if aggregation_method in _MOMENTS:
+        return torch.ops.mvhmr.unprojection_cuboid_moments(features, proj, rot, cen, None if view_mask is None else _mask_bytes(view_mask, features),
+                                                           [float(x) for x in position], [float(x) for x in sides], list(vol), bool(visible_only),
+                                                           _MOMENTS[aggregation_method], _capi.AGG["mean"], _dtype_code(out_dtype), _capi.VARIANT[variant])
     if lens is not None:
         return torch.ops.mvhmr.unprojection_cuboid_lens(features, proj, rot, cen, _lens_fp32(lens, features), [float(x) for x in position],
                                                         [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method], _dtype_code(out_dtype),
@@ -970,8 +1045,15 @@ class VolumeGenerator(nn.Module):
         self.volume_dtype = volume_dtype  # extension: None = float32 like the reference; torch.bfloat16 / float16 for a half-precision consumer
         self.visible_only = bool(visible_only)  # extension: every voxel aggregates only the views that see it
         self.lens_distortion = bool(lens_distortion)  # extension: un-project through the cameras' lens distortion (the class docstring)
+        self.output_channels = output_channels
         self.fused_conv = True            # 1x1 conv + layout pass as one MFMA GEMM wherever its shapes allow (see _fused_path_applies)
         self.to(device)
+
+    @property
+    def volume_channels(self):
+        """channels of the volume forward() returns: output_channels, or twice that for aggregation_method='meanvar' (the mean and the
+        cross-view variance) -- what the volumetric regressor behind it must be built for"""
+        return self.output_channels * (2 if self.aggregation_method == "meanvar" else 1)
 
     # -- geometry the reference builds inside forward(); split out so it can be checked without a GPU
     def cuboid(self):
@@ -1063,6 +1145,8 @@ class VolumeGenerator(nn.Module):
             proj = torch.from_numpy(feature_level_projections(batch['cameras'], images_shape, features_shape))
         # the kernels take raw device pointers: whatever device the packed cameras live on (a loader may pack them on the host)
         proj = proj.to(device=device, dtype=torch.float32).contiguous()
+        _check_moments(self.aggregation_method, batch.get('view_weights'), batch.get('view_confidence'), batch.get('feature_index'),
+                       True if self.lens_distortion else None)
         view_mask = batch.get('view_mask')                                  # optional (B, V): per-sample present views
         if view_mask is not None:
             _check_view_mask(view_mask, proj)                               # (only its (B, V) leading shape is read)

@@ -376,11 +376,28 @@ struct Views {
     const float *weights;
     bool visible = false;                       // the *_visible entry points (no weights there); a null mask packs nothing
     const float *confidence = nullptr;          // the *_confidence entry points (no weights there; `visible` composes); a null mask packs nothing
+    int moments = 0;                            // the *_moments entry points (no weights, no maps there; `visible` composes); a null mask packs nothing
     bool packed() const { return mask || weights; }
 };
+// ---- cross-view variance (include/mvhmr_unproject.h): the route of the visible calls -- the gather family with the per-tap
+// scatter backward and the geometry kernels, which launch their *_moments kernels (Problem::moments); with a mask the views are packed exactly
+// as for a masked call, without one nothing is packed or copied.  The variance is taken around the mean: desc->method must say so.
+int moments_refused(const mvhmr_unproject_desc *desc, int moments)
+{
+    if (moments != MVHMR_MOMENTS_VAR && moments != MVHMR_MOMENTS_MEANVAR)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "moments must be MVHMR_MOMENTS_VAR (1) or MVHMR_MOMENTS_MEANVAR (2)");
+    if (desc->method != MVHMR_AGG_MEAN)
+        return fail(MVHMR_ERR_UNSUPPORTED, "the cross-view variance is taken around the mean: desc->method must be MVHMR_AGG_MEAN (got %d)", desc->method);
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
+        return fail(MVHMR_ERR_UNSUPPORTED, "the cross-view variance needs planar or channels-last features (quad-planar copies: pass the planar features)");
+    if (desc->variant == MVHMR_VARIANT_BRICK)
+        return fail(MVHMR_ERR_UNSUPPORTED, "the cross-view variance runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
+    return MVHMR_OK;
+}
 int views_refused(const mvhmr_unproject_desc *desc, const Views &w)
 {
     int rc = MVHMR_OK;
+    if (w.moments) return moments_refused(desc, w.moments);      // (the checks of a visible and of a masked call are among its own)
     if (w.visible && (rc = visible_refused(desc)) != MVHMR_OK) return rc;
     if (w.confidence && (rc = confidence_refused(desc)) != MVHMR_OK) return rc;
     if (w.mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
@@ -389,10 +406,11 @@ int views_refused(const mvhmr_unproject_desc *desc, const Views &w)
 // the kinds of plan: every view, a mask, weights (with or without a mask), the seeing views of every voxel (with or without a mask),
 // confidence maps (with or without a mask, with or without the seeing test); Shared: shared feature maps (no head: nothing is packed);
 // Lens: lens distortion (no head either: the plain plan of the gather variant)
-enum class Pack { None, Masked, Weighted, Visible, Confidence, Shared, Lens };
+// Moments: the cross-view variance (with or without a mask, with or without the seeing test)
+enum class Pack { None, Masked, Weighted, Visible, Confidence, Shared, Lens, Moments };
 Pack pack_of(const Views &w)
 {
-    return w.confidence ? Pack::Confidence : w.visible ? Pack::Visible : w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None;
+    return w.moments ? Pack::Moments : w.confidence ? Pack::Confidence : w.visible ? Pack::Visible : w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None;
 }
 // the plan whose workspace a plan's total also covers: a weighted or visible call's serves the masked one, a masked call's the unmasked one
 Pack pack_below(Pack pack) { return pack == Pack::Masked || pack == Pack::Shared ? Pack::None : Pack::Masked; }
@@ -401,8 +419,16 @@ void mask_route(mvhmr_unproject_desc *desc, Problem *p, Pack pack)
 {
     desc->variant = MVHMR_VARIANT_GATHER;
     p->masked = 1;
-    p->visible = pack == Pack::Visible;          // (a confidence call's flag is set from the call's own: confidence_route)
+    p->visible = pack == Pack::Visible || pack == Pack::Moments;   // (a confidence or moments call's flag is set from the call's own: confidence_route, moments_route)
     p->conf = pack == Pack::Confidence;
+    p->moments = pack == Pack::Moments ? MVHMR_MOMENTS_MEANVAR : 0;   // (the plans read it as a flag; moments_route sets the call's own)
+}
+// a moments call composes with the seeing test: both ride in the problem once the plan exists
+void moments_route(Problem &p, const Views &w)
+{
+    if (!w.moments) return;
+    p.visible = w.visible;
+    p.moments = w.moments;
 }
 // a confidence call reads the caller's maps (no mask) or the packed ones (pack_views), and composes with the seeing test
 void confidence_route(Problem &p, const Views &w)
@@ -522,7 +548,7 @@ ForwardPlan plan_forward(const mvhmr_unproject_desc *desc, const Problem &p, Pac
         return f;
     }
     f.total = pack == Pack::None ? a.top : max_size(a.top, plan_forward(desc, p, pack_below(pack)).total);
-    if (pack == Pack::Confidence) f.total = max_size(f.total, plan_forward(desc, p, Pack::Visible).total);      // (a null map is the visible call)
+    if (pack == Pack::Confidence || pack == Pack::Moments) f.total = max_size(f.total, plan_forward(desc, p, Pack::Visible).total);      // (a null map is the visible call; a moments query covers its visible twin)
     if (pack == Pack::Shared) {                                                                                 // (a null index is the plain gather call)
         const mvhmr_unproject_desc dg = gather_twin(desc);
         f.total = max_size(f.total, plan_forward(&dg, p, Pack::None).total);
@@ -589,7 +615,8 @@ void place_det_backward(BackwardPlan &b, Arena &a)
     if (d->feat_layout != (brick ? MVHMR_LAYOUT_QUAD : MVHMR_LAYOUT_BVHWC)) b.staged = a.take(brick ? brick_workspace_bytes(p) : featT_bytes(p));
     b.acc = a.take(det_acc_bytes(p));
     // (shared feature maps: the per-sample exponent table and the histogram cnt of the volumes that name each sample)
-    b.scale = a.take(align_up(p.volumes ? shared_det_scale_bytes(p) : det_scale_bytes(p)));
+    // (cross-view variance: four words per (b, c) and the tap marks)
+    b.scale = a.take(align_up(p.volumes ? shared_det_scale_bytes(p) : p.moments ? moments_det_scale_bytes(p) : det_scale_bytes(p)));
 }
 BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, bool det, Pack pack)
 {
@@ -617,7 +644,7 @@ BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, b
         return b;
     }
     b.total = pack == Pack::None ? a.top : max_size(a.top, plan_backward(desc, p, det, pack_below(pack)).total);
-    if (pack == Pack::Confidence) b.total = max_size(b.total, plan_backward(desc, p, det, Pack::Visible).total);
+    if (pack == Pack::Confidence || pack == Pack::Moments) b.total = max_size(b.total, plan_backward(desc, p, det, Pack::Visible).total);
     if (pack == Pack::Shared) {
         const mvhmr_unproject_desc dg = gather_twin(desc);
         b.total = max_size(b.total, plan_backward(&dg, p, det, Pack::None).total);
@@ -669,7 +696,7 @@ GeometryPlan plan_geometry(const mvhmr_unproject_desc *desc, const Problem &p, b
     g.part = a.take(align_up(pack == Pack::Shared ? shared_geom_partial_bytes(p) : geom_partial_bytes(p)));
     if (cuboid) g.pose_part = a.take(align_up(pack == Pack::Shared ? shared_pose_partial_bytes(p) : pose_partial_bytes(p)));
     g.total = pack == Pack::None ? a.top : max_size(a.top, plan_geometry(desc, p, cuboid, pack_below(pack)).total);
-    if (pack == Pack::Confidence) g.total = max_size(g.total, plan_geometry(desc, p, cuboid, Pack::Visible).total);
+    if (pack == Pack::Confidence || pack == Pack::Moments) g.total = max_size(g.total, plan_geometry(desc, p, cuboid, Pack::Visible).total);
     return g;
 }
 
@@ -743,6 +770,7 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
     if (rc != MVHMR_OK) return rc;
     if (views.packed() && (rc = pack_views(f.head, views, workspace, &features, &proj, p, s)) != MVHMR_OK) return rc;
     confidence_route(p, views);
+    moments_route(p, views);
     // planar input whose staged copy this call makes itself: scaled by log2(e) when the kernel that reads it wants that
     if (desc->feat_layout == MVHMR_LAYOUT_BVCHW && brick_fwd_prescales(p)) p.feat_log2e = 1;
 
@@ -775,6 +803,7 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
         }
         if (p.feature_index) return launched(launch_fwd_gather_shared(staged ? staged : features, proj, coords, out, p, s), "shared gather forward");
         if (p.lens) return launched(launch_fwd_gather_lens(staged ? staged : features, proj, coords, out, p, s), "lens gather forward");
+        if (p.moments) return launched(launch_fwd_gather_moments(staged ? staged : features, proj, coords, out, p, s), "moments gather forward");
         return launched(launch_fwd_gather(staged ? staged : features, proj, coords, out, p, s), "gather forward");
     }
     return fail(MVHMR_ERR_INVALID_ARGUMENT, "unknown forward route");
@@ -861,6 +890,7 @@ int launch_backward_default(BackwardPlan &b, const BackwardArgs &c)
         if (rc != MVHMR_OK) return rc;
         rc = p.feature_index ? launched(launch_bwd_gather_shared(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "shared gather backward")
              : p.lens        ? launched(launch_bwd_gather_lens(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "lens gather backward")
+             : p.moments     ? launched(launch_bwd_gather_moments(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "moments gather backward")
                              : launched(launch_bwd_gather(c.grad_out, staged ? staged : c.features, c.proj, coords, gradT, p, s), "gather backward");
         if (rc != MVHMR_OK || !acc) return rc;
         if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_grad_to_planar(gradT, c.grad_features, p, s), "gradient layout pass");   // planar gradient for planar and quad-planar features alike
@@ -893,9 +923,10 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
     rc = clear_gradient(acc, p, sizeof(long long), s);
     if (rc != MVHMR_OK) return rc;
     rc = p.feature_index ? launched(launch_det_scale_shared(c.grad_out, feat, scale, p, s), "deterministic scale pass")
+         : p.moments     ? launched(launch_det_scale_moments(c.grad_out, feat, scale, p, s, c.proj, &coords), "deterministic scale pass")
                          : launched(launch_det_scale(c.grad_out, feat, scale, p, s, brick, c.proj, &coords), "deterministic scale pass");
     if (rc != MVHMR_OK) return rc;
-    const int *kexp = det_exponents(scale, p);
+    const int *kexp = p.moments ? moments_det_exponents(scale, p) : det_exponents(scale, p);
     if (brick) {
         rc = launched(launch_bwd_brick_det(feat, c.grad_out, c.proj, coords, acc, kexp, p, s), "deterministic brick backward");
         if (rc != MVHMR_OK) return rc;
@@ -903,6 +934,7 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
     }
     rc = p.feature_index ? launched(launch_bwd_gather_shared_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic shared gather backward")
          : p.lens        ? launched(launch_bwd_gather_lens_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic lens gather backward")
+         : p.moments     ? launched(launch_bwd_gather_moments_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic moments gather backward")
                          : launched(launch_bwd_gather_det(c.grad_out, feat, c.proj, coords, acc, kexp, p, s), "deterministic gather backward");
     if (rc != MVHMR_OK) return rc;
     if (desc->feat_layout != MVHMR_LAYOUT_BVHWC) return launched(launch_det_grad_to_planar(acc, kexp, c.grad_features, p, s), "gradient layout pass");
@@ -938,6 +970,7 @@ int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     const bool packed = views.packed();
     if (packed && (rc = pack_views(b.head, views, workspace, &features, &proj, b.p, s)) != MVHMR_OK) return rc;
     confidence_route(b.p, views);
+    moments_route(b.p, views);
     // a masked or weighted call's gradient comes in slot order and is unpacked into view order, absent views zero-filled
     void *grad = packed ? at(workspace, b.head.grad) : grad_features;
     const BackwardArgs c{grad_out, features, proj, &coords, grad, workspace, s};
@@ -992,6 +1025,7 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     if (mask && (rc = pack_views(g.head, views, workspace, &features, &proj, g.p, s)) != MVHMR_OK) return rc;
     confidence_route(g.p, views);
+    moments_route(g.p, views);
     // grad_confidence: the kernel's stream of sum_channels dc, then launch_conf_grad (slot order behind the head with a mask, unpacked at the end)
     float *gc = mask && grad_confidence ? reinterpret_cast<float *>(at(workspace, g.packed_grad_conf)) : grad_confidence;
     if (grad_confidence) g.p.conf_stream = reinterpret_cast<float *>(at(workspace, g.conf_stream));
@@ -1047,7 +1081,8 @@ int run_visibility(const mvhmr_unproject_desc *desc, const VolumeSource &v, cons
 bool pack_refused(const mvhmr_unproject_desc *desc, Pack pack)
 {
     return (pack == Pack::Masked && mask_refused(desc) != MVHMR_OK) || (pack == Pack::Weighted && weights_refused(desc) != MVHMR_OK) ||
-           (pack == Pack::Visible && visible_refused(desc) != MVHMR_OK) || (pack == Pack::Confidence && confidence_refused(desc) != MVHMR_OK);
+           (pack == Pack::Visible && visible_refused(desc) != MVHMR_OK) || (pack == Pack::Confidence && confidence_refused(desc) != MVHMR_OK) ||
+           (pack == Pack::Moments && moments_refused(desc, MVHMR_MOMENTS_MEANVAR) != MVHMR_OK);
 }
 size_t forward_need(const mvhmr_unproject_desc *desc, Pack pack)
 {
@@ -1460,6 +1495,68 @@ int mvhmr_unproject_visibility_cuboid(const mvhmr_unproject_desc *desc, const fl
                                       const double position[3], const double sides[3], const uint8_t *view_mask, int32_t *bits, void *hip_stream)
 {
     return run_visibility(desc, cuboid_volume(rot, center, position, sides), proj, view_mask, bits, hip_stream);
+}
+
+// ---- cross-view variance: the _moments entry points with the seeing test as the flag `visible` and `moments` (MVHMR_MOMENTS_VAR /
+// MVHMR_MOMENTS_MEANVAR) behind `view_mask`; out / grad_out hold C or 2C channels
+size_t mvhmr_unproject_forward_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Moments); }
+size_t mvhmr_unproject_forward_cuboid_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Moments); }
+size_t mvhmr_unproject_backward_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Moments); }
+size_t mvhmr_unproject_backward_cuboid_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Moments); }
+size_t mvhmr_unproject_backward_deterministic_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Moments); }
+size_t mvhmr_unproject_backward_cuboid_deterministic_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Moments); }
+size_t mvhmr_unproject_backward_geometry_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Moments); }
+size_t mvhmr_unproject_backward_geometry_cuboid_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Moments); }
+
+int mvhmr_unproject_forward_moments(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, int32_t visible, int32_t moments, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, out, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_forward_cuboid_moments(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, int32_t visible, int32_t moments, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, out, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, false, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, false, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_deterministic_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
+        const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, true, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_cuboid_deterministic_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
+        const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, true, grad_features, workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *coords, const uint8_t *view_mask, int32_t visible, int32_t moments, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
+                        workspace, workspace_bytes, hip_stream);
+}
+
+int mvhmr_unproject_backward_geometry_cuboid_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
+        const float *rot, const float *center, const double position[3], const double sides[3], const uint8_t *view_mask, int32_t visible, int32_t moments, float *grad_proj,
+        float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, grad_proj, nullptr, grad_rot,
+                        grad_center, nullptr, workspace, workspace_bytes, hip_stream);
 }
 
 // ---- per-pixel view confidence maps: the _visible entry points with `view_confidence` (B,V,Hf,Wf) fp32 beside `view_mask` (either may be

@@ -50,6 +50,11 @@ struct Problem {
     // k3, r2max; lens.h) through which the voxels are projected.  Null = pin-hole cameras.  The host route hands such a problem to the *_lens
     // kernels (unproject_lens.hip, unproject_lens_geom.hip); the plane backward builds its tap table through the records and runs as it is.
     const float *lens = nullptr;
+    // Cross-view variance: 1 = the volume holds the population variance of the participating views' samples (C channels),
+    // 2 = their mean and that variance (2C channels: mean first).  0 = the first-order aggregate of `method`.  The participating set is every
+    // present view, or -- with `visible` -- the present views that see the voxel.  The host route hands such a problem to the *_moments kernels
+    // (unproject_moments.hip, unproject_moments_geom.hip): the gather family with the per-tap scatter backward.
+    int moments = 0;
 };
 
 inline Gate make_gate(const Problem &p, bool wants_brick) { return Gate{p.gate_count, p.gate_limit, wants_brick ? 1 : 0}; }
@@ -244,6 +249,22 @@ hipError_t launch_bwd_gather_lens_det(const void *grad_out, const void *featT, c
 hipError_t launch_plane_taps_lens(const float *proj, const Coords &coords, void *tabW, int *tabX, int *cmax, const Problem &p, hipStream_t s);
 hipError_t launch_bwd_geom_lens_kernel(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part,
                                        float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
+
+// cross-view variance (unproject_moments.hip, unproject_moments_geom.hip; Problem::moments): the gather forward, the per-tap scatter backward of
+// both modes, the deterministic scale pass -- its bound carries both halves of grad_out and the features' maximum (moments_det_scale_bytes: four
+// words per (b, c), moments_det_exponents finds K, then a visible problem's tap marks) -- and the moments instances of k_bwd_geom
+// (launch_bwd_geom[_cuboid] call this for them).  out / grad_out hold moments * C channels.
+hipError_t launch_fwd_gather_moments(const void *featT, const float *proj, const Coords &coords, void *out, const Problem &p, hipStream_t s);
+hipError_t launch_bwd_gather_moments(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *gradT, const Problem &p,
+                                     hipStream_t s);
+hipError_t launch_bwd_gather_moments_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
+                                         const int *kexp, const Problem &p, hipStream_t s);
+size_t moments_det_scale_bytes(const Problem &p);
+hipError_t launch_det_scale_moments(const void *grad_out, const void *featT, void *scale, const Problem &p, hipStream_t s, const float *proj,
+                                    const Coords *coords);
+const int *moments_det_exponents(const void *scale, const Problem &p);
+hipError_t launch_bwd_geom_moments_kernel(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part,
+                                          float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
 
 // view masks (view_mask.hip): from mask (B,V) bytes, one thread per sample writes n_b (B ints), slot -> view and view -> slot (-1: masked)
 // tables (B,V ints each) and the projections packed into slot order (absent slots zero); then per-(sample, slot) copies of `bytes_per_view`

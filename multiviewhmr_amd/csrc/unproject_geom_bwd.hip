@@ -377,6 +377,7 @@ template <bool POSE>
 static hipError_t geom_dispatch(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_coords,
                                 float *pose_part, float *wpart, const Problem &p, hipStream_t s)
 {
+    if (p.moments) return launch_bwd_geom_moments_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, POSE, p, s);   // cross-view variance: unproject_moments_geom.hip
     if (p.view_weights) return launch_bwd_geom_weighted_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, wpart, POSE, p, s);
     if (p.confidence) return launch_bwd_geom_conf_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, POSE, p, s);
     if (p.visible) return launch_bwd_geom_seen_kernel(grad_out, featT, proj, coords, part, grad_coords, pose_part, POSE, p, s);

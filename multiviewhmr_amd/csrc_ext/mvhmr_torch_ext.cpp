@@ -7,7 +7,8 @@
 // (visibility-aware aggregation: the *_visible entry points, view_mask nullable, no weights), then `Tensor? view_confidence` (per-pixel confidence maps
 // (B, V, Hf, Wf) fp32: the *_confidence entry points, which take visible_only as a flag; the geometry ops also `Tensor(b!)? grad_confidence`, the tensor they
 // write the gradient w.r.t. the maps into), and last of all `Tensor? feature_index` (shared feature maps: the *_shared entry points; (M,) int32, the volumes'
-// tensors then hold M entries) and `Tensor? lens` (lens distortion: the *_lens entry points; (B, V, 10) fp32 records); mvhmr_visibility::view_visibility[_cuboid] return the
+// tensors then hold M entries) and `Tensor? lens` (lens distortion: the *_lens entry points; (B, V, 10) fp32 records), in front of those two `int moments` (the cross-view variance: the *_moments entry
+// points; 1 = the variance, 2 = mean and variance in 2C channels; view_mask and visible_only compose, nothing else); mvhmr_visibility::view_visibility[_cuboid] return the
 // (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
 // tensor checks, descriptor, output and workspace from the caching allocator, the current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
@@ -66,7 +67,7 @@ void check_tensor(const at::Tensor &t, const at::Tensor &features, const char *n
 // coords (tensor ops) or rot + center (cuboid ops) describe the volume; grad_out is undefined for a forward.
 // M volumes: the tensors that place the volume and grad_out are per volume (M == B without a feature_index)
 void check_inputs(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *coords,
-                  const at::Tensor *rot, const at::Tensor *center, const at::Tensor *grad_out, int64_t M)
+                  const at::Tensor *rot, const at::Tensor *center, const at::Tensor *grad_out, int64_t M, int64_t halves = 1)
 {
     const int64_t B = d.batch, V = d.views, C = d.channels, H = d.feat_h, W = d.feat_w;
     const bool shared = M != B;                                 // (the messages name the leading extent the tensor is checked against)
@@ -87,7 +88,8 @@ void check_inputs(const mvhmr_unproject_desc &d, const at::Tensor &features, con
     if (center)
         check_tensor(*center, features, shared ? "center (M, 3)" : "center (B, 3)", at::kFloat, M * 3);
     if (grad_out)
-        check_tensor(*grad_out, features, shared ? "grad_out (M, C, X, Y, Z)" : "grad_out (B, C, X, Y, Z)", scalar_of(d.out_dtype), M * C * d.vol_x * d.vol_y * d.vol_z);
+        check_tensor(*grad_out, features, shared ? "grad_out (M, C, X, Y, Z)" : "grad_out (B, C, X, Y, Z)", scalar_of(d.out_dtype),
+                     M * halves * C * d.vol_x * d.vol_y * d.vol_z);     // (halves: 2 for the mean and the variance of a moments call)
 }
 
 
@@ -122,7 +124,11 @@ struct ViewArgs {
     const int32_t *index = nullptr;                             // the *_shared entry points: `volumes` volumes read the samples through feature_index
     int32_t volumes = 0;                                        // (the library refuses the selections above beside an index, each with its own text)
     const float *lens = nullptr;                                // the *_lens entry points: (B, V, 10) lens records (the library refuses everything above beside them)
+    int32_t moments = 0;                                        // the *_moments entry points: the cross-view variance (1) or mean and variance (2); mask and visible compose
 };
+
+// the channels of out / grad_out per feature channel: 2 for the mean and the variance
+int64_t halves_of(int64_t moments) { return moments == MVHMR_MOMENTS_MEANVAR ? 2 : 1; }
 
 // shared feature maps (mvhmr_unproject_*_shared): feature_index (M,) int32 on the features' device; null for None
 int64_t volumes_of(const c10::optional<at::Tensor> &feature_index, int64_t B)
@@ -140,7 +146,7 @@ const float *confidence_ptr(const mvhmr_unproject_desc &d, const at::Tensor &fea
 
 ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_mask,
                    const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence,
-                   const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens)
+                   const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens, int64_t moments)
 {
     ViewArgs v{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights), visible_only,
                confidence_ptr(d, features, view_confidence, "view_confidence (B, V, Hf, Wf)")};
@@ -155,6 +161,9 @@ ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, co
         check_tensor(*lens, features, "lens (B, V, 10)", at::kFloat, (int64_t)d.batch * d.views * 10);
         v.lens = lens->data_ptr<float>();
     }
+    v.moments = (int32_t)moments;
+    TORCH_CHECK(!moments || (!v.weights && !v.confidence && !v.index && !v.lens),
+                "mvhmr_unproject: the cross-view variance takes a view mask and visible_only only (view_weights, view_confidence, feature_index and lens are not built yet)");
     TORCH_CHECK(!(v.visible && v.weights), "mvhmr_unproject: visible_only does not take view_weights");
     TORCH_CHECK(!(v.confidence && v.weights), "mvhmr_unproject: view_confidence does not take view_weights");
     return v;
@@ -203,9 +212,9 @@ struct TensorVolume {
     {
         return coords_desc(coords, a.B, a.V, a.C, a.H, a.W, a.method, a.feat_dtype, a.out_dtype, a.layout, a.variant, a.M);
     }
-    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out, int64_t M) const
+    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out, int64_t M, int64_t halves) const
     {
-        check_inputs(d, features, proj, &coords, nullptr, nullptr, grad_out, M);
+        check_inputs(d, features, proj, &coords, nullptr, nullptr, grad_out, M, halves);
     }
     int visibility(const mvhmr_unproject_desc &d, const float *proj, const uint8_t *mask, int32_t *bits, hipStream_t s) const
     {
@@ -216,6 +225,7 @@ struct TensorVolume {
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.moments) return mvhmr_unproject_forward_moments_workspace_bytes(&d);
         if (v.lens) return mvhmr_unproject_forward_lens_workspace_bytes(&d);
         if (v.index) return mvhmr_unproject_forward_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_forward_confidence_workspace_bytes(&d);
@@ -227,6 +237,7 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.moments) return mvhmr_unproject_forward_moments(&d, features, proj, c, mask, v.visible, v.moments, out, ws, n, s);
         if (v.lens) return mvhmr_unproject_forward_lens(&d, features, proj, c, v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, out, ws, n, s);
         if (v.index) return mvhmr_unproject_forward_shared(&d, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, out, ws, n, s);
         if (v.confidence) return mvhmr_unproject_forward_confidence(&d, features, proj, c, mask, v.confidence, v.visible, out, ws, n, s);
@@ -236,6 +247,7 @@ struct TensorVolume {
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.moments) return det ? mvhmr_unproject_backward_deterministic_moments_workspace_bytes(&d) : mvhmr_unproject_backward_moments_workspace_bytes(&d);
         if (v.lens) return det ? mvhmr_unproject_backward_deterministic_lens_workspace_bytes(&d) : mvhmr_unproject_backward_lens_workspace_bytes(&d);
         if (v.index) return det ? mvhmr_unproject_backward_deterministic_shared_workspace_bytes(&d, v.volumes) : mvhmr_unproject_backward_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return det ? mvhmr_unproject_backward_deterministic_confidence_workspace_bytes(&d) : mvhmr_unproject_backward_confidence_workspace_bytes(&d);
@@ -249,6 +261,8 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.moments)
+            return (det ? mvhmr_unproject_backward_deterministic_moments : mvhmr_unproject_backward_moments)(&d, grad_out, features, proj, c, mask, v.visible, v.moments, grad, ws, n, s);
         if (v.lens)
             return (det ? mvhmr_unproject_backward_deterministic_lens : mvhmr_unproject_backward_lens)(&d, grad_out, features, proj, c, v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, grad, ws, n, s);
         if (v.index)
@@ -265,6 +279,7 @@ struct TensorVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.moments) return mvhmr_unproject_backward_geometry_moments_workspace_bytes(&d);
         if (v.lens) return mvhmr_unproject_backward_geometry_lens_workspace_bytes(&d);
         if (v.index) return mvhmr_unproject_backward_geometry_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_backward_geometry_confidence_workspace_bytes(&d);
@@ -277,6 +292,7 @@ struct TensorVolume {
     {
         const float *c = coords.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.moments) return mvhmr_unproject_backward_geometry_moments(&d, grad_out, features, proj, c, mask, v.visible, v.moments, g[0], g[1], ws, n, s);
         if (v.lens) return mvhmr_unproject_backward_geometry_lens(&d, grad_out, features, proj, c, v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, g[0], g[1], ws, n, s);
         if (v.index) return mvhmr_unproject_backward_geometry_shared(&d, grad_out, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, g[0], g[1], ws, n, s);
         if (v.confidence)
@@ -299,9 +315,9 @@ struct CuboidVolume {
     {
         return cuboid_desc(position, sides, vol, a.B, a.V, a.C, a.H, a.W, a.method, a.feat_dtype, a.out_dtype, a.layout, a.variant);
     }
-    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out, int64_t M) const
+    void check(const mvhmr_unproject_desc &d, const at::Tensor &features, const at::Tensor &proj, const at::Tensor *grad_out, int64_t M, int64_t halves) const
     {
-        check_inputs(d, features, proj, nullptr, &rot, &center, grad_out, M);
+        check_inputs(d, features, proj, nullptr, &rot, &center, grad_out, M, halves);
     }
     int visibility(const mvhmr_unproject_desc &d, const float *proj, const uint8_t *mask, int32_t *bits, hipStream_t s) const
     {
@@ -312,6 +328,7 @@ struct CuboidVolume {
 
     size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.moments) return mvhmr_unproject_forward_cuboid_moments_workspace_bytes(&d);
         if (v.lens) return mvhmr_unproject_forward_cuboid_lens_workspace_bytes(&d);
         if (v.index) return mvhmr_unproject_forward_cuboid_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_forward_cuboid_confidence_workspace_bytes(&d);
@@ -323,6 +340,7 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.moments) return mvhmr_unproject_forward_cuboid_moments(&d, features, proj, r, c, position.data(), sides.data(), mask, v.visible, v.moments, out, ws, n, s);
         if (v.lens)
             return mvhmr_unproject_forward_cuboid_lens(&d, features, proj, r, c, position.data(), sides.data(), v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, out, ws, n, s);
         if (v.index) return mvhmr_unproject_forward_cuboid_shared(&d, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, out, ws, n, s);
@@ -336,6 +354,7 @@ struct CuboidVolume {
     }
     size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
     {
+        if (v.moments) return det ? mvhmr_unproject_backward_cuboid_deterministic_moments_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_moments_workspace_bytes(&d);
         if (v.lens) return det ? mvhmr_unproject_backward_cuboid_deterministic_lens_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_lens_workspace_bytes(&d);
         if (v.index)
             return det ? mvhmr_unproject_backward_cuboid_deterministic_shared_workspace_bytes(&d, v.volumes) : mvhmr_unproject_backward_cuboid_shared_workspace_bytes(&d, v.volumes);
@@ -353,6 +372,9 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.moments)
+            return (det ? mvhmr_unproject_backward_cuboid_deterministic_moments : mvhmr_unproject_backward_cuboid_moments)(
+                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.visible, v.moments, grad, ws, n, s);
         if (v.lens)
             return (det ? mvhmr_unproject_backward_cuboid_deterministic_lens : mvhmr_unproject_backward_cuboid_lens)(
                 &d, grad_out, features, proj, r, c, position.data(), sides.data(), v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, grad, ws, n, s);
@@ -376,6 +398,7 @@ struct CuboidVolume {
     }
     size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
     {
+        if (v.moments) return mvhmr_unproject_backward_geometry_cuboid_moments_workspace_bytes(&d);
         if (v.lens) return mvhmr_unproject_backward_geometry_cuboid_lens_workspace_bytes(&d);
         if (v.index) return mvhmr_unproject_backward_geometry_cuboid_shared_workspace_bytes(&d, v.volumes);
         if (v.confidence) return mvhmr_unproject_backward_geometry_cuboid_confidence_workspace_bytes(&d);
@@ -388,6 +411,9 @@ struct CuboidVolume {
     {
         const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
         const uint8_t *mask = v.mask;
+        if (v.moments)
+            return mvhmr_unproject_backward_geometry_cuboid_moments(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.visible, v.moments, g[0], g[1], g[2],
+                                                                    ws, n, s);
         if (v.lens)
             return mvhmr_unproject_backward_geometry_cuboid_lens(&d, grad_out, features, proj, r, c, position.data(), sides.data(), v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, g[0], g[1], g[2], ws, n, s);
         if (v.index)
@@ -411,12 +437,12 @@ struct CuboidVolume {
 template <typename Volume>
 at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a, const c10::optional<at::Tensor> &view_mask,
                    const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence,
-                   const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens)
+                   const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens, int64_t moments)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
-    vol.check(d, features, proj, nullptr, a.M);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens);
-    at::Tensor out = at::empty({a.M, a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
+    vol.check(d, features, proj, nullptr, a.M, halves_of(moments));
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
+    at::Tensor out = at::empty({a.M, halves_of(moments) * a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
     run(features, vol.forward_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
         return vol.forward(d, features.data_ptr(), proj.data_ptr<float>(), views, out.data_ptr(), ws, n, s);
     });
@@ -428,11 +454,11 @@ template <typename Volume>
 at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const DescArgs &a,
                     const c10::optional<at::Tensor> &view_mask, bool deterministic, const c10::optional<at::Tensor> &view_weights, bool visible_only,
                     const c10::optional<at::Tensor> &view_confidence, const c10::optional<at::Tensor> &feature_index,
-                    const c10::optional<at::Tensor> &lens)
+                    const c10::optional<at::Tensor> &lens, int64_t moments)
 {
     const mvhmr_unproject_desc d = vol.desc(a);
-    vol.check(d, features, proj, &grad_out, a.M);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens);
+    vol.check(d, features, proj, &grad_out, a.M, halves_of(moments));
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
     at::Tensor grad = new_feature_grad(d, features);
     run(features, vol.backward_bytes(d, views, deterministic), deterministic, [&](void *ws, size_t n, hipStream_t s) {
         return vol.backward(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, deterministic, grad.data_ptr(), ws, n, s);
@@ -447,14 +473,14 @@ std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &g
                                           std::initializer_list<bool> want, const c10::optional<at::Tensor> &view_mask,
                                           const c10::optional<at::Tensor> &view_weights, const c10::optional<at::Tensor> &grad_weights, bool visible_only,
                                           const c10::optional<at::Tensor> &view_confidence, const c10::optional<at::Tensor> &grad_confidence,
-                                          const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens)
+                                          const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens, int64_t moments)
 {
     const bool want_weights = grad_weights && grad_weights->defined();
     const bool want_conf = grad_confidence && grad_confidence->defined();
     TORCH_CHECK(want_weights || want_conf || std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
     const mvhmr_unproject_desc d = vol.desc(a);
-    vol.check(d, features, proj, &grad_out, a.M);
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens);
+    vol.check(d, features, proj, &grad_out, a.M, halves_of(moments));
+    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
     TORCH_CHECK(!want_weights || views.weights, "mvhmr_unproject: grad_weights needs view_weights");
     TORCH_CHECK(!want_conf || views.confidence, "mvhmr_unproject: grad_confidence needs view_confidence");
     float *gw = const_cast<float *>(weights_ptr(d, features, grad_weights, "grad_weights (B, V)"));
@@ -512,19 +538,19 @@ at::Tensor view_visibility_cuboid_native(const at::Tensor &proj, const at::Tenso
 at::Tensor unprojection_native(const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords, int64_t B, int64_t V, int64_t C,
                                int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
                                const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence,
-                               const OptTensor &feature_index, const OptTensor &lens)
+                               int64_t moments, const OptTensor &feature_index, const OptTensor &lens)
 {
     return forward(TensorVolume{coords}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask, view_weights,
-                   visible_only, view_confidence, feature_index, lens);
+                   visible_only, view_confidence, feature_index, lens, moments);
 }
 
 at::Tensor unprojection_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &coords,
                                         int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method, int64_t feat_dtype,
                                         int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask, bool deterministic,
-                                        const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence, const OptTensor &feature_index, const OptTensor &lens)
+                                        const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence, int64_t moments, const OptTensor &feature_index, const OptTensor &lens)
 {
     return backward(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask,
-                    deterministic, view_weights, visible_only, view_confidence, feature_index, lens);
+                    deterministic, view_weights, visible_only, view_confidence, feature_index, lens, moments);
 }
 
 std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj,
@@ -533,10 +559,10 @@ std::tuple<at::Tensor, at::Tensor> unprojection_backward_geometry_native(const a
                                                                           int64_t variant, bool want_proj, bool want_coords, const OptTensor &view_mask,
                                                                           const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only,
                                                                           const OptTensor &view_confidence, const OptTensor &grad_confidence,
-                                                                          const OptTensor &feature_index, const OptTensor &lens)
+                                                                          int64_t moments, const OptTensor &feature_index, const OptTensor &lens)
 {
     const auto g = backward_geometry(TensorVolume{coords}, grad_out, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)},
-                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index, lens);
+                                     {want_proj, want_coords}, view_mask, view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index, lens, moments);
     return {g[0], g[1]};
 }
 
@@ -544,10 +570,10 @@ at::Tensor unprojection_cuboid_native(const at::Tensor &features, const at::Tens
                                       at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C,
                                       int64_t H, int64_t W, int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant,
                                       const OptTensor &view_mask, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence,
-                                      const OptTensor &feature_index, const OptTensor &lens)
+                                      int64_t moments, const OptTensor &feature_index, const OptTensor &lens)
 {
     return forward(CuboidVolume{rot, center, position, sides, vol}, features, proj, DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)},
-                   view_mask, view_weights, visible_only, view_confidence, feature_index, lens);
+                   view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
 }
 
 at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const at::Tensor &features, const at::Tensor &proj, const at::Tensor &rot,
@@ -555,10 +581,10 @@ at::Tensor unprojection_cuboid_backward_native(const at::Tensor &grad_out, const
                                                at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W, int64_t method,
                                                int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, const OptTensor &view_mask,
                                                bool deterministic, const OptTensor &view_weights, bool visible_only, const OptTensor &view_confidence,
-                                               const OptTensor &feature_index, const OptTensor &lens)
+                                               int64_t moments, const OptTensor &feature_index, const OptTensor &lens)
 {
     return backward(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
-                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask, deterministic, view_weights, visible_only, view_confidence, feature_index, lens);
+                    DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, view_mask, deterministic, view_weights, visible_only, view_confidence, feature_index, lens, moments);
 }
 
 std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geometry_native(
@@ -566,11 +592,11 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> unprojection_cuboid_backward_geom
     at::ArrayRef<double> position, at::ArrayRef<double> sides, at::IntArrayRef vol, int64_t B, int64_t V, int64_t C, int64_t H, int64_t W,
     int64_t method, int64_t feat_dtype, int64_t out_dtype, int64_t layout, int64_t variant, bool want_proj, bool want_rot, bool want_center,
     const OptTensor &view_mask, const OptTensor &view_weights, const OptTensor &grad_weights, bool visible_only, const OptTensor &view_confidence,
-    const OptTensor &grad_confidence, const OptTensor &feature_index, const OptTensor &lens)
+    const OptTensor &grad_confidence, int64_t moments, const OptTensor &feature_index, const OptTensor &lens)
 {
     const auto g = backward_geometry(CuboidVolume{rot, center, position, sides, vol}, grad_out, features, proj,
                                      DescArgs{B, V, C, H, W, method, feat_dtype, out_dtype, layout, variant, volumes_of(feature_index, B)}, {want_proj, want_rot, want_center}, view_mask,
-                                     view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index, lens);
+                                     view_weights, grad_weights, visible_only, view_confidence, grad_confidence, feature_index, lens, moments);
     return {g[0], g[1], g[2]};
 }
 
@@ -640,7 +666,7 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(c
 #define MVHMR_VISIBLE_ARG ", bool visible_only=False"
 #define MVHMR_CONF_ARG ", Tensor? view_confidence=None"
 #define MVHMR_GRAD_CONF_ARG ", Tensor(b!)? grad_confidence=None"
-#define MVHMR_INDEX_ARG ", Tensor? feature_index=None, Tensor? lens=None"
+#define MVHMR_INDEX_ARG ", int moments=0, Tensor? feature_index=None, Tensor? lens=None"      // (moments: the cross-view variance; the index and the lens stay last)
 
 TORCH_LIBRARY(mvhmr_native, m)
 {
