@@ -650,6 +650,77 @@ int mvhmr_unproject_backward_geometry_cuboid_lens(const mvhmr_unproject_desc *de
         const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,        float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream);
 
 /*
+ * The call record (additive within ABI 4): every un-projection call above as one struct, and the way in for new callers.
+ * A named entry point fills a record from its arguments and calls the matching *_call function: the name's suffix is `family`, its
+ * _cuboid infix is `placing`, its _deterministic infix is `deterministic`, its arguments are the fields.  Zero the record, set
+ * struct_size = sizeof(mvhmr_unproject_call), then the fields the family takes:
+ *
+ *   family                    takes (beside features, proj, the placing and the outputs)    a null / zero field
+ *   MVHMR_FAMILY_PLAIN        --
+ *   MVHMR_FAMILY_MASKED       view_mask                                                      null mask: the plain call
+ *   MVHMR_FAMILY_WEIGHTED     view_mask, view_weights; geometry: grad_weights                null weights: the masked (or plain) call
+ *   MVHMR_FAMILY_VISIBLE      view_mask (the seeing test is always on)                       null mask: every view present
+ *   MVHMR_FAMILY_CONFIDENCE   view_mask, view_confidence, visible; geometry: grad_confidence null maps: the visible / masked call, by `visible`
+ *   MVHMR_FAMILY_SHARED       volumes, feature_index                                         null index: volumes == batch, the plain GATHER call
+ *   MVHMR_FAMILY_LENS         lens                                                           null lens: the plain GATHER call
+ *   MVHMR_FAMILY_MOMENTS      view_mask, visible, moments                                    moments 0: MVHMR_ERR_INVALID_ARGUMENT
+ *
+ * SHARED also carries view_mask, view_weights, view_confidence and visible, LENS those and feature_index: the selections that do not compose
+ * with them yet, each refused with its own text (MVHMR_ERR_UNSUPPORTED).  Any other optional input a family does not take must be null / 0
+ * (MVHMR_ERR_INVALID_ARGUMENT), and so must struct_size, family and placing be known values.  Everything else -- validation order, refusal
+ * texts, kernels, bits, workspace sizes -- is that of the named call the record spells.
+ * Placing: MVHMR_PLACING_TENSOR reads coords, MVHMR_PLACING_CUBOID rot, center and the HOST pointers position and sides (3 doubles each).
+ * Per kind: forward reads features, proj and writes out; backward reads grad_out, features, proj and writes grad_features (bitwise
+ * reproducible with `deterministic`); backward_geometry reads the same and writes grad_proj and grad_coords (tensor) or grad_rot, grad_center
+ * (cuboid), grad_weights, grad_confidence -- each nullable, at least one given.
+ * mvhmr_unproject_call_workspace_bytes answers from the descriptor and the record's family, placing, volumes and deterministic alone: it
+ * reads no device pointer, so a record with only those fields set will do.
+ */
+typedef enum mvhmr_family_t {
+    MVHMR_FAMILY_PLAIN = 0,
+    MVHMR_FAMILY_MASKED = 1,
+    MVHMR_FAMILY_WEIGHTED = 2,
+    MVHMR_FAMILY_VISIBLE = 3,
+    MVHMR_FAMILY_CONFIDENCE = 4,
+    MVHMR_FAMILY_SHARED = 5,
+    MVHMR_FAMILY_LENS = 6,
+    MVHMR_FAMILY_MOMENTS = 7
+} mvhmr_family_t;
+typedef enum mvhmr_placing_t { MVHMR_PLACING_TENSOR = 0, MVHMR_PLACING_CUBOID = 1 } mvhmr_placing_t;
+typedef enum mvhmr_call_kind_t { MVHMR_CALL_FORWARD = 0, MVHMR_CALL_BACKWARD = 1, MVHMR_CALL_GEOMETRY = 2 } mvhmr_call_kind_t;
+
+typedef struct mvhmr_unproject_call {
+    uint32_t struct_size;                       /* sizeof(mvhmr_unproject_call) */
+    int32_t family;                             /* mvhmr_family_t */
+    int32_t placing;                            /* mvhmr_placing_t */
+    int32_t deterministic;                      /* backward only: non-zero = the deterministic form */
+    int32_t volumes;                            /* SHARED: M */
+    int32_t visible;                            /* CONFIDENCE, MOMENTS: non-zero = the seeing test */
+    int32_t moments;                            /* MOMENTS: mvhmr_moments_t */
+    int32_t reserved;                           /* 0 */
+    const float *coords;                        /* tensor placing */
+    const float *rot, *center;                  /* cuboid placing */
+    const double *position, *sides;             /*   (host, 3 doubles each) */
+    const uint8_t *view_mask;
+    const float *view_weights, *view_confidence;
+    const int32_t *feature_index;
+    const float *lens;
+    const void *features;
+    const float *proj;
+    const void *grad_out;
+    void *out, *grad_features;
+    float *grad_proj, *grad_coords, *grad_rot, *grad_center, *grad_weights, *grad_confidence;
+} mvhmr_unproject_call;
+
+size_t mvhmr_unproject_call_workspace_bytes(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, int kind /* mvhmr_call_kind_t */);
+int mvhmr_unproject_forward_call(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, void *workspace, size_t workspace_bytes,
+                                 void *hip_stream);
+int mvhmr_unproject_backward_call(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, void *workspace, size_t workspace_bytes,
+                                  void *hip_stream);
+int mvhmr_unproject_backward_geometry_call(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, void *workspace,
+                                           size_t workspace_bytes, void *hip_stream);
+
+/*
  * Layout pass on its own: features (B,V,C,Hf,Wf) -> dst in `dst_layout` (MVHMR_LAYOUT_BVHWC with the channel
  * count rounded up to a multiple of 4 and zero padded, or MVHMR_LAYOUT_QUAD), desc->feat_dtype.
  * desc->feat_layout names the SOURCE: MVHMR_LAYOUT_BVCHW (also assumed for MVHMR_LAYOUT_QUAD descriptors, as before), or

@@ -33,7 +33,8 @@ EXPORTS = (
 ) + tuple("mvhmr_unproject_%s_%s%s" % (n, tag, w) for n in ("forward", "forward_cuboid", "backward", "backward_cuboid", "backward_deterministic",
                                                            "backward_cuboid_deterministic", "backward_geometry", "backward_geometry_cuboid")
           for w in ("", "_workspace_bytes")       # per-sample view masks, per-view confidence weights, visibility-aware aggregation, per-pixel confidence maps, shared feature maps, lens distortion, cross-view variance
-          for tag in ("masked", "weighted", "visible", "confidence", "shared", "lens", "moments")) + ("mvhmr_unproject_visibility", "mvhmr_unproject_visibility_cuboid")
+          for tag in ("masked", "weighted", "visible", "confidence", "shared", "lens", "moments")) + ("mvhmr_unproject_visibility", "mvhmr_unproject_visibility_cuboid") + (
+    "mvhmr_unproject_call_workspace_bytes", "mvhmr_unproject_forward_call", "mvhmr_unproject_backward_call", "mvhmr_unproject_backward_geometry_call")
 
 
 class Desc(ctypes.Structure):
@@ -41,6 +42,41 @@ class Desc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "abi_version", "batch", "views", "channels", "feat_h", "feat_w", "vol_x", "vol_y", "vol_z",
         "method", "feat_dtype", "out_dtype", "feat_layout", "variant")]
+
+
+class Call(ctypes.Structure):
+    """struct mvhmr_unproject_call: zero it, set struct_size, family, placing and the fields the family takes"""
+    _fields_ = ([("struct_size", ctypes.c_uint32)] +
+                [(n, ctypes.c_int32) for n in ("family", "placing", "deterministic", "volumes", "visible", "moments", "reserved")] +
+                [(n, ctypes.c_void_p) for n in (
+                    "coords", "rot", "center", "position", "sides", "view_mask", "view_weights", "view_confidence", "feature_index", "lens",
+                    "features", "proj", "grad_out", "out", "grad_features",
+                    "grad_proj", "grad_coords", "grad_rot", "grad_center", "grad_weights", "grad_confidence")])
+
+
+FAMILY = {"plain": 0, "masked": 1, "weighted": 2, "visible": 3, "confidence": 4, "shared": 5, "lens": 6, "moments": 7}     # mvhmr_family_t
+PLACING_TENSOR, PLACING_CUBOID = 0, 1                     # mvhmr_placing_t
+CALL_FORWARD, CALL_BACKWARD, CALL_GEOMETRY = 0, 1, 2      # mvhmr_call_kind_t
+
+_vp, _i32, _int = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int
+# named family -> (its arguments behind the placing, geometry outputs beyond the placing's own, the queries take `volumes`)
+FAMILIES = {
+    "masked": ([_vp], 0, False),                                      # view_mask
+    "weighted": ([_vp, _vp], 1, False),                               # view_mask, view_weights; grad_weights
+    "visible": ([_vp], 0, False),                                     # view_mask (nullable)
+    "confidence": ([_vp, _vp, _int], 1, False),                       # view_mask, view_confidence, visible; grad_confidence
+    "shared": ([_i32, _vp, _vp, _vp, _vp, _int], 0, True),            # volumes, feature_index, then the refused view_mask, view_weights, view_confidence, visible
+    "lens": ([_vp, _vp, _vp, _vp, _int, _vp], 0, False),              # lens, then the refused view_mask, view_weights, view_confidence, visible, feature_index
+    "moments": ([_vp, _i32, _i32], 0, False),                         # view_mask, visible, moments
+}
+
+
+def record(family, placing=PLACING_TENSOR, **fields):
+    """A zeroed Call of one family with the given fields set (pointers as integers or ctypes pointers cast to c_void_p)."""
+    c = Call(struct_size=ctypes.sizeof(Call), family=FAMILY[family], placing=placing)
+    for name, value in fields.items():
+        setattr(c, name, value)
+    return c
 
 
 _lib = None
@@ -131,78 +167,31 @@ def lib():
     L.mvhmr_build_coord_volumes.restype = ctypes.c_int
     L.mvhmr_build_coord_volumes.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(ctypes.c_double),
                                             ctypes.POINTER(ctypes.c_double), vp]
-    # the *_weighted family: the *_masked signatures with view_weights behind view_mask, the geometry calls also with grad_weights
+    # the named families: every launching signature is lead + placing + the family's own arguments + the outputs + (workspace, bytes, stream)
+    for tag, (middle, extra_outs, query_takes_volumes) in FAMILIES.items():
+        for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
+            for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
+                                     ("backward%s_deterministic" % vol, [dp, vp, vp, vp], 1),
+                                     ("backward_geometry" + vol, [dp, vp, vp, vp], (3 if vol else 2) + extra_outs)):
+                fn = getattr(L, "mvhmr_unproject_%s_%s" % (name, tag))
+                fn.restype = ctypes.c_int
+                fn.argtypes = lead + place + middle + [vp] * outs + [vp, sz, vp]
+                q = getattr(L, "mvhmr_unproject_%s_%s_workspace_bytes" % (name, tag))
+                q.restype = sz
+                q.argtypes = [dp, i32] if query_takes_volumes else [dp]
+    # the visibility bits: (desc, proj, placing, view_mask, bits, stream)
     for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
-        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
-                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
-                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 4 if vol else 3)):
-            fn = getattr(L, "mvhmr_unproject_%s_weighted" % name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = lead + place + [vp, vp] + [vp] * outs + [vp, sz, vp]
-            q = getattr(L, "mvhmr_unproject_%s_weighted_workspace_bytes" % name)
-            q.restype = sz
-            q.argtypes = [dp]
-    # the *_visible family: the *_masked signatures (view_mask nullable); then the visibility bits (desc, proj, placing, view_mask, bits, stream)
-    for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
-        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
-                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
-                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 3 if vol else 2)):
-            fn = getattr(L, "mvhmr_unproject_%s_visible" % name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = lead + place + [vp] + [vp] * outs + [vp, sz, vp]
-            q = getattr(L, "mvhmr_unproject_%s_visible_workspace_bytes" % name)
-            q.restype = sz
-            q.argtypes = [dp]
         fn = getattr(L, "mvhmr_unproject_visibility" + vol)
         fn.restype = ctypes.c_int
         fn.argtypes = [dp, vp] + place + [vp, vp, vp]
-    # the *_confidence family: the *_visible signatures with view_confidence and the flag `visible` behind view_mask, the geometry calls also
-    # with grad_confidence
-    for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
-        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
-                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
-                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 4 if vol else 3)):
-            fn = getattr(L, "mvhmr_unproject_%s_confidence" % name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = lead + place + [vp, vp, ctypes.c_int] + [vp] * outs + [vp, sz, vp]
-            q = getattr(L, "mvhmr_unproject_%s_confidence_workspace_bytes" % name)
-            q.restype = sz
-            q.argtypes = [dp]
-    # the *_shared family: the plain signatures with volumes, feature_index and the (refused) view selections view_mask, view_weights,
-    # view_confidence, visible behind what places the volume; the queries take volumes too
-    for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
-        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
-                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
-                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 3 if vol else 2)):
-            fn = getattr(L, "mvhmr_unproject_%s_shared" % name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = lead + place + [i32, vp, vp, vp, vp, ctypes.c_int] + [vp] * outs + [vp, sz, vp]
-            q = getattr(L, "mvhmr_unproject_%s_shared_workspace_bytes" % name)
-            q.restype = sz
-            q.argtypes = [dp, i32]
-    # the *_lens family: the plain signatures with lens and the (refused) selections view_mask, view_weights, view_confidence, visible,
-    # feature_index behind what places the volume
-    for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
-        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
-                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
-                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 3 if vol else 2)):
-            fn = getattr(L, "mvhmr_unproject_%s_lens" % name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = lead + place + [vp, vp, vp, vp, ctypes.c_int, vp] + [vp] * outs + [vp, sz, vp]
-            q = getattr(L, "mvhmr_unproject_%s_lens_workspace_bytes" % name)
-            q.restype = sz
-            q.argtypes = [dp]
-    # the *_moments family: the *_visible signatures with the flag `visible` and `moments` (MOMENTS_VAR / MOMENTS_MEANVAR) behind view_mask
-    for vol, place in (("", [vp]), ("_cuboid", [vp, vp, d3, d3])):
-        for name, lead, outs in (("forward" + vol, [dp, vp, vp], 1), ("backward" + vol, [dp, vp, vp, vp], 1),
-                                 ("backward%s_deterministic" % vol if vol else "backward_deterministic", [dp, vp, vp, vp], 1),
-                                 ("backward_geometry" + vol, [dp, vp, vp, vp], 3 if vol else 2)):
-            fn = getattr(L, "mvhmr_unproject_%s_moments" % name)
-            fn.restype = ctypes.c_int
-            fn.argtypes = lead + place + [vp, i32, i32] + [vp] * outs + [vp, sz, vp]
-            q = getattr(L, "mvhmr_unproject_%s_moments_workspace_bytes" % name)
-            q.restype = sz
-            q.argtypes = [dp]
+    # the call record: what every name above fills in; the way in for new callers
+    cp = ctypes.POINTER(Call)
+    L.mvhmr_unproject_call_workspace_bytes.restype = sz
+    L.mvhmr_unproject_call_workspace_bytes.argtypes = [dp, cp, ctypes.c_int]
+    for kind in ("forward", "backward", "backward_geometry"):
+        fn = getattr(L, "mvhmr_unproject_%s_call" % kind)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [dp, cp, vp, sz, vp]
     if L.mvhmr_abi_version() != ABI_VERSION:
         raise RuntimeError("libmvhmr_unproject.so speaks ABI %d, this binding %d: rebuild" %
                            (L.mvhmr_abi_version(), ABI_VERSION))

@@ -259,6 +259,52 @@ int open_call(const mvhmr_unproject_desc *desc, const VolumeSource &v, Problem *
     return rc != MVHMR_OK ? rc : make_coords(v, *p, coords);
 }
 
+// ---- the call record (include/mvhmr_unproject.h): what an entry point's name and arguments say, as the routes read it.
+// The rule of the families is written here once.  The view selections (mask, weights, seeing test, confidence maps, moments) select the
+// packed route of the families that take them; a shared or lens record carries them only to be refused (shared_refused, lens_refused).
+using Call = mvhmr_unproject_call;
+VolumeSource placing_of(const Call &c)
+{
+    return c.placing == MVHMR_PLACING_CUBOID ? cuboid_volume(c.rot, c.center, c.position, c.sides) : tensor_volume(c.coords);
+}
+bool selects_views(const Call &c) { return c.family != MVHMR_FAMILY_SHARED && c.family != MVHMR_FAMILY_LENS; }
+const uint8_t *mask_of(const Call &c) { return selects_views(c) ? c.view_mask : nullptr; }                // null: packs nothing
+const float *weights_of(const Call &c) { return selects_views(c) ? c.view_weights : nullptr; }            // null: the masked (or plain) call
+const float *confidence_of(const Call &c) { return selects_views(c) ? c.view_confidence : nullptr; }      // null: the visible or masked call
+bool seeing(const Call &c) { return c.family == MVHMR_FAMILY_VISIBLE || (selects_views(c) && c.visible); }  // a visible call: always
+int moments_of(const Call &c) { return c.family != MVHMR_FAMILY_MOMENTS ? 0 : c.moments ? c.moments : -1; }  // 0: refused as any other unknown value
+bool packed(const Call &c) { return mask_of(c) || weights_of(c); }
+// the optional inputs each family takes: a record that sets another one says what no named call can, and is refused
+enum : unsigned { kMask = 1, kWeights = 2, kConfidence = 4, kVisible = 8, kIndex = 16, kLens = 32, kMoments = 64 };
+constexpr unsigned kTakes[] = {0,                                                   // plain
+                               kMask,                                               // masked
+                               kMask | kWeights,                                    // weighted
+                               kMask | kVisible,                                    // visible (the seeing test is on whatever the flag says)
+                               kMask | kConfidence | kVisible,                      // confidence
+                               kIndex | kMask | kWeights | kConfidence | kVisible,  // shared (the last four: refused with their own texts)
+                               kLens | kMask | kWeights | kConfidence | kVisible | kIndex,     // lens (the last five likewise)
+                               kMask | kVisible | kMoments};                        // moments
+// struct_size, family and placing: what the workspace query checks too
+int check_record(const Call *c)
+{
+    if (!c) return fail(MVHMR_ERR_INVALID_ARGUMENT, "call record is null");
+    if (c->struct_size != sizeof(Call))
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "call record struct_size %u, library expects %zu", c->struct_size, sizeof(Call));
+    if (c->family < MVHMR_FAMILY_PLAIN || c->family > MVHMR_FAMILY_MOMENTS) return fail(MVHMR_ERR_INVALID_ARGUMENT, "unknown call family %d", c->family);
+    if (c->placing != MVHMR_PLACING_TENSOR && c->placing != MVHMR_PLACING_CUBOID) return fail(MVHMR_ERR_INVALID_ARGUMENT, "unknown placing %d", c->placing);
+    return MVHMR_OK;
+}
+int check_call(const Call *c)
+{
+    if (const int rc = check_record(c)) return rc;
+    const unsigned set = (c->view_mask ? kMask : 0) | (c->view_weights ? kWeights : 0) | (c->view_confidence ? kConfidence : 0) | (c->visible ? kVisible : 0) |
+                         (c->feature_index ? kIndex : 0) | (c->lens ? kLens : 0) | (c->moments ? kMoments : 0);
+    if (set & ~kTakes[c->family])
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "call family %d takes none of the optional inputs 0x%x the record sets (mask 1, weights 2, confidence 4, visible 8, "
+                                                "feature_index 16, lens 32, moments 64)", c->family, set & ~kTakes[c->family]);
+    return MVHMR_OK;
+}
+
 // ---- per-sample view masks (include/mvhmr_unproject.h).  k_view_table turns the mask into slot tables and the projections
 // packed into slot order, the features are packed the same way (absent slots zero), and the unmasked route runs on the packed problem with
 // Problem::view_count set: the gather family (forward, per-tap scatter backward, its deterministic form) and the geometry kernels.  Gradients
@@ -311,13 +357,6 @@ int confidence_refused(const mvhmr_unproject_desc *desc)
 // and the geometry kernels, which launch their *_shared kernels (Problem::feature_index).  Every feature-sized region stays sized by the
 // batch; only the geometry partials are per volume.  Refused where a mask is; the view selections (mask, weights, seeing test, confidence
 // maps) do not compose with the index yet and are refused each with its own text.  A null index with volumes == batch is the plain gather call.
-struct SharedIndex {
-    int32_t volumes;
-    const int32_t *index;
-    const uint8_t *mask;
-    const float *weights, *confidence;
-    int visible;
-};
 // the checks that need no index: what the workspace queries ask too
 int shared_shape_refused(const mvhmr_unproject_desc *desc, int32_t volumes)
 {
@@ -329,15 +368,15 @@ int shared_shape_refused(const mvhmr_unproject_desc *desc, int32_t volumes)
         return fail(MVHMR_ERR_UNSUPPORTED, "at most %d volumes per call (the volume index is the grid's y extent; got %d): split the call", kSharedMaxVolumes, volumes);
     return MVHMR_OK;
 }
-int shared_refused(const mvhmr_unproject_desc *desc, const SharedIndex &sh)
+int shared_refused(const mvhmr_unproject_desc *desc, const Call &c)
 {
-    if (sh.mask) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with a view mask is not built yet: un-project the masked samples on their own");
-    if (sh.weights) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with view weights is not built yet: un-project the weighted samples on their own");
-    if (sh.visible) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with visibility-aware aggregation is not built yet: un-project those samples on their own");
-    if (sh.confidence) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with view confidence maps is not built yet: un-project those samples on their own");
-    if (const int rc = shared_shape_refused(desc, sh.volumes)) return rc;
-    if (!sh.index && sh.volumes != desc->batch)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, "a null feature_index is the plain call: volumes (%d) must equal batch (%d)", sh.volumes, desc->batch);
+    if (c.view_mask) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with a view mask is not built yet: un-project the masked samples on their own");
+    if (c.view_weights) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with view weights is not built yet: un-project the weighted samples on their own");
+    if (c.visible) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with visibility-aware aggregation is not built yet: un-project those samples on their own");
+    if (c.view_confidence) return fail(MVHMR_ERR_UNSUPPORTED, "feature_index with view confidence maps is not built yet: un-project those samples on their own");
+    if (const int rc = shared_shape_refused(desc, c.volumes)) return rc;
+    if (!c.feature_index && c.volumes != desc->batch)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "a null feature_index is the plain call: volumes (%d) must equal batch (%d)", c.volumes, desc->batch);
     return MVHMR_OK;
 }
 // ---- lens distortion (include/mvhmr_unproject.h): one Brown-Conrady record per (sample, view) through which the voxels are
@@ -346,13 +385,6 @@ int shared_refused(const mvhmr_unproject_desc *desc, const SharedIndex &sh)
 // Problem::lens to the *_lens kernels.  Nothing is packed or copied, no region is added.  The brick variant and the quad-planar layouts are
 // refused (a brick's window is bounded by the projective image of its corners, which does not hold under distortion); the view selections and
 // the feature index do not compose with the lens yet and are refused each with its own text.  A null lens is the plain gather call.
-struct LensArgs {
-    const float *lens;
-    const uint8_t *mask;
-    const float *weights, *confidence;
-    int visible;
-    const int32_t *index;
-};
 // the checks that need no pointer: what the workspace queries ask too
 int lens_shape_refused(const mvhmr_unproject_desc *desc)
 {
@@ -361,24 +393,15 @@ int lens_shape_refused(const mvhmr_unproject_desc *desc)
     if (desc->variant == MVHMR_VARIANT_BRICK) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
     return MVHMR_OK;
 }
-int lens_refused(const mvhmr_unproject_desc *desc, const LensArgs &la)
+int lens_refused(const mvhmr_unproject_desc *desc, const Call &c)
 {
-    if (la.mask) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with a view mask is not built yet: un-project the masked samples without a lens");
-    if (la.weights) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with view weights is not built yet: un-project the weighted samples without a lens");
-    if (la.visible) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with visibility-aware aggregation is not built yet: the seeing test is pin-hole");
-    if (la.confidence) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with view confidence maps is not built yet: un-project those samples without a lens");
-    if (la.index) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with a feature_index is not built yet: un-project the shared samples without a lens");
+    if (c.view_mask) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with a view mask is not built yet: un-project the masked samples without a lens");
+    if (c.view_weights) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with view weights is not built yet: un-project the weighted samples without a lens");
+    if (c.visible) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with visibility-aware aggregation is not built yet: the seeing test is pin-hole");
+    if (c.view_confidence) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with view confidence maps is not built yet: un-project those samples without a lens");
+    if (c.feature_index) return fail(MVHMR_ERR_UNSUPPORTED, "lens distortion with a feature_index is not built yet: un-project the shared samples without a lens");
     return lens_shape_refused(desc);
 }
-// what selects the packed route of a call, and whether the descriptor can take it
-struct Views {
-    const uint8_t *mask;
-    const float *weights;
-    bool visible = false;                       // the *_visible entry points (no weights there); a null mask packs nothing
-    const float *confidence = nullptr;          // the *_confidence entry points (no weights there; `visible` composes); a null mask packs nothing
-    int moments = 0;                            // the *_moments entry points (no weights, no maps there; `visible` composes); a null mask packs nothing
-    bool packed() const { return mask || weights; }
-};
 // ---- cross-view variance (include/mvhmr_unproject.h): the route of the visible calls -- the gather family with the per-tap
 // scatter backward and the geometry kernels, which launch their *_moments kernels (Problem::moments); with a mask the views are packed exactly
 // as for a masked call, without one nothing is packed or copied.  The variance is taken around the mean: desc->method must say so.
@@ -394,23 +417,36 @@ int moments_refused(const mvhmr_unproject_desc *desc, int moments)
         return fail(MVHMR_ERR_UNSUPPORTED, "the cross-view variance runs the gather kernels: MVHMR_VARIANT_BRICK is not served");
     return MVHMR_OK;
 }
-int views_refused(const mvhmr_unproject_desc *desc, const Views &w)
+// whether the descriptor can take what the record selects: a shared or a lens call answers for itself, the others for each selection
+int call_refused(const mvhmr_unproject_desc *desc, const Call &c)
 {
+    if (c.family == MVHMR_FAMILY_SHARED) return shared_refused(desc, c);
+    if (c.family == MVHMR_FAMILY_LENS) return lens_refused(desc, c);
     int rc = MVHMR_OK;
-    if (w.moments) return moments_refused(desc, w.moments);      // (the checks of a visible and of a masked call are among its own)
-    if (w.visible && (rc = visible_refused(desc)) != MVHMR_OK) return rc;
-    if (w.confidence && (rc = confidence_refused(desc)) != MVHMR_OK) return rc;
-    if (w.mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
-    return w.weights ? weights_refused(desc) : MVHMR_OK;
+    if (moments_of(c)) return moments_refused(desc, moments_of(c));      // (the checks of a visible and of a masked call are among its own)
+    if (seeing(c) && (rc = visible_refused(desc)) != MVHMR_OK) return rc;
+    if (c.view_confidence && (rc = confidence_refused(desc)) != MVHMR_OK) return rc;
+    if (c.view_mask && (rc = mask_refused(desc)) != MVHMR_OK) return rc;
+    return c.view_weights ? weights_refused(desc) : MVHMR_OK;
 }
 // the kinds of plan: every view, a mask, weights (with or without a mask), the seeing views of every voxel (with or without a mask),
 // confidence maps (with or without a mask, with or without the seeing test); Shared: shared feature maps (no head: nothing is packed);
 // Lens: lens distortion (no head either: the plain plan of the gather variant)
 // Moments: the cross-view variance (with or without a mask, with or without the seeing test)
 enum class Pack { None, Masked, Weighted, Visible, Confidence, Shared, Lens, Moments };
-Pack pack_of(const Views &w)
+// the plan a call runs on.  A lens call takes the lens plan with or without records; a shared call without an index is the plain call
+// with the gather variant forced (index_route)
+Pack pack_of(const Call &c)
 {
-    return w.moments ? Pack::Moments : w.confidence ? Pack::Confidence : w.visible ? Pack::Visible : w.weights ? Pack::Weighted : w.mask ? Pack::Masked : Pack::None;
+    if (c.family == MVHMR_FAMILY_LENS) return Pack::Lens;
+    if (c.family == MVHMR_FAMILY_SHARED) return c.feature_index ? Pack::Shared : Pack::None;
+    return moments_of(c) ? Pack::Moments : c.view_confidence ? Pack::Confidence : seeing(c) ? Pack::Visible : c.view_weights ? Pack::Weighted : c.view_mask ? Pack::Masked : Pack::None;
+}
+// the plan a workspace query sizes: the family's own, which covers every call the family degrades to
+Pack pack_of_family(int family)
+{
+    constexpr Pack kPacks[] = {Pack::None, Pack::Masked, Pack::Weighted, Pack::Visible, Pack::Confidence, Pack::Shared, Pack::Lens, Pack::Moments};
+    return kPacks[family];
 }
 // the plan whose workspace a plan's total also covers: a weighted or visible call's serves the masked one, a masked call's the unmasked one
 Pack pack_below(Pack pack) { return pack == Pack::Masked || pack == Pack::Shared ? Pack::None : Pack::Masked; }
@@ -424,28 +460,29 @@ void mask_route(mvhmr_unproject_desc *desc, Problem *p, Pack pack)
     p->moments = pack == Pack::Moments ? MVHMR_MOMENTS_MEANVAR : 0;   // (the plans read it as a flag; moments_route sets the call's own)
 }
 // a moments call composes with the seeing test: both ride in the problem once the plan exists
-void moments_route(Problem &p, const Views &w)
+void moments_route(Problem &p, const Call &c)
 {
-    if (!w.moments) return;
-    p.visible = w.visible;
-    p.moments = w.moments;
+    if (!moments_of(c)) return;
+    p.visible = seeing(c);
+    p.moments = moments_of(c);
 }
 // a confidence call reads the caller's maps (no mask) or the packed ones (pack_views), and composes with the seeing test
-void confidence_route(Problem &p, const Views &w)
+void confidence_route(Problem &p, const Call &c)
 {
-    if (!w.confidence) return;
-    p.visible = w.visible;
-    if (!p.confidence) p.confidence = w.confidence;
+    if (!confidence_of(c)) return;
+    p.visible = seeing(c);
+    if (!p.confidence) p.confidence = confidence_of(c);
 }
-// a shared call: the index and the volume count ride in the problem (the plans read the count: the geometry partials are per volume); a null
-// index with volumes == batch is the plain call with the gather variant (Problem::volumes stays 0)
-Pack shared_pack(const SharedIndex *sh) { return sh && sh->index ? Pack::Shared : Pack::None; }
-void shared_route(const SharedIndex *sh, mvhmr_unproject_desc *dq, const mvhmr_unproject_desc **desc, Problem *p)
+// a lens call: the records ride in the problem (null: the plain gather call).  A shared call: the index and the volume count ride in the
+// problem (the plans read the count: the geometry partials are per volume); a null index with volumes == batch is the plain call with the
+// gather variant (Problem::volumes stays 0)
+void index_route(const Call &c, mvhmr_unproject_desc *dq, const mvhmr_unproject_desc **desc, Problem *p)
 {
-    if (!sh) return;
-    if (sh->index) {
-        p->feature_index = sh->index;
-        p->volumes = sh->volumes;
+    if (c.family == MVHMR_FAMILY_LENS) p->lens = c.lens;
+    if (c.family != MVHMR_FAMILY_SHARED) return;
+    if (c.feature_index) {
+        p->feature_index = c.feature_index;
+        p->volumes = c.volumes;
         return;
     }
     *dq = **desc;
@@ -487,17 +524,18 @@ MaskHead plan_mask_head(Arena &a, const Problem &p, int copies, Pack pack)
     return h;
 }
 // builds the table, packs the features; from here on the call reads the packed features and projections
-int pack_views(const MaskHead &h, const Views &w, void *workspace, const void **features, const float **proj, Problem &p, hipStream_t s)
+int pack_views(const MaskHead &h, const Call &c, void *workspace, const void **features, const float **proj, Problem &p, hipStream_t s)
 {
     void *table = at(workspace, h.table);
-    int rc = launched(w.weights ? launch_view_table_weighted(w.mask, w.weights, *proj, table, p.B, p.V, s) : launch_view_table(w.mask, *proj, table, p.B, p.V, s),
+    const float *weights = weights_of(c), *confidence = confidence_of(c);
+    int rc = launched(weights ? launch_view_table_weighted(mask_of(c), weights, *proj, table, p.B, p.V, s) : launch_view_table(mask_of(c), *proj, table, p.B, p.V, s),
                       "view table");
     if (rc != MVHMR_OK) return rc;
-    if (w.weights) p.view_weights = view_table_weights(table, p.B, p.V);
+    if (weights) p.view_weights = view_table_weights(table, p.B, p.V);
     rc = launched(launch_view_pack(*features, at(workspace, h.feat), table, p.B, p.V, masked_view_bytes(p), s), "view pack");
     if (rc != MVHMR_OK) return rc;
-    if (w.confidence) {
-        rc = launched(launch_view_pack(w.confidence, at(workspace, h.conf), table, p.B, p.V, conf_map_bytes(p), s), "confidence pack");
+    if (confidence) {
+        rc = launched(launch_view_pack(confidence, at(workspace, h.conf), table, p.B, p.V, conf_map_bytes(p), s), "confidence pack");
         if (rc != MVHMR_OK) return rc;
         p.confidence = reinterpret_cast<const float *>(at(workspace, h.conf));
     }
@@ -735,21 +773,20 @@ int query_variant(const mvhmr_unproject_desc *desc, const VolumeSource &v, const
 }
 
 // ---- forward
-int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *features, const float *proj, const Views &views, void *out,
-                void *workspace, size_t workspace_bytes, void *hip_stream, const SharedIndex *shared = nullptr, const LensArgs *lens = nullptr)
+int run_forward(const mvhmr_unproject_desc *desc, const Call &c, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     Problem p0;
     Coords coords;
-    int rc = open_call(desc, v, &p0, &coords);
+    int rc = open_call(desc, placing_of(c), &p0, &coords);
     if (rc != MVHMR_OK) return rc;
+    const void *features = c.features;
+    const float *proj = c.proj;
+    void *out = c.out;
     if (!features || !proj || !out) return fail(MVHMR_ERR_INVALID_ARGUMENT, "features / proj / out must be non-null");
-    if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
-    if (shared && (rc = shared_refused(desc, *shared)) != MVHMR_OK) return rc;
-    if (lens && (rc = lens_refused(desc, *lens)) != MVHMR_OK) return rc;
-    if (lens) p0.lens = lens->lens;                           // (null: the plain gather call)
+    if ((rc = call_refused(desc, c)) != MVHMR_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
     mvhmr_unproject_desc dq;
-    shared_route(shared, &dq, &desc, &p0);
+    index_route(c, &dq, &desc, &p0);
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) {
         // the quad-planar copy times log2(e): only the wave-specialised softmax forward reads it (mvhmr_preferred_layout says when)
         if (!brick_fwd_prescales(p0) || desc->variant == MVHMR_VARIANT_GATHER)
@@ -761,16 +798,16 @@ int run_forward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const v
         desc = &dq;
         p0.feat_log2e = 1;
     }
-    ForwardPlan f = plan_forward(desc, p0, lens ? Pack::Lens : shared ? shared_pack(shared) : pack_of(views));
+    ForwardPlan f = plan_forward(desc, p0, pack_of(c));
     desc = &f.desc;
     Problem &p = f.p;
     rc = variant_conflict(desc, p, pick_variant(desc, p));
     if (rc != MVHMR_OK) return rc;
     rc = check_ws(workspace, workspace_bytes, f.total);
     if (rc != MVHMR_OK) return rc;
-    if (views.packed() && (rc = pack_views(f.head, views, workspace, &features, &proj, p, s)) != MVHMR_OK) return rc;
-    confidence_route(p, views);
-    moments_route(p, views);
+    if (packed(c) && (rc = pack_views(f.head, c, workspace, &features, &proj, p, s)) != MVHMR_OK) return rc;
+    confidence_route(p, c);
+    moments_route(p, c);
     // planar input whose staged copy this call makes itself: scaled by log2(e) when the kernel that reads it wants that
     if (desc->feat_layout == MVHMR_LAYOUT_BVCHW && brick_fwd_prescales(p)) p.feat_log2e = 1;
 
@@ -941,51 +978,52 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
     return launched(launch_det_grad_cast(acc, kexp, c.grad_features, p, s), "gradient cast");
 }
 
-int run_backward(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
-                 const Views &views, bool det, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream,
-                 const SharedIndex *shared = nullptr, const LensArgs *lens = nullptr)
+int run_backward(const mvhmr_unproject_desc *desc, const Call &c, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
     Problem p0;
     Coords coords;
-    int rc = open_call(desc, v, &p0, &coords);
+    int rc = open_call(desc, placing_of(c), &p0, &coords);
     if (rc != MVHMR_OK) return rc;
+    const void *grad_out = c.grad_out, *features = c.features;
+    const float *proj = c.proj;
+    void *grad_features = c.grad_features;
+    const bool det = c.deterministic != 0;
     if (!grad_out || !features || !proj || !grad_features)
         return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_out / features / proj / grad_features must be non-null");
-    if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
-    if (shared && (rc = shared_refused(desc, *shared)) != MVHMR_OK) return rc;
-    if (lens && (rc = lens_refused(desc, *lens)) != MVHMR_OK) return rc;
-    if (lens) p0.lens = lens->lens;
+    if ((rc = call_refused(desc, c)) != MVHMR_OK) return rc;
     mvhmr_unproject_desc dq;
-    shared_route(shared, &dq, &desc, &p0);
+    index_route(c, &dq, &desc, &p0);
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
         return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !bwd_uses_brick(desc, p0) && !quad_to_channels_last_supported(p0))
         return fail(MVHMR_ERR_UNSUPPORTED, "backward from quad-planar features of this shape needs the brick backward (fp32, 2 / 4 / 8 views)");
-    BackwardPlan b = plan_backward(desc, p0, det, lens ? Pack::Lens : shared ? shared_pack(shared) : pack_of(views));
+    BackwardPlan b = plan_backward(desc, p0, det, pack_of(c));
     rc = check_ws(workspace, workspace_bytes, b.total);
     if (rc != MVHMR_OK) return rc;
     if (b.desc.variant == MVHMR_VARIANT_BRICK && !bwd_uses_brick(&b.desc, b.p))
         return fail(MVHMR_ERR_UNSUPPORTED, "the brick variant does not support this shape / dtype / layout");
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    const bool packed = views.packed();
-    if (packed && (rc = pack_views(b.head, views, workspace, &features, &proj, b.p, s)) != MVHMR_OK) return rc;
-    confidence_route(b.p, views);
-    moments_route(b.p, views);
+    const bool slots = packed(c);
+    if (slots && (rc = pack_views(b.head, c, workspace, &features, &proj, b.p, s)) != MVHMR_OK) return rc;
+    confidence_route(b.p, c);
+    moments_route(b.p, c);
     // a masked or weighted call's gradient comes in slot order and is unpacked into view order, absent views zero-filled
-    void *grad = packed ? at(workspace, b.head.grad) : grad_features;
-    const BackwardArgs c{grad_out, features, proj, &coords, grad, workspace, s};
-    rc = det ? launch_backward_det(b, c) : launch_backward_default(b, c);
-    if (rc != MVHMR_OK || !packed) return rc;
+    void *grad = slots ? at(workspace, b.head.grad) : grad_features;
+    const BackwardArgs args{grad_out, features, proj, &coords, grad, workspace, s};
+    rc = det ? launch_backward_det(b, args) : launch_backward_default(b, args);
+    if (rc != MVHMR_OK || !slots) return rc;
     return launched(launch_view_unpack(grad, grad_features, at(workspace, b.head.table), b.p.B, b.p.V, masked_view_bytes(b.p), s), "view unpack");
 }
 
 // ---- geometry backward
-int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const void *grad_out, const void *features, const float *proj,
-                 const Views &views, float *grad_proj, float *grad_coords, float *grad_rot, float *grad_center, float *grad_weights, void *workspace,
-                 size_t workspace_bytes, void *hip_stream, float *grad_confidence = nullptr, const SharedIndex *shared = nullptr,
-                 const LensArgs *lens = nullptr)
+int run_geometry(const mvhmr_unproject_desc *desc, const Call &c, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    const bool mask = views.packed();
+    const VolumeSource v = placing_of(c);
+    const void *grad_out = c.grad_out, *features = c.features;
+    const float *proj = c.proj;
+    float *grad_proj = c.grad_proj, *grad_coords = c.grad_coords, *grad_rot = c.grad_rot, *grad_center = c.grad_center;
+    float *grad_weights = c.grad_weights, *grad_confidence = c.grad_confidence;
+    const bool mask = packed(c), weighted = weights_of(c), maps = confidence_of(c);
     Problem p0;
     Coords coords;
     int rc = check_desc(desc, &p0);
@@ -997,35 +1035,32 @@ int run_geometry(const mvhmr_unproject_desc *desc, const VolumeSource &v, const 
     if (!v.cuboid && !v.coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, no_tensor);
     rc = make_coords(v, p0, &coords);
     if (rc != MVHMR_OK) return rc;
-    if (grad_weights && !views.weights) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_weights without view_weights: nothing to differentiate");
-    if (grad_confidence && !views.confidence) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_confidence without view_confidence: nothing to differentiate");
+    if (grad_weights && !weighted) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_weights without view_weights: nothing to differentiate");
+    if (grad_confidence && !maps) return fail(MVHMR_ERR_INVALID_ARGUMENT, "grad_confidence without view_confidence: nothing to differentiate");
     if (!v.cuboid && !grad_proj && !grad_coords && !grad_weights && !grad_confidence)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, views.weights      ? "grad_proj, grad_coords and grad_weights are all null: nothing to compute"
-                                                : views.confidence ? "grad_proj, grad_coords and grad_confidence are all null: nothing to compute"
-                                                                   : "grad_proj and grad_coords are both null: nothing to compute");
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, weighted ? "grad_proj, grad_coords and grad_weights are all null: nothing to compute"
+                                                : maps   ? "grad_proj, grad_coords and grad_confidence are all null: nothing to compute"
+                                                         : "grad_proj and grad_coords are both null: nothing to compute");
     if (v.cuboid && !grad_proj && !grad_rot && !grad_center && !grad_weights && !grad_confidence)
-        return fail(MVHMR_ERR_INVALID_ARGUMENT, views.weights      ? "grad_proj, grad_rot, grad_center and grad_weights are all null: nothing to compute"
-                                                : views.confidence ? "grad_proj, grad_rot, grad_center and grad_confidence are all null: nothing to compute"
-                                                                   : "grad_proj, grad_rot and grad_center are all null: nothing to compute");
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, weighted ? "grad_proj, grad_rot, grad_center and grad_weights are all null: nothing to compute"
+                                                : maps   ? "grad_proj, grad_rot, grad_center and grad_confidence are all null: nothing to compute"
+                                                         : "grad_proj, grad_rot and grad_center are all null: nothing to compute");
     if (!data) return fail(MVHMR_ERR_INVALID_ARGUMENT, no_data);
-    if ((rc = views_refused(desc, views)) != MVHMR_OK) return rc;
-    if (shared && (rc = shared_refused(desc, *shared)) != MVHMR_OK) return rc;
-    if (lens && (rc = lens_refused(desc, *lens)) != MVHMR_OK) return rc;
-    if (lens) p0.lens = lens->lens;
+    if ((rc = call_refused(desc, c)) != MVHMR_OK) return rc;
     mvhmr_unproject_desc dq;
-    shared_route(shared, &dq, &desc, &p0);
+    index_route(c, &dq, &desc, &p0);
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E)
         return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout: hand the backward the features as they are");
     if (desc->feat_layout == MVHMR_LAYOUT_QUAD && !quad_to_channels_last_supported(p0))
         return fail(MVHMR_ERR_UNSUPPORTED, "quad-planar features of this shape cannot be converted to channels-last (C %% 4 == 0, C <= 4092, B * V <= 65535)");
-    GeometryPlan g = plan_geometry(desc, p0, v.cuboid, lens ? Pack::Lens : shared ? shared_pack(shared) : pack_of(views));
+    GeometryPlan g = plan_geometry(desc, p0, v.cuboid, pack_of(c));
     rc = check_ws(workspace, workspace_bytes, g.total);
     if (rc != MVHMR_OK) return rc;
     const Problem &p = g.p;
     hipStream_t s = static_cast<hipStream_t>(hip_stream);
-    if (mask && (rc = pack_views(g.head, views, workspace, &features, &proj, g.p, s)) != MVHMR_OK) return rc;
-    confidence_route(g.p, views);
-    moments_route(g.p, views);
+    if (mask && (rc = pack_views(g.head, c, workspace, &features, &proj, g.p, s)) != MVHMR_OK) return rc;
+    confidence_route(g.p, c);
+    moments_route(g.p, c);
     // grad_confidence: the kernel's stream of sum_channels dc, then launch_conf_grad (slot order behind the head with a mask, unpacked at the end)
     float *gc = mask && grad_confidence ? reinterpret_cast<float *>(at(workspace, g.packed_grad_conf)) : grad_confidence;
     if (grad_confidence) g.p.conf_stream = reinterpret_cast<float *>(at(workspace, g.conf_stream));
@@ -1084,68 +1119,38 @@ bool pack_refused(const mvhmr_unproject_desc *desc, Pack pack)
            (pack == Pack::Visible && visible_refused(desc) != MVHMR_OK) || (pack == Pack::Confidence && confidence_refused(desc) != MVHMR_OK) ||
            (pack == Pack::Moments && moments_refused(desc, MVHMR_MOMENTS_MEANVAR) != MVHMR_OK);
 }
-size_t forward_need(const mvhmr_unproject_desc *desc, Pack pack)
+// Only the descriptor and the record's family, placing, volumes and deterministic are read, never a device pointer: what a family degrades
+// to with a null pointer is not known here, and its plan's total covers it.
+size_t call_need(const mvhmr_unproject_desc *desc, const Call &c, int kind)
 {
     Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || pack_refused(desc, pack)) return 0;
-    return plan_forward(desc, p, pack).total;
-}
-size_t backward_need(const mvhmr_unproject_desc *desc, bool det, Pack pack)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E || pack_refused(desc, pack)) return 0;
-    return plan_backward(desc, p, det, pack).total;
-}
-size_t geometry_need(const mvhmr_unproject_desc *desc, bool cuboid, Pack pack)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E || pack_refused(desc, pack)) return 0;
-    return plan_geometry(desc, p, cuboid, pack).total;
-}
-
-// the *_shared queries: the checks of the call that do not need a pointer, then the plan's total (a null index is not known here: the
-// total covers it)
-bool shared_query_refused(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_shape_refused(desc, volumes) != MVHMR_OK; }
-size_t shared_forward_need(const mvhmr_unproject_desc *desc, int32_t volumes)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || shared_query_refused(desc, volumes)) return 0;
-    p.volumes = volumes;
-    return plan_forward(desc, p, Pack::Shared).total;
-}
-size_t shared_backward_need(const mvhmr_unproject_desc *desc, int32_t volumes, bool det)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || shared_query_refused(desc, volumes)) return 0;
-    p.volumes = volumes;
-    return plan_backward(desc, p, det, Pack::Shared).total;
-}
-size_t shared_geometry_need(const mvhmr_unproject_desc *desc, int32_t volumes, bool cuboid)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || shared_query_refused(desc, volumes)) return 0;
-    p.volumes = volumes;
-    return plan_geometry(desc, p, cuboid, Pack::Shared).total;
+    if (check_desc(desc, &p) != MVHMR_OK) return 0;
+    const Pack pack = pack_of_family(c.family);
+    if (pack == Pack::Shared) {
+        if (shared_shape_refused(desc, c.volumes) != MVHMR_OK) return 0;
+        p.volumes = c.volumes;
+    } else if (pack == Pack::Lens) {
+        if (lens_shape_refused(desc) != MVHMR_OK) return 0;
+    } else if ((kind != MVHMR_CALL_FORWARD && desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) || pack_refused(desc, pack)) {
+        return 0;
+    }
+    switch (kind) {
+    case MVHMR_CALL_FORWARD: return plan_forward(desc, p, pack).total;
+    case MVHMR_CALL_BACKWARD: return plan_backward(desc, p, c.deterministic != 0, pack).total;
+    case MVHMR_CALL_GEOMETRY: return plan_geometry(desc, p, c.placing == MVHMR_PLACING_CUBOID, pack).total;
+    }
+    fail(MVHMR_ERR_INVALID_ARGUMENT, "unknown call kind %d", kind);
+    return 0;
 }
 
-// the *_lens queries: the checks of the call that need no pointer, then the plan's total (a null lens is not known here: the total covers it)
-size_t lens_forward_need(const mvhmr_unproject_desc *desc)
+// a zeroed record of one family: what every named entry point starts from
+Call record(int family, bool deterministic = false)
 {
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || lens_shape_refused(desc) != MVHMR_OK) return 0;
-    return plan_forward(desc, p, Pack::Lens).total;
-}
-size_t lens_backward_need(const mvhmr_unproject_desc *desc, bool det)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || lens_shape_refused(desc) != MVHMR_OK) return 0;
-    return plan_backward(desc, p, det, Pack::Lens).total;
-}
-size_t lens_geometry_need(const mvhmr_unproject_desc *desc, bool cuboid)
-{
-    Problem p;
-    if (check_desc(desc, &p) != MVHMR_OK || lens_shape_refused(desc) != MVHMR_OK) return 0;
-    return plan_geometry(desc, p, cuboid, Pack::Lens).total;
+    Call r{};
+    r.struct_size = sizeof(Call);
+    r.family = family;
+    r.deterministic = deterministic;
+    return r;
 }
 
 }  // namespace
@@ -1212,278 +1217,155 @@ int mvhmr_unproject_backward_supported(const mvhmr_unproject_desc *desc)
 }
 
 
-size_t mvhmr_unproject_forward_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::None); }
-size_t mvhmr_unproject_backward_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::None); }
-size_t mvhmr_unproject_backward_deterministic_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::None); }
-size_t mvhmr_unproject_backward_geometry_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::None); }
-size_t mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::None); }
-size_t mvhmr_unproject_forward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Masked); }
-size_t mvhmr_unproject_forward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Masked); }
-size_t mvhmr_unproject_backward_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Masked); }
-size_t mvhmr_unproject_backward_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Masked); }
-size_t mvhmr_unproject_backward_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Masked); }
-size_t mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Masked); }
-size_t mvhmr_unproject_backward_geometry_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Masked); }
-size_t mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Masked); }
-
-// The launching entry points: each names what places the volume (tensor / cuboid), the mask (null: none) and, for the feature backward,
-// the mode, and forwards to the one route of its kind of call.
-int mvhmr_unproject_forward(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
-                            void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+// ---- the call record: the four functions every un-projection entry point goes through
+size_t mvhmr_unproject_call_workspace_bytes(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, int kind)
 {
-    return run_forward(desc, tensor_volume(coords), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream);
+    return check_record(call) == MVHMR_OK ? call_need(desc, *call, kind) : 0;
 }
 
-int mvhmr_unproject_forward_cuboid(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
-                                   const float *center, const double position[3], const double sides[3], void *out, void *workspace,
-                                   size_t workspace_bytes, void *hip_stream)
+int mvhmr_unproject_forward_call(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream);
+    const int rc = check_call(call);
+    return rc != MVHMR_OK ? rc : run_forward(desc, *call, workspace, workspace_bytes, hip_stream);
 }
 
-int mvhmr_unproject_forward_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
-                                   const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+int mvhmr_unproject_backward_call(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, void *workspace, size_t workspace_bytes, void *hip_stream)
 {
-    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, nullptr}, out, workspace, workspace_bytes, hip_stream);
+    const int rc = check_call(call);
+    return rc != MVHMR_OK ? rc : run_backward(desc, *call, workspace, workspace_bytes, hip_stream);
 }
 
-int mvhmr_unproject_forward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
-                                          const float *center, const double position[3], const double sides[3], const uint8_t *view_mask,
-                                          void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
+int mvhmr_unproject_backward_geometry_call(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, void *workspace, size_t workspace_bytes,
+                                           void *hip_stream)
 {
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, nullptr}, out, workspace, workspace_bytes, hip_stream);
+    const int rc = check_call(call);
+    return rc != MVHMR_OK ? rc : run_geometry(desc, *call, workspace, workspace_bytes, hip_stream);
 }
 
-int mvhmr_unproject_backward(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                             const float *coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace, workspace_bytes, hip_stream);
-}
+// ---- the named entry points (ABI 4): each fills a record from its arguments and calls the record function of its kind.  A name is
+// mvhmr_unproject_<kind>[_cuboid][_deterministic][_<family>]; MVHMR_SHIMS writes the four launching names and the four queries of one
+// (family, placing) from three tables: what places the volume (PLACE_*, GEOM_*), and per family its arguments behind the placing (ARGS_*),
+// the geometry call's own output (GOUT_*) and the query's argument (QARG_*), each with the statements that put them into the record r.
+#define PLACE_ARGS_TENSOR const float *coords
+#define PLACE_SET_TENSOR r.placing = MVHMR_PLACING_TENSOR, r.coords = coords
+#define GEOM_ARGS_TENSOR float *grad_proj, float *grad_coords
+#define GEOM_SET_TENSOR r.grad_proj = grad_proj, r.grad_coords = grad_coords
+#define PLACE_ARGS_CUBOID const float *rot, const float *center, const double position[3], const double sides[3]
+#define PLACE_SET_CUBOID r.placing = MVHMR_PLACING_CUBOID, r.rot = rot, r.center = center, r.position = position, r.sides = sides
+#define GEOM_ARGS_CUBOID float *grad_proj, float *grad_rot, float *grad_center
+#define GEOM_SET_CUBOID r.grad_proj = grad_proj, r.grad_rot = grad_rot, r.grad_center = grad_center
 
-int mvhmr_unproject_backward_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                    const float *rot, const float *center, const double position[3], const double sides[3],
-                                    void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace,
-                        workspace_bytes, hip_stream);
-}
+#define ARGS_PLAIN
+#define SET_PLAIN (void)0
+#define ARGS_MASKED const uint8_t *view_mask,
+#define SET_MASKED r.view_mask = view_mask
+#define ARGS_WEIGHTED const uint8_t *view_mask, const float *view_weights,
+#define SET_WEIGHTED r.view_mask = view_mask, r.view_weights = view_weights
+#define ARGS_VISIBLE const uint8_t *view_mask,
+#define SET_VISIBLE r.view_mask = view_mask
+#define ARGS_CONFIDENCE const uint8_t *view_mask, const float *view_confidence, int visible,
+#define SET_CONFIDENCE r.view_mask = view_mask, r.view_confidence = view_confidence, r.visible = visible != 0
+#define ARGS_MOMENTS const uint8_t *view_mask, int32_t visible, int32_t moments,
+#define SET_MOMENTS r.view_mask = view_mask, r.visible = visible != 0, r.moments = moments
+#define ARGS_SHARED int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible,
+#define SET_SHARED r.volumes = volumes, r.feature_index = feature_index, r.view_mask = view_mask, r.view_weights = view_weights, r.view_confidence = view_confidence, r.visible = visible != 0
+#define ARGS_LENS const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index,
+#define SET_LENS r.lens = lens, r.view_mask = view_mask, r.view_weights = view_weights, r.view_confidence = view_confidence, r.visible = visible != 0, r.feature_index = feature_index
 
-int mvhmr_unproject_backward_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                           const float *coords, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace, workspace_bytes, hip_stream);
-}
+#define GOUT_PLAIN
+#define GOUT_MASKED
+#define GOUT_VISIBLE
+#define GOUT_MOMENTS
+#define GOUT_SHARED
+#define GOUT_LENS
+#define GOUT_WEIGHTED float *grad_weights,
+#define GOUT_CONFIDENCE float *grad_confidence,
+#define GSET_PLAIN (void)0
+#define GSET_MASKED (void)0
+#define GSET_VISIBLE (void)0
+#define GSET_MOMENTS (void)0
+#define GSET_SHARED (void)0
+#define GSET_LENS (void)0
+#define GSET_WEIGHTED r.grad_weights = grad_weights
+#define GSET_CONFIDENCE r.grad_confidence = grad_confidence
 
-int mvhmr_unproject_backward_cuboid_deterministic(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                                  const float *rot, const float *center, const double position[3], const double sides[3],
-                                                  void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace,
-                        workspace_bytes, hip_stream);
-}
+#define QARG_MASKED
+#define QARG_WEIGHTED
+#define QARG_VISIBLE
+#define QARG_CONFIDENCE
+#define QARG_MOMENTS
+#define QARG_LENS
+#define QARG_SHARED , int32_t volumes
+#define QSET_MASKED (void)0
+#define QSET_WEIGHTED (void)0
+#define QSET_VISIBLE (void)0
+#define QSET_CONFIDENCE (void)0
+#define QSET_MOMENTS (void)0
+#define QSET_LENS (void)0
+#define QSET_SHARED r.volumes = volumes
 
-int mvhmr_unproject_backward_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                    const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes,
-                                    void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr}, false, grad_features, workspace, workspace_bytes, hip_stream);
-}
+#define MVHMR_TAIL void *workspace, size_t workspace_bytes, void *hip_stream
+#define MVHMR_LAUNCHERS(F, SFX, P, CUB)                                                                                                                  \
+    int mvhmr_unproject_forward##CUB##SFX(const mvhmr_unproject_desc *desc, const void *features, const float *proj, PLACE_ARGS_##P, ARGS_##F void *out,  \
+                                          MVHMR_TAIL)                                                                                                    \
+    {                                                                                                                                                    \
+        Call r = record(MVHMR_FAMILY_##F);                                                                                                               \
+        PLACE_SET_##P, SET_##F, r.features = features, r.proj = proj, r.out = out;                                                                       \
+        return mvhmr_unproject_forward_call(desc, &r, workspace, workspace_bytes, hip_stream);                                                           \
+    }                                                                                                                                                    \
+    int mvhmr_unproject_backward##CUB##SFX(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,               \
+                                           PLACE_ARGS_##P, ARGS_##F void *grad_features, MVHMR_TAIL)                                                     \
+    {                                                                                                                                                    \
+        Call r = record(MVHMR_FAMILY_##F);                                                                                                               \
+        PLACE_SET_##P, SET_##F, r.grad_out = grad_out, r.features = features, r.proj = proj, r.grad_features = grad_features;                            \
+        return mvhmr_unproject_backward_call(desc, &r, workspace, workspace_bytes, hip_stream);                                                          \
+    }                                                                                                                                                    \
+    int mvhmr_unproject_backward##CUB##_deterministic##SFX(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,                  \
+                                                           const float *proj, PLACE_ARGS_##P, ARGS_##F void *grad_features, MVHMR_TAIL)                  \
+    {                                                                                                                                                    \
+        Call r = record(MVHMR_FAMILY_##F, true);                                                                                                         \
+        PLACE_SET_##P, SET_##F, r.grad_out = grad_out, r.features = features, r.proj = proj, r.grad_features = grad_features;                            \
+        return mvhmr_unproject_backward_call(desc, &r, workspace, workspace_bytes, hip_stream);                                                          \
+    }                                                                                                                                                    \
+    int mvhmr_unproject_backward_geometry##CUB##SFX(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,      \
+                                                    PLACE_ARGS_##P, ARGS_##F GEOM_ARGS_##P, GOUT_##F MVHMR_TAIL)                                         \
+    {                                                                                                                                                    \
+        Call r = record(MVHMR_FAMILY_##F);                                                                                                               \
+        PLACE_SET_##P, SET_##F, GEOM_SET_##P, GSET_##F, r.grad_out = grad_out, r.features = features, r.proj = proj;                                     \
+        return mvhmr_unproject_backward_geometry_call(desc, &r, workspace, workspace_bytes, hip_stream);                                                 \
+    }
+#define MVHMR_QUERY(NAME, F, P, KIND, DET)                                                                                                               \
+    size_t NAME##_workspace_bytes(const mvhmr_unproject_desc *desc QARG_##F)                                                                             \
+    {                                                                                                                                                    \
+        Call r = record(MVHMR_FAMILY_##F, DET);                                                                                                          \
+        r.placing = MVHMR_PLACING_##P, QSET_##F;                                                                                                         \
+        return mvhmr_unproject_call_workspace_bytes(desc, &r, KIND);                                                                                     \
+    }
+#define MVHMR_SHIMS(F, SFX, P, CUB)                                                                                                                      \
+    MVHMR_LAUNCHERS(F, SFX, P, CUB)                                                                                                                      \
+    MVHMR_QUERY(mvhmr_unproject_forward##CUB##SFX, F, P, MVHMR_CALL_FORWARD, false)                                                                      \
+    MVHMR_QUERY(mvhmr_unproject_backward##CUB##SFX, F, P, MVHMR_CALL_BACKWARD, false)                                                                    \
+    MVHMR_QUERY(mvhmr_unproject_backward##CUB##_deterministic##SFX, F, P, MVHMR_CALL_BACKWARD, true)                                                     \
+    MVHMR_QUERY(mvhmr_unproject_backward_geometry##CUB##SFX, F, P, MVHMR_CALL_GEOMETRY, false)
+#define MVHMR_FAMILY_SHIMS(F, SFX) MVHMR_SHIMS(F, SFX, TENSOR, ) MVHMR_SHIMS(F, SFX, CUBOID, _cuboid)
 
-int mvhmr_unproject_backward_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                           const float *rot, const float *center, const double position[3], const double sides[3],
-                                           const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr}, false, grad_features, workspace,
-                        workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                                  const float *coords, const uint8_t *view_mask, void *grad_features, void *workspace,
-                                                  size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr}, true, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_cuboid_deterministic_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
-                                                         const float *proj, const float *rot, const float *center, const double position[3],
-                                                         const double sides[3], const uint8_t *view_mask, void *grad_features, void *workspace,
-                                                         size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr}, true, grad_features, workspace,
-                        workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                      const float *coords, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes,
-                                      void *hip_stream)
-{
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
-                        workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_cuboid(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                             const float *rot, const float *center, const double position[3], const double sides[3],
-                                             float *grad_proj, float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes,
-                                             void *hip_stream)
-{
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, nullptr, grad_rot,
-                        grad_center, nullptr, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                             const float *coords, const uint8_t *view_mask, float *grad_proj, float *grad_coords, void *workspace,
-                                             size_t workspace_bytes, void *hip_stream)
-{
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
-                        workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_cuboid_masked(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                                    const float *rot, const float *center, const double position[3], const double sides[3],
-                                                    const uint8_t *view_mask, float *grad_proj, float *grad_rot, float *grad_center, void *workspace,
-                                                    size_t workspace_bytes, void *hip_stream)
-{
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr}, grad_proj, nullptr, grad_rot,
-                        grad_center, nullptr, workspace, workspace_bytes, hip_stream);
-}
-
-// ---- per-view confidence weights: the _masked entry points with `view_weights` beside `view_mask` (either may be null)
-size_t mvhmr_unproject_forward_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Weighted); }
-size_t mvhmr_unproject_forward_cuboid_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Weighted); }
-size_t mvhmr_unproject_backward_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Weighted); }
-size_t mvhmr_unproject_backward_cuboid_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Weighted); }
-size_t mvhmr_unproject_backward_deterministic_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Weighted); }
-size_t mvhmr_unproject_backward_cuboid_deterministic_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Weighted); }
-size_t mvhmr_unproject_backward_geometry_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Weighted); }
-size_t mvhmr_unproject_backward_geometry_cuboid_weighted_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Weighted); }
-
-int mvhmr_unproject_forward_weighted(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
-                                     const uint8_t *view_mask, const float *view_weights, void *out, void *workspace, size_t workspace_bytes,
-                                     void *hip_stream)
-{
-    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, view_weights}, out, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_forward_cuboid_weighted(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot,
-                                            const float *center, const double position[3], const double sides[3], const uint8_t *view_mask,
-                                            const float *view_weights, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, view_weights}, out, workspace, workspace_bytes,
-                       hip_stream);
-}
-
-int mvhmr_unproject_backward_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                      const float *coords, const uint8_t *view_mask, const float *view_weights, void *grad_features, void *workspace,
-                                      size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, view_weights}, false, grad_features, workspace,
-                        workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_cuboid_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                             const float *rot, const float *center, const double position[3], const double sides[3],
-                                             const uint8_t *view_mask, const float *view_weights, void *grad_features, void *workspace,
-                                             size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, view_weights}, false, grad_features,
-                        workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_deterministic_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                                    const float *coords, const uint8_t *view_mask, const float *view_weights, void *grad_features,
-                                                    void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, view_weights}, true, grad_features, workspace,
-                        workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_cuboid_deterministic_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features,
-                                                           const float *proj, const float *rot, const float *center, const double position[3],
-                                                           const double sides[3], const uint8_t *view_mask, const float *view_weights,
-                                                           void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, view_weights}, true, grad_features,
-                        workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                               const float *coords, const uint8_t *view_mask, const float *view_weights, float *grad_proj,
-                                               float *grad_coords, float *grad_weights, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, view_weights}, grad_proj, grad_coords, nullptr, nullptr,
-                        grad_weights, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_cuboid_weighted(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-                                                      const float *rot, const float *center, const double position[3], const double sides[3],
-                                                      const uint8_t *view_mask, const float *view_weights, float *grad_proj, float *grad_rot,
-                                                      float *grad_center, float *grad_weights, void *workspace, size_t workspace_bytes,
-                                                      void *hip_stream)
-{
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, view_weights}, grad_proj, nullptr,
-                        grad_rot, grad_center, grad_weights, workspace, workspace_bytes, hip_stream);
-}
-
-// ---- visibility-aware aggregation: the _masked entry points (view_mask may be null) with every voxel aggregating only the views that see it
-size_t mvhmr_unproject_forward_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Visible); }
-size_t mvhmr_unproject_forward_cuboid_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Visible); }
-size_t mvhmr_unproject_backward_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Visible); }
-size_t mvhmr_unproject_backward_cuboid_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Visible); }
-size_t mvhmr_unproject_backward_deterministic_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Visible); }
-size_t mvhmr_unproject_backward_cuboid_deterministic_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Visible); }
-size_t mvhmr_unproject_backward_geometry_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Visible); }
-size_t mvhmr_unproject_backward_geometry_cuboid_visible_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Visible); }
-
-int mvhmr_unproject_forward_visible(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, nullptr, true}, out, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_forward_cuboid_visible(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, nullptr, true}, out, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, true}, false, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_cuboid_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, true}, false, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_deterministic_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, true}, true, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_cuboid_deterministic_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, true}, true, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *coords, const uint8_t *view_mask, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, true}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
-                        workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_cuboid_visible(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *rot, const float *center, const double position[3], const double sides[3], const uint8_t *view_mask, float *grad_proj,
-        float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, true}, grad_proj, nullptr, grad_rot,
-                        grad_center, nullptr, workspace, workspace_bytes, hip_stream);
-}
+// the plain family has no suffix, and the five queries ABI 4 gave it (the forward and feature-backward ones serve both placings)
+#define QARG_PLAIN
+#define QSET_PLAIN (void)0
+MVHMR_LAUNCHERS(PLAIN, , TENSOR, )
+MVHMR_LAUNCHERS(PLAIN, , CUBOID, _cuboid)
+MVHMR_QUERY(mvhmr_unproject_forward, PLAIN, TENSOR, MVHMR_CALL_FORWARD, false)
+MVHMR_QUERY(mvhmr_unproject_backward, PLAIN, TENSOR, MVHMR_CALL_BACKWARD, false)
+MVHMR_QUERY(mvhmr_unproject_backward_deterministic, PLAIN, TENSOR, MVHMR_CALL_BACKWARD, true)
+MVHMR_QUERY(mvhmr_unproject_backward_geometry, PLAIN, TENSOR, MVHMR_CALL_GEOMETRY, false)
+MVHMR_QUERY(mvhmr_unproject_backward_geometry_cuboid, PLAIN, CUBOID, MVHMR_CALL_GEOMETRY, false)
+MVHMR_FAMILY_SHIMS(MASKED, _masked)
+MVHMR_FAMILY_SHIMS(WEIGHTED, _weighted)
+MVHMR_FAMILY_SHIMS(VISIBLE, _visible)
+MVHMR_FAMILY_SHIMS(CONFIDENCE, _confidence)
+MVHMR_FAMILY_SHIMS(SHARED, _shared)
+MVHMR_FAMILY_SHIMS(LENS, _lens)
+MVHMR_FAMILY_SHIMS(MOMENTS, _moments)
 
 int mvhmr_unproject_visibility(const mvhmr_unproject_desc *desc, const float *proj, const float *coords, const uint8_t *view_mask, int32_t *bits,
                                void *hip_stream)
@@ -1495,284 +1377,6 @@ int mvhmr_unproject_visibility_cuboid(const mvhmr_unproject_desc *desc, const fl
                                       const double position[3], const double sides[3], const uint8_t *view_mask, int32_t *bits, void *hip_stream)
 {
     return run_visibility(desc, cuboid_volume(rot, center, position, sides), proj, view_mask, bits, hip_stream);
-}
-
-// ---- cross-view variance: the _moments entry points with the seeing test as the flag `visible` and `moments` (MVHMR_MOMENTS_VAR /
-// MVHMR_MOMENTS_MEANVAR) behind `view_mask`; out / grad_out hold C or 2C channels
-size_t mvhmr_unproject_forward_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Moments); }
-size_t mvhmr_unproject_forward_cuboid_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Moments); }
-size_t mvhmr_unproject_backward_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Moments); }
-size_t mvhmr_unproject_backward_cuboid_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Moments); }
-size_t mvhmr_unproject_backward_deterministic_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Moments); }
-size_t mvhmr_unproject_backward_cuboid_deterministic_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Moments); }
-size_t mvhmr_unproject_backward_geometry_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Moments); }
-size_t mvhmr_unproject_backward_geometry_cuboid_moments_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Moments); }
-
-int mvhmr_unproject_forward_moments(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, int32_t visible, int32_t moments, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, out, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_forward_cuboid_moments(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, int32_t visible, int32_t moments, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, out, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, false, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_cuboid_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, false, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_deterministic_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, true, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_cuboid_deterministic_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, int32_t visible, int32_t moments, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, true, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *coords, const uint8_t *view_mask, int32_t visible, int32_t moments, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
-                        workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_cuboid_moments(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *rot, const float *center, const double position[3], const double sides[3], const uint8_t *view_mask, int32_t visible, int32_t moments, float *grad_proj,
-        float *grad_rot, float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, nullptr, moments ? moments : -1 /* 0: refused as any other unknown value */}, grad_proj, nullptr, grad_rot,
-                        grad_center, nullptr, workspace, workspace_bytes, hip_stream);
-}
-
-// ---- per-pixel view confidence maps: the _visible entry points with `view_confidence` (B,V,Hf,Wf) fp32 beside `view_mask` (either may be
-// null) and the seeing test as a flag; the geometry calls also write grad_confidence
-size_t mvhmr_unproject_forward_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Confidence); }
-size_t mvhmr_unproject_forward_cuboid_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return forward_need(desc, Pack::Confidence); }
-size_t mvhmr_unproject_backward_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Confidence); }
-size_t mvhmr_unproject_backward_cuboid_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, false, Pack::Confidence); }
-size_t mvhmr_unproject_backward_deterministic_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Confidence); }
-size_t mvhmr_unproject_backward_cuboid_deterministic_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return backward_need(desc, true, Pack::Confidence); }
-size_t mvhmr_unproject_backward_geometry_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, false, Pack::Confidence); }
-size_t mvhmr_unproject_backward_geometry_cuboid_confidence_workspace_bytes(const mvhmr_unproject_desc *desc) { return geometry_need(desc, true, Pack::Confidence); }
-
-int mvhmr_unproject_forward_confidence(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, const float *view_confidence, int visible, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_forward(desc, tensor_volume(coords), features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, out, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, false, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_deterministic_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, true, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
-        const uint8_t *view_mask, const float *view_confidence, int visible, float *grad_proj, float *grad_coords, float *grad_confidence, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, grad_proj, grad_coords, nullptr, nullptr, nullptr, workspace, workspace_bytes, hip_stream, grad_confidence);
-}
-
-int mvhmr_unproject_forward_cuboid_confidence(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, const float *view_confidence, int visible, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, out, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_cuboid_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, false, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_cuboid_deterministic_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, const float *view_confidence, int visible, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, true, grad_features, workspace, workspace_bytes, hip_stream);
-}
-
-int mvhmr_unproject_backward_geometry_cuboid_confidence(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot, const float *center, const double position[3], const double sides[3],
-        const uint8_t *view_mask, const float *view_confidence, int visible, float *grad_proj, float *grad_rot, float *grad_center, float *grad_confidence, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{view_mask, nullptr, visible != 0, view_confidence}, grad_proj, nullptr, grad_rot, grad_center, nullptr, workspace, workspace_bytes, hip_stream, grad_confidence);
-}
-
-// ---- shared feature maps: the plain entry points with `volumes` and `feature_index` behind what places the volume, then the view selections
-// of the other families (view_mask, view_weights, view_confidence, visible), which do not compose with the index yet: each must be null / 0
-size_t mvhmr_unproject_forward_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_forward_need(desc, volumes); }
-size_t mvhmr_unproject_forward_cuboid_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_forward_need(desc, volumes); }
-size_t mvhmr_unproject_backward_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_backward_need(desc, volumes, false); }
-size_t mvhmr_unproject_backward_cuboid_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_backward_need(desc, volumes, false); }
-size_t mvhmr_unproject_backward_deterministic_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_backward_need(desc, volumes, true); }
-size_t mvhmr_unproject_backward_cuboid_deterministic_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_backward_need(desc, volumes, true); }
-size_t mvhmr_unproject_backward_geometry_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_geometry_need(desc, volumes, false); }
-size_t mvhmr_unproject_backward_geometry_cuboid_shared_workspace_bytes(const mvhmr_unproject_desc *desc, int32_t volumes) { return shared_geometry_need(desc, volumes, true); }
-
-#define MVHMR_SHARED_ARGS int32_t volumes, const int32_t *feature_index, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible
-#define MVHMR_SHARED_INDEX const SharedIndex sh{volumes, feature_index, view_mask, view_weights, view_confidence, visible}
-
-int mvhmr_unproject_forward_shared(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords, MVHMR_SHARED_ARGS,
-        void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_SHARED_INDEX;
-    return run_forward(desc, tensor_volume(coords), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream, &sh);
-}
-
-int mvhmr_unproject_forward_cuboid_shared(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center,
-        const double position[3], const double sides[3], MVHMR_SHARED_ARGS, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_SHARED_INDEX;
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream, &sh);
-}
-
-int mvhmr_unproject_backward_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
-        MVHMR_SHARED_ARGS, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_SHARED_INDEX;
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace, workspace_bytes, hip_stream, &sh);
-}
-
-int mvhmr_unproject_backward_cuboid_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot,
-        const float *center, const double position[3], const double sides[3], MVHMR_SHARED_ARGS, void *grad_features, void *workspace, size_t workspace_bytes,
-        void *hip_stream)
-{
-    MVHMR_SHARED_INDEX;
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace,
-                        workspace_bytes, hip_stream, &sh);
-}
-
-int mvhmr_unproject_backward_deterministic_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *coords, MVHMR_SHARED_ARGS, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_SHARED_INDEX;
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace, workspace_bytes, hip_stream, &sh);
-}
-
-int mvhmr_unproject_backward_cuboid_deterministic_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *rot, const float *center, const double position[3], const double sides[3], MVHMR_SHARED_ARGS, void *grad_features, void *workspace,
-        size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_SHARED_INDEX;
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace,
-                        workspace_bytes, hip_stream, &sh);
-}
-
-int mvhmr_unproject_backward_geometry_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *coords, MVHMR_SHARED_ARGS, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_SHARED_INDEX;
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
-                        workspace, workspace_bytes, hip_stream, nullptr, &sh);
-}
-
-int mvhmr_unproject_backward_geometry_cuboid_shared(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *rot, const float *center, const double position[3], const double sides[3], MVHMR_SHARED_ARGS, float *grad_proj, float *grad_rot,
-        float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_SHARED_INDEX;
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, nullptr, grad_rot,
-                        grad_center, nullptr, workspace, workspace_bytes, hip_stream, nullptr, &sh);
-}
-
-// ---- lens distortion: the plain entry points with `lens` behind what places the volume, then the view selections of the other families and the
-// feature index, which do not compose with the lens yet: each must be null / 0
-size_t mvhmr_unproject_forward_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_forward_need(desc); }
-size_t mvhmr_unproject_forward_cuboid_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_forward_need(desc); }
-size_t mvhmr_unproject_backward_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_backward_need(desc, false); }
-size_t mvhmr_unproject_backward_cuboid_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_backward_need(desc, false); }
-size_t mvhmr_unproject_backward_deterministic_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_backward_need(desc, true); }
-size_t mvhmr_unproject_backward_cuboid_deterministic_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_backward_need(desc, true); }
-size_t mvhmr_unproject_backward_geometry_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_geometry_need(desc, false); }
-size_t mvhmr_unproject_backward_geometry_cuboid_lens_workspace_bytes(const mvhmr_unproject_desc *desc) { return lens_geometry_need(desc, true); }
-
-#define MVHMR_LENS_ARGS const float *lens, const uint8_t *view_mask, const float *view_weights, const float *view_confidence, int visible, const int32_t *feature_index
-#define MVHMR_LENS_RECORDS const LensArgs la{lens, view_mask, view_weights, view_confidence, visible, feature_index}
-
-int mvhmr_unproject_forward_lens(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *coords, MVHMR_LENS_ARGS,
-        void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_LENS_RECORDS;
-    return run_forward(desc, tensor_volume(coords), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream, nullptr, &la);
-}
-
-int mvhmr_unproject_forward_cuboid_lens(const mvhmr_unproject_desc *desc, const void *features, const float *proj, const float *rot, const float *center,
-        const double position[3], const double sides[3], MVHMR_LENS_ARGS, void *out, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_LENS_RECORDS;
-    return run_forward(desc, cuboid_volume(rot, center, position, sides), features, proj, Views{nullptr, nullptr}, out, workspace, workspace_bytes, hip_stream,
-                       nullptr, &la);
-}
-
-int mvhmr_unproject_backward_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *coords,
-        MVHMR_LENS_ARGS, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_LENS_RECORDS;
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace, workspace_bytes, hip_stream,
-                        nullptr, &la);
-}
-
-int mvhmr_unproject_backward_cuboid_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj, const float *rot,
-        const float *center, const double position[3], const double sides[3], MVHMR_LENS_ARGS, void *grad_features, void *workspace, size_t workspace_bytes,
-        void *hip_stream)
-{
-    MVHMR_LENS_RECORDS;
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, false, grad_features, workspace,
-                        workspace_bytes, hip_stream, nullptr, &la);
-}
-
-int mvhmr_unproject_backward_deterministic_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *coords, MVHMR_LENS_ARGS, void *grad_features, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_LENS_RECORDS;
-    return run_backward(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace, workspace_bytes, hip_stream,
-                        nullptr, &la);
-}
-
-int mvhmr_unproject_backward_cuboid_deterministic_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *rot, const float *center, const double position[3], const double sides[3], MVHMR_LENS_ARGS, void *grad_features, void *workspace,
-        size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_LENS_RECORDS;
-    return run_backward(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, true, grad_features, workspace,
-                        workspace_bytes, hip_stream, nullptr, &la);
-}
-
-int mvhmr_unproject_backward_geometry_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *coords, MVHMR_LENS_ARGS, float *grad_proj, float *grad_coords, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_LENS_RECORDS;
-    return run_geometry(desc, tensor_volume(coords), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, grad_coords, nullptr, nullptr, nullptr,
-                        workspace, workspace_bytes, hip_stream, nullptr, nullptr, &la);
-}
-
-int mvhmr_unproject_backward_geometry_cuboid_lens(const mvhmr_unproject_desc *desc, const void *grad_out, const void *features, const float *proj,
-        const float *rot, const float *center, const double position[3], const double sides[3], MVHMR_LENS_ARGS, float *grad_proj, float *grad_rot,
-        float *grad_center, void *workspace, size_t workspace_bytes, void *hip_stream)
-{
-    MVHMR_LENS_RECORDS;
-    return run_geometry(desc, cuboid_volume(rot, center, position, sides), grad_out, features, proj, Views{nullptr, nullptr}, grad_proj, nullptr, grad_rot,
-                        grad_center, nullptr, workspace, workspace_bytes, hip_stream, nullptr, nullptr, &la);
 }
 
 int mvhmr_preferred_layout(const mvhmr_unproject_desc *desc)

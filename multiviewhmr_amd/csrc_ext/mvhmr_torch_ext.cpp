@@ -1,16 +1,14 @@
 // PyTorch-ROCm C++ extension over the C ABI (include/mvhmr_unproject.h): the host side of every un-projection launch, as the ops
 // mvhmr_native::unprojection[_backward[_geometry]] / unprojection_cuboid[_backward[_geometry]] that multiviewhmr_amd/aggregation.py calls
 // from its torch.library ops and from _FusedAggregate, and of the DLT triangulation (triangulate_dlt[_backward], multiview.py).  Every
-// un-projection op takes a trailing `Tensor? view_mask` (None: the unmasked C entry point), the two feature backwards a trailing
-// `bool deterministic`, and all of them behind that `Tensor? view_weights` (per-view confidence weights: the *_weighted entry points; the
-// geometry ops also `Tensor(a!)? grad_weights`, the (B, V) fp32 tensor they write the gradient w.r.t. the weights into) and last `bool visible_only`
-// (visibility-aware aggregation: the *_visible entry points, view_mask nullable, no weights), then `Tensor? view_confidence` (per-pixel confidence maps
-// (B, V, Hf, Wf) fp32: the *_confidence entry points, which take visible_only as a flag; the geometry ops also `Tensor(b!)? grad_confidence`, the tensor they
-// write the gradient w.r.t. the maps into), and last of all `Tensor? feature_index` (shared feature maps: the *_shared entry points; (M,) int32, the volumes'
-// tensors then hold M entries) and `Tensor? lens` (lens distortion: the *_lens entry points; (B, V, 10) fp32 records), in front of those two `int moments` (the cross-view variance: the *_moments entry
-// points; 1 = the variance, 2 = mean and variance in 2C channels; view_mask and visible_only compose, nothing else); mvhmr_visibility::view_visibility[_cuboid] return the
-// (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what places the volume.  Per call:
-// tensor checks, descriptor, output and workspace from the caching allocator, the current HIP stream, one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
+// un-projection op takes the optional inputs of the call record behind its descriptor fields -- `Tensor? view_mask`, `Tensor? view_weights`,
+// `bool visible_only`, `Tensor? view_confidence`, `int moments`, `Tensor? feature_index` ((M,) int32: the volumes' tensors then hold M
+// entries), `Tensor? lens` ((B, V, 10) fp32 records) -- the two feature backwards also `bool deterministic`, the geometry ops also
+// `Tensor(a!)? grad_weights` and `Tensor(b!)? grad_confidence`, the tensors they write the gradients w.r.t. the weights and the maps into.
+// view_args() turns them into one mvhmr_unproject_call and names its family; mvhmr_visibility::view_visibility[_cuboid] return the
+// (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what
+// places the volume.  Per call: tensor checks, descriptor, record, output and workspace from the caching allocator, the current HIP stream,
+// one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <c10/core/DeviceGuard.h>
@@ -115,18 +113,6 @@ const float *weights_ptr(const mvhmr_unproject_desc &d, const at::Tensor &featur
     return view_weights->data_ptr<float>();
 }
 
-// what selects a sample's views: the mask, the weights, both or neither (the C entry point family follows)
-struct ViewArgs {
-    const uint8_t *mask;
-    const float *weights;
-    bool visible = false;                                       // the *_visible entry points: every voxel aggregates the views that see it
-    const float *confidence = nullptr;                          // the *_confidence entry points: per-pixel confidence maps (visible is their flag)
-    const int32_t *index = nullptr;                             // the *_shared entry points: `volumes` volumes read the samples through feature_index
-    int32_t volumes = 0;                                        // (the library refuses the selections above beside an index, each with its own text)
-    const float *lens = nullptr;                                // the *_lens entry points: (B, V, 10) lens records (the library refuses everything above beside them)
-    int32_t moments = 0;                                        // the *_moments entry points: the cross-view variance (1) or mean and variance (2); mask and visible compose
-};
-
 // the channels of out / grad_out per feature channel: 2 for the mean and the variance
 int64_t halves_of(int64_t moments) { return moments == MVHMR_MOMENTS_MEANVAR ? 2 : 1; }
 
@@ -144,29 +130,43 @@ const float *confidence_ptr(const mvhmr_unproject_desc &d, const at::Tensor &fea
     return t->data_ptr<float>();
 }
 
-ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_mask,
-                   const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence,
-                   const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens, int64_t moments)
+// the call record of an op: its optional inputs checked against the descriptor, and the family they name -- the one place that chooses it.
+// The library refuses the selections a family carries without taking them (a mask beside a lens ...), each with its own text.
+mvhmr_unproject_call view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, const c10::optional<at::Tensor> &view_mask,
+                               const c10::optional<at::Tensor> &view_weights, bool visible_only, const c10::optional<at::Tensor> &view_confidence,
+                               const c10::optional<at::Tensor> &feature_index, const c10::optional<at::Tensor> &lens, int64_t moments)
 {
-    ViewArgs v{mask_ptr(d, features, view_mask), weights_ptr(d, features, view_weights), visible_only,
-               confidence_ptr(d, features, view_confidence, "view_confidence (B, V, Hf, Wf)")};
+    mvhmr_unproject_call c{};
+    c.struct_size = sizeof(c);
+    c.view_mask = mask_ptr(d, features, view_mask);
+    c.view_weights = weights_ptr(d, features, view_weights);
+    c.visible = visible_only;
+    c.view_confidence = confidence_ptr(d, features, view_confidence, "view_confidence (B, V, Hf, Wf)");
     if (feature_index && feature_index->defined()) {
         TORCH_CHECK(feature_index->dim() == 1 && feature_index->numel() >= 1 && feature_index->numel() <= INT32_MAX,
                     "mvhmr_unproject: feature_index must be a non-empty (M,) tensor");
         check_tensor(*feature_index, features, "feature_index (M,)", at::kInt, feature_index->numel());
-        v.index = feature_index->data_ptr<int32_t>();
-        v.volumes = (int32_t)feature_index->numel();
+        c.feature_index = feature_index->data_ptr<int32_t>();
+        c.volumes = (int32_t)feature_index->numel();
     }
     if (lens && lens->defined()) {
         check_tensor(*lens, features, "lens (B, V, 10)", at::kFloat, (int64_t)d.batch * d.views * 10);
-        v.lens = lens->data_ptr<float>();
+        c.lens = lens->data_ptr<float>();
     }
-    v.moments = (int32_t)moments;
-    TORCH_CHECK(!moments || (!v.weights && !v.confidence && !v.index && !v.lens),
+    c.moments = (int32_t)moments;
+    TORCH_CHECK(!moments || (!c.view_weights && !c.view_confidence && !c.feature_index && !c.lens),
                 "mvhmr_unproject: the cross-view variance takes a view mask and visible_only only (view_weights, view_confidence, feature_index and lens are not built yet)");
-    TORCH_CHECK(!(v.visible && v.weights), "mvhmr_unproject: visible_only does not take view_weights");
-    TORCH_CHECK(!(v.confidence && v.weights), "mvhmr_unproject: view_confidence does not take view_weights");
-    return v;
+    TORCH_CHECK(!(c.visible && c.view_weights), "mvhmr_unproject: visible_only does not take view_weights");
+    TORCH_CHECK(!(c.view_confidence && c.view_weights), "mvhmr_unproject: view_confidence does not take view_weights");
+    c.family = c.moments           ? MVHMR_FAMILY_MOMENTS
+               : c.lens            ? MVHMR_FAMILY_LENS
+               : c.feature_index   ? MVHMR_FAMILY_SHARED
+               : c.view_confidence ? MVHMR_FAMILY_CONFIDENCE
+               : c.visible         ? MVHMR_FAMILY_VISIBLE
+               : c.view_weights    ? MVHMR_FAMILY_WEIGHTED
+               : c.view_mask       ? MVHMR_FAMILY_MASKED
+                                   : MVHMR_FAMILY_PLAIN;
+    return c;
 }
 
 // the common tail: workspace, the features' device, the current HIP stream, one C-ABI call.  The workspace comes from the caching
@@ -174,15 +174,17 @@ ViewArgs view_args(const mvhmr_unproject_desc &d, const at::Tensor &features, co
 // torch.use_deterministic_algorithms(True) at::empty fills new memory (torch.utils.deterministic.fill_uninitialized_memory) --
 // gigabytes of scratch the kernels overwrite or clear themselves
 template <typename Launch>
-void run(const at::Tensor &features, size_t need, bool unfilled, Launch launch)
+void run(const at::Tensor &features, const mvhmr_unproject_desc &d, const mvhmr_unproject_call &c, mvhmr_call_kind_t kind, Launch launch)
 {
+    const size_t need = mvhmr_unproject_call_workspace_bytes(&d, &c, kind);
+    const bool unfilled = kind == MVHMR_CALL_BACKWARD && c.deterministic;
     c10::DeviceGuard guard(features.device());
     c10::DataPtr raw;
     at::Tensor filled;
     if (unfilled) raw = c10::GetAllocator(features.device().type())->allocate(need);
     else filled = at::empty({(int64_t)need}, features.options().dtype(at::kByte));
     void *ws = unfilled ? raw.get() : filled.data_ptr();
-    const int status = launch(need ? ws : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream());
+    const int status = launch(&d, &c, need ? ws : nullptr, need, c10::hip::getCurrentHIPStream(features.device().index()).stream());
     TORCH_CHECK(status == MVHMR_OK, "mvhmr_unproject: ", mvhmr_last_error());
 }
 
@@ -202,8 +204,8 @@ struct DescArgs {
     int64_t M;                                                  // volumes: B, or the length of the feature_index
 };
 
-// ---- what places the volume.  Each form knows its descriptor, its tensors' checks, the shapes of its geometry gradients and its C
-// entry points (mask == null: the unmasked one; det: the _deterministic one).
+// ---- what places the volume.  Each form knows its descriptor, its tensors' checks, the shapes of its geometry gradients, the placing
+// fields and geometry outputs of the call record, and its visibility call.
 struct TensorVolume {
     const at::Tensor &coords;                                   // (B, X, Y, Z, 3)
     static constexpr const char *kNothingAsked = "mvhmr_unproject: neither gradient was asked for";
@@ -223,85 +225,12 @@ struct TensorVolume {
     // gradients w.r.t. proj (B,V,3,4) and coords (B,X,Y,Z,3)
     std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, coords.sizes().vec()}; }
 
-    size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
+    void place(mvhmr_unproject_call &c) const
     {
-        if (v.moments) return mvhmr_unproject_forward_moments_workspace_bytes(&d);
-        if (v.lens) return mvhmr_unproject_forward_lens_workspace_bytes(&d);
-        if (v.index) return mvhmr_unproject_forward_shared_workspace_bytes(&d, v.volumes);
-        if (v.confidence) return mvhmr_unproject_forward_confidence_workspace_bytes(&d);
-        if (v.visible) return mvhmr_unproject_forward_visible_workspace_bytes(&d);
-        if (v.weights) return mvhmr_unproject_forward_weighted_workspace_bytes(&d);
-        return v.mask ? mvhmr_unproject_forward_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
+        c.placing = MVHMR_PLACING_TENSOR;
+        c.coords = coords.data_ptr<float>();
     }
-    int forward(const mvhmr_unproject_desc &d, const void *features, const float *proj, const ViewArgs &v, void *out, void *ws, size_t n, hipStream_t s) const
-    {
-        const float *c = coords.data_ptr<float>();
-        const uint8_t *mask = v.mask;
-        if (v.moments) return mvhmr_unproject_forward_moments(&d, features, proj, c, mask, v.visible, v.moments, out, ws, n, s);
-        if (v.lens) return mvhmr_unproject_forward_lens(&d, features, proj, c, v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, out, ws, n, s);
-        if (v.index) return mvhmr_unproject_forward_shared(&d, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, out, ws, n, s);
-        if (v.confidence) return mvhmr_unproject_forward_confidence(&d, features, proj, c, mask, v.confidence, v.visible, out, ws, n, s);
-        if (v.visible) return mvhmr_unproject_forward_visible(&d, features, proj, c, mask, out, ws, n, s);
-        if (v.weights) return mvhmr_unproject_forward_weighted(&d, features, proj, c, mask, v.weights, out, ws, n, s);
-        return mask ? mvhmr_unproject_forward_masked(&d, features, proj, c, mask, out, ws, n, s) : mvhmr_unproject_forward(&d, features, proj, c, out, ws, n, s);
-    }
-    size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
-    {
-        if (v.moments) return det ? mvhmr_unproject_backward_deterministic_moments_workspace_bytes(&d) : mvhmr_unproject_backward_moments_workspace_bytes(&d);
-        if (v.lens) return det ? mvhmr_unproject_backward_deterministic_lens_workspace_bytes(&d) : mvhmr_unproject_backward_lens_workspace_bytes(&d);
-        if (v.index) return det ? mvhmr_unproject_backward_deterministic_shared_workspace_bytes(&d, v.volumes) : mvhmr_unproject_backward_shared_workspace_bytes(&d, v.volumes);
-        if (v.confidence) return det ? mvhmr_unproject_backward_deterministic_confidence_workspace_bytes(&d) : mvhmr_unproject_backward_confidence_workspace_bytes(&d);
-        if (v.visible) return det ? mvhmr_unproject_backward_deterministic_visible_workspace_bytes(&d) : mvhmr_unproject_backward_visible_workspace_bytes(&d);
-        if (v.weights) return det ? mvhmr_unproject_backward_deterministic_weighted_workspace_bytes(&d) : mvhmr_unproject_backward_weighted_workspace_bytes(&d);
-        if (v.mask) return det ? mvhmr_unproject_backward_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_masked_workspace_bytes(&d);
-        return det ? mvhmr_unproject_backward_deterministic_workspace_bytes(&d) : mvhmr_unproject_backward_workspace_bytes(&d);
-    }
-    int backward(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, bool det, void *grad,
-                 void *ws, size_t n, hipStream_t s) const
-    {
-        const float *c = coords.data_ptr<float>();
-        const uint8_t *mask = v.mask;
-        if (v.moments)
-            return (det ? mvhmr_unproject_backward_deterministic_moments : mvhmr_unproject_backward_moments)(&d, grad_out, features, proj, c, mask, v.visible, v.moments, grad, ws, n, s);
-        if (v.lens)
-            return (det ? mvhmr_unproject_backward_deterministic_lens : mvhmr_unproject_backward_lens)(&d, grad_out, features, proj, c, v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, grad, ws, n, s);
-        if (v.index)
-            return (det ? mvhmr_unproject_backward_deterministic_shared : mvhmr_unproject_backward_shared)(&d, grad_out, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, grad, ws, n, s);
-        if (v.confidence)
-            return (det ? mvhmr_unproject_backward_deterministic_confidence : mvhmr_unproject_backward_confidence)(&d, grad_out, features, proj, c, mask, v.confidence,
-                                                                                                                    v.visible, grad, ws, n, s);
-        if (v.visible) return (det ? mvhmr_unproject_backward_deterministic_visible : mvhmr_unproject_backward_visible)(&d, grad_out, features, proj, c, mask, grad, ws, n, s);
-        if (v.weights)
-            return (det ? mvhmr_unproject_backward_deterministic_weighted : mvhmr_unproject_backward_weighted)(&d, grad_out, features, proj, c, mask, v.weights,
-                                                                                                                grad, ws, n, s);
-        if (mask) return (det ? mvhmr_unproject_backward_deterministic_masked : mvhmr_unproject_backward_masked)(&d, grad_out, features, proj, c, mask, grad, ws, n, s);
-        return (det ? mvhmr_unproject_backward_deterministic : mvhmr_unproject_backward)(&d, grad_out, features, proj, c, grad, ws, n, s);
-    }
-    size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
-    {
-        if (v.moments) return mvhmr_unproject_backward_geometry_moments_workspace_bytes(&d);
-        if (v.lens) return mvhmr_unproject_backward_geometry_lens_workspace_bytes(&d);
-        if (v.index) return mvhmr_unproject_backward_geometry_shared_workspace_bytes(&d, v.volumes);
-        if (v.confidence) return mvhmr_unproject_backward_geometry_confidence_workspace_bytes(&d);
-        if (v.visible) return mvhmr_unproject_backward_geometry_visible_workspace_bytes(&d);
-        if (v.weights) return mvhmr_unproject_backward_geometry_weighted_workspace_bytes(&d);
-        return v.mask ? mvhmr_unproject_backward_geometry_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_workspace_bytes(&d);
-    }
-    int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, float *const *g,
-                 float *grad_weights, float *grad_confidence, void *ws, size_t n, hipStream_t s) const
-    {
-        const float *c = coords.data_ptr<float>();
-        const uint8_t *mask = v.mask;
-        if (v.moments) return mvhmr_unproject_backward_geometry_moments(&d, grad_out, features, proj, c, mask, v.visible, v.moments, g[0], g[1], ws, n, s);
-        if (v.lens) return mvhmr_unproject_backward_geometry_lens(&d, grad_out, features, proj, c, v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, g[0], g[1], ws, n, s);
-        if (v.index) return mvhmr_unproject_backward_geometry_shared(&d, grad_out, features, proj, c, v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, g[0], g[1], ws, n, s);
-        if (v.confidence)
-            return mvhmr_unproject_backward_geometry_confidence(&d, grad_out, features, proj, c, mask, v.confidence, v.visible, g[0], g[1], grad_confidence, ws, n, s);
-        if (v.visible) return mvhmr_unproject_backward_geometry_visible(&d, grad_out, features, proj, c, mask, g[0], g[1], ws, n, s);
-        if (v.weights) return mvhmr_unproject_backward_geometry_weighted(&d, grad_out, features, proj, c, mask, v.weights, g[0], g[1], grad_weights, ws, n, s);
-        return mask ? mvhmr_unproject_backward_geometry_masked(&d, grad_out, features, proj, c, mask, g[0], g[1], ws, n, s)
-                    : mvhmr_unproject_backward_geometry(&d, grad_out, features, proj, c, g[0], g[1], ws, n, s);
-    }
+    void geometry_outputs(mvhmr_unproject_call &c, float *const *g) const { c.grad_proj = g[0]; c.grad_coords = g[1]; }
 };
 
 // the cuboid recipe (mvhmr_unproject_*_cuboid): rot (B,3,3) and center (B,3) on the device, position / sides / vol 3 values each
@@ -326,111 +255,15 @@ struct CuboidVolume {
     // gradients w.r.t. proj (B,V,3,4), rot (B,3,3) and center (B,3) -- (M,3,3) and (M,3) under a feature_index
     std::vector<std::vector<int64_t>> geometry_shapes(const mvhmr_unproject_desc &d) const { return {{d.batch, d.views, 3, 4}, rot.sizes().vec(), center.sizes().vec()}; }
 
-    size_t forward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
+    void place(mvhmr_unproject_call &c) const
     {
-        if (v.moments) return mvhmr_unproject_forward_cuboid_moments_workspace_bytes(&d);
-        if (v.lens) return mvhmr_unproject_forward_cuboid_lens_workspace_bytes(&d);
-        if (v.index) return mvhmr_unproject_forward_cuboid_shared_workspace_bytes(&d, v.volumes);
-        if (v.confidence) return mvhmr_unproject_forward_cuboid_confidence_workspace_bytes(&d);
-        if (v.visible) return mvhmr_unproject_forward_cuboid_visible_workspace_bytes(&d);
-        if (v.weights) return mvhmr_unproject_forward_cuboid_weighted_workspace_bytes(&d);
-        return v.mask ? mvhmr_unproject_forward_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_forward_workspace_bytes(&d);
+        c.placing = MVHMR_PLACING_CUBOID;
+        c.rot = rot.data_ptr<float>();
+        c.center = center.data_ptr<float>();
+        c.position = position.data();
+        c.sides = sides.data();
     }
-    int forward(const mvhmr_unproject_desc &d, const void *features, const float *proj, const ViewArgs &v, void *out, void *ws, size_t n, hipStream_t s) const
-    {
-        const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
-        const uint8_t *mask = v.mask;
-        if (v.moments) return mvhmr_unproject_forward_cuboid_moments(&d, features, proj, r, c, position.data(), sides.data(), mask, v.visible, v.moments, out, ws, n, s);
-        if (v.lens)
-            return mvhmr_unproject_forward_cuboid_lens(&d, features, proj, r, c, position.data(), sides.data(), v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, out, ws, n, s);
-        if (v.index) return mvhmr_unproject_forward_cuboid_shared(&d, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, out, ws, n, s);
-        if (v.confidence)
-            return mvhmr_unproject_forward_cuboid_confidence(&d, features, proj, r, c, position.data(), sides.data(), mask, v.confidence, v.visible, out, ws, n, s);
-        if (v.visible) return mvhmr_unproject_forward_cuboid_visible(&d, features, proj, r, c, position.data(), sides.data(), mask, out, ws, n, s);
-        if (v.weights)
-            return mvhmr_unproject_forward_cuboid_weighted(&d, features, proj, r, c, position.data(), sides.data(), mask, v.weights, out, ws, n, s);
-        return mask ? mvhmr_unproject_forward_cuboid_masked(&d, features, proj, r, c, position.data(), sides.data(), mask, out, ws, n, s)
-                    : mvhmr_unproject_forward_cuboid(&d, features, proj, r, c, position.data(), sides.data(), out, ws, n, s);
-    }
-    size_t backward_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v, bool det) const
-    {
-        if (v.moments) return det ? mvhmr_unproject_backward_cuboid_deterministic_moments_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_moments_workspace_bytes(&d);
-        if (v.lens) return det ? mvhmr_unproject_backward_cuboid_deterministic_lens_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_lens_workspace_bytes(&d);
-        if (v.index)
-            return det ? mvhmr_unproject_backward_cuboid_deterministic_shared_workspace_bytes(&d, v.volumes) : mvhmr_unproject_backward_cuboid_shared_workspace_bytes(&d, v.volumes);
-        if (v.confidence)
-            return det ? mvhmr_unproject_backward_cuboid_deterministic_confidence_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_confidence_workspace_bytes(&d);
-        if (v.visible)
-            return det ? mvhmr_unproject_backward_cuboid_deterministic_visible_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_visible_workspace_bytes(&d);
-        if (v.weights)
-            return det ? mvhmr_unproject_backward_cuboid_deterministic_weighted_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_weighted_workspace_bytes(&d);
-        if (v.mask) return det ? mvhmr_unproject_backward_cuboid_deterministic_masked_workspace_bytes(&d) : mvhmr_unproject_backward_cuboid_masked_workspace_bytes(&d);
-        return det ? mvhmr_unproject_backward_deterministic_workspace_bytes(&d) : mvhmr_unproject_backward_workspace_bytes(&d);
-    }
-    int backward(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, bool det, void *grad,
-                 void *ws, size_t n, hipStream_t s) const
-    {
-        const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
-        const uint8_t *mask = v.mask;
-        if (v.moments)
-            return (det ? mvhmr_unproject_backward_cuboid_deterministic_moments : mvhmr_unproject_backward_cuboid_moments)(
-                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.visible, v.moments, grad, ws, n, s);
-        if (v.lens)
-            return (det ? mvhmr_unproject_backward_cuboid_deterministic_lens : mvhmr_unproject_backward_cuboid_lens)(
-                &d, grad_out, features, proj, r, c, position.data(), sides.data(), v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, grad, ws, n, s);
-        if (v.index)
-            return (det ? mvhmr_unproject_backward_cuboid_deterministic_shared : mvhmr_unproject_backward_cuboid_shared)(
-                &d, grad_out, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, grad, ws, n, s);
-        if (v.confidence)
-            return (det ? mvhmr_unproject_backward_cuboid_deterministic_confidence : mvhmr_unproject_backward_cuboid_confidence)(
-                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.confidence, v.visible, grad, ws, n, s);
-        if (v.visible)
-            return (det ? mvhmr_unproject_backward_cuboid_deterministic_visible : mvhmr_unproject_backward_cuboid_visible)(
-                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, grad, ws, n, s);
-        if (v.weights)
-            return (det ? mvhmr_unproject_backward_cuboid_deterministic_weighted : mvhmr_unproject_backward_cuboid_weighted)(
-                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.weights, grad, ws, n, s);
-        if (mask)
-            return (det ? mvhmr_unproject_backward_cuboid_deterministic_masked : mvhmr_unproject_backward_cuboid_masked)(
-                &d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, grad, ws, n, s);
-        return (det ? mvhmr_unproject_backward_cuboid_deterministic : mvhmr_unproject_backward_cuboid)(&d, grad_out, features, proj, r, c, position.data(),
-                                                                                                     sides.data(), grad, ws, n, s);
-    }
-    size_t geometry_bytes(const mvhmr_unproject_desc &d, const ViewArgs &v) const
-    {
-        if (v.moments) return mvhmr_unproject_backward_geometry_cuboid_moments_workspace_bytes(&d);
-        if (v.lens) return mvhmr_unproject_backward_geometry_cuboid_lens_workspace_bytes(&d);
-        if (v.index) return mvhmr_unproject_backward_geometry_cuboid_shared_workspace_bytes(&d, v.volumes);
-        if (v.confidence) return mvhmr_unproject_backward_geometry_cuboid_confidence_workspace_bytes(&d);
-        if (v.visible) return mvhmr_unproject_backward_geometry_cuboid_visible_workspace_bytes(&d);
-        if (v.weights) return mvhmr_unproject_backward_geometry_cuboid_weighted_workspace_bytes(&d);
-        return v.mask ? mvhmr_unproject_backward_geometry_cuboid_masked_workspace_bytes(&d) : mvhmr_unproject_backward_geometry_cuboid_workspace_bytes(&d);
-    }
-    int geometry(const mvhmr_unproject_desc &d, const void *grad_out, const void *features, const float *proj, const ViewArgs &v, float *const *g,
-                 float *grad_weights, float *grad_confidence, void *ws, size_t n, hipStream_t s) const
-    {
-        const float *r = rot.data_ptr<float>(), *c = center.data_ptr<float>();
-        const uint8_t *mask = v.mask;
-        if (v.moments)
-            return mvhmr_unproject_backward_geometry_cuboid_moments(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.visible, v.moments, g[0], g[1], g[2],
-                                                                    ws, n, s);
-        if (v.lens)
-            return mvhmr_unproject_backward_geometry_cuboid_lens(&d, grad_out, features, proj, r, c, position.data(), sides.data(), v.lens, v.mask, v.weights, v.confidence, v.visible, v.index, g[0], g[1], g[2], ws, n, s);
-        if (v.index)
-            return mvhmr_unproject_backward_geometry_cuboid_shared(&d, grad_out, features, proj, r, c, position.data(), sides.data(), v.volumes, v.index, v.mask, v.weights, v.confidence, v.visible, g[0], g[1], g[2], ws, n, s);
-        if (v.confidence)
-            return mvhmr_unproject_backward_geometry_cuboid_confidence(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.confidence,
-                                                                       v.visible, g[0], g[1], g[2], grad_confidence, ws, n, s);
-        if (v.visible)
-            return mvhmr_unproject_backward_geometry_cuboid_visible(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, g[0], g[1], g[2],
-                                                                    ws, n, s);
-        if (v.weights)
-            return mvhmr_unproject_backward_geometry_cuboid_weighted(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, v.weights, g[0],
-                                                                     g[1], g[2], grad_weights, ws, n, s);
-        return mask ? mvhmr_unproject_backward_geometry_cuboid_masked(&d, grad_out, features, proj, r, c, position.data(), sides.data(), mask, g[0], g[1], g[2],
-                                                                      ws, n, s)
-                    : mvhmr_unproject_backward_geometry_cuboid(&d, grad_out, features, proj, r, c, position.data(), sides.data(), g[0], g[1], g[2], ws, n, s);
-    }
+    void geometry_outputs(mvhmr_unproject_call &c, float *const *g) const { c.grad_proj = g[0]; c.grad_rot = g[1]; c.grad_center = g[2]; }
 };
 
 // ---- one body per kind of call.  features: the tensor the library reads (planar, channels-last or the quad-planar byte buffer)
@@ -441,11 +274,13 @@ at::Tensor forward(const Volume &vol, const at::Tensor &features, const at::Tens
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, nullptr, a.M, halves_of(moments));
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
+    mvhmr_unproject_call c = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
     at::Tensor out = at::empty({a.M, halves_of(moments) * a.C, d.vol_x, d.vol_y, d.vol_z}, features.options().dtype(scalar_of(a.out_dtype)));
-    run(features, vol.forward_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
-        return vol.forward(d, features.data_ptr(), proj.data_ptr<float>(), views, out.data_ptr(), ws, n, s);
-    });
+    vol.place(c);
+    c.features = features.data_ptr();
+    c.proj = proj.data_ptr<float>();
+    c.out = out.data_ptr();
+    run(features, d, c, MVHMR_CALL_FORWARD, mvhmr_unproject_forward_call);
     return out;
 }
 
@@ -458,11 +293,15 @@ at::Tensor backward(const Volume &vol, const at::Tensor &grad_out, const at::Ten
 {
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out, a.M, halves_of(moments));
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
+    mvhmr_unproject_call c = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
     at::Tensor grad = new_feature_grad(d, features);
-    run(features, vol.backward_bytes(d, views, deterministic), deterministic, [&](void *ws, size_t n, hipStream_t s) {
-        return vol.backward(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, deterministic, grad.data_ptr(), ws, n, s);
-    });
+    vol.place(c);
+    c.deterministic = deterministic;
+    c.grad_out = grad_out.data_ptr();
+    c.features = features.data_ptr();
+    c.proj = proj.data_ptr<float>();
+    c.grad_features = grad.data_ptr();
+    run(features, d, c, MVHMR_CALL_BACKWARD, mvhmr_unproject_backward_call);
     return grad;
 }
 
@@ -480,11 +319,11 @@ std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &g
     TORCH_CHECK(want_weights || want_conf || std::any_of(want.begin(), want.end(), [](bool w) { return w; }), Volume::kNothingAsked);
     const mvhmr_unproject_desc d = vol.desc(a);
     vol.check(d, features, proj, &grad_out, a.M, halves_of(moments));
-    const ViewArgs views = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
-    TORCH_CHECK(!want_weights || views.weights, "mvhmr_unproject: grad_weights needs view_weights");
-    TORCH_CHECK(!want_conf || views.confidence, "mvhmr_unproject: grad_confidence needs view_confidence");
-    float *gw = const_cast<float *>(weights_ptr(d, features, grad_weights, "grad_weights (B, V)"));
-    float *gc = const_cast<float *>(confidence_ptr(d, features, grad_confidence, "grad_confidence (B, V, Hf, Wf)"));
+    mvhmr_unproject_call c = view_args(d, features, view_mask, view_weights, visible_only, view_confidence, feature_index, lens, moments);
+    TORCH_CHECK(!want_weights || c.view_weights, "mvhmr_unproject: grad_weights needs view_weights");
+    TORCH_CHECK(!want_conf || c.view_confidence, "mvhmr_unproject: grad_confidence needs view_confidence");
+    c.grad_weights = const_cast<float *>(weights_ptr(d, features, grad_weights, "grad_weights (B, V)"));
+    c.grad_confidence = const_cast<float *>(confidence_ptr(d, features, grad_confidence, "grad_confidence (B, V, Hf, Wf)"));
     const auto opts = features.options().dtype(at::kFloat);
     const auto shapes = vol.geometry_shapes(d);
     std::vector<at::Tensor> grads;
@@ -494,9 +333,12 @@ std::vector<at::Tensor> backward_geometry(const Volume &vol, const at::Tensor &g
         grads.push_back(w ? at::empty(shapes[i], opts) : at::empty({0}, opts));
         ptrs.push_back(w ? grads.back().data_ptr<float>() : nullptr);
     }
-    run(features, vol.geometry_bytes(d, views), false, [&](void *ws, size_t n, hipStream_t s) {
-        return vol.geometry(d, grad_out.data_ptr(), features.data_ptr(), proj.data_ptr<float>(), views, ptrs.data(), gw, gc, ws, n, s);
-    });
+    vol.place(c);
+    vol.geometry_outputs(c, ptrs.data());
+    c.grad_out = grad_out.data_ptr();
+    c.features = features.data_ptr();
+    c.proj = proj.data_ptr<float>();
+    run(features, d, c, MVHMR_CALL_GEOMETRY, mvhmr_unproject_backward_geometry_call);
     return grads;
 }
 
