@@ -103,3 +103,200 @@ def test_option_rigs_keep_their_budget():
     for tag, name, method, kw in rig.option_cases():
         res = rig.option_reference(tag)
         rig.assert_budget(res, tag)
+
+
+# ----------------------------------------------------------------------------------------------- the geometry path
+"""The premise of the geometry rigs (lattice_rig.GEO_RIGS: maps with power-of-two H and W, so that kx = (W - 1) / H and ky = (H - 1) / W
+are dyadic), for `sum`, `max` and power-of-two `mean`:
+
+  * the rig's float64 geometry oracle, tests/geomgrad_oracle.py (written independently, from the forward's fp32 positions) and an fp32
+    numpy restatement of k_bwd_geom's order that rounds after EVERY operation agree bit for bit; the restatement's sum over voxels runs
+    in two different random orders;
+  * geo_budget < 2^24;
+  * no rig is trivially easy: >= 60 % of the compared grad_coords and of grad_proj are non-zero, <= 15 % `max` ties; over the set of
+    rigs, live voxel-views lie in each border band, exactly on pixel 0 and on the last pixel, behind the camera and at z == 0;
+  * the rigs SEE the slips the GPU tests are there to catch: the restatement with one of them applied no longer has the oracle's bits."""
+import geomgrad_oracle                                            # noqa: E402
+
+F32 = np.float32
+GEO_PLAIN = [n for n in sorted(rig.GEO_RIGS) if "M" not in rig.GEO_RIGS[n] and n != "geo_conf"]
+
+
+def _geo_methods(name):
+    V = rig.GEO_RIGS[name]["V"]
+    return [m for m in METHODS if m != "mean" or V & (V - 1) == 0]
+
+
+def _fma(a, b, c):
+    """fmaf: the product is exact in float64 (24 + 24 bits), one rounding to fp32 at the end"""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(F32)
+
+
+def _kernel_order32(feats, proj, coords, grad, method, seed, slip=None):
+    """k_bwd_geom (csrc/unproject_geom_bwd.hip) and make_geo_rec (csrc/geom_bwd_common.h) in numpy fp32, one rounding per operation, in
+    the kernel's order; the channel sum runs channel by channel and the voxel sum of grad_proj in the random order of `seed`, both in
+    fp32 (the kernel keeps a fixed tree and float64 across blocks: any order must do on the rig).
+    slip: None, or one deliberate mistake -- 'x1_lt' (xin1 = x1 < W - 1), 'no_value_mask' (a clamped tap keeps its value), 'swap_k'
+    (kx and ky exchanged).  -> grad_proj (B,V,3,4), grad_coords (B,X,Y,Z,3) fp32"""
+    B, V, C, H, W = feats.shape
+    vol = coords.shape[1:4]
+    N = int(np.prod(vol))
+    rng = np.random.default_rng(seed)
+    gp = np.zeros((B, V, 3, 4), F32)
+    gc = np.zeros((B, N, 3), F32)
+    kx, ky = F32(W - 1) / F32(H), F32(H - 1) / F32(W)
+    if slip == "swap_k":
+        kx, ky = ky, kx
+    for b in range(B):
+        X = coords[b].reshape(N, 3).astype(F32)
+        g = grad[b].reshape(C, N).astype(F32)
+        recs = []
+        for v in range(V):
+            P = proj[b, v].astype(F32).ravel()
+            row = lambda r: _fma(P[4 * r + 3], F32(1), _fma(P[4 * r + 2], X[:, 2], _fma(P[4 * r + 1], X[:, 1], P[4 * r] * X[:, 0])))
+            a, bb, z = row(0), row(1), row(2)
+            front = z > 0
+            zs = np.where(front, z, F32(1))
+            u, w = a / zs, bb / zs
+            ix = ((F32(2) * (u / F32(H) - F32(0.5)) + F32(1)) * F32(0.5)) * F32(W - 1)
+            iy = ((F32(2) * (w / F32(W) - F32(0.5)) + F32(1)) * F32(0.5)) * F32(H - 1)
+            assert ix.dtype == F32 and iy.dtype == F32
+            valid = front & (ix >= -1) & (ix < W) & (iy >= -1) & (iy < H)
+            fx0, fy0 = np.where(valid, np.floor(ix), F32(0)), np.where(valid, np.floor(iy), F32(0))
+            x0, y0 = fx0.astype(np.int64), fy0.astype(np.int64)
+            x1, y1 = x0 + 1, y0 + 1
+            ixv, iyv = np.where(valid, ix, F32(0)), np.where(valid, iy, F32(0))
+            wx1, wx0 = ixv - fx0, (fx0 + F32(1)) - ixv
+            wy1, wy0 = iyv - fy0, (fy0 + F32(1)) - iyv
+            xin0, yin0, yin1 = x0 >= 0, y0 >= 0, y1 <= H - 1
+            xin1 = x1 < W - 1 if slip == "x1_lt" else x1 <= W - 1
+            xc0, xc1 = np.where(xin0, x0, 0), np.where(xin1, x1, W - 1)
+            yc0, yc1 = np.where(yin0, y0, 0), np.where(yin1, y1, H - 1)
+            fm = feats[b, v].astype(F32)
+            vals, wts = [], []
+            for (yc, yin, wy), (xc, xin, wx) in (((yc0, yin0, wy0), (xc0, xin0, wx0)), ((yc0, yin0, wy0), (xc1, xin1, wx1)),
+                                                 ((yc1, yin1, wy1), (xc0, xin0, wx0)), ((yc1, yin1, wy1), (xc1, xin1, wx1))):
+                inside = xin & yin
+                val = fm[:, yc, xc]
+                vals.append(val if slip == "no_value_mask" else np.where(inside[None], val, F32(0)))
+                wts.append(np.where(inside, wx * wy, F32(0)))
+            a00, a01, a10, a11 = vals
+            s = _fma(a11, wts[3], _fma(a10, wts[2], _fma(a01, wts[1], a00 * wts[0])))
+            dx = _fma(wy0, a01 - a00, wy1 * (a11 - a10))
+            dy = _fma(wx0, a10 - a00, wx1 * (a11 - a01))
+            m = valid[None]
+            recs.append(dict(s=np.where(m, s, F32(0)), dx=np.where(m, dx, F32(0)), dy=np.where(m, dy, F32(0)), valid=valid, z=zs, u=u, w=w, P=P))
+        S = np.stack([r["s"] for r in recs])
+        if method == "sum":
+            ds = np.broadcast_to(g[None], S.shape)
+        elif method == "mean":
+            ds = np.broadcast_to((g / F32(V))[None], S.shape)
+        else:
+            am = np.zeros(S.shape[1:], np.int64)
+            for v in range(1, V):
+                am = np.where(S[v] > np.take_along_axis(S, am[None], 0)[0], v, am)
+            ds = np.where(np.arange(V)[:, None, None] == am[None], g[None], F32(0))
+        g0 = np.zeros((N, 3), F32)
+        order = rng.permutation(N)
+        for v in range(V):
+            r = recs[v]
+            Gx, Gy = np.zeros(N, F32), np.zeros(N, F32)
+            for c in range(C):
+                Gx, Gy = _fma(ds[v, c], r["dx"][c], Gx), _fma(ds[v, c], r["dy"][c], Gy)
+            du, dw = Gx * kx, Gy * ky
+            d = np.stack([du / r["z"], dw / r["z"], -(_fma(du, r["u"], dw * r["w"]) / r["z"])], 1)
+            d = np.where(r["valid"][:, None], d, F32(0))
+            assert d.dtype == F32
+            P = r["P"]
+            for k in range(3):
+                g0[:, k] = _fma(P[8 + k], d[:, 2], _fma(P[4 + k], d[:, 1], _fma(P[k], d[:, 0], g0[:, k])))
+            Xh = np.concatenate([X, np.ones((N, 1), F32)], 1)
+            for n in order:
+                gp[b, v] = _fma(d[n][:, None], Xh[n][None, :], gp[b, v])
+        gc[b] = g0
+    return gp, gc.reshape((B,) + tuple(vol) + (3,))
+
+
+def _compared_coords(name, gc):
+    """the grad_coords entries a rig compares for the 'not trivially easy' condition: all, or the seeded voxels of a sparse grad_out"""
+    seeded = rig.geo_problem(name)[4].get("seeded")
+    return gc if seeded is None else gc[:, seeded]
+
+
+@pytest.mark.parametrize("name", GEO_PLAIN)
+def test_geometry_oracles_and_the_fp32_restatement_agree_bit_for_bit(name):
+    feats, proj, coords, _, extras = rig.geo_problem(name)
+    for method in _geo_methods(name):
+        grad, res, _ = rig.geo_reference(name, method)
+        gp64, gc64 = geomgrad_oracle.geometry_grad(feats, proj, coords, grad, method)
+        assert np.array_equal(gc64, res["grad_coords"]), (name, method, "the two float64 oracles differ in grad_coords")
+        if "proj" in extras["want"]:
+            assert np.array_equal(gp64, res["grad_proj"]), (name, method, "the two float64 oracles differ in grad_proj")
+        for seed in (1, 2):
+            gp32, gc32 = _kernel_order32(feats, proj, coords, grad, method, seed)
+            assert _same_bits(gc32, res["grad_coords"]), (name, method, "fp32 restatement, grad_coords", seed)
+            if "proj" in extras["want"]:
+                assert _same_bits(gp32, res["grad_proj"]), (name, method, "fp32 restatement, grad_proj", seed)
+
+
+def test_cuboid_rig_pose_gradients_agree_with_the_pose_oracle():
+    """grad_rot / grad_center of the rig's oracle against tests/posegrad_oracle.py (float64 from fp32 voxel centres): equal exactly; the
+    unrotated sample's grad_center is exactly 0, the others' is not"""
+    import posegrad_oracle
+    feats, proj, coords, _, ex = rig.geo_problem("geo_pose")
+    for method in _geo_methods("geo_pose"):
+        grad, res, _ = rig.geo_reference("geo_pose", method)
+        d32, X32 = posegrad_oracle.cuboid_points(ex["rotations"], ex["centers"], ex["position"], ex["sides"], coords.shape[1:4])
+        assert np.array_equal(X32.numpy(), coords) and np.array_equal(d32.numpy().reshape(len(coords), -1, 3), ex["d"])
+        gp, gr, gcen = posegrad_oracle.pose_grad(feats, proj, ex["rotations"], ex["centers"], ex["position"], ex["sides"], coords.shape[1:4], grad, method)
+        assert np.array_equal(gp, res["grad_proj"]) and np.array_equal(gr, res["grad_rot"]) and np.array_equal(gcen, res["grad_center"])
+        assert (res["grad_center"][0] == 0).all() and (res["grad_center"][1:] != 0).any(1).all()
+        assert (res["grad_rot"] != 0).mean() >= 0.6
+
+
+@pytest.mark.parametrize("name", sorted(rig.GEO_RIGS))
+def test_geometry_budget_and_difficulty(name):
+    feats, proj, coords, _, extras = rig.geo_problem(name) if "M" not in rig.GEO_RIGS[name] else (None,) * 4 + (dict(want=()),)
+    if feats is None:                                                # the shared rig is read through its option case alone
+        tags = [t[0] for t in rig.geo_option_cases() if t[1] == name]
+        for tag in tags:
+            res = rig.geo_option_reference(tag)
+            assert 0 < res["geo_budget"] < rig.LIMIT
+            assert (res["grad_proj"] != 0).mean() >= 0.6 * 3 / 4, (tag, "one of the four samples is named by no volume")
+            assert (res["grad_coords"][[0, 1, 2, 4]] != 0).mean() >= 0.6, tag
+        return
+    for method in _geo_methods(name):
+        _, res, ties = rig.geo_reference(name, method)
+        rig.assert_geo_budget(res, "%s %s" % (name, method))
+        assert 0 < res["geo_budget"] < rig.LIMIT
+        assert (_compared_coords(name, res["grad_coords"]) != 0).mean() >= 0.6, (name, method)
+        if "proj" in extras["want"]:
+            assert (res["grad_proj"] != 0).mean() >= 0.6, (name, method)
+        assert ties <= 0.15, (name, method, ties)
+
+
+def test_geometry_rigs_cover_every_border_condition_between_them():
+    total = dict.fromkeys(rig.GEO_STATS, 0)
+    for name in GEO_PLAIN:
+        st = rig.geo_reference(name, "sum")[1]["stats"]
+        for k in total:
+            total[k] += st[k]
+    for key in ("ix_lo", "ix_hi", "iy_lo", "iy_hi", "ix0", "ixW", "iy0", "iyH", "behind", "z0"):
+        assert total[key] > 0, (key, total)
+
+
+def test_geometry_option_rigs_keep_their_budget():
+    for tag, name, method, kw in rig.geo_option_cases():
+        res = rig.geo_option_reference(tag)
+        rig.assert_geo_budget(res, tag)
+        assert (res["grad_coords"] != 0).any() and (res["grad_proj"] != 0).any(), tag
+
+
+@pytest.mark.parametrize("slip", ["x1_lt", "no_value_mask", "swap_k"])
+def test_the_rigs_see_a_slip_in_the_restatement(slip):
+    """each deliberate mistake changes bits of grad_coords AND of grad_proj on geo_v3 (a non-square map, so kx != ky), though it stays
+    under the 1e-4-of-the-maximum bar for grad_proj that the smooth-data tests apply"""
+    feats, proj, coords, _, _ = rig.geo_problem("geo_v3")
+    grad, res, _ = rig.geo_reference("geo_v3", "sum")
+    gp32, gc32 = _kernel_order32(feats, proj, coords, grad, "sum", 1, slip=slip)
+    assert not _same_bits(gc32, res["grad_coords"]) and not _same_bits(gp32, res["grad_proj"]), slip

@@ -10,6 +10,10 @@ through conftest.record_err with bound 0.0.  Softmax is not exact and stays with
 bit-exact by design (its fixed-point scale is not a power of two) and is held to a bound derived from its code instead
 (test_plane_backward_stays_inside_its_derived_bound).
 
+The geometry gradients (grad_proj, grad_coords, the cuboid's grad_rot / grad_center) are held to the bits of lattice_rig.geo_oracle on the
+geometry rigs (power-of-two maps), every route and option family, and the kept ix == -1 / iy == -1 boundary to a bound derived from the
+code: the section "the geometry path" at the end.
+
 Deterministic mode: every backward runs again under torch.use_deterministic_algorithms(True).  Its int64 fixed point uses a power-of-two
 exponent (det_scale.h) whose quantum lies orders of magnitude below the rig's, so the result must have the oracle's bits too."""
 import ctypes
@@ -411,3 +415,196 @@ def test_channels_last_to_quad_image(feat, gpu):
             src = _ints((1, 2, C, H, 5), C + H)
             got, _ = _convert(src.transpose(0, 1, 3, 4, 2), src.shape, feat, _capi.LAYOUT_BVHWC, _capi.LAYOUT_QUAD, gpu, 0)
             _image_equal("BVHWC->QUAD %s C%d H%d" % (feat, C, H), got, _quad_image(src))
+
+
+# ----------------------------------------------------------------------------------------------- the geometry path
+# grad_proj, grad_coords and the cuboid's grad_rot / grad_center against lattice_rig.geo_oracle on the geometry rigs (power-of-two maps: kx
+# and ky are dyadic, every step of k_bwd_geom's chain is exact; tests/test_lattice_cpu.py checks that premise).  grad_proj[b, v] sums every
+# voxel of a sample, so ONE voxel handled wrongly -- the tail of the last tile, a tap in a border band, a tap whose value must be zero at a
+# valid clamped address -- moves it by a whole quantum of the rig although it stays far below 1e-4 of the sum.
+def _geo_hold(tag, grads, res, extras):
+    for key, got in grads.items():
+        if got is not None:
+            _hold("geometry %s %s" % (tag, key), got, res[key])
+
+
+def _geo_call(name, method, gpu, feat="f32", out=None, variant="gather", proj_grad=True, coords_grad=True, det=False, channels_last=False, grad=None, **options):
+    """one call of the tensor route on a geometry rig -> dict(grad_proj, grad_coords) (None where no gradient was asked for)"""
+    feats, proj, coords, _, _ = rig.geo_problem(name)
+    grad = rig.geo_reference(name, method)[0] if grad is None else grad
+    f = _features(feats, dict(feat=feat, cl=channels_last), gpu).detach()
+    p = torch.from_numpy(proj).to(gpu).requires_grad_(proj_grad)
+    c = torch.from_numpy(coords).to(gpu).requires_grad_(coords_grad)
+    res = aggregation.unprojection(f, p, c, aggregation_method=method, variant=variant, out_dtype=DT[out or feat], **options)
+    with _Deterministic(det):
+        res.backward(torch.from_numpy(grad).to(gpu).to(res.dtype))
+    return dict(grad_proj=p.grad, grad_coords=c.grad)
+
+
+GEO_TENSOR_RIGS = ["geo_v1", "geo_v3", "geo_v4", "geo_v5", "geo_v8", "geo_v9", "geo_v16", "geo_c260", "geo_h16", "geo_coords_big", "geo_many_tiles"]
+
+
+@pytest.mark.parametrize("name", GEO_TENSOR_RIGS)
+def test_geometry_gradients_have_the_oracles_bits(name, gpu):
+    """k_bwd_geom + k_geom_reduce on every rig, `sum`, `max` and power-of-two `mean`: 1, 3, 4, 5, 8, 9 and 16 views (each CPL, kMaxViews),
+    a ragged last tile, C % 4 != 0, a second 256-channel group, non-square maps, a volume whose grad_coords alone is asked for (part ==
+    nullptr) and one of 272 tiles per sample with a sparse grad_out (k_geom_reduce's stride takes a second trip)"""
+    extras = rig.geo_problem(name)[4]
+    V = rig.GEO_RIGS[name]["V"]
+    for method in ("sum", "max") + (("mean",) if V & (V - 1) == 0 else ()):
+        _, res, _ = rig.geo_reference(name, method)
+        got = _geo_call(name, method, gpu, proj_grad="proj" in extras["want"])
+        assert (got["grad_proj"] is None) == ("proj" not in extras["want"])
+        _geo_hold("%s %s" % (name, method), got, res, extras)
+
+
+@pytest.mark.parametrize("proj_grad,coords_grad", [(True, False), (False, True), (True, True)])
+def test_geometry_gradients_whichever_tensor_asks(proj_grad, coords_grad, gpu):
+    """the three requires_grad combinations of (proj_matricies, coord_volumes): a null `part` resp. `grad_coords` in the launch"""
+    for method in ("sum", "max"):
+        _, res, _ = rig.geo_reference("geo_v3", method)
+        got = _geo_call("geo_v3", method, gpu, proj_grad=proj_grad, coords_grad=coords_grad)
+        assert (got["grad_proj"] is not None) == proj_grad and (got["grad_coords"] is not None) == coords_grad
+        _geo_hold("geo_v3 %s proj=%d coords=%d" % (method, proj_grad, coords_grad), got, res, None)
+
+
+@pytest.mark.parametrize("variant,det", [("gather", False), ("gather", True), ("auto", False), ("brick", False)])
+def test_geometry_gradients_do_not_depend_on_mode_or_forward_route(variant, det, gpu):
+    """geo_v4 in default and deterministic mode, and behind the AUTO and the brick forward: the geometry backward is the same kernel"""
+    for method in ("sum", "max", "mean"):
+        _, res, _ = rig.geo_reference("geo_v4", method)
+        _geo_hold("geo_v4 %s %s%s" % (method, variant, " deterministic" if det else ""), _geo_call("geo_v4", method, gpu, variant=variant, det=det), res, None)
+
+
+@pytest.mark.parametrize("name", ["geo_v3", "geo_v5", "geo_v9"])
+@pytest.mark.parametrize("feat,out", [("f32", "f32"), ("f32", "bf16"), ("f16", "f16"), ("f16", "f32")])
+def test_geometry_gradients_in_every_storage_combination(name, feat, out, gpu):
+    """the four (feature, volume) type pairs geom_dispatch instantiates, on one rig per Row<T, CPL> specialisation (CPL = 4, 2, 1): the
+    rig's whole-number features and grad_out are exact in fp16 / bf16, so the fp32 gradients keep the oracle's bits"""
+    for method in ("sum", "max"):
+        _, res, _ = rig.geo_reference(name, method)
+        _geo_hold("%s %s %s->%s" % (name, method, feat, out), _geo_call(name, method, gpu, feat=feat, out=out), res, None)
+
+
+@pytest.mark.parametrize("feat", ["f32", "f16"])
+def test_geometry_gradients_from_channels_last_features(feat, gpu):
+    for method in ("sum", "mean"):
+        _, res, _ = rig.geo_reference("geo_v4", method)
+        _geo_hold("geo_v4 %s %s channels-last" % (method, feat), _geo_call("geo_v4", method, gpu, feat=feat, channels_last=True), res, None)
+
+
+def test_cuboid_route_pose_gradients_have_the_oracles_bits(gpu):
+    """The POSE instances: grad_rot, grad_center and grad_proj of unprojection_cuboid with sides = extent - 1 (step 1), whole-number
+    centres, sample 0 unrotated (its grad_center must be exactly 0: dX/dc = I - R) and the others a quarter turn of the lattice about its
+    centre, so every voxel centre R d + c is a whole number again"""
+    feats, proj, coords, _, ex = rig.geo_problem("geo_pose")
+    for method in ("sum", "max"):
+        grad, res, _ = rig.geo_reference("geo_pose", method)
+        f = torch.from_numpy(feats).to(gpu)
+        p = torch.from_numpy(proj).to(gpu).requires_grad_(True)
+        r = torch.from_numpy(ex["rotations"]).to(gpu).requires_grad_(True)
+        c = torch.from_numpy(ex["centers"]).to(gpu).requires_grad_(True)
+        out = aggregation.unprojection_cuboid(f, p, r, c, ex["position"], ex["sides"], coords.shape[1:4], method, variant="gather")
+        out.backward(torch.from_numpy(grad).to(gpu))
+        _geo_hold("geo_pose %s" % method, dict(grad_proj=p.grad, grad_rot=r.grad, grad_center=c.grad), res, None)
+        assert not c.grad[0].any() and c.grad[1:].any()
+
+
+@pytest.mark.parametrize("tag", [t[0] for t in rig.geo_option_cases()])
+def test_option_route_geometry_gradients(tag, gpu):
+    """The geometry backward of every option family on its own rig: view_mask (the MASK instances: a full, a single-view and an empty sample),
+    view_weights (with grad_weights, which the same kernel produces), visible_only (alone and with a mask), feature_index (a repeated, a skipped and an out-of-range entry: grad_proj sums over
+    the volumes naming a sample, an unnamed sample gets exact zeros) and view_confidence (the gradient also flows through the sampled
+    confidence).  All share k_bwd_geom's arithmetic chain: bit equality."""
+    _, name, method, kw = next(t for t in rig.geo_option_cases() if t[0] == tag)
+    res = rig.geo_option_reference(tag)
+    args = {k: (torch.from_numpy(v).to(gpu) if isinstance(v, np.ndarray) else v) for k, v in kw.items()}
+    if "view_weights" in kw:
+        args["view_weights"].requires_grad_(True)
+    got = _geo_call(name, method, gpu, grad=res["grad_out"], **args)
+    if "view_weights" in kw:
+        got["grad_weights"] = args["view_weights"].grad
+    _geo_hold("option %s" % tag, got, res, None)
+    if "feature_index" in kw:
+        assert not got["grad_proj"][2].any() and not got["grad_coords"][3].any()      # sample 2 is never named; volume 3 names sample 7
+
+
+def test_zero_lens_geometry_gradients_carry_the_plain_bits(gpu):
+    """lens= with all five coefficients zero (arbitrary intrinsics, a large r2max): k_bwd_geom_lens must give the plain call's bits"""
+    B, V = rig.GEO_RIGS["geo_v3"]["B"], rig.GEO_RIGS["geo_v3"]["V"]
+    lens = np.zeros((B, V, 10), np.float32)
+    lens[..., :4] = np.random.default_rng(3).uniform(-50, 50, (B, V, 4))
+    lens[..., 9] = 1e30
+    for method in ("sum", "max"):
+        _, res, _ = rig.geo_reference("geo_v3", method)
+        _geo_hold("geo_v3 %s zero lens" % method, _geo_call("geo_v3", method, gpu, lens=torch.from_numpy(lens).to(gpu)), res, None)
+
+
+def _kept_boundary_problem():
+    """V = 1, a 5 x 9 map (W - 1 = 8 and H - 1 = 4 are powers of two), a (4, 4, 3) volume at (i, j, k), depth 2.  Sample 0: ix = i - 1
+    (voxels with i = 0 land on ix == -1 exactly), iy = j / 2 + 1 / 4 inside; sample 1: iy = j - 1 (j = 0 lands on iy == -1), ix = i + 1 / 2.
+    Every fp32 step of the POSITION is exact (u = H (i - 1) / 8 with H / 8 = 0.625, and 0.625 m / 5 = m / 8 is a representable
+    quotient; likewise w = W (2 j + 1) / 16 with W / 16 = 0.5625), so kernel and oracle agree on ix, iy and the fractions bit for bit;
+    the features and grad_out are random reals, and kx = 8 / 5, ky = 4 / 9 round: the gradient itself is not exact."""
+    H, W, vol = 5, 9, (4, 4, 3)
+    rng = np.random.default_rng(91)
+    feats = rng.standard_normal((2, 1, 6, H, W)).astype(np.float32)
+    feats[:, :, :, 0, :] += np.sign(feats[:, :, :, 0, :])             # row 0 and column 0 well away from zero
+    feats[:, :, :, :, 0] += np.sign(feats[:, :, :, :, 0])
+    grad = rng.standard_normal((2, 6) + vol).astype(np.float32)
+    grid = np.stack(np.meshgrid(*[np.arange(s) for s in vol], indexing="ij"), -1).astype(np.float32)
+    coords = np.broadcast_to(grid, (2,) + grid.shape).copy()
+    d = 2.0
+    proj = np.zeros((2, 1, 3, 4), np.float32)
+    proj[0, 0, 0] = (d * H / 8, 0, 0, -d * H / 8)                     # u = H (i - 1) / 8      -> ix = i - 1
+    proj[0, 0, 1] = (0, d * W / 8, 0, d * W / 16)                     # w = W (2 j + 1) / 16   -> iy = j / 2 + 1 / 4
+    proj[1, 0, 0] = (d * H / 8, 0, 0, d * H / 16)                     # u = H (2 i + 1) / 16   -> ix = i + 1 / 2
+    proj[1, 0, 1] = (0, d * W / 4, 0, -d * W / 4)                     # w = W (j - 1) / 4      -> iy = j - 1
+    proj[:, 0, 2, 3] = d
+    return feats, proj, coords, grad, H, W
+
+
+def test_the_kept_boundary_has_its_gradient(gpu):
+    """make_geo_rec keeps ix == -1 and iy == -1 ("the tap at x = 0 has weight 0 but a gradient"): there the sample is 0 but ds/dix is the
+    interpolated value of column 0.  No lattice point can lie there (the lattice has ix = (c + t) (W - 1) / (q d); -q d / (W - 1) is no
+    half-integer), so this problem is built by hand (_kept_boundary_problem) and grad_coords is compared PER VOXEL, each against a bound of
+    its own derived from the code, with every term taken from the float64 oracle:
+
+        |got - ref| <= ((1 + u)^R - 1) * T,   u = 2^-24,   T = sum_r |P[r][k]| * (the chain evaluated with every tap value, every ds and
+                                                              u, w replaced by their magnitudes: the sum |terms| of that element)
+
+    R = 24 counts the fp32 roundings on the longest path from a feature value to grad_coords in k_bwd_geom:  3 in ds/dix (the difference of
+    two taps, ty * difference, the fmaf with wy0 * difference);  11 in the channel sum (CPL = 4 fmaf per lane, the 6 additions of
+    wave_sum's tree, one into acc);  3 for du (the division that makes kx, G * kx, / z);  4 more for dh[2] (u = a / z, dw * w, the fmaf,
+    / z);  3 fmaf of P^T dh.  The positions, fractions and weights are exact by construction (asserted below against fp32)."""
+    feats, proj, coords, grad, H, W = _kept_boundary_problem()
+    B, V, C = feats.shape[:3]
+    N = int(np.prod(coords.shape[1:4]))
+    ref = rig.geo_oracle(feats, proj, coords, grad, "sum")["grad_coords"].reshape(B, N, 3)
+    bound = np.zeros((B, N, 3))
+    edge = np.zeros((B, N), bool)
+    kx, ky = (W - 1) / H, (H - 1) / W
+    for b in range(B):
+        pts = coords[b].reshape(N, 3)
+        t = rig.geotaps64(proj[b, 0], pts, feats[b, 0].reshape(C, H * W), H, W)
+        for key in ("ix", "iy", "u", "w"):
+            assert np.array_equal(t[key].astype(np.float32).astype(np.float64), t[key]), "the position is not exact in fp32: test error"
+        assert t["valid"].all()
+        edge[b] = (t["ix"] == -1) if b == 0 else (t["iy"] == -1)
+        assert edge[b].sum() == 12 and ((t["iy"] > 0) & (t["iy"] < H - 1) if b == 0 else (t["ix"] > 0) & (t["ix"] < W - 1))[edge[b]].all()
+        g = np.abs(grad[b].reshape(C, N).astype(np.float64))
+        du, dw = (g * t["adx"]).sum(0) * kx, (g * t["ady"]).sum(0) * ky
+        dh = np.stack([du / t["z"], dw / t["z"], (du * np.abs(t["u"]) + dw * np.abs(t["w"])) / t["z"]], 1)          # (N, 3) magnitudes
+        bound[b] = ((1 + 2.0 ** -24) ** 24 - 1) * (dh @ np.abs(proj[b, 0, :, :3].astype(np.float64)))
+    for b in range(B):                               # non-zero, and by far more than the bound: a kernel that drops the boundary cannot pass
+        assert (np.abs(ref[b][edge[b]][:, b]) > 1e3 * bound[b][edge[b]][:, b]).all(), "the oracle's boundary gradient must not be zero"
+    f = torch.from_numpy(feats).to(gpu)
+    c = torch.from_numpy(coords).to(gpu).requires_grad_(True)
+    out = aggregation.unprojection(f, torch.from_numpy(proj).to(gpu), c, aggregation_method="sum", variant="gather")
+    assert not out.detach().reshape(B, C, N).permute(0, 2, 1)[torch.from_numpy(edge).to(gpu)].any()                # the SAMPLE there is zero
+    out.backward(torch.from_numpy(grad).to(gpu))
+    err = np.abs(c.grad.cpu().numpy().astype(np.float64).reshape(B, N, 3) - ref)
+    worst = int(np.argmax(err - bound))
+    print("kept boundary: max err %.3e (on the boundary %.3e), its bound %.3e, largest |ref| %.3e" % (err.max(), err[edge].max(), bound.ravel()[np.argmax(err)], np.abs(ref).max()))
+    record_err("lattice kept boundary grad_coords per voxel (derived bound)", float(err.ravel()[worst]), float(bound.ravel()[worst]))
+    assert (err <= bound).all()

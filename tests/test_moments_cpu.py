@@ -371,3 +371,45 @@ def test_lattice_fp32_emulation_of_the_pinned_order_carries_the_float64_bits():
             var = (acc / n[None]).astype(np.float32)
             want = ref["out"][b].reshape(2 * C, N).astype(np.float32)
             assert np.array_equal(mu[cmp_[b]], want[:C][cmp_[b]]) and np.array_equal(var[cmp_[b]], want[C:][cmp_[b]]), (tag, b)
+
+
+# ------------------------------------------------------------------------------------ the lattice case's geometry gradients
+# the same construction on power-of-two maps, on which kx = (W - 1) / H and ky = (H - 1) / W are dyadic (lattice_rig.GEO_RIGS)
+LATTICE_GEO = dict(B=3, V=4, C=5, H=8, W=8, vol=(3, 4, 5), seed=74, fmax=1, gmax=1, depths=(2,))   # (5, 4, 7) or fmax = 2 break grad_proj's budget
+
+
+def lattice_geometry_reference(method, kw, cfg=LATTICE_GEO):
+    """-> (the rig's arrays, grad_out as the test must feed it, lattice_rig.geo_oracle's dict) for 'var' / 'meanvar' at the voxels whose
+    participating count n is a power of two (grad_out is zero elsewhere).  ds is restated from the README's definition in float64 --
+    var = (1 / n) sum_S (s_v - mu)^2, so ds_v = (2 g_v / n)(s_v - mu) + g_m / n for v in S, 0 outside -- on lattice_rig.geotaps64's samples
+    and handed to the geometry oracle; S = every view (a view that misses the map takes part with its sample of zero), the present ones
+    under view_mask, the seeing ones under visible_only.  The geometry budget is asserted."""
+    (feats, proj, coords), grad, res = lattice_reference(cfg, method, kw)
+    B, V, C, H, W = feats.shape
+    N = int(np.prod(coords.shape[1:4]))
+    g = grad.reshape(B, -1, N).astype(np.float64)
+    g_m, g_v = (g[:, :C], g[:, C:]) if method == "meanvar" else (np.zeros((B, C, N)), g)
+    ds = np.zeros((B, V, C, N))
+    for b in range(B):
+        T = [lattice_rig.geotaps64(proj[b, v], coords[b].reshape(-1, 3), feats[b, v].reshape(C, H * W), H, W) for v in range(V)]
+        part = np.stack([np.full(N, True if "view_mask" not in kw else bool(kw["view_mask"][b, v])) & (T[v]["seen"] if kw.get("visible_only") else True)
+                         for v in range(V)])
+        n = part.sum(0)
+        assert np.array_equal(n, res["count"][b].ravel())
+        S = np.stack([t["s"] for t in T])
+        mu = np.where(part[:, None], S, 0.0).sum(0) / np.maximum(n, 1)
+        ds[b] = np.where(part[:, None], (2 * g_v[b] / np.maximum(n, 1))[None] * (S - mu[None]) + (g_m[b] / np.maximum(n, 1))[None], 0.0)
+    geo = lattice_rig.geo_oracle(feats, proj, coords, None, "given", ds=ds)
+    lattice_rig.assert_geo_budget(geo, "moments geometry %s" % method)
+    return (feats, proj, coords), grad, geo
+
+
+@pytest.mark.parametrize("method", ["var", "meanvar"])
+def test_lattice_geometry_premise(method):
+    """budget < 2^24, and the float64 restatement equals tests/moments_oracle.py's independent autograd oracle exactly on the rig"""
+    for tag, kw in lattice_cases(LATTICE_GEO["B"], LATTICE_GEO["V"]):
+        (feats, proj, coords), grad, geo = lattice_geometry_reference(method, kw)
+        assert 0 < geo["geo_budget"] < lattice_rig.LIMIT
+        ref = mo.moments_unprojection(feats, proj, coords, grad, method, mask=kw.get("view_mask"), visible=kw.get("visible_only", False))
+        assert np.array_equal(ref["grad_proj"], geo["grad_proj"]) and np.array_equal(ref["grad_coords"], geo["grad_coords"]), (tag, method)
+        assert (geo["grad_coords"] != 0).mean() >= (0.1 if tag == "mask" else 0.3) and (geo["grad_proj"] != 0).any(), (tag, method)

@@ -13,7 +13,7 @@ import posegrad_oracle
 from conftest import record_err
 from multiviewhmr_amd import aggregation
 from test_geometry_grad_gpu import REL
-from test_moments_cpu import LATTICE, LATTICE_V2, lattice_cases, lattice_reference, var_bound
+from test_moments_cpu import LATTICE, LATTICE_GEO, LATTICE_V2, lattice_cases, lattice_geometry_reference, lattice_reference, var_bound
 from test_unproject_gpu import _bound, _err, _ring_problem
 from test_view_mask_gpu import SHAPES, _mask
 
@@ -113,6 +113,24 @@ def test_bit_equality_on_the_lattice_rig(cfg, method, deterministic, gpu):
         assert cmp_.float().mean() >= 0.5, tag
         assert torch.equal(r["out"][cmp_], want[cmp_]), (tag, method, "forward")
         assert torch.equal(r["gf"], torch.from_numpy(ref["grad_features"]).to(torch.float32).to(gpu)), (tag, method, "features.grad")
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_geometry_bit_equality_on_the_lattice_rig(method, gpu):
+    """The lattice case on power-of-two maps (kx and ky dyadic; lattice_rig.GEO_RIGS' construction): grad_proj and grad_coords of
+    k_bwd_geom_moments carry the bits of the float64 oracle, plain, masked and under visible_only.  grad_out is zero at the voxels whose
+    participating count is no power of two, where the division by n rounds.  tests/test_moments_cpu.py::test_lattice_geometry_premise
+    holds the budget and the agreement of the two oracles."""
+    for tag, kw in lattice_cases(LATTICE_GEO["B"], LATTICE_GEO["V"]):
+        (feats, proj, coords), grad, ref = lattice_geometry_reference(method, kw)
+        f, p, c, go = (_t(x, gpu) for x in (feats, proj, coords, grad))
+        mask = None if "view_mask" not in kw else torch.from_numpy(kw["view_mask"])
+        r = _run(f, p, c, method, variant="gather", go=go, mask=mask, visible=kw.get("visible_only", False))
+        for key, name in (("gp", "grad_proj"), ("gc", "grad_coords")):
+            want = ref[name].astype(np.float32)
+            assert np.array_equal(want.astype(np.float64), ref[name]), "the oracle's value is not an fp32 number: rig error"
+            record_err("lattice moments geometry %s %s %s" % (method, tag, name), _err(r[key].double().cpu().numpy(), ref[name]), 0.0)
+            assert torch.equal(r[key].view(torch.int32), torch.from_numpy(want).to(gpu).view(torch.int32)), (tag, method, name)
 
 
 # ------------------------------------------------------------------------------------ 2. the float64 oracle on general inputs
