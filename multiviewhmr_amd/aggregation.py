@@ -15,6 +15,7 @@ registered autograd formula) whose host side runs in the PyTorch-ROCm C++ extens
 route of every un-projection launch, VolumeGenerator's fused conv + un-projection included.  There is no CPU / eager fallback: the
 call raises if the tensors are not on a HIP device or the library or the extension is not built.
 """
+import collections
 import ctypes
 import functools
 import os
@@ -146,138 +147,126 @@ def _op_defined(name):
         return False
 
 
-# The four families of un-projection ops: family -> (the tensors that place the volume, the non-tensor arguments that go with them, masked).
-# Each family is mvhmr::<family> with <family>_backward, <family>_backward_deterministic (the feature gradient, bitwise reproducible: what
-# autograd runs under torch.use_deterministic_algorithms(True)) and <family>_backward_geometry (fp32 gradients w.r.t. proj_matricies and
-# the placing tensors -- coord_volumes, or the cuboid's rotations and centers; an output not asked for comes back empty; `variant` plays
-# no part).  Arguments: features, proj, the placing tensors, view_mask (B, V) uint8 on the features' device, nonzero = present (masked
-# and weighted families), view_weights (B, V) fp32 there as well (weighted families: per-view confidence weights, a view is present when its
-# mask byte is nonzero and its weight > 0; DESIGN.md 5.9 -- the geometry backward differentiates w.r.t. them too), the placing arguments,
-# then method, out_dtype, variant.  The cuboid families feed the same kernels from the cuboid recipe
-# (mvhmr_unproject_*_cuboid) instead of a coordinate tensor.  The masked families (mvhmr_unproject_*_masked) read planar or channels-last
-# features, never a quad-planar copy, and run the gather kernels with a per-sample view count.  The visible families
-# (mvhmr_unproject_*_visible) are masked families -- view_mask is all ones when the caller gave none -- in which every voxel aggregates only
-# the views that see it.  The confidence families (mvhmr_unproject_*_confidence) are masked families too, with
-# view_confidence (B, V, Hf, Wf) fp32 behind view_mask: per-pixel confidence maps sampled like one more channel; the geometry
-# backward differentiates w.r.t. them as well; their *_visible twins add the seeing test.  Their view_mask is `Tensor?`: None is the null
-# mask of the C entry points, with which nothing is packed or copied.  The shared families (mvhmr_unproject_*_shared) take
-# feature_index (M,) int32 on the features' device behind the placing tensors, which then hold M entries: volume m reads sample
-# feature_index[m]; the forward returns M volumes, the feature gradient has B samples; the index is not differentiable.  The lens families
-# (mvhmr_unproject_*_lens) take lens (B, V, 10) fp32 on the features' device behind the placing tensors: the voxels are
-# projected through the records; features are read as the plain families read them (the feature backward takes the plane route wherever the
-# plain gather call does); the lens is not differentiable.
-_CUBOID_ARGS = ("float[] position", "float[] sides", "int[] vol")
-_FAMILIES = {
-    "unprojection": (("coords",), (), False),
-    "unprojection_masked": (("coords",), (), True),
-    "unprojection_cuboid": (("rot", "center"), _CUBOID_ARGS, False),
-    "unprojection_cuboid_masked": (("rot", "center"), _CUBOID_ARGS, True),
-    "unprojection_weighted": (("coords",), (), True, True),
-    "unprojection_cuboid_weighted": (("rot", "center"), _CUBOID_ARGS, True, True),
-    "unprojection_visible": (("coords",), (), True, False, True),
-    "unprojection_cuboid_visible": (("rot", "center"), _CUBOID_ARGS, True, False, True),
-    "unprojection_confidence": (("coords",), (), True, False, False, True),
-    "unprojection_cuboid_confidence": (("rot", "center"), _CUBOID_ARGS, True, False, False, True),
-    "unprojection_confidence_visible": (("coords",), (), True, False, True, True),
-    "unprojection_cuboid_confidence_visible": (("rot", "center"), _CUBOID_ARGS, True, False, True, True),
-    "unprojection_shared": (("coords",), (), False, False, False, False, True),
-    "unprojection_cuboid_shared": (("rot", "center"), _CUBOID_ARGS, False, False, False, False, True),
-    "unprojection_lens": (("coords",), (), False, False, False, False, False, True),
-    "unprojection_cuboid_lens": (("rot", "center"), _CUBOID_ARGS, False, False, False, False, False, True),
+# The un-projection ops are 2 placings x 9 kinds = 18 families.  Each family is mvhmr::<family> with <family>_backward,
+# <family>_backward_deterministic (the feature gradient, bitwise reproducible: what autograd runs under
+# torch.use_deterministic_algorithms(True)) and <family>_backward_geometry (fp32 gradients w.r.t. proj_matricies, the placing tensors and the
+# differentiable option tensors; an output not asked for comes back empty; `variant` plays no part).  An op's arguments are features, proj,
+# the placing tensors, the kind's option tensors, the placing's arguments, the kind's arguments, then method, out_dtype, variant.  All 18 run
+# on the extension's six ops: what a kind adds travels there as defaulted keyword arguments.
+class _Option(collections.namedtuple("_Option", "name optional grad", defaults=(False, None))):
+    """One option tensor of a kind, behind the geometry tensors.  name: its name in the op's schema, which is also the extension keyword it
+    feeds; optional: `Tensor?` in the schema -- None is the null pointer of the C entry points, with which nothing is packed or copied;
+    grad: the extension keyword of its gradient buffer when the geometry backward differentiates w.r.t. it, else None"""
+
+
+class _Kind(collections.namedtuple("_Kind", "options extras constants", defaults=((), (), {}))):
+    """options: the _Option tensors in schema order; extras: the kind's non-tensor schema arguments, which feed the extension keywords of
+    the same names; constants: the extension keywords the kind implies"""
+
+
+_MASK, _NULLABLE_MASK = _Option("view_mask"), _Option("view_mask", optional=True)       # (B, V) uint8 on the features' device, nonzero = present
+_WEIGHTS = _Option("view_weights", grad="grad_weights")                                   # (B, V) fp32: present = mask byte nonzero and weight > 0
+_CONFIDENCE = _Option("view_confidence", grad="grad_confidence")                         # (B, V, Hf, Wf) fp32 maps, sampled like one more channel
+_PLACINGS = {                                            # the tensors that place the volume, the arguments that go with them
+    "unprojection": (("coords",), ()),
+    "unprojection_cuboid": (("rot", "center"), ("float[] position", "float[] sides", "int[] vol")),     # the same kernels, fed the cuboid recipe
+}
+# Why the kinds are what they are.  A kind with a view_mask reads planar or channels-last features, never a quad-planar copy, and runs the
+# gather kernels with a per-sample view count (DESIGN.md 5.8); so does _shared.  Where the mask is not nullable the C entry point wants one:
+# the front door hands all ones when the caller gave none.  _shared: the placing tensors hold M entries, volume m reads sample
+# feature_index[m]; M volumes come back, the feature gradient has B samples.  _lens reads features as the plain kind does (the feature
+# backward takes the plane route wherever the plain gather call does).  _moments: `method` is the moment the variance is taken around, mean;
+# moments 1 is the variance (C channels), 2 the mean and the variance (2C); the feature gradient has the features' C channels.
+_KINDS = {
+    "": _Kind(),
+    "_masked": _Kind(options=(_MASK,)),                                                                        # DESIGN.md 5.8
+    "_weighted": _Kind(options=(_MASK, _WEIGHTS)),                                                             # 5.9
+    "_visible": _Kind(options=(_MASK,), constants={"visible_only": True}),                                     # 5.10
+    "_confidence": _Kind(options=(_NULLABLE_MASK, _CONFIDENCE)),                                               # 5.11
+    "_confidence_visible": _Kind(options=(_NULLABLE_MASK, _CONFIDENCE), constants={"visible_only": True}),
+    "_shared": _Kind(options=(_Option("feature_index"),)),                                                     # 5.12: (M,) int32
+    "_lens": _Kind(options=(_Option("lens"),)),                                                                # 5.13: (B, V, 10) fp32
+    "_moments": _Kind(options=(_NULLABLE_MASK,), extras=("bool visible_only", "int moments")),                 # 5.14
 }
 
 
 class _Family:
-    """the implementations of one family's ops, each taking the ops' arguments positionally"""
+    """the implementations of one family's ops, each taking the ops' arguments positionally; every attribute is derived from the placing
+    and the kind"""
 
-    def __init__(self, name, places, extras, masked, weighted=False, visible=False, confidence=False, shared=False, lens=False):
-        self.name, self.masked, self.weighted, self.visible, self.confidence, self.shared = name, masked, weighted, visible, confidence, shared
-        self.lens = lens
-        self.native = "unprojection_cuboid" if extras else "unprojection"       # the extension's op: view_mask / view_weights are trailing arguments there
+    def __init__(self, name, native, places, place_extras, kind):
+        self.name, self.native = name, native                                   # native: the extension's op, the placing's plain family
+        self.options, self.constants = kind.options, kind.constants
         self.geo = ("proj",) + places                                           # the geometry tensors, behind features
-        self.tensors = (("features",) + self.geo + (("view_mask",) if masked else ()) + (("view_weights",) if weighted else ())
-                        + (("view_confidence",) if confidence else ()) + (("feature_index",) if shared else ()) + (("lens",) if lens else ()))
-        self.grads = self.geo + (("view_weights",) if weighted else ()) + (("view_confidence",) if confidence else ())   # what the geometry backward differentiates
-        self.extras = extras
-        self.n_inputs = len(self.tensors) + len(extras) + 3
+        self.tensors = ("features",) + self.geo + tuple(o.name for o in kind.options)
+        self.grads = self.geo + tuple(o.name for o in kind.options if o.grad)   # what the geometry backward differentiates
+        self.extras = place_extras + kind.extras
+        self.place_args, self.kind_args = (tuple(e.split()[1] for e in extras) for extras in (place_extras, kind.extras))
+        self.names = (self.tensors + self.place_args + self.kind_args + ("method", "out_dtype", "variant")
+                      + tuple("want_" + g for g in self.grads))                 # the ops' arguments in schema order (want_*: the geometry backward's)
+        self.n_inputs = len(self.tensors) + len(self.extras) + 3
+        self.masked, self.weighted, self.confidence, self.shared, self.lens = (
+            t in self.tensors for t in ("view_mask", "view_weights", "view_confidence", "feature_index", "lens"))
+        self.visible = kind.constants.get("visible_only", False)
 
     def schema(self):
-        # (a confidence family's view_mask is optional: None reaches the C entry point as a null mask, and nothing is packed or copied)
-        kind = lambda t: "Tensor? " if self.confidence and t == "view_mask" else "Tensor "  # noqa: E731
-        return ", ".join([kind(t) + t for t in self.tensors] + list(self.extras) + ["int method", "int out_dtype", "int variant"])
+        nullable = {o.name for o in self.options if o.optional}
+        return ", ".join(["Tensor%s %s" % ("?" if t in nullable else "", t) for t in self.tensors] + list(self.extras)
+                         + ["int method", "int out_dtype", "int variant"])
 
-    def split(self, args):
-        """-> features, (proj, *placing tensors), (view_mask or None, view_weights or None, view_confidence or None), placing arguments,
-        (method, out_dtype, variant), want_* flags (default True)"""
-        n, k = len(self.tensors), len(self.tensors) + len(self.extras)
-        g = 1 + len(self.geo)
-        want = tuple(args[k + 3:])
-        views = (args[g] if self.masked else None, args[g + 1] if self.weighted else None, args[g + 1] if self.confidence else None)
-        return (args[0], tuple(args[1:g]), views, tuple(args[n:k]), tuple(args[k:k + 3]), want + (True,) * (len(self.grads) - len(want)))
+    def bind(self, args):
+        """the ops' positional arguments by name"""
+        return dict(zip(self.names, args))
 
-    def index(self, args):
-        """a shared family's feature_index (behind the geometry tensors), else None"""
-        return args[1 + len(self.geo)] if self.shared else None
+    def volume(self, a):
+        return tuple(a["vol"]) if self.place_args else tuple(a[self.geo[1]].shape[1:4])
 
-    def lens_of(self, args):
-        """a lens family's records (behind the geometry tensors), else None"""
-        return args[1 + len(self.geo)] if self.lens else None
-
-    def volume(self, geo, extra):
-        return tuple(extra[2]) if extra else tuple(geo[1].shape[1:4])
-
-    def native_args(self, args, geometry=False):
-        """the extension's leading arguments (the view the library reads, proj, placing tensors and arguments, descriptor fields), then
-        (view_mask, view_weights, view_confidence)"""
-        features, geo, views, extra, (method, out_dtype, variant), _ = self.split(args)
-        layout = None
+    def call(self, op, a, lead=(), want=(), geometry=False, **keywords):
+        """the extension's op for bound arguments `a`: the view the library reads, proj, the placing tensors and arguments, the descriptor's
+        fields, the want_* flags; everything the kind adds by keyword.  A kind with a view_mask, _shared and the geometry backward read
+        channels-last features as they are or a planar copy, the others what _feature_layout decides"""
+        features, layout = a["features"], None
         if self.masked or self.shared or geometry:
             features, layout = _geometry_read_layout(features)
-        read, desc = _native_args(features, self.volume(geo, extra), method, out_dtype, variant, layout)
-        return (read,) + geo + extra + desc, views
+        read, desc = _native_args(features, self.volume(a), a["method"], a["out_dtype"], a["variant"], layout)
+        keywords.update(self.constants)
+        keywords.update((o.name, a[o.name]) for o in self.options)
+        keywords.update((n, a[n]) for n in self.kind_args)
+        return getattr(_native(), self.native + op)(*lead, read, *(a[n] for n in self.geo + self.place_args), *desc, *want, **keywords)
 
     def forward(self, *args):
-        lead, (mask, weights, conf) = self.native_args(args)
-        return getattr(_native(), self.native)(*lead, mask, weights, self.visible, conf, feature_index=self.index(args), lens=self.lens_of(args))
+        return self.call("", self.bind(args))
 
     def backward(self, deterministic, grad_out, *args):
         """gradient w.r.t. features (the geometry's is backward_geometry)"""
-        lead, (mask, weights, conf) = self.native_args(args)
-        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, weights, self.visible, conf, feature_index=self.index(args), lens=self.lens_of(args))
+        return self.call("_backward", self.bind(args), (grad_out.contiguous(),), deterministic=deterministic)
 
     def backward_geometry(self, grad_out, *args):
-        """planar features go through the library's channels-last pass, channels-last ones are read as they are; the gradient w.r.t.
-        view_weights or view_confidence (weighted and confidence families, last) is written by the extension into the tensor handed to it"""
-        lead, (mask, weights, conf) = self.native_args(args, geometry=True)
-        want = self.split(args)[5]
-        op = getattr(_native(), self.native + "_backward_geometry")
-        if self.confidence:
-            gc = conf.new_empty(conf.shape if want[-1] else (0,))
-            tail = (mask, None, None, self.visible, conf, gc if want[-1] else None)
-            if not any(want[:-1]):                         # the maps' gradient alone: the extension's outputs stay empty
-                op(grad_out.contiguous(), *lead, *want[:-1], *tail)
-                return tuple(conf.new_empty((0,)) for _ in self.geo) + (gc,)
-            return tuple(op(grad_out.contiguous(), *lead, *want[:-1], *tail)) + (gc,)
-        if not self.weighted:
-            return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, self.visible, None, None, feature_index=self.index(args), lens=self.lens_of(args)))
-        gw = weights.new_empty(weights.shape if want[-1] else (0,))
-        if not any(want[:-1]):                             # the weights' gradient alone: the extension's outputs stay empty
-            op(grad_out.contiguous(), *lead, *want[:-1], mask, weights, gw)
-            return tuple(weights.new_empty((0,)) for _ in self.geo) + (gw,)
-        return tuple(op(grad_out.contiguous(), *lead, *want[:-1], mask, weights, gw if want[-1] else None)) + (gw,)
+        """planar features go through the library's channels-last pass, channels-last ones are read as they are.  The extension returns the
+        gradients of the geometry tensors; the gradient w.r.t. a differentiable option tensor is written by it into the buffer handed to it,
+        and may be the only one asked for"""
+        a = self.bind(args)
+        want = [a.get("want_" + g, True) for g in self.grads]
+        n, buffers, asked = len(self.geo), [], {}
+        for o, w in zip((o for o in self.options if o.grad), want[n:]):
+            buffers.append(a[o.name].new_empty(a[o.name].shape if w else (0,)))
+            if w:
+                asked[o.grad] = buffers[-1]
+        return tuple(self.call("_backward_geometry", a, (grad_out.contiguous(),), want[:n], geometry=True, **asked)) + tuple(buffers)
 
     def fake_forward(self, *args):
-        features, geo, _, extra, (_, out_dtype, _), _ = self.split(args)
-        volumes = self.index(args).shape[0] if self.shared else features.shape[0]
-        return features.new_empty((volumes, features.shape[2]) + self.volume(geo, extra), dtype=_DTYPES[out_dtype])
+        a = self.bind(args)
+        features = a["features"]
+        volumes = a["feature_index"].shape[0] if self.shared else features.shape[0]
+        halves = 2 if a.get("moments") == _MOMENTS["meanvar"] else 1
+        return features.new_empty((volumes, halves * features.shape[2]) + self.volume(a), dtype=_DTYPES[a["out_dtype"]])
 
     def fake_backward(self, grad_out, features, *args):
         return torch.empty_like(features)
 
     def fake_backward_geometry(self, grad_out, *args):
-        _, geo, views, _, _, want = self.split(args)
-        diff = geo + ((views[1],) if self.weighted else ()) + ((views[2],) if self.confidence else ())
-        return tuple(t.new_empty(t.shape if w else (0,), dtype=torch.float32) for t, w in zip(diff, want))
+        a = self.bind(args)
+        return tuple(a[g].new_empty(a[g].shape if a.get("want_" + g, True) else (0,), dtype=torch.float32) for g in self.grads)
 
     def setup_context(self, ctx, inputs, output):
         ctx.save_for_backward(*inputs[:len(self.tensors)])
@@ -287,7 +276,7 @@ class _Family:
         ops, saved = torch.ops.mvhmr, ctx.saved_tensors
         op = getattr(ops, self.name + ("_backward_deterministic" if torch.are_deterministic_algorithms_enabled() else "_backward"))
         g = op(grad_out, *saved, *ctx.args) if ctx.needs_input_grad[0] else None
-        at = [1 + i for i in range(len(self.geo))] + ([len(self.tensors) - 1] if self.weighted or self.confidence else [])   # the differentiable inputs behind features
+        at = [self.tensors.index(g) for g in self.grads]   # the differentiable inputs behind features
         want = tuple(ctx.needs_input_grad[i] for i in at)
         grads = [g] + [None] * (self.n_inputs - 1)
         if any(want):                                      # a features-only backward launches nothing more
@@ -313,61 +302,17 @@ class _Family:
         torch.library.register_autograd(name, self.autograd, setup_context=self.setup_context)
 
 
-class _MomentsFamily(_Family):
-    """mvhmr::unprojection_moments / mvhmr::unprojection_cuboid_moments (the *_moments entry points; DESIGN.md 5.14): a masked family whose
-    view_mask is `Tensor?` (None: the null mask, nothing is packed or copied), with `bool visible_only` and `int moments` (1: the variance, C
-    channels; 2: the mean and the variance, 2C channels) behind the placing arguments.  `method` is the moment the variance is taken around:
-    mean.  The feature gradient has the features' C channels; the geometry backward is the family's usual one."""
-
-    def __init__(self, name, places, extras):
-        super().__init__(name, places, extras, True)
-        self.place_extras = extras
-        self.extras = tuple(extras) + ("bool visible_only", "int moments")
-        self.n_inputs = len(self.tensors) + len(self.extras) + 3
-
-    def schema(self):
-        kind = lambda t: "Tensor? " if t == "view_mask" else "Tensor "  # noqa: E731
-        return ", ".join([kind(t) + t for t in self.tensors] + list(self.extras) + ["int method", "int out_dtype", "int variant"])
-
-    def native_args(self, args, geometry=False):
-        """-> the extension's leading arguments, view_mask, visible_only, moments"""
-        features, geo, views, extra, (method, out_dtype, variant), _ = self.split(args)
-        features, layout = _geometry_read_layout(features)
-        place, visible, moments = tuple(extra[:-2]), bool(extra[-2]), int(extra[-1])
-        read, desc = _native_args(features, self.volume(geo, place), method, out_dtype, variant, layout)
-        return (read,) + geo + place + desc, views[0], visible, moments
-
-    def forward(self, *args):
-        lead, mask, visible, moments = self.native_args(args)
-        return getattr(_native(), self.native)(*lead, mask, None, visible, None, moments)
-
-    def backward(self, deterministic, grad_out, *args):
-        lead, mask, visible, moments = self.native_args(args)
-        return getattr(_native(), self.native + "_backward")(grad_out.contiguous(), *lead, mask, deterministic, None, visible, None, moments)
-
-    def backward_geometry(self, grad_out, *args):
-        lead, mask, visible, moments = self.native_args(args, geometry=True)
-        want = self.split(args)[5]
-        op = getattr(_native(), self.native + "_backward_geometry")
-        return tuple(op(grad_out.contiguous(), *lead, *want, mask, None, None, visible, None, None, moments))
-
-    def fake_forward(self, *args):
-        features, geo, _, extra, (_, out_dtype, _), _ = self.split(args)
-        halves = 2 if int(extra[-1]) == _MOMENTS["meanvar"] else 1
-        return features.new_empty((features.shape[0], halves * features.shape[2]) + self.volume(geo, tuple(extra[:-2])), dtype=_DTYPES[out_dtype])
-
-
-_OPS = {name: _Family(name, *spec) for name, spec in _FAMILIES.items()}
-_OPS["unprojection_moments"] = _MomentsFamily("unprojection_moments", ("coords",), ())
-_OPS["unprojection_cuboid_moments"] = _MomentsFamily("unprojection_cuboid_moments", ("rot", "center"), _CUBOID_ARGS)
+_OPS = {base + suffix: _Family(base + suffix, base, places, place_extras, kind)
+        for base, (places, place_extras) in _PLACINGS.items() for suffix, kind in _KINDS.items()}
 for _family in _OPS.values():
     _family.register()
 _op_backward = functools.partial(_OPS["unprojection"].backward, False)          # (grad_out, features, proj, coords, method, out_dtype, variant)
 
 
-def _check_call(features, proj_matricies, volume, volume_shape, aggregation_method, variant, out_dtype, same_device):
-    """The argument checks unprojection() and unprojection_cuboid() share.  volume: the tensors that place the volume; volume_shape(B)
-    raises when they do not fit, else returns (X, Y, Z); same_device: refuse proj_matricies / volume on another device than features.
+def _check_call(features, proj_matricies, volume, volume_shape, aggregation_method, variant, out_dtype, same_device, feature_index=None):
+    """The argument checks unprojection() and unprojection_cuboid() share.  volume: the tensors that place the volume; volume_shape(n)
+    raises when they do not hold n volumes (B, or the checked feature_index's M), else returns (X, Y, Z); same_device: refuse
+    proj_matricies / volume on another device than features.
     -> (out_dtype with its default applied, (X, Y, Z), the zero volume when there is nothing to launch or None)"""
     for t in (features, proj_matricies) + volume:
         if not torch.is_tensor(t):
@@ -381,7 +326,8 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
     B, V = features.shape[:2]
     if tuple(proj_matricies.shape) != (B, V, 3, 4):
         raise RuntimeError("unprojection: proj_matricies must be (%d, %d, 3, 4), got %s" % (B, V, tuple(proj_matricies.shape)))
-    vol = volume_shape(B)
+    n = B if feature_index is None else feature_index.shape[0]
+    vol = volume_shape(n)
     if not features.is_cuda:
         raise RuntimeError("unprojection: features live on %s; this implementation runs only on a HIP device "
                            "(MI355X) and has no CPU path" % features.device)
@@ -390,10 +336,10 @@ def _check_call(features, proj_matricies, volume, volume_shape, aggregation_meth
                            % ((features.device, proj_matricies.device) + tuple(t.device for t in volume)))
     if out_dtype is None:
         out_dtype = torch.float16 if features.dtype == torch.float16 else torch.float32
-    if features.numel() == 0 or 0 in vol:
-        # empty batch / empty volume: the reference's zero-initialised volume comes back (aggregation.py:25-28), nothing to launch
+    if features.numel() == 0 or 0 in vol or n == 0:
+        # empty batch / empty volume / no volumes: the reference's zero-initialised volume comes back (aggregation.py:25-28), nothing to launch
         channels = features.shape[2] * (2 if aggregation_method == "meanvar" else 1)
-        return out_dtype, vol, torch.zeros((B, channels) + vol, dtype=out_dtype, device=features.device)
+        return out_dtype, vol, torch.zeros((n, channels) + vol, dtype=out_dtype, device=features.device)
     return out_dtype, vol, None
 
 
@@ -456,59 +402,14 @@ def unprojection(features, proj_matricies, coord_volumes, aggregation_method='so
                     ValueError).  With view_mask, view_weights, visible_only, view_confidence or feature_index it raises ValueError (not built
                     yet).  Runs the gather kernels ('auto' too; 'brick' is refused); DESIGN.md 5.13.
     """
-    def volume_shape(B):
-        n = B if feature_index is None else feature_index.shape[0]
+    def volume_shape(n):
         if coord_volumes.dim() != 5 or coord_volumes.shape[0] != n or coord_volumes.shape[4] != 3:
             raise RuntimeError("unprojection: coord_volumes must be (%d, X, Y, Z, 3), got %s" % (n, tuple(coord_volumes.shape)))
         return tuple(coord_volumes.shape[1:4])
 
-    _check_moments(aggregation_method, view_weights, view_confidence, feature_index, lens)
-    if lens is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_lens(lens, features, view_mask, view_weights, visible_only, view_confidence, feature_index)
-    if feature_index is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_feature_index(feature_index, features, view_mask, view_weights, visible_only, view_confidence)
-
-    if view_mask is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_view_mask(view_mask, features)
-    if view_weights is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_view_weights(view_weights, features, aggregation_method)
-    _check_visible_only(visible_only, view_weights)
-    if view_confidence is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_view_confidence(view_confidence, features, aggregation_method, view_weights)
-    out_dtype, _, empty = _check_call(features, proj_matricies, (coord_volumes,), volume_shape, aggregation_method, variant, out_dtype,
-                                      same_device=True)
-    if feature_index is not None and (empty is not None or feature_index.shape[0] == 0):
-        return features.new_zeros((feature_index.shape[0], features.shape[2]) + tuple(coord_volumes.shape[1:4]), dtype=out_dtype)
-    if empty is not None:
-        return empty
-    # no detach: the op differentiates w.r.t. proj and coords too (the casts carry the gradients back to the caller's dtypes)
-    proj = proj_matricies.to(torch.float32).contiguous()
-    coords = coord_volumes.to(torch.float32).contiguous()
-    if aggregation_method in _MOMENTS:
-        return torch.ops.mvhmr.unprojection_moments(features, proj, coords, None if view_mask is None else _mask_bytes(view_mask, features),
-                                                    bool(visible_only), _MOMENTS[aggregation_method], _capi.AGG["mean"], _dtype_code(out_dtype),
-                                                    _capi.VARIANT[variant])
-    if lens is not None:
-        return torch.ops.mvhmr.unprojection_lens(features, proj, coords, _lens_fp32(lens, features), _capi.AGG[aggregation_method],
-                                                 _dtype_code(out_dtype), _lens_variant(variant))
-    if feature_index is not None:
-        return torch.ops.mvhmr.unprojection_shared(features, proj, coords, _index_int32(feature_index, features), _capi.AGG[aggregation_method],
-                                                   _dtype_code(out_dtype), _capi.VARIANT[variant])
-    if view_confidence is not None:
-        op = torch.ops.mvhmr.unprojection_confidence_visible if visible_only else torch.ops.mvhmr.unprojection_confidence
-        return op(features, proj, coords, None if view_mask is None else _mask_bytes(view_mask, features), _weights_fp32(view_confidence, features),
-                  _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
-    if visible_only:
-        return torch.ops.mvhmr.unprojection_visible(features, proj, coords, _weighted_mask(view_mask, features), _capi.AGG[aggregation_method],
-                                                    _dtype_code(out_dtype), _capi.VARIANT[variant])
-    if view_weights is not None:
-        return torch.ops.mvhmr.unprojection_weighted(features, proj, coords, _weighted_mask(view_mask, features), _weights_fp32(view_weights, features),
-                                                     _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
-    if view_mask is not None:
-        mask = _mask_bytes(view_mask, features)
-        return torch.ops.mvhmr.unprojection_masked(features, proj, coords, mask, _capi.AGG[aggregation_method], _dtype_code(out_dtype),
-                                                   _capi.VARIANT[variant])
-    return torch.ops.mvhmr.unprojection(features, proj, coords, _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
+    return _unproject("unprojection", features, proj_matricies, (coord_volumes,), volume_shape, True, None, aggregation_method, out_dtype, variant,
+                      dict(view_mask=view_mask, view_weights=view_weights, visible_only=visible_only, view_confidence=view_confidence,
+                           feature_index=feature_index, lens=lens))
 
 
 def _check_moments(aggregation_method, view_weights=None, view_confidence=None, feature_index=None, lens=None):
@@ -522,25 +423,46 @@ def _check_moments(aggregation_method, view_weights=None, view_confidence=None, 
                              "pass a view_mask and / or visible_only=True" % (aggregation_method, what))
 
 
-def _check_view_mask(view_mask, features):
-    """view_mask (B, V) bool or an integer dtype, any device: raises TypeError / RuntimeError as _check_call does"""
+def _check_options(shape, aggregation_method, view_mask=None, view_weights=None, visible_only=False, view_confidence=None, feature_index=None,
+                   lens=None):
+    """The one place the options of a call are checked, for unprojection(), unprojection_cuboid() and VolumeGenerator.forward.  shape: the
+    features' (B, V, Hf, Wf), or None when they are not a 5-D tensor -- _check_call refuses those next; until then only the checks that read
+    no shape run.  The order decides which refusal a call with several mistakes gets."""
+    _check_moments(aggregation_method, view_weights, view_confidence, feature_index, lens)
+    if shape is not None:
+        views = tuple(shape[:2])
+        if lens is not None:
+            _check_lens(lens, views, view_mask, view_weights, visible_only, view_confidence, feature_index)
+        if feature_index is not None:
+            _check_feature_index(feature_index, shape[0], view_mask, view_weights, visible_only, view_confidence)
+        if view_mask is not None:
+            _check_view_mask(view_mask, views)
+        if view_weights is not None:
+            _check_view_weights(view_weights, views, aggregation_method)
+    _check_visible_only(visible_only, view_weights)
+    if shape is not None and view_confidence is not None:
+        _check_view_confidence(view_confidence, tuple(shape), aggregation_method, view_weights)
+
+
+def _check_view_mask(view_mask, views):
+    """view_mask (B, V) = views, bool or an integer dtype, any device: raises TypeError / RuntimeError as _check_call does"""
     if not torch.is_tensor(view_mask):
         raise TypeError("unprojection: view_mask must be a (B, V) tensor of bool or integers, got %s" % type(view_mask).__name__)
     if view_mask.dtype.is_floating_point or view_mask.dtype.is_complex:
         raise TypeError("unprojection: view_mask must be bool or an integer dtype, got %s" % view_mask.dtype)
-    if tuple(view_mask.shape) != tuple(features.shape[:2]):
-        raise RuntimeError("unprojection: view_mask must be %s, got %s" % (tuple(features.shape[:2]), tuple(view_mask.shape)))
+    if tuple(view_mask.shape) != views:
+        raise RuntimeError("unprojection: view_mask must be %s, got %s" % (views, tuple(view_mask.shape)))
 
 
-def _check_lens(lens, features, view_mask=None, view_weights=None, visible_only=False, view_confidence=None, feature_index=None):
+def _check_lens(lens, views, view_mask=None, view_weights=None, visible_only=False, view_confidence=None, feature_index=None):
     """lens (B, V, 10) of a floating dtype, any device: raises TypeError / RuntimeError as _check_view_weights does, ValueError when it requires
     grad and beside a view selection or a feature_index"""
     if not torch.is_tensor(lens):
         raise TypeError("unprojection: lens must be a (B, V, 10) floating tensor, got %s" % type(lens).__name__)
     if not lens.dtype.is_floating_point:
         raise TypeError("unprojection: lens must be a floating dtype, got %s" % lens.dtype)
-    if tuple(lens.shape) != tuple(features.shape[:2]) + (10,):
-        raise RuntimeError("unprojection: lens must be (B, V, 10) = %s, got %s" % (tuple(features.shape[:2]) + (10,), tuple(lens.shape)))
+    if tuple(lens.shape) != views + (10,):
+        raise RuntimeError("unprojection: lens must be (B, V, 10) = %s, got %s" % (views + (10,), tuple(lens.shape)))
     if lens.requires_grad:
         raise ValueError("unprojection: lens is not differentiable in this version (DESIGN.md 5.13): pass lens.detach()")
     for given, what in ((view_mask is not None, "view_mask"), (view_weights is not None, "view_weights"), (bool(visible_only), "visible_only=True"),
@@ -562,7 +484,7 @@ def _lens_variant(variant):
 _MAX_VOLUMES = 65535                                    # the *_shared entry points: the volume index is the grid's y extent (mvhmr_unproject.h)
 
 
-def _check_feature_index(feature_index, features, view_mask=None, view_weights=None, visible_only=False, view_confidence=None):
+def _check_feature_index(feature_index, B, view_mask=None, view_weights=None, visible_only=False, view_confidence=None):
     """feature_index (M,) of an integer dtype, any device: raises TypeError / RuntimeError as _check_view_mask does, IndexError for a CPU entry
     outside [0, B) (a device index is not inspected: no synchronisation), ValueError for M > 65535 and beside a view selection"""
     if not torch.is_tensor(feature_index):
@@ -578,7 +500,6 @@ def _check_feature_index(feature_index, features, view_mask=None, view_weights=N
                              "on their own" % what)
     if feature_index.shape[0] > _MAX_VOLUMES:
         raise ValueError("unprojection: feature_index names %d volumes, at most %d per call: split the call" % (feature_index.shape[0], _MAX_VOLUMES))
-    B = features.shape[0]
     if not feature_index.is_cuda and feature_index.device.type != "meta" and feature_index.numel():
         lo, hi = int(feature_index.min()), int(feature_index.max())
         if lo < 0 or hi >= B:
@@ -602,26 +523,25 @@ def _mask_bytes(view_mask, features):
     return (view_mask != 0).to(device=features.device, dtype=torch.uint8).contiguous()
 
 
-def _check_view_weights(view_weights, features, aggregation_method):
-    """view_weights (B, V) of a floating dtype, any device: raises TypeError / RuntimeError as _check_view_mask does, ValueError for 'max'"""
+def _check_view_weights(view_weights, views, aggregation_method):
+    """view_weights (B, V) = views, of a floating dtype, any device: raises TypeError / RuntimeError as _check_view_mask does, ValueError for 'max'"""
     if not torch.is_tensor(view_weights):
         raise TypeError("unprojection: view_weights must be a (B, V) floating tensor, got %s" % type(view_weights).__name__)
     if not view_weights.dtype.is_floating_point:
         raise TypeError("unprojection: view_weights must be a floating dtype (a bool / integer tensor is a view_mask), got %s" % view_weights.dtype)
-    if tuple(view_weights.shape) != tuple(features.shape[:2]):
-        raise RuntimeError("unprojection: view_weights must be %s, got %s" % (tuple(features.shape[:2]), tuple(view_weights.shape)))
+    if tuple(view_weights.shape) != views:
+        raise RuntimeError("unprojection: view_weights must be %s, got %s" % (views, tuple(view_weights.shape)))
     if aggregation_method == "max":
         raise ValueError("unprojection: aggregation_method 'max' has no weighted form (pass a view_mask, not view_weights)")
 
 
-def _check_view_confidence(view_confidence, features, aggregation_method, view_weights=None):
-    """view_confidence (B, V, Hf, Wf) of a floating dtype, any device: raises TypeError / RuntimeError as _check_view_weights does, ValueError for
-    'max' and together with view_weights"""
+def _check_view_confidence(view_confidence, want, aggregation_method, view_weights=None):
+    """view_confidence (B, V, Hf, Wf) = want, of a floating dtype, any device: raises TypeError / RuntimeError as _check_view_weights does,
+    ValueError for 'max' and together with view_weights"""
     if not torch.is_tensor(view_confidence):
         raise TypeError("unprojection: view_confidence must be a (B, V, Hf, Wf) floating tensor, got %s" % type(view_confidence).__name__)
     if not view_confidence.dtype.is_floating_point:
         raise TypeError("unprojection: view_confidence must be a floating dtype, got %s" % view_confidence.dtype)
-    want = tuple(features.shape[:2]) + tuple(features.shape[3:])
     if tuple(view_confidence.shape) != want:
         raise RuntimeError("unprojection: view_confidence must be %s, got %s" % (want, tuple(view_confidence.shape)))
     if aggregation_method == "max":
@@ -636,11 +556,50 @@ def _weights_fp32(view_weights, features):
     return view_weights.to(device=features.device, dtype=torch.float32).contiguous()
 
 
-def _weighted_mask(view_mask, features):
-    """the weighted ops' view_mask: the caller's, or all present"""
-    if view_mask is None:
-        return torch.ones(tuple(features.shape[:2]), dtype=torch.uint8, device=features.device)
-    return _mask_bytes(view_mask, features)
+_AS_READ = {"view_mask": _mask_bytes, "view_weights": _weights_fp32, "view_confidence": _weights_fp32, "feature_index": _index_int32,
+            "lens": _lens_fp32}
+# Which family takes a call: the first whose needs are all given ("moments": aggregation_method is 'var' or 'meanvar').  The checks have
+# refused every combination no family is built for, so what a later row would add is absent by then.
+_PRECEDENCE = (
+    ("_moments", {"moments"}),
+    ("_lens", {"lens"}),
+    ("_shared", {"feature_index"}),
+    ("_confidence_visible", {"view_confidence", "visible_only"}),
+    ("_confidence", {"view_confidence"}),
+    ("_visible", {"visible_only"}),
+    ("_weighted", {"view_weights"}),
+    ("_masked", {"view_mask"}),
+    ("", set()),
+)
+
+
+def _unproject(placing, features, proj_matricies, volume, volume_shape, same_device, cuboid, aggregation_method, out_dtype, variant, options):
+    """What unprojection() and unprojection_cuboid() do.  placing: the plain family's name; volume, volume_shape, same_device: as for
+    _check_call; cuboid: (position, sides) or None; options: the callers' keyword options by name, absent ones None (visible_only: False)"""
+    shape = None
+    if torch.is_tensor(features) and features.dim() == 5:
+        B, V, _, Hf, Wf = features.shape
+        shape = (B, V, Hf, Wf)
+    _check_options(shape, aggregation_method, **options)
+    out_dtype, vol, empty = _check_call(features, proj_matricies, volume, volume_shape, aggregation_method, variant, out_dtype, same_device,
+                                        options["feature_index"])
+    if empty is not None:
+        return empty
+    moments = _MOMENTS.get(aggregation_method, 0)
+    given = {name for name, value in options.items() if (value if name == "visible_only" else value is not None)}
+    if moments:
+        given.add("moments")
+    family = _OPS[placing + next(kind for kind, needs in _PRECEDENCE if needs <= given)]
+    # no detach: the op differentiates w.r.t. the geometry too (the casts carry the gradients back to the caller's device and dtype)
+    geometry = [t.to(device=features.device, dtype=torch.float32).contiguous() for t in (proj_matricies,) + volume]
+    # an option tensor as the library reads it.  The one a family can be chosen without is the mask: None where the family takes a null mask,
+    # else all views present
+    tensors = [_AS_READ[o.name](options[o.name], features) if options[o.name] is not None
+               else None if o.optional else torch.ones(shape[:2], dtype=torch.uint8, device=features.device) for o in family.options]
+    place = () if cuboid is None else ([float(x) for x in cuboid[0]], [float(x) for x in cuboid[1]], list(vol))
+    kind = [{"visible_only": bool(options["visible_only"]), "moments": moments}[name] for name in family.kind_args]
+    return getattr(torch.ops.mvhmr, family.name)(features, *geometry, *tensors, *place, *kind, _capi.AGG["mean" if moments else aggregation_method],
+                                                 _dtype_code(out_dtype), _lens_variant(variant) if family.lens else _capi.VARIANT[variant])
 
 
 # DLT triangulation (mvhmr_triangulate_dlt[_weighted] and mvhmr_triangulate_dlt_backward) as mvhmr::triangulate_dlt[_backward]: proj (B,V,3,4),
@@ -701,69 +660,16 @@ def unprojection_cuboid(features, proj_matricies, rotations, centers, position, 
     edge lengths); volume_shape: (X, Y, Z).  Differentiable w.r.t. features, proj_matricies, rotations and centers (and view_weights).
     view_mask, view_weights, visible_only, view_confidence, feature_index, lens: as for `unprojection`; with feature_index (M,) rotations are
     (M,3,3) and centers (M,3) -- one pose per volume, position / sides / volume_shape shared -- and their gradients are per volume."""
-    def checked_shape(B):
-        n = B if feature_index is None else feature_index.shape[0]
+    def checked_shape(n):
         if tuple(rotations.shape) != (n, 3, 3) or tuple(centers.shape) != (n, 3):
             raise RuntimeError("unprojection: rotations must be (%d, 3, 3) and centers (%d, 3), got %s and %s"
                                % (n, n, tuple(rotations.shape), tuple(centers.shape)))
         return tuple(int(v) for v in volume_shape)
 
-    _check_moments(aggregation_method, view_weights, view_confidence, feature_index, lens)
-    if lens is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_lens(lens, features, view_mask, view_weights, visible_only, view_confidence, feature_index)
-    if feature_index is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_feature_index(feature_index, features, view_mask, view_weights, visible_only, view_confidence)
-
-    if view_mask is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_view_mask(view_mask, features)
-    if view_weights is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_view_weights(view_weights, features, aggregation_method)
-    _check_visible_only(visible_only, view_weights)
-    if view_confidence is not None and torch.is_tensor(features) and features.dim() == 5:
-        _check_view_confidence(view_confidence, features, aggregation_method, view_weights)
-    out_dtype, vol, empty = _check_call(features, proj_matricies, (rotations, centers), checked_shape, aggregation_method, variant,
-                                        out_dtype, same_device=False)
-    if feature_index is not None and (empty is not None or feature_index.shape[0] == 0):
-        return features.new_zeros((feature_index.shape[0], features.shape[2]) + vol, dtype=out_dtype)
-    if empty is not None:
-        return empty
-    dev = features.device                               # the cuboid's few numbers move to the features' device
-    # no detach: the op differentiates w.r.t. proj, rot and center too (the casts carry the gradients back to the caller's device and dtype)
-    proj = proj_matricies.to(device=dev, dtype=torch.float32).contiguous()
-    rot = rotations.to(device=dev, dtype=torch.float32).contiguous()
-    cen = centers.to(device=dev, dtype=torch.float32).contiguous()
-    if aggregation_method in _MOMENTS:
-        return torch.ops.mvhmr.unprojection_cuboid_moments(features, proj, rot, cen, None if view_mask is None else _mask_bytes(view_mask, features),
-                                                           [float(x) for x in position], [float(x) for x in sides], list(vol), bool(visible_only),
-                                                           _MOMENTS[aggregation_method], _capi.AGG["mean"], _dtype_code(out_dtype), _capi.VARIANT[variant])
-    if lens is not None:
-        return torch.ops.mvhmr.unprojection_cuboid_lens(features, proj, rot, cen, _lens_fp32(lens, features), [float(x) for x in position],
-                                                        [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method], _dtype_code(out_dtype),
-                                                        _lens_variant(variant))
-    if feature_index is not None:
-        return torch.ops.mvhmr.unprojection_cuboid_shared(features, proj, rot, cen, _index_int32(feature_index, features), [float(x) for x in position],
-                                                          [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method], _dtype_code(out_dtype),
-                                                          _capi.VARIANT[variant])
-    if view_confidence is not None:
-        op = torch.ops.mvhmr.unprojection_cuboid_confidence_visible if visible_only else torch.ops.mvhmr.unprojection_cuboid_confidence
-        return op(features, proj, rot, cen, None if view_mask is None else _mask_bytes(view_mask, features), _weights_fp32(view_confidence, features),
-                  [float(x) for x in position], [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method], _dtype_code(out_dtype),
-                  _capi.VARIANT[variant])
-    if visible_only:
-        return torch.ops.mvhmr.unprojection_cuboid_visible(features, proj, rot, cen, _weighted_mask(view_mask, features), [float(x) for x in position],
-                                                           [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method],
-                                                           _dtype_code(out_dtype), _capi.VARIANT[variant])
-    if view_weights is not None:
-        return torch.ops.mvhmr.unprojection_cuboid_weighted(features, proj, rot, cen, _weighted_mask(view_mask, features),
-                                                            _weights_fp32(view_weights, features), [float(x) for x in position],
-                                                            [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method],
-                                                            _dtype_code(out_dtype), _capi.VARIANT[variant])
-    if view_mask is not None:
-        return torch.ops.mvhmr.unprojection_cuboid_masked(features, proj, rot, cen, _mask_bytes(view_mask, features), [float(x) for x in position],
-                                                          [float(x) for x in sides], list(vol), _capi.AGG[aggregation_method],
-                                                          _dtype_code(out_dtype), _capi.VARIANT[variant])
-    return torch.ops.mvhmr.unprojection_cuboid(features, proj, rot, cen, [float(x) for x in position], [float(x) for x in sides], list(vol),
-                                               _capi.AGG[aggregation_method], _dtype_code(out_dtype), _capi.VARIANT[variant])
+    # same_device=False: the cuboid's few numbers move to the features' device
+    return _unproject("unprojection_cuboid", features, proj_matricies, (rotations, centers), checked_shape, False, (position, sides), aggregation_method,
+                      out_dtype, variant, dict(view_mask=view_mask, view_weights=view_weights, visible_only=visible_only,
+                                               view_confidence=view_confidence, feature_index=feature_index, lens=lens))
 
 
 def _visibility_args(proj_matricies, feature_shape, view_mask):
@@ -776,7 +682,7 @@ def _visibility_args(proj_matricies, feature_shape, view_mask):
         raise RuntimeError("view_visibility: proj_matricies live on %s; this implementation runs only on a HIP device" % proj_matricies.device)
     Hf, Wf = (int(x) for x in feature_shape)
     if view_mask is not None:
-        _check_view_mask(view_mask, proj_matricies)                          # (only its (B, V) leading shape is read)
+        _check_view_mask(view_mask, tuple(proj_matricies.shape[:2]))
     proj = proj_matricies.detach().to(torch.float32).contiguous()
     return proj, Hf, Wf, None if view_mask is None else _mask_bytes(view_mask, proj)
 
@@ -941,7 +847,7 @@ class _FusedAggregate(torch.autograd.Function):
         if not any(ctx.needs_input_grad[:3]):
             return (None, None, None) + g_geo + (None,) * 5
         det = torch.are_deterministic_algorithms_enabled()                                   # bitwise reproducible feature and wgrad kernels
-        gy = _native().unprojection_cuboid_backward(grad_out.contiguous(), quad, proj, rot, center, *ctx.geometry, *ctx.desc, None, det).view(
+        gy = _native().unprojection_cuboid_backward(grad_out.contiguous(), quad, proj, rot, center, *ctx.geometry, *ctx.desc, deterministic=det).view(
             B * V, Cout, Hf * Wf)                                                                # gradient w.r.t. the conv output, planar
         xf = x.view(B * V, Cin, Hf * Wf)
         if ctx.needs_input_grad[0]:
@@ -1145,42 +1051,27 @@ class VolumeGenerator(nn.Module):
             proj = torch.from_numpy(feature_level_projections(batch['cameras'], images_shape, features_shape))
         # the kernels take raw device pointers: whatever device the packed cameras live on (a loader may pack them on the host)
         proj = proj.to(device=device, dtype=torch.float32).contiguous()
-        _check_moments(self.aggregation_method, batch.get('view_weights'), batch.get('view_confidence'), batch.get('feature_index'),
-                       True if self.lens_distortion else None)
-        view_mask = batch.get('view_mask')                                  # optional (B, V): per-sample present views
-        if view_mask is not None:
-            _check_view_mask(view_mask, proj)                               # (only its (B, V) leading shape is read)
-        view_weights = batch.get('view_weights')                            # optional (B, V): per-view confidences
-        if view_weights is not None:
-            _check_view_weights(view_weights, proj, self.aggregation_method)
-        view_confidence = batch.get('view_confidence')                      # optional (B, V, Hf, Wf): per-pixel confidence maps
-        if view_confidence is not None:
-            meta = torch.empty((batch_size, n_views, 1) + features_shape, device="meta")
-            _check_view_confidence(view_confidence, meta, self.aggregation_method, view_weights)
-        feature_index = batch.get('feature_index')                          # optional (M,): M volumes share the samples' feature maps
-        if feature_index is not None:
-            meta = torch.empty((batch_size, n_views, 1) + features_shape, device="meta")
-            _check_feature_index(feature_index, meta, view_mask, view_weights, self.visible_only, view_confidence)
-            rots, centers = self.volume_pose(batch, proj_org, images_shape, feature_index=feature_index)
-        elif view_weights is not None:
-            rots, centers = self.volume_pose(batch, proj_org, images_shape, view_mask, view_weights)
-        else:
-            rots, centers = (self.volume_pose(batch, proj_org, images_shape) if view_mask is None
-                             else self.volume_pose(batch, proj_org, images_shape, view_mask))
+        # the batch's optional keys: view_mask (B, V) per-sample present views, view_weights (B, V) per-view confidences (5.9),
+        # view_confidence (B, V, Hf, Wf) per-pixel confidence maps (5.11), feature_index (M,): M volumes share the samples' feature maps,
+        # -> (M, C, S, S, S) (5.12), lens (B, V, 10): the lens records, read only under lens_distortion (5.13)
+        options = {key: batch.get(key) for key in ("view_mask", "view_weights", "view_confidence", "feature_index")}
+        options["visible_only"] = self.visible_only
+        options["lens"] = batch.get('lens') if self.lens_distortion else None
+        if self.lens_distortion and options["lens"] is None:
+            options["lens"] = torch.from_numpy(feature_level_lens(batch['cameras'], images_shape, features_shape))
+        _check_options((batch_size, n_views) + features_shape, self.aggregation_method, **options)     # before anything runs
+        given = {key: value for key, value in options.items() if value is not None and value is not False}
+        # (a batch without options calls volume_pose and unprojection_cuboid exactly as one before the options existed)
+        rots, centers = self.volume_pose(batch, proj_org, images_shape, **{key: given[key] for key in ("view_mask", "view_weights", "feature_index")
+                                                                          if key in given})
         cub = self.cuboid()
         S = self.volume_size
         rots = rots.to(device=device, dtype=torch.float32).contiguous()
         centers = centers.to(device=device, dtype=torch.float32).contiguous()
 
-        _check_visible_only(self.visible_only, view_weights)
-        lens = None
-        if self.lens_distortion:
-            lens = batch.get('lens')                                          # optional (B, V, 10): the lens records
-            if lens is None:
-                lens = torch.from_numpy(feature_level_lens(batch['cameras'], images_shape, features_shape))
-            meta = torch.empty((batch_size, n_views, 1) + features_shape, device="meta")
-            _check_lens(lens, meta, view_mask, view_weights, self.visible_only, view_confidence, feature_index)
-        if lens is None and view_mask is None and view_weights is None and view_confidence is None and feature_index is None and not self.visible_only and self._fused_path_applies(features, S):   # (the fused conv writes the quad-planar copy, which a mask, weights, confidence maps or visible_only do not take)
+        # (the fused conv writes the quad-planar copy, which no option takes: a lens call runs the gather family, the others read planar or
+        # channels-last features)
+        if not given and self._fused_path_applies(features, S):
             # 1x1 conv and layout pass in one MFMA GEMM, its output only ever exists in the layout the brick forward stages
             conv = self.process_feature[0]
             return _FusedAggregate.apply(features, conv.weight, conv.bias, proj, rots, centers, tuple(cub.position), tuple(cub.sides),
@@ -1190,19 +1081,8 @@ class VolumeGenerator(nn.Module):
         features = self.process_feature(features)
         features = features.view(batch_size, n_views, *features.shape[1:])
         # the coordinate volumes (aggregation.py:138-187) are never materialised: the kernels evaluate the cuboid recipe per voxel
-        masked = {} if view_mask is None else {"view_mask": view_mask}       # (an unmasked batch calls exactly as before)
-        if view_weights is not None:
-            masked["view_weights"] = view_weights
-        if self.visible_only:
-            masked["visible_only"] = True
-        if view_confidence is not None:
-            masked["view_confidence"] = view_confidence
-        if feature_index is not None:
-            masked["feature_index"] = feature_index                           # -> (M, C, S, S, S)
-        if lens is not None:
-            masked["lens"] = lens                                             # (the gather family: the fused conv's quad-planar copy is not taken)
         return unprojection_cuboid(features, proj, rots, centers, cub.position, cub.sides, (S, S, S),
-                                   aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **masked)
+                                   aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **given)
 
     def _fused_path_applies(self, features, S):
         """The fused conv writes the quad-planar layout, which the un-projection consumes for every geometry (brick kernels as it
@@ -1233,18 +1113,10 @@ class VolumeGenerator(nn.Module):
         return L.mvhmr_unproject_selected_variant(ctypes.byref(desc)) > 0 and L.mvhmr_unproject_backward_supported(ctypes.byref(desc)) == 1
 
 
-def _cfg_visible_only(cfg):
-    """MODEL.AGGREGATION.VISIBLE_ONLY, an extension key the reference's cfg tree does not have: absent (however the tree says so) = False"""
+def _cfg_flag(cfg, key):
+    """MODEL.AGGREGATION.<key>, an extension key the reference's cfg tree does not have: absent (however the tree says so) = False"""
     try:
-        return bool(cfg.MODEL.AGGREGATION.VISIBLE_ONLY)
-    except (AttributeError, KeyError):
-        return False
-
-
-def _cfg_lens_distortion(cfg):
-    """MODEL.AGGREGATION.LENS_DISTORTION, an extension key the reference's cfg tree does not have: absent (however the tree says so) = False"""
-    try:
-        return bool(cfg.MODEL.AGGREGATION.LENS_DISTORTION)
+        return bool(getattr(cfg.MODEL.AGGREGATION, key))
     except (AttributeError, KeyError):
         return False
 
@@ -1260,5 +1132,5 @@ def build_volume_generator(cfg):
                            kind=cfg.DATASET.KIND,
                            dataset=cfg.DATASET.TYPE,
                            volume_aggregation_method=cfg.MODEL.AGGREGATION.METHOD,
-                           visible_only=_cfg_visible_only(cfg),
-                           lens_distortion=_cfg_lens_distortion(cfg))
+                           visible_only=_cfg_flag(cfg, "VISIBLE_ONLY"),
+                           lens_distortion=_cfg_flag(cfg, "LENS_DISTORTION"))
