@@ -852,6 +852,13 @@ int mvhmr_unproject_query_variant_cuboid(const mvhmr_unproject_desc *desc, const
  * per device AND kernel; a second GPU driven from the same process must get its own opt-in). */
 unsigned long long mvhmr_internal_lds_cache_key(int device, const void *kernel);
 
+/* Testing hook: where a deterministic feature backward keeps its exponent table K[b][c] (int32, batch * channels entries; the scale pass
+ * of DESIGN.md 5.7 writes it before any tap is added).  Answered from the plan alone -- the descriptor and what the record selects; no
+ * device pointer is read: *offset is the table's byte offset inside the caller's workspace, *count its length.  `call` is a backward
+ * record with `deterministic` set, checked and refused as mvhmr_unproject_backward_call would; a plan that takes the plane route has no
+ * scale pass and answers MVHMR_ERR_UNSUPPORTED ("... no scale pass"). */
+int mvhmr_internal_det_exponent_table(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, size_t *offset, size_t *count);
+
 int mvhmr_abi_version(void);
 const char *mvhmr_status_string(int status);
 const char *mvhmr_last_error(void);

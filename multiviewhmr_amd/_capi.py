@@ -21,7 +21,7 @@ EXPORTS = (
     "mvhmr_unproject_forward_workspace_bytes", "mvhmr_unproject_backward_workspace_bytes",
     "mvhmr_unproject_forward", "mvhmr_unproject_backward", "mvhmr_build_coord_volumes",
     "mvhmr_unproject_selected_variant", "mvhmr_preferred_layout", "mvhmr_feature_layout_bytes", "mvhmr_convert_features",
-    "mvhmr_unproject_query_variant", "mvhmr_internal_lds_cache_key",
+    "mvhmr_unproject_query_variant", "mvhmr_internal_lds_cache_key", "mvhmr_internal_det_exponent_table",
     "mvhmr_unproject_forward_cuboid", "mvhmr_unproject_backward_cuboid",
     "mvhmr_conv1x1_to_quad", "mvhmr_conv1x1_to_quad_supported", "mvhmr_conv1x1_planar", "mvhmr_conv1x1_planar_supported", "mvhmr_conv1x1_wgrad", "mvhmr_conv1x1_wgrad_supported", "mvhmr_unproject_query_variant_cuboid",
     "mvhmr_unproject_backward_supported", "mvhmr_triangulate_dlt", "mvhmr_triangulate_dlt_weighted",
@@ -192,6 +192,8 @@ def lib():
         fn = getattr(L, "mvhmr_unproject_%s_call" % kind)
         fn.restype = ctypes.c_int
         fn.argtypes = [dp, cp, vp, sz, vp]
+    L.mvhmr_internal_det_exponent_table.restype = ctypes.c_int
+    L.mvhmr_internal_det_exponent_table.argtypes = [dp, cp, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     if L.mvhmr_abi_version() != ABI_VERSION:
         raise RuntimeError("libmvhmr_unproject.so speaks ABI %d, this binding %d: rebuild" %
                            (L.mvhmr_abi_version(), ABI_VERSION))

@@ -652,9 +652,7 @@ void place_det_backward(BackwardPlan &b, Arena &a)
     b.route = brick ? Bwd::DetBrick : Bwd::DetGather;
     if (d->feat_layout != (brick ? MVHMR_LAYOUT_QUAD : MVHMR_LAYOUT_BVHWC)) b.staged = a.take(brick ? brick_workspace_bytes(p) : featT_bytes(p));
     b.acc = a.take(det_acc_bytes(p));
-    // (shared feature maps: the per-sample exponent table and the histogram cnt of the volumes that name each sample)
-    // (cross-view variance: four words per (b, c) and the tap marks)
-    b.scale = a.take(align_up(p.volumes ? shared_det_scale_bytes(p) : p.moments ? moments_det_scale_bytes(p) : det_scale_bytes(p)));
+    b.scale = a.take(align_up(det_scale_bytes(p)));                      // (every family's: unproject_det.hip has the one layout)
 }
 BackwardPlan plan_backward(const mvhmr_unproject_desc *desc, const Problem &p, bool det, Pack pack)
 {
@@ -959,11 +957,9 @@ int launch_backward_det(const BackwardPlan &b, const BackwardArgs &c)
     void *scale = at(c.workspace, b.scale);
     rc = clear_gradient(acc, p, sizeof(long long), s);
     if (rc != MVHMR_OK) return rc;
-    rc = p.feature_index ? launched(launch_det_scale_shared(c.grad_out, feat, scale, p, s), "deterministic scale pass")
-         : p.moments     ? launched(launch_det_scale_moments(c.grad_out, feat, scale, p, s, c.proj, &coords), "deterministic scale pass")
-                         : launched(launch_det_scale(c.grad_out, feat, scale, p, s, brick, c.proj, &coords), "deterministic scale pass");
+    rc = launched(launch_det_scale(c.grad_out, feat, scale, p, s, brick, c.proj, &coords), "deterministic scale pass");
     if (rc != MVHMR_OK) return rc;
-    const int *kexp = p.moments ? moments_det_exponents(scale, p) : det_exponents(scale, p);
+    const int *kexp = det_exponents(scale, p);
     if (brick) {
         rc = launched(launch_bwd_brick_det(feat, c.grad_out, c.proj, coords, acc, kexp, p, s), "deterministic brick backward");
         if (rc != MVHMR_OK) return rc;
@@ -1143,6 +1139,26 @@ size_t call_need(const mvhmr_unproject_desc *desc, const Call &c, int kind)
     return 0;
 }
 
+// where the deterministic backward of this call keeps K (mvhmr_internal_det_exponent_table): run_backward's checks and plan, no launch
+int det_exponent_table(const mvhmr_unproject_desc *desc, const Call &c, size_t *offset, size_t *count)
+{
+    Problem p0;
+    int rc = check_desc(desc, &p0);
+    if (rc != MVHMR_OK) return rc;
+    if (!offset || !count) return fail(MVHMR_ERR_INVALID_ARGUMENT, "offset / count must be non-null");
+    if (!c.deterministic) return fail(MVHMR_ERR_INVALID_ARGUMENT, "the exponent table belongs to the deterministic backward: set call->deterministic");
+    if ((rc = call_refused(desc, c)) != MVHMR_OK) return rc;
+    mvhmr_unproject_desc dq;
+    index_route(c, &dq, &desc, &p0);
+    if (desc->feat_layout == MVHMR_LAYOUT_QUAD_LOG2E) return fail(MVHMR_ERR_UNSUPPORTED, "MVHMR_LAYOUT_QUAD_LOG2E is a forward-only layout");
+    const BackwardPlan b = plan_backward(desc, p0, true, pack_of(c));
+    if (b.route == Bwd::Plane) return fail(MVHMR_ERR_UNSUPPORTED, "this call takes the plane backward: no scale pass");
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(kAlign);                       // (never read: det_exponents only places K)
+    *offset = b.scale + (size_t)(reinterpret_cast<const unsigned char *>(det_exponents(base, b.p)) - base);
+    *count = (size_t)b.p.B * b.p.C;
+    return MVHMR_OK;
+}
+
 // a zeroed record of one family: what every named entry point starts from
 Call record(int family, bool deterministic = false)
 {
@@ -1160,6 +1176,12 @@ extern "C" {
 int mvhmr_abi_version(void) { return MVHMR_ABI_VERSION; }
 
 unsigned long long mvhmr_internal_lds_cache_key(int device, const void *kernel) { return dynamic_lds_cache_key(device, kernel); }
+
+int mvhmr_internal_det_exponent_table(const mvhmr_unproject_desc *desc, const mvhmr_unproject_call *call, size_t *offset, size_t *count)
+{
+    const int rc = check_call(call);
+    return rc != MVHMR_OK ? rc : det_exponent_table(desc, *call, offset, count);
+}
 
 const char *mvhmr_last_error(void) { return g_err; }
 

@@ -135,6 +135,16 @@ __device__ __forceinline__ float bilerp(float v00, float v01, float v10, float v
     return __fmaf_rn(v11, w11, __fmaf_rn(v10, w10, __fmaf_rn(v01, w01, __fmul_rn(v00, w00))));
 }
 
+// the confidence map of one (b, v), (H, W) fp32, sampled with the taps of the features: a tap outside the map has the value 0
+__device__ __forceinline__ float sample_conf(const float *__restrict__ cm, const Taps &t, int H, int W)
+{
+    if (!t.any) return 0.f;
+    const bool xin0 = t.rx0 >= 0, xin1 = t.rx0 + 1 <= W - 1, yin0 = t.ry0 >= 0, yin1 = t.ry0 + 1 <= H - 1;
+    const float c00 = (xin0 && yin0) ? cm[t.y0 * W + t.x0] : 0.f, c01 = (xin1 && yin0) ? cm[t.y0 * W + t.x1] : 0.f;
+    const float c10 = (xin0 && yin1) ? cm[t.y1 * W + t.x0] : 0.f, c11 = (xin1 && yin1) ? cm[t.y1 * W + t.x1] : 0.f;
+    return bilerp(c00, c01, c10, c11, t.w00, t.w01, t.w10, t.w11);
+}
+
 __device__ __forceinline__ float vmax(float a, float b)
 {
     float r;
@@ -644,6 +654,17 @@ template <> __device__ __forceinline__ unsigned pack2<bf16_t>(float a, float b)
     typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
     const bf16x2 h = {(bf16_t)a, (bf16_t)b};
     return __builtin_bit_cast(unsigned, h);
+}
+
+// output stores bypass-ish the caches (nt): the volume is written once and must not displace the feature rows in L2
+__device__ __forceinline__ void store_streaming(float *p, float v) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ void store_streaming(__half *p, float v)
+{
+    __builtin_nontemporal_store(__half_as_ushort(from_f32<__half>(v)), reinterpret_cast<unsigned short *>(p));   // fp32 first, then fp16
+}
+__device__ __forceinline__ void store_streaming(bf16_t *p, float v)
+{
+    __builtin_nontemporal_store(__builtin_bit_cast(unsigned short, (bf16_t)v), reinterpret_cast<unsigned short *>(p));
 }
 
 __device__ __forceinline__ int uniform(int x) { return __builtin_amdgcn_readfirstlane(x); }

@@ -85,10 +85,13 @@ hipError_t launch_bwd_gather(const void *grad_out, const void *featT, const floa
 
 // deterministic mode (unproject_det.hip, det_scale.h): the scale pass writes K[b][c] into `scale` (det_scale_bytes(p)) from grad_out and the
 // channels-last feature copy; k_bwd_gather_det adds int64 fixed point into gradI (zeroed, channels-last (B,V,HW,C4)); the conversion passes
-// write the caller's planar or channels-last gradient (NaN for a poisoned (b, c))
+// write the caller's planar or channels-last gradient (NaN for a poisoned (b, c)).  One scale pass serves every family: what the bound
+// ranges over is read off the problem (view_count, view_weights, visible, conf / confidence, feature_index / volumes, moments), the layout
+// of `scale` off its route flags alone, so det_scale_bytes answers before any pointer exists, and det_exponents finds K in it.  feat is the
+// channels-last copy, or the quad-planar one (quad: the plain route only); a call whose bound ranges over the tapped pixels (visible,
+// confidence, moments) needs proj and coords
 size_t det_scale_bytes(const Problem &p);
-// (a visible problem's softmax bound ranges over the pixels its seeing voxel-views tap: it needs proj and coords, and det_scale_bytes has the marks)
-hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale, const Problem &p, hipStream_t s, bool quad = false,   // feat: channels-last copy, or the quad-planar one (quad)
+hipError_t launch_det_scale(const void *grad_out, const void *feat, void *scale, const Problem &p, hipStream_t s, bool quad = false,
                             const float *proj = nullptr, const Coords *coords = nullptr);
 const int *det_exponents(const void *scale, const Problem &p);
 hipError_t launch_bwd_gather_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
@@ -198,17 +201,14 @@ hipError_t launch_bwd_geom_seen_kernel(const void *grad_out, const void *featT, 
                                        float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
 
 // per-pixel view confidence (unproject_confidence.hip; Problem::confidence): the gather forward and the per-tap scatter backward of both modes
-// (launch_fwd_gather / launch_bwd_gather / launch_bwd_gather_det call these for confidence problems), the deterministic scale pass
-// (launch_det_scale calls it; its regions lie behind det_scale_bytes' three words per (b, c): conf_det_scale_extra_bytes), and grad_confidence
-// (B, V, Hf, Wf) fp32 from the geometry kernel's stream: bitwise reproducible, integer atomics only, every element written
+// (launch_fwd_gather / launch_bwd_gather / launch_bwd_gather_det call these for confidence problems; the deterministic scale pass is
+// launch_det_scale's, whose bound carries the sample's largest confidence pixel), and grad_confidence (B, V, Hf, Wf) fp32 from the
+// geometry kernel's stream: bitwise reproducible, integer atomics only, every element written
 hipError_t launch_fwd_gather_conf(const void *featT, const float *proj, const Coords &coords, void *out, const Problem &p, hipStream_t s);
 hipError_t launch_bwd_gather_conf(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *gradT, const Problem &p,
                                   hipStream_t s);
 hipError_t launch_bwd_gather_conf_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
                                       const int *kexp, const Problem &p, hipStream_t s);
-size_t conf_det_scale_extra_bytes(const Problem &p);
-hipError_t launch_det_scale_conf(const void *grad_out, const void *featT, void *scale, const Problem &p, hipStream_t s, const float *proj,
-                                 const Coords *coords);
 size_t conf_grad_stream_bytes(const Problem &p);
 size_t conf_grad_acc_bytes(const Problem &p);
 size_t conf_grad_max_bytes(const Problem &p);
@@ -219,8 +219,7 @@ hipError_t launch_bwd_geom_conf_kernel(const void *grad_out, const void *featT, 
                                        float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
 
 // shared feature maps (unproject_shared.hip, unproject_shared_geom.hip; Problem::feature_index / volumes): the gather forward, the per-tap scatter
-// backward of both modes, the deterministic scale pass -- one exponent per FEATURE sample and channel whose bound carries cnt[b], the number of
-// volumes that name b (shared_det_scale_bytes: det_scale_bytes' three words per (b, c), det_exponents finds K, then the B-word histogram) --
+// backward of both modes (launch_det_scale's exponents are per FEATURE sample and channel, and carry cnt[b], the number of volumes that name b)
 // and the geometry backward, whose grad_proj and pose partials are per VOLUME (shared_geom_partial_bytes / shared_pose_partial_bytes) and are
 // summed per (b, v) over the volumes that name b in ascending order.  The volume index is the grid's y extent.
 constexpr int kSharedMaxVolumes = 65535;
@@ -229,8 +228,6 @@ hipError_t launch_bwd_gather_shared(const void *grad_out, const void *featT, con
                                     hipStream_t s);
 hipError_t launch_bwd_gather_shared_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
                                         const int *kexp, const Problem &p, hipStream_t s);
-size_t shared_det_scale_bytes(const Problem &p);
-hipError_t launch_det_scale_shared(const void *grad_out, const void *featT, void *scale, const Problem &p, hipStream_t s);
 size_t shared_geom_partial_bytes(const Problem &p);
 size_t shared_pose_partial_bytes(const Problem &p);
 hipError_t launch_bwd_geom_shared(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part, float *grad_proj,
@@ -251,18 +248,13 @@ hipError_t launch_bwd_geom_lens_kernel(const void *grad_out, const void *featT, 
                                        float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
 
 // cross-view variance (unproject_moments.hip, unproject_moments_geom.hip; Problem::moments): the gather forward, the per-tap scatter backward of
-// both modes, the deterministic scale pass -- its bound carries both halves of grad_out and the features' maximum (moments_det_scale_bytes: four
-// words per (b, c), moments_det_exponents finds K, then a visible problem's tap marks) -- and the moments instances of k_bwd_geom
-// (launch_bwd_geom[_cuboid] call this for them).  out / grad_out hold moments * C channels.
+// both modes (launch_det_scale's bound carries both halves of grad_out and the largest feature a participating view taps) and the moments
+// instances of k_bwd_geom (launch_bwd_geom[_cuboid] call this for them).  out / grad_out hold moments * C channels.
 hipError_t launch_fwd_gather_moments(const void *featT, const float *proj, const Coords &coords, void *out, const Problem &p, hipStream_t s);
 hipError_t launch_bwd_gather_moments(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *gradT, const Problem &p,
                                      hipStream_t s);
 hipError_t launch_bwd_gather_moments_det(const void *grad_out, const void *featT, const float *proj, const Coords &coords, unsigned long long *gradI,
                                          const int *kexp, const Problem &p, hipStream_t s);
-size_t moments_det_scale_bytes(const Problem &p);
-hipError_t launch_det_scale_moments(const void *grad_out, const void *featT, void *scale, const Problem &p, hipStream_t s, const float *proj,
-                                    const Coords *coords);
-const int *moments_det_exponents(const void *scale, const Problem &p);
 hipError_t launch_bwd_geom_moments_kernel(const void *grad_out, const void *featT, const float *proj, const Coords &coords, float *part,
                                           float *grad_coords, float *pose_part, bool pose, const Problem &p, hipStream_t s);
 

@@ -41,16 +41,6 @@ __device__ __forceinline__ UConf uniform_conf(const ConfRec &r)
     return u;
 }
 
-// the confidence map of one (b, v), (H, W) fp32, sampled with the taps of the features: a tap outside the map has the value 0
-__device__ __forceinline__ float sample_conf(const float *__restrict__ cm, const Taps &t, int H, int W)
-{
-    if (!t.any) return 0.f;
-    const bool xin0 = t.rx0 >= 0, xin1 = t.rx0 + 1 <= W - 1, yin0 = t.ry0 >= 0, yin1 = t.ry0 + 1 <= H - 1;
-    const float c00 = (xin0 && yin0) ? cm[t.y0 * W + t.x0] : 0.f, c01 = (xin1 && yin0) ? cm[t.y0 * W + t.x1] : 0.f;
-    const float c10 = (xin0 && yin1) ? cm[t.y1 * W + t.x0] : 0.f, c11 = (xin1 && yin1) ? cm[t.y1 * W + t.x1] : 0.f;
-    return bilerp(c00, c01, c10, c11, t.w00, t.w01, t.w10, t.w11);
-}
-
 // LDS: [ tap records (voxel, view) | c (voxel, view) | bitmask, one word per voxel | the kernel's tile ]
 __device__ __forceinline__ size_t conf_head_bytes(int V) { return (sizeof(ConfRec) + sizeof(float)) * kConfTile * V + sizeof(unsigned) * kConfTile; }
 
@@ -90,27 +80,6 @@ __device__ __forceinline__ void build_conf_records(ConfRec *recs, float *cw, uns
         cw[j * V + v] = c;
     }
     __syncthreads();
-}
-
-__device__ __forceinline__ void store_conf(float *p, float v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void store_conf(__half *p, float v)
-{
-    __builtin_nontemporal_store(__half_as_ushort(from_f32<__half>(v)), reinterpret_cast<unsigned short *>(p));   // fp32 first, then fp16
-}
-__device__ __forceinline__ void store_conf(bf16_t *p, float v)
-{
-    __builtin_nontemporal_store(__builtin_bit_cast(unsigned short, (bf16_t)v), reinterpret_cast<unsigned short *>(p));
-}
-
-__device__ __forceinline__ unsigned abs_bits(float x) { return __builtin_bit_cast(unsigned, x) & 0x7fffffffu; }
-__device__ __forceinline__ unsigned wave_max_u32(unsigned m)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned t = (unsigned)__shfl_xor((int)m, o);
-        m = t > m ? t : m;
-    }
-    return m;
 }
 
 }  // namespace
@@ -197,7 +166,7 @@ k_fwd_gather_conf(const TF *__restrict__ featT, const float *__restrict__ proj, 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int c = cq * 4 + i;
-                if (c < C) store_conf(&out[((long long)b * C + c) * N + n], t.v[i]);
+                if (c < C) store_streaming(&out[((long long)b * C + c) * N + n], t.v[i]);
             }
         }
     }
@@ -331,101 +300,6 @@ k_bwd_gather_conf(const TO *__restrict__ grad_out, const TF *__restrict__ featT,
     }
 }
 
-// ------------------------------------------------------------------------------------------ deterministic scale pass
-// max |grad_out| of each (b, c) row of the (B, C, N) volume gradient: block (row, chunk) -- k_det_gmax
-template <typename TO>
-__global__ void __launch_bounds__(256) k_conf_gmax(const TO *__restrict__ grad_out, unsigned *__restrict__ gmax, long long N)
-{
-    const long long row = blockIdx.x;
-    const TO *g = grad_out + row * N;
-    unsigned m = 0;
-    for (long long n = (long long)blockIdx.y * 256 + threadIdx.x; n < N; n += (long long)gridDim.y * 256) {
-        const unsigned a = abs_bits(to_f32<TO>(g[n]));
-        m = a > m ? a : m;
-    }
-    m = wave_max_u32(m);
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(gmax + row, m);
-}
-
-// the largest positive pixel of a sample's maps (bits of the float; NaN and negative pixels never raise it, +Inf does): a bilinear sample is a
-// convex combination of its taps and zeros, so this bounds every c_v of the sample
-__global__ void __launch_bounds__(256) k_conf_cmax(const float *__restrict__ conf, unsigned *__restrict__ cmax, long long per_sample)
-{
-    const int b = blockIdx.y;
-    const float *c = conf + (long long)b * per_sample;
-    unsigned m = 0;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_sample; i += (long long)gridDim.x * 256) {
-        const float x = c[i];
-        const unsigned a = x > 0.f ? __builtin_bit_cast(unsigned, x) : 0u;
-        m = a > m ? a : m;
-    }
-    m = wave_max_u32(m);
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(cmax + b, m);
-}
-
-// softmax: one byte per pixel of every (b, slot) map that a voxel-view taking part taps -- all four clamped taps, those of weight 0 too: the
-// kernels' samples multiply every tap they load, so a non-finite value under a zero-weight tap reaches s_v and must poison the (b, c)
-// (thread per (voxel, slot): the very test and taps of build_conf_records; every writer stores the same 1) -- k_det_mark_seen
-__global__ void __launch_bounds__(256) k_conf_mark(const float *__restrict__ proj, const Coords coords, const float *__restrict__ conf,
-                                                   unsigned char *__restrict__ marks, int V, int H, int W, long long N, const int *__restrict__ nvs,
-                                                   int visible)
-{
-    const long long bv = blockIdx.y;
-    const int b = (int)(bv / V), v = (int)(bv % V);
-    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (n >= N || (nvs && v >= nvs[b])) return;
-    float X0, X1, X2;
-    voxel_xyz(coords, b, N, n, X0, X1, X2);
-    const float *P = proj + bv * 12;
-    if (visible && !view_sees(P, X0, X1, X2, H, W)) return;
-    const Taps t = make_taps(P, X0, X1, X2, H, W);
-    if (!(sample_conf(conf + bv * H * W, t, H, W) > 0.f)) return;
-    unsigned char *m = marks + bv * (long long)H * W;
-    m[t.y0 * W + t.x0] = 1;                                                       // (clamped into the map whatever the position)
-    m[t.y0 * W + t.x1] = 1;
-    m[t.y1 * W + t.x0] = 1;
-    m[t.y1 * W + t.x1] = 1;
-}
-
-constexpr int kConfPix = 64;
-template <typename TF>
-__global__ void __launch_bounds__(256) k_conf_fmax(const TF *__restrict__ featT, const unsigned char *__restrict__ marks, unsigned *__restrict__ fmax,
-                                                   int V, int C, int C4, int HW)
-{
-    const long long bv = blockIdx.y;
-    const int b = (int)(bv / V), p0 = blockIdx.x * kConfPix, p1 = p0 + kConfPix < HW ? p0 + kConfPix : HW;
-    const TF *f = featT + bv * (long long)HW * C4;
-    const unsigned char *mk = marks + bv * (long long)HW;
-    for (int c = threadIdx.x; c < C; c += 256) {
-        unsigned m = 0;
-        for (int p = p0; p < p1; ++p) {
-            if (!mk[p]) continue;                                                 // block-uniform
-            const unsigned a = abs_bits(to_f32<TF>(f[(long long)p * C4 + c]));
-            m = a > m ? a : m;
-        }
-        if (m) atomicMax(fmax + (long long)b * C + c, m);
-    }
-}
-
-// K[b][c]: N * bound * 2^K < 2^62 with bound = max|g| (1 + 2 Fmax) for softmax, max|g| * cmax[b] for sum (|ds| = |g| c_v: without the
-// confidence the int64 sums can wrap), max|g| for mean (|ds| = |g| c_v / W <= |g|)
-__global__ void __launch_bounds__(256) k_conf_det_exponent(const unsigned *__restrict__ gmax, const unsigned *__restrict__ fmax,
-                                                           const unsigned *__restrict__ cmax, int *__restrict__ kexp, long long BC, int method, int C,
-                                                           int log2n)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= BC) return;
-    const unsigned gb = gmax[i], fb = method == AGG_SOFTMAX ? fmax[i] : 0u, cb = method == AGG_SUM ? cmax[i / C] : 0u;
-    if (gb >= 0x7f800000u || fb >= 0x7f800000u || cb >= 0x7f800000u) { kexp[i] = kDetPoison; return; }
-    const double g = (double)__builtin_bit_cast(float, gb), f = (double)__builtin_bit_cast(float, fb), c = (double)__builtin_bit_cast(float, cb);
-    const double bound = method == AGG_SOFTMAX ? g * (1.0 + 2.0 * f) : method == AGG_SUM ? g * c : g;
-    if (bound == 0.0) { kexp[i] = 0; return; }
-    if (!(bound < 3.4028234663852886e38)) { kexp[i] = kDetPoison; return; }     // ds itself may overflow fp32
-    int e;
-    frexp(bound, &e);                                                           // bound < 2^e
-    kexp[i] = 62 - log2n - e;
-}
-
 // ------------------------------------------------------------------------------------------ grad_confidence
 // the exponent of one (b, v) from the bits of its largest |dc|: N * max * 2^K < 2^62; poison when the maximum is not finite
 __device__ __forceinline__ int conf_grad_exponent(unsigned maxbits, int log2n)
@@ -433,20 +307,6 @@ __device__ __forceinline__ int conf_grad_exponent(unsigned maxbits, int log2n)
     if (maxbits >= 0x7f800000u) return kDetPoison;
     const int e = (int)(maxbits >> 23) - 126;                                     // max < 2^e (a denormal maximum: < 2^-126)
     return 62 - log2n - e;
-}
-
-// largest |dc| of each (b, v) row of the (B, V, N) stream: block (row, chunk), integer atomicMax on the bits
-__global__ void __launch_bounds__(256) k_conf_grad_max(const float *__restrict__ stream, unsigned *__restrict__ smax, long long N)
-{
-    const long long row = blockIdx.x;
-    const float *g = stream + row * N;
-    unsigned m = 0;
-    for (long long n = (long long)blockIdx.y * 256 + threadIdx.x; n < N; n += (long long)gridDim.y * 256) {
-        const unsigned a = abs_bits(g[n]);
-        m = a > m ? a : m;
-    }
-    m = wave_max_u32(m);
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(smax + row, m);
 }
 
 // thread per (voxel, slot): dc of the stream times the four tap weights, in fixed point, into the int64 map of (b, slot).  The taps are those
@@ -488,13 +348,6 @@ __global__ void __launch_bounds__(256) k_conf_grad_convert(const unsigned long l
 namespace {
 
 size_t conf_head_host(int V) { return (sizeof(ConfRec) + sizeof(float)) * kConfTile * (size_t)V + sizeof(unsigned) * kConfTile; }
-int log2_ceil(long long N) { return N > 1 ? 64 - __builtin_clzll((unsigned long long)(N - 1)) : 0; }
-unsigned chunks_of(long long N)
-{
-    const long long c = (N + 2047) / 2048;
-    return (unsigned)(c < 1 ? 1 : c > 64 ? 64 : c);
-}
-
 template <typename TF, typename TO, int METHOD>
 hipError_t fwd_conf_v(const TF *featT, const float *proj, const Coords &coords, TO *out, const Problem &p, hipStream_t s)
 {
@@ -598,45 +451,6 @@ hipError_t launch_bwd_gather_conf_det(const void *grad_out, const void *featT, c
     return bwd_conf<unsigned long long>(grad_out, featT, proj, coords, gradI, kexp, p, s);
 }
 
-// behind the three words per (b, c) of det_scale_bytes: cmax (B words, padded to 16 B), then the tap marks of every (b, slot) map
-size_t conf_det_scale_extra_bytes(const Problem &p) { return ((size_t)p.B * sizeof(unsigned) + 15) / 16 * 16 + (size_t)p.B * p.V * p.H * p.W; }
-
-hipError_t launch_det_scale_conf(const void *grad_out, const void *featT, void *scale, const Problem &p, hipStream_t s, const float *proj,
-                                 const Coords *coords)
-{
-    if (!p.confidence || !proj || !coords) return hipErrorInvalidValue;
-    const long long BC = (long long)p.B * p.C;
-    if (BC > 0x7fffffffll || (long long)p.B * p.V > 65535) return hipErrorNotSupported;
-    unsigned *gmax = static_cast<unsigned *>(scale), *fmax = gmax + BC;
-    int *kexp = reinterpret_cast<int *>(fmax + BC);
-    unsigned *cmax = reinterpret_cast<unsigned *>(kexp + BC);
-    unsigned char *marks = reinterpret_cast<unsigned char *>(cmax) + ((size_t)p.B * sizeof(unsigned) + 15) / 16 * 16;
-    const int HW = p.H * p.W;
-    hipError_t e = hipMemsetAsync(gmax, 0, (size_t)BC * 2 * sizeof(unsigned), s);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(cmax, 0, (size_t)p.B * sizeof(unsigned), s);
-    if (e != hipSuccess) return e;
-    const dim3 g1((unsigned)BC, chunks_of(p.N));
-    if (p.out_bf16) hipLaunchKernelGGL(k_conf_gmax<bf16_t>, g1, dim3(256), 0, s, (const bf16_t *)grad_out, gmax, p.N);
-    else if (p.out_f16) hipLaunchKernelGGL(k_conf_gmax<__half>, g1, dim3(256), 0, s, (const __half *)grad_out, gmax, p.N);
-    else hipLaunchKernelGGL(k_conf_gmax<float>, g1, dim3(256), 0, s, (const float *)grad_out, gmax, p.N);
-    if (p.method == AGG_SUM) {
-        const long long per = (long long)p.V * HW;
-        hipLaunchKernelGGL(k_conf_cmax, dim3(chunks_of(per), (unsigned)p.B), dim3(256), 0, s, p.confidence, cmax, per);
-    }
-    if (p.method == AGG_SOFTMAX) {
-        e = hipMemsetAsync(marks, 0, (size_t)p.B * p.V * HW, s);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(k_conf_mark, dim3((unsigned)((p.N + 255) / 256), (unsigned)(p.B * p.V)), dim3(256), 0, s, proj, *coords, p.confidence, marks,
-                           p.V, p.H, p.W, p.N, p.view_count, p.visible);
-        const dim3 g2((unsigned)((HW + kConfPix - 1) / kConfPix), (unsigned)(p.B * p.V));
-        if (p.feat_f16) hipLaunchKernelGGL(k_conf_fmax<__half>, g2, dim3(256), 0, s, (const __half *)featT, marks, fmax, p.V, p.C, p.C4, HW);
-        else hipLaunchKernelGGL(k_conf_fmax<float>, g2, dim3(256), 0, s, (const float *)featT, marks, fmax, p.V, p.C, p.C4, HW);
-    }
-    hipLaunchKernelGGL(k_conf_det_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gmax, fmax, cmax, kexp, BC, p.method, p.C, log2_ceil(p.N));
-    return hipGetLastError();
-}
-
 // grad_confidence (B, V, Hf, Wf) fp32 from the stream the geometry kernel wrote: acc conf_grad_acc_bytes of int64, smax conf_grad_max_bytes
 size_t conf_grad_stream_bytes(const Problem &p) { return (size_t)p.B * p.V * p.N * sizeof(float); }
 size_t conf_grad_acc_bytes(const Problem &p) { return (size_t)p.B * p.V * p.H * p.W * sizeof(long long); }
@@ -653,7 +467,8 @@ hipError_t launch_conf_grad(const float *stream, const float *proj, const Coords
     if (e != hipSuccess) return e;
     e = hipMemsetAsync(smax, 0, conf_grad_max_bytes(p), s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_conf_grad_max, dim3((unsigned)(p.B * p.V), chunks_of(p.N)), dim3(256), 0, s, stream, smax, p.N);
+    // largest |dc| of each (b, v) row of the (B, V, N) stream: the scale pass's row maxima (det_scale.h)
+    hipLaunchKernelGGL((k_det_gmax<float, DetRowsIdentity>), dim3((unsigned)(p.B * p.V), chunks_of(p.N)), dim3(256), 0, s, stream, smax, p.N);
     hipLaunchKernelGGL(k_conf_grad_scatter, dim3((unsigned)((p.N + 255) / 256), (unsigned)(p.B * p.V)), dim3(256), 0, s, stream, smax, proj, coords, acc,
                        p.V, p.H, p.W, p.N, log2n);
     hipLaunchKernelGGL(k_conf_grad_convert, dim3(chunks_of(HW), (unsigned)(p.B * p.V)), dim3(256), 0, s, acc, smax, grad_conf, HW, log2n);

@@ -48,18 +48,6 @@ __device__ __forceinline__ void build_records(TapRec *recs, const float *__restr
     }
 }
 
-// output stores bypass-ish the caches (nt): the volume is written once and must not displace the feature rows in L2
-__device__ __forceinline__ void store_streaming(float *p, float v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void store_streaming(__half *p, float v)
-{
-    __builtin_nontemporal_store(__half_as_ushort(from_f32<__half>(v)), reinterpret_cast<unsigned short *>(p));   // fp32 first, then fp16
-}
-
-__device__ __forceinline__ void store_streaming(bf16_t *p, float v)
-{
-    __builtin_nontemporal_store(__builtin_bit_cast(unsigned short, (bf16_t)v), reinterpret_cast<unsigned short *>(p));
-}
-
 struct UTap { int o00, o01, o10, o11; float w00, w01, w10, w11; };
 __device__ __forceinline__ UTap uniform_rec(const TapRec &r)
 {

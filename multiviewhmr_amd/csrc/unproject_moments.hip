@@ -77,16 +77,6 @@ __device__ __forceinline__ void build_mom_records(MomRec *recs, unsigned *vbits,
     __syncthreads();
 }
 
-__device__ __forceinline__ void store_mom(float *p, float v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void store_mom(__half *p, float v)
-{
-    __builtin_nontemporal_store(__half_as_ushort(from_f32<__half>(v)), reinterpret_cast<unsigned short *>(p));   // fp32 first, then fp16
-}
-__device__ __forceinline__ void store_mom(bf16_t *p, float v)
-{
-    __builtin_nontemporal_store(__builtin_bit_cast(unsigned short, (bf16_t)v), reinterpret_cast<unsigned short *>(p));
-}
-
 // the pinned arithmetic over the set bits of a fixed-V instance; bits != 0
 template <int V>
 __device__ __forceinline__ float mom_mean(const float (&s)[V], unsigned bits, float cnt)
@@ -108,7 +98,6 @@ __device__ __forceinline__ float mom_var(const float (&s)[V], unsigned bits, flo
     return __fdiv_rn(acc, cnt);
 }
 
-__device__ __forceinline__ unsigned mom_abs_bits(float x) { return __builtin_bit_cast(unsigned, x) & 0x7fffffffu; }
 
 }  // namespace
 
@@ -220,7 +209,7 @@ k_fwd_gather_moments(const TF *__restrict__ featT, const float *__restrict__ pro
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int c = cq * 4 + i;
-                    if (c < C) store_mom(&out[((long long)b * CO + coff + c) * N + n], t.v[i]);
+                    if (c < C) store_streaming(&out[((long long)b * CO + coff + c) * N + n], t.v[i]);
                 }
             }
         }
@@ -367,88 +356,6 @@ k_bwd_gather_moments(const TO *__restrict__ grad_out, const TF *__restrict__ fea
     }
 }
 
-// ------------------------------------------------------------------------------------------ deterministic scale pass
-// K[b][c] with N * bound * 2^K < 2^62 (det_scale.h) for bound = max|g_m| + 4 max|g_v| Fmax >= |ds|: n >= 1, |s_v - mu| <= 2 Fmax with Fmax
-// the largest |feature| of (b, c) a participating view can tap.  Maxima with integer atomicMax on the bits of |x|, as unproject_det.hip.
-template <typename TO>
-__global__ void __launch_bounds__(256) k_mom_gmax(const TO *__restrict__ grad_out, unsigned *__restrict__ gmax, int C, int halves, long long N)
-{
-    // row = (b * C + c) * halves + h: h = halves - 1 is the variance half; gmax holds [g_m rows | g_v rows]
-    const long long row = blockIdx.x / halves;
-    const int h = (int)(blockIdx.x % halves);
-    const long long b = row / C, c = row % C;
-    const TO *g = grad_out + ((b * halves + h) * C + c) * N;
-    unsigned m = 0;
-    for (long long n = (long long)blockIdx.y * 256 + threadIdx.x; n < N; n += (long long)gridDim.y * 256) {
-        const unsigned a = mom_abs_bits(to_f32<TO>(g[n]));
-        m = a > m ? a : m;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned t = (unsigned)__shfl_xor((int)m, o);
-        m = t > m ? t : m;
-    }
-    const bool is_var = h == halves - 1;
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(gmax + (is_var ? (long long)gridDim.x / halves : 0) + row, m);
-}
-
-// one byte per pixel a participating voxel-view taps (thread per (voxel, slot): the very test and taps the backward uses; every writer stores
-// the same 1, so the order plays no part); a sample that is identically zero taps nothing
-__global__ void __launch_bounds__(256) k_mom_mark(const float *__restrict__ proj, const Coords coords, unsigned char *__restrict__ marks, int V, int H,
-                                                  int W, long long N, const int *__restrict__ nvs, int visible)
-{
-    const long long bv = blockIdx.y;
-    const int b = (int)(bv / V), v = (int)(bv % V);
-    const long long n = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (n >= N || (nvs && v >= nvs[b])) return;                                   // slots behind the present views are absent
-    float X0, X1, X2;
-    voxel_xyz(coords, b, N, n, X0, X1, X2);
-    const float *P = proj + bv * 12;
-    if (visible && !view_sees(P, X0, X1, X2, H, W)) return;
-    const Taps t = make_taps(P, X0, X1, X2, H, W);                                // clamped to the map whatever the position
-    if (!t.any) return;
-    unsigned char *m = marks + bv * (long long)H * W;
-    m[t.y0 * W + t.x0] = 1;
-    m[t.y0 * W + t.x1] = 1;
-    m[t.y1 * W + t.x0] = 1;
-    m[t.y1 * W + t.x1] = 1;
-}
-
-constexpr int kMomPix = 64;
-template <typename TF>
-__global__ void __launch_bounds__(256) k_mom_fmax(const TF *__restrict__ featT, const unsigned char *__restrict__ marks, unsigned *__restrict__ fmax,
-                                                  int V, int C, int C4, int HW)
-{
-    const long long bv = blockIdx.y;
-    const int b = (int)(bv / V), p0 = blockIdx.x * kMomPix, p1 = p0 + kMomPix < HW ? p0 + kMomPix : HW;
-    const TF *f = featT + bv * (long long)HW * C4;
-    const unsigned char *mk = marks + bv * (long long)HW;
-    for (int c = threadIdx.x; c < C; c += 256) {
-        unsigned m = 0;
-        for (int p = p0; p < p1; ++p) {
-            if (!mk[p]) continue;                                                 // block-uniform
-            const unsigned a = mom_abs_bits(to_f32<TF>(f[(long long)p * C4 + c]));
-            m = a > m ? a : m;
-        }
-        if (m) atomicMax(fmax + (long long)b * C + c, m);
-    }
-}
-
-__global__ void __launch_bounds__(256) k_mom_exponent(const unsigned *__restrict__ gm, const unsigned *__restrict__ gv, const unsigned *__restrict__ fmax,
-                                                      int *__restrict__ kexp, long long BC, int log2n)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= BC) return;
-    const unsigned a = gm[i], v = gv[i], f = fmax[i];
-    if (a >= 0x7f800000u || v >= 0x7f800000u || f >= 0x7f800000u) { kexp[i] = kDetPoison; return; }
-    const double bound = (double)__builtin_bit_cast(float, a) + 4.0 * (double)__builtin_bit_cast(float, v) * (double)__builtin_bit_cast(float, f);
-    if (bound == 0.0) { kexp[i] = 0; return; }
-    if (bound >= 3.4028234663852886e38) { kexp[i] = kDetPoison; return; }  // ds itself may overflow fp32
-    int e;
-    frexp(bound, &e);                                                    // bound < 2^e
-    kexp[i] = 62 - log2n - e;
-}
-
 // ------------------------------------------------------------------------------------------ launchers
 namespace {
 
@@ -549,42 +456,6 @@ hipError_t launch_bwd_gather_moments_det(const void *grad_out, const void *featT
                                          const int *kexp, const Problem &p, hipStream_t s)
 {
     return bwd_mom<unsigned long long>(grad_out, featT, proj, coords, gradI, kexp, p, s);
-}
-
-// max|g_m|, max|g_v|, Fmax, K: four words per (b, c); behind them the tap marks, one byte per pixel of every (b, slot) map
-size_t moments_det_scale_bytes(const Problem &p) { return (size_t)p.B * p.C * 4 * sizeof(int) + (size_t)p.B * p.V * p.H * p.W; }
-
-const int *moments_det_exponents(const void *scale, const Problem &p) { return static_cast<const int *>(scale) + 3 * (long long)p.B * p.C; }
-
-hipError_t launch_det_scale_moments(const void *grad_out, const void *featT, void *scale, const Problem &p, hipStream_t s, const float *proj,
-                                    const Coords *coords)
-{
-    const long long BC = (long long)p.B * p.C;
-    const int halves = p.moments;
-    if ((halves != 1 && halves != 2) || !proj || !coords) return hipErrorInvalidValue;
-    if (BC * halves > 0x7fffffffll || (long long)p.B * p.V > 65535) return hipErrorNotSupported;
-    unsigned *gm = static_cast<unsigned *>(scale), *gv = gm + BC, *fmax = gv + BC;
-    int *kexp = reinterpret_cast<int *>(fmax + BC);
-    unsigned char *marks = reinterpret_cast<unsigned char *>(kexp + BC);
-    const int HW = p.H * p.W;
-    hipError_t e = hipMemsetAsync(gm, 0, (size_t)BC * 3 * sizeof(unsigned), s);
-    if (e != hipSuccess) return e;
-    e = hipMemsetAsync(marks, 0, (size_t)p.B * p.V * HW, s);
-    if (e != hipSuccess) return e;
-    long long chunks = (p.N + 2047) / 2048;
-    chunks = chunks < 1 ? 1 : chunks > 64 ? 64 : chunks;
-    const dim3 g1((unsigned)(BC * halves), (unsigned)chunks);
-    if (p.out_bf16) hipLaunchKernelGGL(k_mom_gmax<bf16_t>, g1, dim3(256), 0, s, (const bf16_t *)grad_out, gm, p.C, halves, p.N);
-    else if (p.out_f16) hipLaunchKernelGGL(k_mom_gmax<__half>, g1, dim3(256), 0, s, (const __half *)grad_out, gm, p.C, halves, p.N);
-    else hipLaunchKernelGGL(k_mom_gmax<float>, g1, dim3(256), 0, s, (const float *)grad_out, gm, p.C, halves, p.N);
-    hipLaunchKernelGGL(k_mom_mark, dim3((unsigned)((p.N + 255) / 256), (unsigned)(p.B * p.V)), dim3(256), 0, s, proj, *coords, marks, p.V, p.H, p.W, p.N,
-                       p.view_count, p.visible);
-    const dim3 g2((unsigned)((HW + kMomPix - 1) / kMomPix), (unsigned)(p.B * p.V));
-    if (p.feat_f16) hipLaunchKernelGGL(k_mom_fmax<__half>, g2, dim3(256), 0, s, (const __half *)featT, marks, fmax, p.V, p.C, p.C4, HW);
-    else hipLaunchKernelGGL(k_mom_fmax<float>, g2, dim3(256), 0, s, (const float *)featT, marks, fmax, p.V, p.C, p.C4, HW);
-    const int log2n = p.N > 1 ? 64 - __builtin_clzll((unsigned long long)(p.N - 1)) : 0;
-    hipLaunchKernelGGL(k_mom_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gm, gv, fmax, kexp, BC, log2n);
-    return hipGetLastError();
 }
 
 }  // namespace mvhmr

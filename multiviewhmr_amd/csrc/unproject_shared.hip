@@ -9,7 +9,7 @@
 //   forward writes its tile's zeros and returns, the backward returns.
 // k_bwd_gather_shared serves both modes of the feature backward (float atomics / int64 fixed point), as k_bwd_gather_weighted does; volumes
 // that share a sample add into the same rows of the (B, V, HW, C4) accumulator, which the atomics sum.
-// The deterministic scale pass (k_shared_*) fixes ONE exponent K[b][c] per FEATURE sample and channel: max|g| over every volume that names b
+// The deterministic scale pass (unproject_det.hip: k_det_count, the shared row map of k_det_gmax) fixes ONE exponent K[b][c] per FEATURE sample and channel: max|g| over every volume that names b
 // (integer atomicMax over (idx[m], c): exact in any order), and the bound carries the number of those volumes, cnt[b] (a B-word histogram built
 // with integer atomics): cnt[b] * N * bound * 2^K < 2^62.  A pixel receives at most one tap per voxel, view and VOLUME; without cnt[b] the int64
 // sums of a sample named many times can wrap.
@@ -59,17 +59,6 @@ __device__ __forceinline__ void build_shared_records(ShRec *recs, const float *_
     }
 }
 
-__device__ __forceinline__ void store_sh(float *p, float v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void store_sh(__half *p, float v)
-{
-    __builtin_nontemporal_store(__half_as_ushort(from_f32<__half>(v)), reinterpret_cast<unsigned short *>(p));   // fp32 first, then fp16
-}
-__device__ __forceinline__ void store_sh(bf16_t *p, float v)
-{
-    __builtin_nontemporal_store(__builtin_bit_cast(unsigned short, (bf16_t)v), reinterpret_cast<unsigned short *>(p));
-}
-
-__device__ __forceinline__ unsigned sh_abs_bits(float x) { return __builtin_bit_cast(unsigned, x) & 0x7fffffffu; }
 
 }  // namespace
 
@@ -101,7 +90,7 @@ k_fwd_gather_shared(const TF *__restrict__ featT, const float *__restrict__ proj
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int c = cq * 4 + i;
-                    if (c < C) store_sh(&out[((long long)m * C + c) * N + n], 0.f);
+                    if (c < C) store_streaming(&out[((long long)m * C + c) * N + n], 0.f);
                 }
             }
         }
@@ -171,7 +160,7 @@ k_fwd_gather_shared(const TF *__restrict__ featT, const float *__restrict__ proj
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int c = cq * 4 + i;
-                if (c < C) store_sh(&out[((long long)m * C + c) * N + n], t.v[i]);
+                if (c < C) store_streaming(&out[((long long)m * C + c) * N + n], t.v[i]);
             }
         }
     }
@@ -312,78 +301,6 @@ k_bwd_gather_shared(const TO *__restrict__ grad_out, const TF *__restrict__ feat
     }
 }
 
-// ------------------------------------------------------------------------------------------ deterministic scale pass
-// cnt[b] = the number of volumes that name feature sample b (entries outside [0, B) name none): integer atomics, exact in any order
-__global__ void __launch_bounds__(256) k_shared_count(const int *__restrict__ fidx, int *__restrict__ cnt, int M, int B)
-{
-    const int m = blockIdx.x * 256 + threadIdx.x;
-    if (m >= M) return;
-    const int fb = fidx[m];
-    if ((unsigned)fb < (unsigned)B) atomicAdd(cnt + fb, 1);
-}
-
-// max |grad_out| of each (volume, channel) row of the (M, C, N) volume gradient, reduced over the volumes of a sample into gmax[idx[m]][c]:
-// block (row, chunk)
-template <typename TO>
-__global__ void __launch_bounds__(256) k_shared_gmax(const TO *__restrict__ grad_out, const int *__restrict__ fidx, unsigned *__restrict__ gmax, int B,
-                                                     int C, long long N)
-{
-    const long long row = blockIdx.x;
-    const int m = (int)(row / C), c = (int)(row - (long long)m * C);
-    const int fb = uniform(fidx[m]);
-    if ((unsigned)fb >= (unsigned)B) return;
-    const TO *g = grad_out + row * N;
-    unsigned mx = 0;
-    for (long long n = (long long)blockIdx.y * 256 + threadIdx.x; n < N; n += (long long)gridDim.y * 256) {
-        const unsigned a = sh_abs_bits(to_f32<TO>(g[n]));
-        mx = a > mx ? a : mx;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned t = (unsigned)__shfl_xor((int)mx, o);
-        mx = t > mx ? t : mx;
-    }
-    if ((threadIdx.x & 63) == 0 && mx) atomicMax(gmax + (long long)fb * C + c, mx);
-}
-
-// max |feature| of each (b, c) over all views and pixels, from the channels-last copy (BV, HW, C4) (k_det_fmax): per feature sample, as ever
-constexpr int kShPix = 64;
-template <typename TF>
-__global__ void __launch_bounds__(256) k_shared_fmax(const TF *__restrict__ featT, unsigned *__restrict__ fmax, int V, int C, int C4, int HW)
-{
-    const long long bv = blockIdx.y;
-    const int b = (int)(bv / V), p0 = blockIdx.x * kShPix, p1 = p0 + kShPix < HW ? p0 + kShPix : HW;
-    const TF *f = featT + bv * (long long)HW * C4;
-    for (int c = threadIdx.x; c < C; c += 256) {
-        unsigned mx = 0;
-        for (int p = p0; p < p1; ++p) {
-            const unsigned a = sh_abs_bits(to_f32<TF>(f[(long long)p * C4 + c]));
-            mx = a > mx ? a : mx;
-        }
-        if (mx) atomicMax(fmax + (long long)b * C + c, mx);
-    }
-}
-
-// K[b][c] from the two maxima and the count: cnt[b] * N * bound * 2^K < 2^62 (det_scale.h); a sample no volume names adds nothing (K = 0)
-__global__ void __launch_bounds__(256) k_shared_exponent(const unsigned *__restrict__ gmax, const unsigned *__restrict__ fmax, const int *__restrict__ cnt,
-                                                         int *__restrict__ kexp, long long BC, int C, int method, int V, int log2n)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= BC) return;
-    const int n = cnt[i / C];
-    if (n == 0) { kexp[i] = 0; return; }
-    const unsigned gb = gmax[i], fb = method == AGG_SOFTMAX ? fmax[i] : 0u;
-    if (gb >= 0x7f800000u || fb >= 0x7f800000u) { kexp[i] = kDetPoison; return; }
-    const double g = (double)__builtin_bit_cast(float, gb), f = (double)__builtin_bit_cast(float, fb);
-    const double bound = method == AGG_SOFTMAX ? g * (1.0 + 2.0 * f) : method == AGG_MEAN ? g / V : g;
-    if (bound == 0.0) { kexp[i] = 0; return; }
-    if (bound >= 3.4028234663852886e38) { kexp[i] = kDetPoison; return; }  // ds itself may overflow fp32
-    int e;
-    frexp(bound, &e);                                                    // bound < 2^e
-    const int log2c = n > 1 ? 32 - __builtin_clz((unsigned)(n - 1)) : 0; // cnt <= 2^log2c
-    kexp[i] = 62 - log2n - log2c - e;
-}
-
 // ------------------------------------------------------------------------------------------ launchers
 namespace {
 
@@ -488,39 +405,6 @@ hipError_t launch_bwd_gather_shared_det(const void *grad_out, const void *featT,
                                         const int *kexp, const Problem &p, hipStream_t s)
 {
     return bwd_shared<unsigned long long>(grad_out, featT, proj, coords, gradI, kexp, p, s);
-}
-
-// gmax, fmax, K: three words per (b, c) of the FEATURE samples (det_exponents finds K), then cnt: one word per feature sample
-size_t shared_det_scale_bytes(const Problem &p) { return (size_t)p.B * p.C * 3 * sizeof(int) + (size_t)p.B * sizeof(int); }
-
-hipError_t launch_det_scale_shared(const void *grad_out, const void *featT, void *scale, const Problem &p, hipStream_t s)
-{
-    const long long BC = (long long)p.B * p.C, MC = (long long)p.volumes * p.C;
-    unsigned *gmax = static_cast<unsigned *>(scale), *fmax = gmax + BC;
-    int *kexp = reinterpret_cast<int *>(fmax + BC), *cnt = kexp + BC;
-    if (!p.feature_index || p.volumes < 1 || BC > 0x7fffffffll || MC > 0x7fffffffll) return hipErrorNotSupported;
-    if (p.method == AGG_SOFTMAX && (long long)p.B * p.V > 65535) return hipErrorNotSupported;       // (k_shared_fmax: the maps are the grid's y extent)
-    hipError_t e = hipMemsetAsync(scale, 0, shared_det_scale_bytes(p), s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_shared_count, dim3((unsigned)((p.volumes + 255) / 256)), dim3(256), 0, s, p.feature_index, cnt, p.volumes, p.B);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    long long chunks = (p.N + 2047) / 2048;
-    chunks = chunks < 1 ? 1 : chunks > 64 ? 64 : chunks;
-    const dim3 g1((unsigned)MC, (unsigned)chunks);
-    if (p.out_bf16) hipLaunchKernelGGL(k_shared_gmax<bf16_t>, g1, dim3(256), 0, s, (const bf16_t *)grad_out, p.feature_index, gmax, p.B, p.C, p.N);
-    else if (p.out_f16) hipLaunchKernelGGL(k_shared_gmax<__half>, g1, dim3(256), 0, s, (const __half *)grad_out, p.feature_index, gmax, p.B, p.C, p.N);
-    else hipLaunchKernelGGL(k_shared_gmax<float>, g1, dim3(256), 0, s, (const float *)grad_out, p.feature_index, gmax, p.B, p.C, p.N);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if (p.method == AGG_SOFTMAX) {
-        const int HW = p.H * p.W;
-        const dim3 g2((unsigned)((HW + kShPix - 1) / kShPix), (unsigned)(p.B * p.V));
-        if (p.feat_f16) hipLaunchKernelGGL(k_shared_fmax<__half>, g2, dim3(256), 0, s, (const __half *)featT, fmax, p.V, p.C, p.C4, HW);
-        else hipLaunchKernelGGL(k_shared_fmax<float>, g2, dim3(256), 0, s, (const float *)featT, fmax, p.V, p.C, p.C4, HW);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    const int log2n = p.N > 1 ? 64 - __builtin_clzll((unsigned long long)(p.N - 1)) : 0;
-    hipLaunchKernelGGL(k_shared_exponent, dim3((unsigned)((BC + 255) / 256)), dim3(256), 0, s, gmax, fmax, cnt, kexp, BC, p.C, p.method, p.V, log2n);
-    return hipGetLastError();
 }
 
 }  // namespace mvhmr

@@ -70,16 +70,6 @@ __device__ __forceinline__ void build_seen_records(SeenRec *recs, unsigned *vbit
     __syncthreads();
 }
 
-__device__ __forceinline__ void store_seen(float *p, float v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void store_seen(__half *p, float v)
-{
-    __builtin_nontemporal_store(__half_as_ushort(from_f32<__half>(v)), reinterpret_cast<unsigned short *>(p));   // fp32 first, then fp16
-}
-__device__ __forceinline__ void store_seen(bf16_t *p, float v)
-{
-    __builtin_nontemporal_store(__builtin_bit_cast(unsigned short, (bf16_t)v), reinterpret_cast<unsigned short *>(p));
-}
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ forward
@@ -160,7 +150,7 @@ k_fwd_gather_seen(const TF *__restrict__ featT, const float *__restrict__ proj, 
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int c = cq * 4 + i;
-                if (c < C) store_seen(&out[((long long)b * C + c) * N + n], t.v[i]);
+                if (c < C) store_streaming(&out[((long long)b * C + c) * N + n], t.v[i]);
             }
         }
     }

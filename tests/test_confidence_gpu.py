@@ -281,7 +281,7 @@ def test_gradients_repeat_bitwise(method, masked, gpu):
 
 @pytest.mark.parametrize("masked", [False, True])
 def test_deterministic_softmax_with_visible_only(masked, gpu):
-    """the scale pass's marks under the seeing test (k_conf_mark's visible branch): bitwise repeats, and the oracle's feature gradient"""
+    """the scale pass's marks under the seeing test (k_det_mark's visible branch): bitwise repeats, and the oracle's feature gradient"""
     shape = SHAPES[0]
     B, V, H, W = (shape[k] for k in "BVHW")
     feats, proj, coords = _problem(shape, seed=90)
