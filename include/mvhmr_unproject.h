@@ -39,7 +39,7 @@ extern "C" {
                                  the *_masked entry points and their *_masked_workspace_bytes queries (per-sample view masks), the
                                  *_weighted entry points and their *_weighted_workspace_bytes queries (per-view confidence weights), the
                                  *_visible entry points, their *_visible_workspace_bytes queries and mvhmr_unproject_visibility[_cuboid]
-                                 (visibility-aware aggregation) */
+                                 (visibility-aware aggregation), the mvhmr_soft_argmax3d_* entry points (volumetric soft-argmax) */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -832,6 +832,47 @@ int mvhmr_triangulate_dlt_backward(const float *proj, const float *points, const
 int mvhmr_build_coord_volumes(float *coords, const float *rot, const float *center, int32_t batch,
                               int32_t volume_size, const double position[3], const double sides[3],
                               void *hip_stream);
+
+/*
+ * Volumetric 3-D soft-argmax (additive within ABI 4): keypoints from (B,J,X,Y,Z) heat volumes without a softmaxed
+ * copy and -- on the cuboid route -- without coordinate volumes.  Per slice (b,j), N = X*Y*Z, flat index n = (i*Y + j')*Z + k:
+ *     p_n = exp(beta v_n) / sum_m exp(beta v_m)      L = ln sum_m exp(beta v_m)      mu = sum_n p_n u_n          (fp32 arithmetic)
+ * Tensor route (coords non-null): u_n = coords[b,n,:], keypoint = mu.  Cuboid route (coords NULL): u_n is the un-rotated offset
+ * (position + step*index) - center[b] in the roundings of mvhmr_build_coord_volumes, keypoint = rot[b] mu + center[b] in its FMA order.
+ *   volumes      (B,J,X,Y,Z) of `dtype` (MVHMR_F32 / MVHMR_F16 / MVHMR_BF16), device                              [read]
+ *   coords       (B,X,Y,Z,3) fp32, device, or NULL: then rot (B,9), center (B,3) fp32 device, position / sides 3 host doubles each
+ *   beta         finite; it is rounded to fp32 (as beta * log2(e)) before it meets the volume
+ *   keypoints    (B,J,3) fp32     logsumexp (B,J) fp32     moment (B,J,3) fp32: mu in the accumulation frame    [write, all non-null]
+ *   workspace    mvhmr_soft_argmax3d_workspace_bytes(...) bytes, 16-byte aligned: the per-split records
+ * A -inf entry beside finite ones contributes exactly 0; a slice holding a NaN, +inf or nothing but -inf gives NaN in all three outputs.
+ * Sizes: every extent >= 1, N < 2^31, B*J <= 2^31 - 1 (MVHMR_ERR_INVALID_ARGUMENT otherwise); unknown dtype: MVHMR_ERR_INVALID_ARGUMENT; a null,
+ * short or misaligned workspace: MVHMR_ERR_WORKSPACE.  No atomics: every output is bitwise reproducible.  The number of blocks a slice is
+ * split over, mvhmr_soft_argmax3d_splits, is a function of the sizes alone (never of the device), so results do not depend on the card.
+ */
+int32_t mvhmr_soft_argmax3d_splits(int32_t batch, int32_t joints, int64_t voxels);
+size_t mvhmr_soft_argmax3d_workspace_bytes(int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y, int32_t vol_z);
+int mvhmr_soft_argmax3d_forward(const void *volumes, int32_t dtype, const float *coords, const float *rot, const float *center,
+                                const double position[3], const double sides[3], int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y,
+                                int32_t vol_z, double beta, float *keypoints, float *logsumexp, float *moment, void *workspace,
+                                size_t workspace_bytes, void *hip_stream);
+/*
+ * Its backward w.r.t. the volume: with g = grad_keypoints (B,J,3), g_L = grad_logsumexp (B,J) (each fp32 or NULL = zero; both NULL is
+ * MVHMR_ERR_INVALID_ARGUMENT), h = g on the tensor route and rot[b]^T g on the cuboid route,
+ *     grad_volumes[n] = beta p_n (h . (u_n - mu) + g_L),     p_n = exp(beta v_n - L) recomputed from logsumexp, never stored
+ * logsumexp and moment are the forward's outputs; grad_volumes (B,J,X,Y,Z) is written in `dtype`.  No workspace.
+ */
+int mvhmr_soft_argmax3d_backward(const void *volumes, int32_t dtype, const float *coords, const float *rot, const float *center,
+                                 const double position[3], const double sides[3], int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y,
+                                 int32_t vol_z, double beta, const float *logsumexp, const float *moment, const float *grad_keypoints,
+                                 const float *grad_logsumexp, void *grad_volumes, void *hip_stream);
+/* tensor route: grad_coords[b,n,:] = sum_j p_{j,n} g_{b,j,:}, j in index order; (B,X,Y,Z,3) fp32 */
+int mvhmr_soft_argmax3d_backward_coords(const void *volumes, int32_t dtype, int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y,
+                                        int32_t vol_z, double beta, const float *logsumexp, const float *grad_keypoints, float *grad_coords,
+                                        void *hip_stream);
+/* cuboid route: grad_rot[b] = sum_j g_{b,j} mu_{b,j}^T (B,9), grad_center[b] = sum_j (g_{b,j} - rot[b]^T g_{b,j}) (B,3), j in index order;
+ * either output may be NULL, not both */
+int mvhmr_soft_argmax3d_backward_pose(const float *rot, const float *moment, const float *grad_keypoints, float *grad_rot, float *grad_center,
+                                      int32_t batch, int32_t joints, void *hip_stream);
 
 /* Which kernel AUTO would run for this problem (an mvhmr_variant_t), for logs and tests. */
 int mvhmr_unproject_selected_variant(const mvhmr_unproject_desc *desc);

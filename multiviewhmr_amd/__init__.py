@@ -6,11 +6,15 @@ Public surface mirrors the reference modules it replaces:
     multiviewhmr_amd.multiview     <->  utils/multiview.py      (Camera, projection helpers, DLT triangulation)
     multiviewhmr_amd.volumetric    <->  utils/volumetric.py     (Cuboid3D, get_rotation_matrix, rotate_coord_volume)
 
+and, beyond them, multiviewhmr_amd.softargmax: the volumetric 3-D soft-argmax that turns a heat volume back into keypoints
+(soft_argmax_3d, soft_argmax_3d_cuboid).
+
 The compute lives in lib/libmvhmr_unproject.so (hand-written HIP for gfx950 behind the C ABI of
 include/mvhmr_unproject.h); there is no CPU or PyTorch fallback -- importing is cheap, calling
 `unprojection` without the built library or without a HIP device raises.
 """
 __version__ = "0.1.0"
 
-from . import aggregation, multiview, volumetric  # noqa: F401
+from . import aggregation, multiview, softargmax, volumetric  # noqa: F401
 from .aggregation import VolumeGenerator, build_volume_generator, unprojection  # noqa: F401
+from .softargmax import soft_argmax_3d, soft_argmax_3d_cuboid  # noqa: F401

@@ -34,7 +34,10 @@ EXPORTS = (
                                                            "backward_cuboid_deterministic", "backward_geometry", "backward_geometry_cuboid")
           for w in ("", "_workspace_bytes")       # per-sample view masks, per-view confidence weights, visibility-aware aggregation, per-pixel confidence maps, shared feature maps, lens distortion, cross-view variance
           for tag in ("masked", "weighted", "visible", "confidence", "shared", "lens", "moments")) + ("mvhmr_unproject_visibility", "mvhmr_unproject_visibility_cuboid") + (
-    "mvhmr_unproject_call_workspace_bytes", "mvhmr_unproject_forward_call", "mvhmr_unproject_backward_call", "mvhmr_unproject_backward_geometry_call")
+    "mvhmr_unproject_call_workspace_bytes", "mvhmr_unproject_forward_call", "mvhmr_unproject_backward_call", "mvhmr_unproject_backward_geometry_call") + (
+    # the volumetric soft-argmax (softargmax.py)
+    "mvhmr_soft_argmax3d_splits", "mvhmr_soft_argmax3d_workspace_bytes", "mvhmr_soft_argmax3d_forward", "mvhmr_soft_argmax3d_backward",
+    "mvhmr_soft_argmax3d_backward_coords", "mvhmr_soft_argmax3d_backward_pose")
 
 
 class Desc(ctypes.Structure):
@@ -192,6 +195,20 @@ def lib():
         fn = getattr(L, "mvhmr_unproject_%s_call" % kind)
         fn.restype = ctypes.c_int
         fn.argtypes = [dp, cp, vp, sz, vp]
+    # the volumetric soft-argmax: (volumes, dtype, coords | rot, center, position, sides, B, J, X, Y, Z, beta, ...)
+    place, sizes, dbl = [vp, vp, vp, d3, d3], [i32] * 5, ctypes.c_double
+    L.mvhmr_soft_argmax3d_splits.restype = i32
+    L.mvhmr_soft_argmax3d_splits.argtypes = [i32, i32, ctypes.c_int64]
+    L.mvhmr_soft_argmax3d_workspace_bytes.restype = sz
+    L.mvhmr_soft_argmax3d_workspace_bytes.argtypes = sizes
+    L.mvhmr_soft_argmax3d_forward.restype = ctypes.c_int
+    L.mvhmr_soft_argmax3d_forward.argtypes = [vp, i32] + place + sizes + [dbl, vp, vp, vp, vp, sz, vp]
+    L.mvhmr_soft_argmax3d_backward.restype = ctypes.c_int
+    L.mvhmr_soft_argmax3d_backward.argtypes = [vp, i32] + place + sizes + [dbl, vp, vp, vp, vp, vp, vp]
+    L.mvhmr_soft_argmax3d_backward_coords.restype = ctypes.c_int
+    L.mvhmr_soft_argmax3d_backward_coords.argtypes = [vp, i32] + sizes + [dbl, vp, vp, vp, vp]
+    L.mvhmr_soft_argmax3d_backward_pose.restype = ctypes.c_int
+    L.mvhmr_soft_argmax3d_backward_pose.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
     L.mvhmr_internal_det_exponent_table.restype = ctypes.c_int
     L.mvhmr_internal_det_exponent_table.argtypes = [dp, cp, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     if L.mvhmr_abi_version() != ABI_VERSION:

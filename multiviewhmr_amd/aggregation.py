@@ -1039,6 +1039,12 @@ class VolumeGenerator(nn.Module):
         return coords
 
     def forward(self, features, proj_matricies, batch, use_gt=True):
+        return self.forward_with_pose(features, proj_matricies, batch, use_gt=use_gt)[0]
+
+    def forward_with_pose(self, features, proj_matricies, batch, use_gt=True):
+        """forward(), and the pose it placed the volume with: (volumes, rotations (B,3,3), centers (B,3)), the float32 device tensors the
+        un-projection read.  In training the rotation is a draw from numpy's global stream, which a caller cannot repeat; soft_argmax()
+        needs exactly these two to map the volume back to world points.  The same numpy draws and launches as forward()."""
         features_shape = tuple(features.shape[-2:])
         images_shape = tuple(batch['images'].shape[2:-1])
         batch_size, n_views = batch['images'].shape[:2]
@@ -1075,14 +1081,21 @@ class VolumeGenerator(nn.Module):
             # 1x1 conv and layout pass in one MFMA GEMM, its output only ever exists in the layout the brick forward stages
             conv = self.process_feature[0]
             return _FusedAggregate.apply(features, conv.weight, conv.bias, proj, rots, centers, tuple(cub.position), tuple(cub.sides),
-                                         (S, S, S), _capi.AGG[self.aggregation_method], self.volume_dtype or torch.float32)
+                                         (S, S, S), _capi.AGG[self.aggregation_method], self.volume_dtype or torch.float32), rots, centers
 
         features = features.view(-1, *features.shape[2:])
         features = self.process_feature(features)
         features = features.view(batch_size, n_views, *features.shape[1:])
         # the coordinate volumes (aggregation.py:138-187) are never materialised: the kernels evaluate the cuboid recipe per voxel
         return unprojection_cuboid(features, proj, rots, centers, cub.position, cub.sides, (S, S, S),
-                                   aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **given)
+                                   aggregation_method=self.aggregation_method, out_dtype=self.volume_dtype, **given), rots, centers
+
+    def soft_argmax(self, volumes, rotations, centers, beta=1.0, return_logsumexp=False):
+        """World keypoints (B, J, 3) of heat volumes (B, J, S, S, S) that live on this module's cuboid, placed by the rotations and centers
+        forward_with_pose returned (softargmax.soft_argmax_3d_cuboid: no coordinate volume; differentiable w.r.t. all three tensors)."""
+        from . import softargmax
+        cub = self.cuboid()
+        return softargmax.soft_argmax_3d_cuboid(volumes, rotations, centers, cub.position, cub.sides, beta=beta, return_logsumexp=return_logsumexp)
 
     def _fused_path_applies(self, features, S):
         """The fused conv writes the quad-planar layout, which the un-projection consumes for every geometry (brick kernels as it

@@ -1571,4 +1571,92 @@ int mvhmr_build_coord_volumes(float *coords, const float *rot, const float *cent
                     "coord volume build");
 }
 
+// ---- volumetric soft-argmax (soft_argmax3d.hip)
+namespace {
+struct SaCall { Coords coords; float c2, beta; int X; };
+
+int sa_open(int32_t dtype, const float *coords, const float *rot, const float *center, const double *position, const double *sides, int32_t batch,
+            int32_t joints, int32_t vol_x, int32_t vol_y, int32_t vol_z, double beta, bool placed, SaCall *out)
+{
+    if (batch < 1 || joints < 1 || vol_x < 1 || vol_y < 1 || vol_z < 1)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d: every dimension must be >= 1 (B=%d J=%d vol=%dx%dx%d)", batch, joints, vol_x, vol_y, vol_z);
+    if ((long long)vol_x * vol_y * vol_z > 0x7fffffffLL || (long long)batch * joints > 0x7fffffffLL)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d: X*Y*Z and B*J must stay below 2^31 (vol=%dx%dx%d, B=%d J=%d)", vol_x, vol_y, vol_z, batch, joints);
+    if (dtype < MVHMR_F32 || dtype > MVHMR_BF16) return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d: unknown dtype %d", dtype);
+    if (!(beta == beta) || beta - beta != 0.0) return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d: beta must be finite");
+    Problem p{};
+    p.X = vol_x; p.Y = vol_y; p.Z = vol_z;
+    out->X = vol_x;
+    out->beta = (float)beta;
+    out->c2 = (float)(beta * 1.4426950408889634);
+    if (!placed) { out->coords = Coords{}; return MVHMR_OK; }
+    if (coords) { out->coords = coords_from_tensor(coords, p); return MVHMR_OK; }
+    return coords_from_cuboid(rot, center, position, sides, p, &out->coords);
+}
+}  // namespace
+
+int32_t mvhmr_soft_argmax3d_splits(int32_t batch, int32_t joints, int64_t voxels)
+{
+    if (batch < 1 || joints < 1 || voxels < 1) return 0;
+    return sa3d_splits(batch, joints, voxels);
+}
+
+size_t mvhmr_soft_argmax3d_workspace_bytes(int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y, int32_t vol_z)
+{
+    if (batch < 1 || joints < 1 || vol_x < 1 || vol_y < 1 || vol_z < 1) return 0;
+    return sa3d_workspace_floats(batch, joints, (long long)vol_x * vol_y * vol_z) * sizeof(float);
+}
+
+int mvhmr_soft_argmax3d_forward(const void *volumes, int32_t dtype, const float *coords, const float *rot, const float *center,
+                                const double position[3], const double sides[3], int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y,
+                                int32_t vol_z, double beta, float *keypoints, float *logsumexp, float *moment, void *workspace,
+                                size_t workspace_bytes, void *hip_stream)
+{
+    if (!volumes || !keypoints || !logsumexp || !moment) return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d: volumes / keypoints / logsumexp / moment must be non-null");
+    SaCall c;
+    const int rc = sa_open(dtype, coords, rot, center, position, sides, batch, joints, vol_x, vol_y, vol_z, beta, true, &c);
+    if (rc != MVHMR_OK) return rc;
+    const size_t need = mvhmr_soft_argmax3d_workspace_bytes(batch, joints, vol_x, vol_y, vol_z);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u))
+        return fail(MVHMR_ERR_WORKSPACE, "soft_argmax3d: workspace of %zu bytes needed, 16-byte aligned (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    return launched(launch_sa3d_forward(volumes, dtype, c.coords, batch, joints, c.X, c.c2, keypoints, logsumexp, moment, static_cast<float *>(workspace),
+                                        static_cast<hipStream_t>(hip_stream)), "soft_argmax3d forward");
+}
+
+int mvhmr_soft_argmax3d_backward(const void *volumes, int32_t dtype, const float *coords, const float *rot, const float *center,
+                                 const double position[3], const double sides[3], int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y,
+                                 int32_t vol_z, double beta, const float *logsumexp, const float *moment, const float *grad_keypoints,
+                                 const float *grad_logsumexp, void *grad_volumes, void *hip_stream)
+{
+    if (!volumes || !logsumexp || !moment || !grad_volumes) return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d backward: volumes / logsumexp / moment / grad_volumes must be non-null");
+    if (!grad_keypoints && !grad_logsumexp) return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d backward: grad_keypoints and grad_logsumexp are both null: nothing to compute");
+    SaCall c;
+    const int rc = sa_open(dtype, coords, rot, center, position, sides, batch, joints, vol_x, vol_y, vol_z, beta, true, &c);
+    if (rc != MVHMR_OK) return rc;
+    return launched(launch_sa3d_backward(volumes, dtype, c.coords, batch, joints, c.X, c.c2, c.beta, logsumexp, moment, grad_keypoints, grad_logsumexp,
+                                         grad_volumes, static_cast<hipStream_t>(hip_stream)), "soft_argmax3d backward");
+}
+
+int mvhmr_soft_argmax3d_backward_coords(const void *volumes, int32_t dtype, int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y, int32_t vol_z,
+                                        double beta, const float *logsumexp, const float *grad_keypoints, float *grad_coords, void *hip_stream)
+{
+    if (!volumes || !logsumexp || !grad_keypoints || !grad_coords) return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d backward_coords: null pointer");
+    SaCall c;
+    const int rc = sa_open(dtype, nullptr, nullptr, nullptr, nullptr, nullptr, batch, joints, vol_x, vol_y, vol_z, beta, false, &c);
+    if (rc != MVHMR_OK) return rc;
+    return launched(launch_sa3d_backward_coords(volumes, dtype, batch, joints, (long long)vol_x * vol_y * vol_z, c.c2, logsumexp, grad_keypoints, grad_coords,
+                                                static_cast<hipStream_t>(hip_stream)), "soft_argmax3d backward_coords");
+}
+
+int mvhmr_soft_argmax3d_backward_pose(const float *rot, const float *moment, const float *grad_keypoints, float *grad_rot, float *grad_center,
+                                      int32_t batch, int32_t joints, void *hip_stream)
+{
+    if (!rot || !moment || !grad_keypoints) return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d backward_pose: rot / moment / grad_keypoints must be non-null");
+    if (!grad_rot && !grad_center) return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d backward_pose: grad_rot and grad_center are both null: nothing to compute");
+    if (batch < 1 || joints < 1 || (long long)batch * joints > 0x7fffffffLL)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "soft_argmax3d backward_pose: batch and joints must be >= 1 and B*J below 2^31 (got %d, %d)", batch, joints);
+    return launched(launch_sa3d_backward_pose(rot, moment, grad_keypoints, grad_rot, grad_center, batch, joints, static_cast<hipStream_t>(hip_stream)),
+                    "soft_argmax3d pose gradient");
+}
+
 }  // extern "C"

@@ -7,11 +7,14 @@ k_fwd_brick is held to zero scratch here, and so is k_bwd_geom: it holds 3 V val
 channels per lane shrink with V to keep that at <= 48), and a spill inside its channel loop would cost a scratch round trip per tap.  k_fwd_brick_groups and k_bwd_brick keep a cold noinline slow path whose call frame is
 scratch OUTSIDE their hot loops; their loops are checked on the device assembly instead (check_loops.py).  k_bwd_brick's one
 counted wait, wait_vmcnt(n_at) after the flush atomics, relies on vmcnt retiring in issue order: an extra vector-memory operation
-the compiler adds among the wave's youngest could only make that wait cover more, never less."""
+the compiler adds among the wave's youngest could only make that wait cover more, never less.
+
+The soft-argmax kernels (k_sa3d_*) stream the volume once with up to 20 accumulators and 24 coordinates live per lane: a spill would add
+scratch traffic to a kernel whose whole budget is one read of the volume, so they are held to zero scratch too."""
 import re
 import sys
 
-NO_SCRATCH = ("k_fwd_brick", "k_bwd_geom")
+NO_SCRATCH = ("k_fwd_brick", "k_bwd_geom", "k_sa3d")
 EXEMPT = re.compile(r"k_fwd_brick_groups")      # (k_fwd_ws: cold noinline slow path + prologue spills outside its loops; check_loops.py holds the loops)
 text = open(sys.argv[1]).read()
 bad = []

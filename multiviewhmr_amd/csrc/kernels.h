@@ -275,4 +275,17 @@ hipError_t launch_view_unpack(const void *src, void *dst, const void *table, int
 hipError_t launch_build_coords(float *coords_out, const float *rot, const float *center, int B, int S,
                                const double pos[3], const double sides[3], hipStream_t s);
 
+// volumetric soft-argmax (soft_argmax3d.hip).  `dtype` is an mvhmr_dtype_t of vol / grad_vol; coords.ptr selects the tensor
+// route, else the cuboid recipe; c2 = fl32(beta * log2 e).  ws holds sa3d_workspace_floats(B, J, N) floats of per-split records.
+int sa3d_splits(long long B, long long J, long long N);
+size_t sa3d_workspace_floats(long long B, long long J, long long N);
+hipError_t launch_sa3d_forward(const void *vol, int dtype, const Coords &coords, int B, int J, int X, float c2, float *keypoints, float *lse,
+                               float *moment, float *ws, hipStream_t s);
+hipError_t launch_sa3d_backward(const void *vol, int dtype, const Coords &coords, int B, int J, int X, float c2, float beta, const float *lse,
+                                const float *moment, const float *grad_kp, const float *grad_lse, void *grad_vol, hipStream_t s);
+hipError_t launch_sa3d_backward_coords(const void *vol, int dtype, int B, int J, long long N, float c2, const float *lse, const float *grad_kp,
+                                       float *grad_coords, hipStream_t s);
+hipError_t launch_sa3d_backward_pose(const float *rot, const float *moment, const float *grad_kp, float *grad_rot, float *grad_center, int B, int J,
+                                     hipStream_t s);
+
 }  // namespace mvhmr

@@ -8,7 +8,8 @@
 // view_args() turns them into one mvhmr_unproject_call and names its family; mvhmr_visibility::view_visibility[_cuboid] return the
 // (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what
 // places the volume.  Per call: tensor checks, descriptor, record, output and workspace from the caching allocator, the current HIP stream,
-// one C-ABI call.  Host code only: the kernels live in libmvhmr_unproject.so.
+// one C-ABI call.  mvhmr_softargmax::soft_argmax3d[_cuboid] and their backwards are the volumetric soft-argmax (softargmax.py).  Host code only: the
+// kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <c10/core/DeviceGuard.h>
@@ -496,6 +497,137 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> triangulate_dlt_backward_native(c
     return {gp, gu, gc};
 }
 
+// Volumetric soft-argmax (mvhmr_soft_argmax3d_*; multiviewhmr_amd/softargmax.py): volumes (B,J,X,Y,Z) fp32 / fp16 / bf16, every other tensor
+// fp32; the tensor route places the voxels by coords (B,X,Y,Z,3), the cuboid route by rot (B,3,3), center (B,3), position, sides.  The same
+// per-call tail as above: checks, outputs and workspace from the caching allocator, the current stream, one C-ABI call.
+struct SaPlace {
+    const float *coords = nullptr, *rot = nullptr, *center = nullptr;
+    const double *position = nullptr, *sides = nullptr;
+};
+
+int32_t sa_dtype(const at::Tensor &volumes)
+{
+    const at::ScalarType t = volumes.scalar_type();
+    TORCH_CHECK(t == at::kFloat || t == at::kHalf || t == at::kBFloat16, "mvhmr_soft_argmax3d: volumes must be fp32, fp16 or bf16, got ", t);
+    return t == at::kHalf ? MVHMR_F16 : t == at::kBFloat16 ? MVHMR_BF16 : MVHMR_F32;
+}
+
+void sa_check_volumes(const at::Tensor &volumes)
+{
+    TORCH_CHECK(volumes.is_cuda() && volumes.is_contiguous() && volumes.dim() == 5 && volumes.numel() > 0,
+                "mvhmr_soft_argmax3d: volumes must be a contiguous, non-empty (B, J, X, Y, Z) tensor on a HIP device");
+    TORCH_CHECK(volumes.size(2) * volumes.size(3) * volumes.size(4) < (int64_t(1) << 31) && volumes.size(0) * volumes.size(1) < (int64_t(1) << 31),
+                "mvhmr_soft_argmax3d: X*Y*Z and B*J must stay below 2^31");
+}
+
+SaPlace sa_place(const at::Tensor &volumes, const at::Tensor *coords, const at::Tensor *rot, const at::Tensor *center, at::ArrayRef<double> position,
+                 at::ArrayRef<double> sides)
+{
+    sa_check_volumes(volumes);
+    const int64_t B = volumes.size(0), N = volumes.size(2) * volumes.size(3) * volumes.size(4);
+    SaPlace p;
+    if (coords) {
+        TORCH_CHECK(coords->dim() == 5 && coords->size(0) == B && coords->size(1) == volumes.size(2) && coords->size(2) == volumes.size(3) &&
+                    coords->size(3) == volumes.size(4) && coords->size(4) == 3, "mvhmr_soft_argmax3d: coord_volumes must be (B, X, Y, Z, 3) of the volumes' extents");
+        check_tensor(*coords, volumes, "coord_volumes (B, X, Y, Z, 3)", at::kFloat, B * N * 3);
+        p.coords = coords->data_ptr<float>();
+    } else {
+        TORCH_CHECK(position.size() == 3 && sides.size() == 3, "mvhmr_soft_argmax3d: position and sides take 3 values each");
+        check_tensor(*rot, volumes, "rotations (B, 3, 3)", at::kFloat, B * 9);
+        check_tensor(*center, volumes, "centers (B, 3)", at::kFloat, B * 3);
+        p.rot = rot->data_ptr<float>(); p.center = center->data_ptr<float>(); p.position = position.data(); p.sides = sides.data();
+    }
+    return p;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sa_forward(const at::Tensor &volumes, const SaPlace &p, double beta)
+{
+    const int64_t B = volumes.size(0), J = volumes.size(1), X = volumes.size(2), Y = volumes.size(3), Z = volumes.size(4);
+    c10::DeviceGuard guard(volumes.device());
+    const auto f32 = volumes.options().dtype(at::kFloat);
+    at::Tensor kp = at::empty({B, J, 3}, f32), lse = at::empty({B, J}, f32), mom = at::empty({B, J, 3}, f32);
+    const size_t need = mvhmr_soft_argmax3d_workspace_bytes((int32_t)B, (int32_t)J, (int32_t)X, (int32_t)Y, (int32_t)Z);
+    at::Tensor ws = at::empty({(int64_t)need}, volumes.options().dtype(at::kByte));
+    check_status(mvhmr_soft_argmax3d_forward(volumes.data_ptr(), sa_dtype(volumes), p.coords, p.rot, p.center, p.position, p.sides, (int32_t)B, (int32_t)J,
+                                             (int32_t)X, (int32_t)Y, (int32_t)Z, beta, kp.data_ptr<float>(), lse.data_ptr<float>(), mom.data_ptr<float>(),
+                                             ws.data_ptr(), need, c10::hip::getCurrentHIPStream(volumes.device().index()).stream()));
+    return {kp, lse, mom};
+}
+
+at::Tensor sa_backward(const at::Tensor &volumes, const SaPlace &p, double beta, const at::Tensor &lse, const at::Tensor &moment,
+                       const c10::optional<at::Tensor> &grad_kp, const c10::optional<at::Tensor> &grad_lse)
+{
+    const int64_t B = volumes.size(0), J = volumes.size(1), X = volumes.size(2), Y = volumes.size(3), Z = volumes.size(4);
+    check_tensor(lse, volumes, "logsumexp (B, J)", at::kFloat, B * J);
+    check_tensor(moment, volumes, "moment (B, J, 3)", at::kFloat, B * J * 3);
+    const bool has_k = grad_kp && grad_kp->defined(), has_l = grad_lse && grad_lse->defined();
+    TORCH_CHECK(has_k || has_l, "mvhmr_soft_argmax3d: the backward needs grad_keypoints or grad_logsumexp");
+    if (has_k) check_tensor(*grad_kp, volumes, "grad_keypoints (B, J, 3)", at::kFloat, B * J * 3);
+    if (has_l) check_tensor(*grad_lse, volumes, "grad_logsumexp (B, J)", at::kFloat, B * J);
+    c10::DeviceGuard guard(volumes.device());
+    at::Tensor gv = at::empty_like(volumes);
+    check_status(mvhmr_soft_argmax3d_backward(volumes.data_ptr(), sa_dtype(volumes), p.coords, p.rot, p.center, p.position, p.sides, (int32_t)B, (int32_t)J,
+                                              (int32_t)X, (int32_t)Y, (int32_t)Z, beta, lse.data_ptr<float>(), moment.data_ptr<float>(),
+                                              has_k ? grad_kp->data_ptr<float>() : nullptr, has_l ? grad_lse->data_ptr<float>() : nullptr, gv.data_ptr(),
+                                              c10::hip::getCurrentHIPStream(volumes.device().index()).stream()));
+    return gv;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> soft_argmax3d_native(const at::Tensor &volumes, const at::Tensor &coords, double beta)
+{
+    return sa_forward(volumes, sa_place(volumes, &coords, nullptr, nullptr, {}, {}), beta);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> soft_argmax3d_cuboid_native(const at::Tensor &volumes, const at::Tensor &rot, const at::Tensor &center,
+                                                                           at::ArrayRef<double> position, at::ArrayRef<double> sides, double beta)
+{
+    return sa_forward(volumes, sa_place(volumes, nullptr, &rot, &center, position, sides), beta);
+}
+
+at::Tensor soft_argmax3d_backward_native(const at::Tensor &volumes, const at::Tensor &coords, double beta, const at::Tensor &lse, const at::Tensor &moment,
+                                         const c10::optional<at::Tensor> &grad_kp, const c10::optional<at::Tensor> &grad_lse)
+{
+    return sa_backward(volumes, sa_place(volumes, &coords, nullptr, nullptr, {}, {}), beta, lse, moment, grad_kp, grad_lse);
+}
+
+at::Tensor soft_argmax3d_cuboid_backward_native(const at::Tensor &volumes, const at::Tensor &rot, const at::Tensor &center, at::ArrayRef<double> position,
+                                                at::ArrayRef<double> sides, double beta, const at::Tensor &lse, const at::Tensor &moment,
+                                                const c10::optional<at::Tensor> &grad_kp, const c10::optional<at::Tensor> &grad_lse)
+{
+    return sa_backward(volumes, sa_place(volumes, nullptr, &rot, &center, position, sides), beta, lse, moment, grad_kp, grad_lse);
+}
+
+// grad_coords (B,X,Y,Z,3) of the tensor route
+at::Tensor soft_argmax3d_backward_coords_native(const at::Tensor &volumes, double beta, const at::Tensor &lse, const at::Tensor &grad_kp)
+{
+    sa_check_volumes(volumes);
+    const int64_t B = volumes.size(0), J = volumes.size(1), X = volumes.size(2), Y = volumes.size(3), Z = volumes.size(4);
+    check_tensor(lse, volumes, "logsumexp (B, J)", at::kFloat, B * J);
+    check_tensor(grad_kp, volumes, "grad_keypoints (B, J, 3)", at::kFloat, B * J * 3);
+    c10::DeviceGuard guard(volumes.device());
+    at::Tensor gc = at::empty({B, X, Y, Z, 3}, volumes.options().dtype(at::kFloat));
+    check_status(mvhmr_soft_argmax3d_backward_coords(volumes.data_ptr(), sa_dtype(volumes), (int32_t)B, (int32_t)J, (int32_t)X, (int32_t)Y, (int32_t)Z, beta,
+                                                     lse.data_ptr<float>(), grad_kp.data_ptr<float>(), gc.data_ptr<float>(),
+                                                     c10::hip::getCurrentHIPStream(volumes.device().index()).stream()));
+    return gc;
+}
+
+// grad_rot (B,3,3) and grad_center (B,3) of the cuboid route
+std::tuple<at::Tensor, at::Tensor> soft_argmax3d_backward_pose_native(const at::Tensor &rot, const at::Tensor &moment, const at::Tensor &grad_kp)
+{
+    TORCH_CHECK(rot.is_cuda() && rot.dim() == 3 && rot.size(1) == 3 && rot.size(2) == 3 && moment.dim() == 3 && moment.size(0) == rot.size(0) &&
+                moment.size(1) >= 1 && moment.size(2) == 3, "mvhmr_soft_argmax3d: rotations must be (B, 3, 3) on a HIP device and moment (B, J, 3)");
+    const int64_t B = rot.size(0), J = moment.size(1);
+    TORCH_CHECK(B >= 1 && B * J < (int64_t(1) << 31), "mvhmr_soft_argmax3d: B*J must stay below 2^31");
+    check_tensor(rot, rot, "rotations (B, 3, 3)", at::kFloat, B * 9);
+    check_tensor(moment, rot, "moment (B, J, 3)", at::kFloat, B * J * 3);
+    check_tensor(grad_kp, rot, "grad_keypoints (B, J, 3)", at::kFloat, B * J * 3);
+    c10::DeviceGuard guard(rot.device());
+    at::Tensor gr = at::empty({B, 3, 3}, rot.options()), gc = at::empty({B, 3}, rot.options());
+    check_status(mvhmr_soft_argmax3d_backward_pose(rot.data_ptr<float>(), moment.data_ptr<float>(), grad_kp.data_ptr<float>(), gr.data_ptr<float>(),
+                                                   gc.data_ptr<float>(), (int32_t)B, (int32_t)J, c10::hip::getCurrentHIPStream(rot.device().index()).stream()));
+    return {gr, gc};
+}
 
 }  // namespace
 
@@ -549,6 +681,28 @@ TORCH_LIBRARY_IMPL(mvhmr_visibility, CUDA, m)
 {
     m.impl("view_visibility", &view_visibility_native);
     m.impl("view_visibility_cuboid", &view_visibility_cuboid_native);
+}
+
+// the volumetric soft-argmax reads a volume, it un-projects nothing: a namespace of its own as well
+TORCH_LIBRARY(mvhmr_softargmax, m)
+{
+    m.def("soft_argmax3d(Tensor volumes, Tensor coords, float beta) -> (Tensor, Tensor, Tensor)");
+    m.def("soft_argmax3d_cuboid(Tensor volumes, Tensor rot, Tensor center, float[] position, float[] sides, float beta) -> (Tensor, Tensor, Tensor)");
+    m.def("soft_argmax3d_backward(Tensor volumes, Tensor coords, float beta, Tensor logsumexp, Tensor moment, Tensor? grad_keypoints, Tensor? grad_logsumexp) -> Tensor");
+    m.def("soft_argmax3d_cuboid_backward(Tensor volumes, Tensor rot, Tensor center, float[] position, float[] sides, float beta, Tensor logsumexp, Tensor moment, "
+          "Tensor? grad_keypoints, Tensor? grad_logsumexp) -> Tensor");
+    m.def("soft_argmax3d_backward_coords(Tensor volumes, float beta, Tensor logsumexp, Tensor grad_keypoints) -> Tensor");
+    m.def("soft_argmax3d_backward_pose(Tensor rot, Tensor moment, Tensor grad_keypoints) -> (Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(mvhmr_softargmax, CUDA, m)
+{
+    m.impl("soft_argmax3d", &soft_argmax3d_native);
+    m.impl("soft_argmax3d_cuboid", &soft_argmax3d_cuboid_native);
+    m.impl("soft_argmax3d_backward", &soft_argmax3d_backward_native);
+    m.impl("soft_argmax3d_cuboid_backward", &soft_argmax3d_cuboid_backward_native);
+    m.impl("soft_argmax3d_backward_coords", &soft_argmax3d_backward_coords_native);
+    m.impl("soft_argmax3d_backward_pose", &soft_argmax3d_backward_pose_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)
