@@ -39,7 +39,8 @@ extern "C" {
                                  the *_masked entry points and their *_masked_workspace_bytes queries (per-sample view masks), the
                                  *_weighted entry points and their *_weighted_workspace_bytes queries (per-view confidence weights), the
                                  *_visible entry points, their *_visible_workspace_bytes queries and mvhmr_unproject_visibility[_cuboid]
-                                 (visibility-aware aggregation), the mvhmr_soft_argmax3d_* entry points (volumetric soft-argmax) */
+                                 (visibility-aware aggregation), the mvhmr_soft_argmax3d_* entry points (volumetric soft-argmax), the
+                                 mvhmr_sample_volume_* entry points (trilinear volume sampling at world points) */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -873,6 +874,55 @@ int mvhmr_soft_argmax3d_backward_coords(const void *volumes, int32_t dtype, int3
  * either output may be NULL, not both */
 int mvhmr_soft_argmax3d_backward_pose(const float *rot, const float *moment, const float *grad_keypoints, float *grad_rot, float *grad_center,
                                       int32_t batch, int32_t joints, void *hip_stream);
+
+/*
+ * Trilinear volume sampling at world points (additive within ABI 4): reads (B,C,X,Y,Z) volumes that live on the cuboid
+ * recipe of mvhmr_build_coord_volumes -- voxel (i,j,k) at rot (position + step*(i,j,k) - center) + center, step_a = fl32(sides_a / (S_a - 1))
+ * -- back at N world points per sample.  The inverse uses rot^T: rot must be orthonormal (not checked).  Per point x, every line one
+ * rounded fp32 operation, volume values widened to fp32 first:
+ *     y_i = x_i - c_i      d_a = fma(R[2][a], y_2, fma(R[1][a], y_1, R[0][a] * y_0))      o_a = c_a - fl32(position_a)
+ *     t_a = (d_a + o_a) / step_a                                                       -> index, the continuous voxel index
+ *     unless -1 < t_a < S_a on every axis (a NaN fails): sample 0 and no gradient through this point
+ *     i0 = floor(t), w1 = t - i0, w0 = (i0 + 1) - t, w(dx,dy,dz) = (wx * wy) * wz; a tap outside the grid counts as value 0
+ *     sample = fma chain over the taps in the order dx*4 + dy*2 + dz; a tap whose weight is exactly 0 is not read
+ * (zero padding, align_corners = True; the last rule is the one departure from a 5-D grid_sample: a point on a lattice node returns the
+ * node's value whatever its neighbours hold, -inf included).
+ *   volumes      (B,C,X,Y,Z) of `dtype` (MVHMR_F32 / MVHMR_F16 / MVHMR_BF16), device                                [read]
+ *   points       (B,N,3) fp32 world coordinates; rot (B,9), center (B,3) fp32, device; position / sides 3 host doubles each
+ *   paired       0: every point samples every channel, samples is (B,C,N).  1: requires N == C, point j samples channel j, samples is (B,C)
+ *   samples      fp32 [write]       index (B,N,3) fp32 [write]; reported for points outside the volume too, NaN for a NaN point
+ * Sizes: batch, channels, points >= 1, every extent >= 2, X*Y*Z < 2^31, B*C and B*N below 2^31 (MVHMR_ERR_INVALID_ARGUMENT otherwise, as for
+ * an unknown dtype or a null pointer).  No atomics anywhere: every output and gradient is bitwise reproducible.
+ */
+int32_t mvhmr_sample_volume_chunk_points(void);
+size_t mvhmr_sample_volume_workspace_bytes(int32_t batch, int32_t points);
+int mvhmr_sample_volume_forward(const void *volumes, int32_t dtype, const float *points, const float *rot, const float *center,
+                                const double position[3], const double sides[3], int32_t batch, int32_t channels, int32_t vol_x, int32_t vol_y,
+                                int32_t vol_z, int32_t n_points, int32_t paired, float *samples, float *index, void *hip_stream);
+/*
+ * Its backward w.r.t. the volume, from the forward's index and g = grad_samples (shaped like samples): grad_volumes (B,C,X,Y,Z) in `dtype`
+ * is zero-filled by the call, then grad_volumes[b,c,voxel] = sum of w * g[b,c,n] over the taps of nonzero weight that land on the voxel, in
+ * ascending point index by acc = fma(w, g, acc), the first term w * g.  Points are taken in chunks of mvhmr_sample_volume_chunk_points()
+ * (a constant of the library): per chunk the taps are sorted by (voxel, point) into the workspace, every voxel gets one owner, and the owner
+ * adds its chunk's sum to the stored value -- a 16-bit grad_volumes is therefore rounded once per chunk that touches the voxel.
+ *   workspace    mvhmr_sample_volume_workspace_bytes(batch, points) bytes, 16-byte aligned (a function of the two sizes alone); a null,
+ *                short or misaligned one is MVHMR_ERR_WORKSPACE (a paired call has no collisions and leaves it untouched, the rule holds all the same).
+ */
+int mvhmr_sample_volume_backward_volumes(int32_t dtype, const float *index, const float *grad_samples, int32_t batch, int32_t channels,
+                                         int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t n_points, int32_t paired, void *grad_volumes,
+                                         void *workspace, size_t workspace_bytes, void *hip_stream);
+/*
+ * Its backward w.r.t. the geometry.  With q = dL/dt (out-of-grid taps count as value 0, the cell is floor(t); channels summed in index
+ * order) and u = q / step:
+ *     grad_points[b,n] = rot_b u_n      grad_rot[b][i][a] = sum_n y_{n,i} u_{n,a}      grad_center[b] = sum_n (u_n - rot_b u_n)
+ * the sums over n in index order.  grad_points (B,N,3), grad_rot (B,9), grad_center (B,3) fp32 may each be NULL, not all of them.  The
+ * workspace (same query, same rules) holds u.
+ */
+int mvhmr_sample_volume_backward_geometry(const void *volumes, int32_t dtype, const float *points, const float *rot, const float *center,
+                                          const double position[3], const double sides[3], int32_t batch, int32_t channels, int32_t vol_x,
+                                          int32_t vol_y, int32_t vol_z, int32_t n_points, int32_t paired, const float *index,
+                                          const float *grad_samples, float *grad_points, float *grad_rot, float *grad_center, void *workspace,
+                                          size_t workspace_bytes, void *hip_stream);
 
 /* Which kernel AUTO would run for this problem (an mvhmr_variant_t), for logs and tests. */
 int mvhmr_unproject_selected_variant(const mvhmr_unproject_desc *desc);

@@ -7,7 +7,8 @@ Public surface mirrors the reference modules it replaces:
     multiviewhmr_amd.volumetric    <->  utils/volumetric.py     (Cuboid3D, get_rotation_matrix, rotate_coord_volume)
 
 and, beyond them, multiviewhmr_amd.softargmax: the volumetric 3-D soft-argmax that turns a heat volume back into keypoints
-(soft_argmax_3d, soft_argmax_3d_cuboid).
+(soft_argmax_3d, soft_argmax_3d_cuboid), and multiviewhmr_amd.volsample: reading a volume back at world points (sample_volume_cuboid,
+volumetric_cross_entropy).
 
 The compute lives in lib/libmvhmr_unproject.so (hand-written HIP for gfx950 behind the C ABI of
 include/mvhmr_unproject.h); there is no CPU or PyTorch fallback -- importing is cheap, calling
@@ -15,6 +16,7 @@ include/mvhmr_unproject.h); there is no CPU or PyTorch fallback -- importing is 
 """
 __version__ = "0.1.0"
 
-from . import aggregation, multiview, softargmax, volumetric  # noqa: F401
+from . import aggregation, multiview, softargmax, volsample, volumetric  # noqa: F401
 from .aggregation import VolumeGenerator, build_volume_generator, unprojection  # noqa: F401
 from .softargmax import soft_argmax_3d, soft_argmax_3d_cuboid  # noqa: F401
+from .volsample import sample_volume_cuboid, volumetric_cross_entropy  # noqa: F401

@@ -37,7 +37,10 @@ EXPORTS = (
     "mvhmr_unproject_call_workspace_bytes", "mvhmr_unproject_forward_call", "mvhmr_unproject_backward_call", "mvhmr_unproject_backward_geometry_call") + (
     # the volumetric soft-argmax (softargmax.py)
     "mvhmr_soft_argmax3d_splits", "mvhmr_soft_argmax3d_workspace_bytes", "mvhmr_soft_argmax3d_forward", "mvhmr_soft_argmax3d_backward",
-    "mvhmr_soft_argmax3d_backward_coords", "mvhmr_soft_argmax3d_backward_pose")
+    "mvhmr_soft_argmax3d_backward_coords", "mvhmr_soft_argmax3d_backward_pose") + (
+    # trilinear volume sampling at world points (volsample.py)
+    "mvhmr_sample_volume_chunk_points", "mvhmr_sample_volume_workspace_bytes", "mvhmr_sample_volume_forward",
+    "mvhmr_sample_volume_backward_volumes", "mvhmr_sample_volume_backward_geometry")
 
 
 class Desc(ctypes.Structure):
@@ -209,6 +212,17 @@ def lib():
     L.mvhmr_soft_argmax3d_backward_coords.argtypes = [vp, i32] + sizes + [dbl, vp, vp, vp, vp]
     L.mvhmr_soft_argmax3d_backward_pose.restype = ctypes.c_int
     L.mvhmr_soft_argmax3d_backward_pose.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp]
+    # volume sampling: (..., B, C, X, Y, Z, N, paired, ...)
+    L.mvhmr_sample_volume_chunk_points.restype = i32
+    L.mvhmr_sample_volume_chunk_points.argtypes = []
+    L.mvhmr_sample_volume_workspace_bytes.restype = sz
+    L.mvhmr_sample_volume_workspace_bytes.argtypes = [i32, i32]
+    L.mvhmr_sample_volume_forward.restype = ctypes.c_int
+    L.mvhmr_sample_volume_forward.argtypes = [vp, i32, vp, vp, vp, d3, d3] + [i32] * 7 + [vp, vp, vp]
+    L.mvhmr_sample_volume_backward_volumes.restype = ctypes.c_int
+    L.mvhmr_sample_volume_backward_volumes.argtypes = [i32, vp, vp] + [i32] * 7 + [vp, vp, sz, vp]
+    L.mvhmr_sample_volume_backward_geometry.restype = ctypes.c_int
+    L.mvhmr_sample_volume_backward_geometry.argtypes = [vp, i32, vp, vp, vp, d3, d3] + [i32] * 7 + [vp, vp, vp, vp, vp, vp, sz, vp]
     L.mvhmr_internal_det_exponent_table.restype = ctypes.c_int
     L.mvhmr_internal_det_exponent_table.argtypes = [dp, cp, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     if L.mvhmr_abi_version() != ABI_VERSION:

@@ -1097,6 +1097,13 @@ class VolumeGenerator(nn.Module):
         cub = self.cuboid()
         return softargmax.soft_argmax_3d_cuboid(volumes, rotations, centers, cub.position, cub.sides, beta=beta, return_logsumexp=return_logsumexp)
 
+    def sample(self, volumes, points, rotations, centers, paired=False, return_index=False):
+        """Volumes (B, C, S, S, S) that live on this module's cuboid, placed by the rotations and centers forward_with_pose returned, read
+        trilinearly at the world points (B, N, 3) (volsample.sample_volume_cuboid; differentiable w.r.t. all four tensors)."""
+        from . import volsample
+        cub = self.cuboid()
+        return volsample.sample_volume_cuboid(volumes, points, rotations, centers, cub.position, cub.sides, paired=paired, return_index=return_index)
+
     def _fused_path_applies(self, features, S):
         """The fused conv writes the quad-planar layout, which the un-projection consumes for every geometry (brick kernels as it
         is, gather kernels through one conversion; the device-side gate picks per call).  So only shapes, dtypes and devices

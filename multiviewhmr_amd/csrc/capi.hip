@@ -1659,4 +1659,91 @@ int mvhmr_soft_argmax3d_backward_pose(const float *rot, const float *moment, con
                     "soft_argmax3d pose gradient");
 }
 
+// ---- trilinear volume sampling at world points (volume_sample.hip)
+namespace {
+int vs_sizes(int32_t dtype, int32_t batch, int32_t channels, int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t n_points, int32_t paired)
+{
+    if (batch < 1 || channels < 1 || n_points < 1)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume: batch, channels and points must be >= 1 (B=%d C=%d N=%d)", batch, channels, n_points);
+    if (vol_x < 2 || vol_y < 2 || vol_z < 2)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume: every extent must be >= 2: a one-voxel axis has no step (vol=%dx%dx%d)", vol_x, vol_y, vol_z);
+    if ((long long)vol_x * vol_y * vol_z > 0x7fffffffLL || (long long)batch * channels > 0x7fffffffLL || (long long)batch * n_points > 0x7fffffffLL)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume: X*Y*Z, B*C and B*N must stay below 2^31 (vol=%dx%dx%d, B=%d C=%d N=%d)", vol_x, vol_y, vol_z,
+                    batch, channels, n_points);
+    if (dtype < MVHMR_F32 || dtype > MVHMR_BF16) return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume: unknown dtype %d", dtype);
+    if (paired != 0 && paired != 1) return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume: paired must be 0 or 1, got %d", paired);
+    if (paired && n_points != channels)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume: a paired call samples channel j at point j and needs N == C (N=%d C=%d)", n_points, channels);
+    return MVHMR_OK;
+}
+
+int vs_cuboid(const float *rot, const float *center, const double *position, const double *sides, int32_t vol_x, int32_t vol_y, int32_t vol_z, Coords *out)
+{
+    Problem p{};
+    p.X = vol_x; p.Y = vol_y; p.Z = vol_z;
+    return coords_from_cuboid(rot, center, position, sides, p, out);
+}
+
+int vs_workspace(void *workspace, size_t workspace_bytes, int32_t batch, int32_t n_points)
+{
+    const size_t need = vs3d_workspace_bytes(batch, n_points);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u))
+        return fail(MVHMR_ERR_WORKSPACE, "sample_volume: workspace of %zu bytes needed, 16-byte aligned (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    return MVHMR_OK;
+}
+}  // namespace
+
+int32_t mvhmr_sample_volume_chunk_points(void) { return vs3d_chunk_points(); }
+
+size_t mvhmr_sample_volume_workspace_bytes(int32_t batch, int32_t points)
+{
+    if (batch < 1 || points < 1) return 0;
+    return vs3d_workspace_bytes(batch, points);
+}
+
+int mvhmr_sample_volume_forward(const void *volumes, int32_t dtype, const float *points, const float *rot, const float *center,
+                                const double position[3], const double sides[3], int32_t batch, int32_t channels, int32_t vol_x, int32_t vol_y,
+                                int32_t vol_z, int32_t n_points, int32_t paired, float *samples, float *index, void *hip_stream)
+{
+    if (!volumes || !points || !samples || !index) return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume: volumes / points / samples / index must be non-null");
+    int rc = vs_sizes(dtype, batch, channels, vol_x, vol_y, vol_z, n_points, paired);
+    if (rc != MVHMR_OK) return rc;
+    Coords cs;
+    if ((rc = vs_cuboid(rot, center, position, sides, vol_x, vol_y, vol_z, &cs)) != MVHMR_OK) return rc;
+    return launched(launch_vs3d_forward(volumes, dtype, cs, points, batch, channels, vol_x, n_points, paired, samples, index,
+                                        static_cast<hipStream_t>(hip_stream)), "sample_volume forward");
+}
+
+int mvhmr_sample_volume_backward_volumes(int32_t dtype, const float *index, const float *grad_samples, int32_t batch, int32_t channels,
+                                         int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t n_points, int32_t paired, void *grad_volumes,
+                                         void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!index || !grad_samples || !grad_volumes) return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume backward_volumes: index / grad_samples / grad_volumes must be non-null");
+    int rc = vs_sizes(dtype, batch, channels, vol_x, vol_y, vol_z, n_points, paired);
+    if (rc != MVHMR_OK) return rc;
+    if ((rc = vs_workspace(workspace, workspace_bytes, batch, n_points)) != MVHMR_OK) return rc;
+    return launched(launch_vs3d_backward_volumes(dtype, index, grad_samples, batch, channels, vol_x, vol_y, vol_z, n_points, paired, grad_volumes, workspace,
+                                                 static_cast<hipStream_t>(hip_stream)), "sample_volume volume gradient");
+}
+
+int mvhmr_sample_volume_backward_geometry(const void *volumes, int32_t dtype, const float *points, const float *rot, const float *center,
+                                          const double position[3], const double sides[3], int32_t batch, int32_t channels, int32_t vol_x,
+                                          int32_t vol_y, int32_t vol_z, int32_t n_points, int32_t paired, const float *index,
+                                          const float *grad_samples, float *grad_points, float *grad_rot, float *grad_center, void *workspace,
+                                          size_t workspace_bytes, void *hip_stream)
+{
+    if (!volumes || !points || !index || !grad_samples)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume backward_geometry: volumes / points / index / grad_samples must be non-null");
+    if (!grad_points && !grad_rot && !grad_center)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "sample_volume backward_geometry: grad_points, grad_rot and grad_center are all null: nothing to compute");
+    int rc = vs_sizes(dtype, batch, channels, vol_x, vol_y, vol_z, n_points, paired);
+    if (rc != MVHMR_OK) return rc;
+    Coords cs;
+    if ((rc = vs_cuboid(rot, center, position, sides, vol_x, vol_y, vol_z, &cs)) != MVHMR_OK) return rc;
+    if ((rc = vs_workspace(workspace, workspace_bytes, batch, n_points)) != MVHMR_OK) return rc;
+    return launched(launch_vs3d_backward_geometry(volumes, dtype, cs, points, index, grad_samples, batch, channels, vol_x, n_points, paired, grad_points,
+                                                  grad_rot, grad_center, static_cast<float *>(workspace), static_cast<hipStream_t>(hip_stream)),
+                    "sample_volume geometry gradient");
+}
+
 }  // extern "C"

@@ -10,11 +10,14 @@ counted wait, wait_vmcnt(n_at) after the flush atomics, relies on vmcnt retiring
 the compiler adds among the wave's youngest could only make that wait cover more, never less.
 
 The soft-argmax kernels (k_sa3d_*) stream the volume once with up to 20 accumulators and 24 coordinates live per lane: a spill would add
-scratch traffic to a kernel whose whole budget is one read of the volume, so they are held to zero scratch too."""
+scratch traffic to a kernel whose whole budget is one read of the volume, so they are held to zero scratch too.
+
+The volume-sampling kernels (k_vs3d_*) keep a point's eight tap offsets and weights, and up to 32 tap values, in registers while dozens of
+gather loads are in flight: scratch traffic would queue behind those loads, so they are held to zero scratch as well."""
 import re
 import sys
 
-NO_SCRATCH = ("k_fwd_brick", "k_bwd_geom", "k_sa3d")
+NO_SCRATCH = ("k_fwd_brick", "k_bwd_geom", "k_sa3d", "k_vs3d")
 EXEMPT = re.compile(r"k_fwd_brick_groups")      # (k_fwd_ws: cold noinline slow path + prologue spills outside its loops; check_loops.py holds the loops)
 text = open(sys.argv[1]).read()
 bad = []

@@ -288,4 +288,17 @@ hipError_t launch_sa3d_backward_coords(const void *vol, int dtype, int B, int J,
 hipError_t launch_sa3d_backward_pose(const float *rot, const float *moment, const float *grad_kp, float *grad_rot, float *grad_center, int B, int J,
                                      hipStream_t s);
 
+// trilinear volume sampling at world points (volume_sample.hip).  `dtype` is an mvhmr_dtype_t of vol / grad_vol; cs is the
+// cuboid recipe (never a tensor); index (B,N,3) is the forward's continuous voxel index, which both backwards read.  ws holds
+// vs3d_workspace_bytes(B, N) bytes: the sorted tap tables of the volume gradient, or the (B,N,3) per-point u of the geometry gradient.
+int vs3d_chunk_points();
+size_t vs3d_workspace_bytes(long long B, long long N);
+hipError_t launch_vs3d_forward(const void *vol, int dtype, const Coords &cs, const float *points, int B, int C, int X, int N, int paired,
+                               float *samples, float *index, hipStream_t s);
+hipError_t launch_vs3d_backward_volumes(int dtype, const float *index, const float *grad_samples, int B, int C, int X, int Y, int Z, int N, int paired,
+                                        void *grad_vol, void *ws, hipStream_t s);
+hipError_t launch_vs3d_backward_geometry(const void *vol, int dtype, const Coords &cs, const float *points, const float *index, const float *grad_samples,
+                                         int B, int C, int X, int N, int paired, float *grad_points, float *grad_rot, float *grad_center, float *ws,
+                                         hipStream_t s);
+
 }  // namespace mvhmr

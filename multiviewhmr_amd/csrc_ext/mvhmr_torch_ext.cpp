@@ -8,7 +8,8 @@
 // view_args() turns them into one mvhmr_unproject_call and names its family; mvhmr_visibility::view_visibility[_cuboid] return the
 // (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what
 // places the volume.  Per call: tensor checks, descriptor, record, output and workspace from the caching allocator, the current HIP stream,
-// one C-ABI call.  mvhmr_softargmax::soft_argmax3d[_cuboid] and their backwards are the volumetric soft-argmax (softargmax.py).  Host code only: the
+// one C-ABI call.  mvhmr_softargmax::soft_argmax3d[_cuboid] and their backwards are the volumetric soft-argmax (softargmax.py),
+// mvhmr_volsample::sample_volume and its two backwards the trilinear read-back of a volume at world points (volsample.py).  Host code only: the
 // kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -629,6 +630,100 @@ std::tuple<at::Tensor, at::Tensor> soft_argmax3d_backward_pose_native(const at::
     return {gr, gc};
 }
 
+
+// Trilinear volume sampling at world points (mvhmr_sample_volume_*; multiviewhmr_amd/volsample.py): volumes (B,C,X,Y,Z) fp32 / fp16 / bf16 on
+// the cuboid of rot (B,3,3), center (B,3), position, sides; points (B,N,3); every tensor but the volume fp32.  The same per-call tail again.
+struct VsCall {
+    int64_t B, C, X, Y, Z, N;
+    int32_t dtype, paired;
+    hipStream_t stream;
+};
+
+VsCall vs_open(const at::Tensor &volumes, int64_t points, bool paired)
+{
+    TORCH_CHECK(volumes.is_cuda() && volumes.is_contiguous() && volumes.dim() == 5 && volumes.numel() > 0,
+                "mvhmr_sample_volume: volumes must be a contiguous, non-empty (B, C, X, Y, Z) tensor on a HIP device");
+    VsCall c{volumes.size(0), volumes.size(1), volumes.size(2), volumes.size(3), volumes.size(4), points, 0, paired ? 1 : 0, nullptr};
+    TORCH_CHECK(c.X >= 2 && c.Y >= 2 && c.Z >= 2, "mvhmr_sample_volume: every extent of the volume must be >= 2");
+    const int64_t lim = int64_t(1) << 31;
+    TORCH_CHECK(c.N >= 1 && c.X * c.Y * c.Z < lim && c.B * c.C < lim && c.B * c.N < lim, "mvhmr_sample_volume: N >= 1; X*Y*Z, B*C and B*N must stay below 2^31");
+    TORCH_CHECK(!paired || c.N == c.C, "mvhmr_sample_volume: a paired call needs N == C, got N = ", c.N, ", C = ", c.C);
+    c.dtype = sa_dtype(volumes);
+    c.stream = c10::hip::getCurrentHIPStream(volumes.device().index()).stream();
+    return c;
+}
+
+void vs_check_place(const VsCall &c, const at::Tensor &volumes, const at::Tensor &points, const at::Tensor &rot, const at::Tensor &center,
+                    at::ArrayRef<double> position, at::ArrayRef<double> sides)
+{
+    TORCH_CHECK(position.size() == 3 && sides.size() == 3, "mvhmr_sample_volume: position and sides take 3 values each");
+    TORCH_CHECK(points.dim() == 3 && points.size(0) == c.B && points.size(2) == 3, "mvhmr_sample_volume: points must be (B, N, 3)");
+    check_tensor(points, volumes, "points (B, N, 3)", at::kFloat, c.B * c.N * 3);
+    check_tensor(rot, volumes, "rotations (B, 3, 3)", at::kFloat, c.B * 9);
+    check_tensor(center, volumes, "centers (B, 3)", at::kFloat, c.B * 3);
+}
+
+int64_t vs_sample_numel(const VsCall &c) { return c.paired ? c.B * c.C : c.B * c.C * c.N; }
+
+at::Tensor vs_workspace(const VsCall &c, const at::Tensor &volumes, size_t *bytes)
+{
+    *bytes = mvhmr_sample_volume_workspace_bytes((int32_t)c.B, (int32_t)c.N);
+    return at::empty({(int64_t)*bytes}, volumes.options().dtype(at::kByte));
+}
+
+std::tuple<at::Tensor, at::Tensor> sample_volume_native(const at::Tensor &volumes, const at::Tensor &points, const at::Tensor &rot, const at::Tensor &center,
+                                                        at::ArrayRef<double> position, at::ArrayRef<double> sides, bool paired)
+{
+    const VsCall c = vs_open(volumes, points.dim() == 3 ? points.size(1) : 0, paired);
+    vs_check_place(c, volumes, points, rot, center, position, sides);
+    c10::DeviceGuard guard(volumes.device());
+    const auto f32 = volumes.options().dtype(at::kFloat);
+    at::Tensor samples = paired ? at::empty({c.B, c.C}, f32) : at::empty({c.B, c.C, c.N}, f32), index = at::empty({c.B, c.N, 3}, f32);
+    check_status(mvhmr_sample_volume_forward(volumes.data_ptr(), c.dtype, points.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(),
+                                             position.data(), sides.data(), (int32_t)c.B, (int32_t)c.C, (int32_t)c.X, (int32_t)c.Y, (int32_t)c.Z, (int32_t)c.N,
+                                             c.paired, samples.data_ptr<float>(), index.data_ptr<float>(), c.stream));
+    return {samples, index};
+}
+
+// grad_volumes, shaped and typed like volumes (of which only shape, dtype and device are read)
+at::Tensor sample_volume_backward_volumes_native(const at::Tensor &volumes, const at::Tensor &index, const at::Tensor &grad_samples, bool paired)
+{
+    const VsCall c = vs_open(volumes, index.dim() == 3 ? index.size(1) : 0, paired);
+    check_tensor(index, volumes, "index (B, N, 3)", at::kFloat, c.B * c.N * 3);
+    check_tensor(grad_samples, volumes, "grad_samples", at::kFloat, vs_sample_numel(c));
+    c10::DeviceGuard guard(volumes.device());
+    at::Tensor gv = at::empty_like(volumes);
+    size_t need;
+    at::Tensor ws = vs_workspace(c, volumes, &need);
+    check_status(mvhmr_sample_volume_backward_volumes(c.dtype, index.data_ptr<float>(), grad_samples.data_ptr<float>(), (int32_t)c.B, (int32_t)c.C, (int32_t)c.X,
+                                                      (int32_t)c.Y, (int32_t)c.Z, (int32_t)c.N, c.paired, gv.data_ptr(), ws.data_ptr(), need, c.stream));
+    return gv;
+}
+
+// (grad_points (B,N,3), grad_rot (B,3,3), grad_center (B,3)); what is not asked for comes back with 0 elements
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_volume_backward_geometry_native(const at::Tensor &volumes, const at::Tensor &points, const at::Tensor &rot,
+                                                                                      const at::Tensor &center, at::ArrayRef<double> position,
+                                                                                      at::ArrayRef<double> sides, bool paired, const at::Tensor &index,
+                                                                                      const at::Tensor &grad_samples, bool need_points, bool need_pose)
+{
+    const VsCall c = vs_open(volumes, points.dim() == 3 ? points.size(1) : 0, paired);
+    vs_check_place(c, volumes, points, rot, center, position, sides);
+    check_tensor(index, volumes, "index (B, N, 3)", at::kFloat, c.B * c.N * 3);
+    check_tensor(grad_samples, volumes, "grad_samples", at::kFloat, vs_sample_numel(c));
+    TORCH_CHECK(need_points || need_pose, "mvhmr_sample_volume: the geometry backward needs an output to compute");
+    c10::DeviceGuard guard(volumes.device());
+    const auto f32 = volumes.options().dtype(at::kFloat);
+    at::Tensor gp = at::empty({need_points ? c.B : 0, c.N, 3}, f32), gr = at::empty({need_pose ? c.B : 0, 3, 3}, f32), gc = at::empty({need_pose ? c.B : 0, 3}, f32);
+    size_t need;
+    at::Tensor ws = vs_workspace(c, volumes, &need);
+    check_status(mvhmr_sample_volume_backward_geometry(volumes.data_ptr(), c.dtype, points.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(),
+                                                       position.data(), sides.data(), (int32_t)c.B, (int32_t)c.C, (int32_t)c.X, (int32_t)c.Y, (int32_t)c.Z,
+                                                       (int32_t)c.N, c.paired, index.data_ptr<float>(), grad_samples.data_ptr<float>(),
+                                                       need_points ? gp.data_ptr<float>() : nullptr, need_pose ? gr.data_ptr<float>() : nullptr,
+                                                       need_pose ? gc.data_ptr<float>() : nullptr, ws.data_ptr(), need, c.stream));
+    return {gp, gr, gc};
+}
+
 }  // namespace
 
 // the descriptor's fields after an op's tensors, and the cuboid ops' arguments
@@ -703,6 +798,22 @@ TORCH_LIBRARY_IMPL(mvhmr_softargmax, CUDA, m)
     m.impl("soft_argmax3d_cuboid_backward", &soft_argmax3d_cuboid_backward_native);
     m.impl("soft_argmax3d_backward_coords", &soft_argmax3d_backward_coords_native);
     m.impl("soft_argmax3d_backward_pose", &soft_argmax3d_backward_pose_native);
+}
+
+// reading a volume back at world points: again neither un-projection nor soft-argmax
+TORCH_LIBRARY(mvhmr_volsample, m)
+{
+    m.def("sample_volume(Tensor volumes, Tensor points, Tensor rot, Tensor center, float[] position, float[] sides, bool paired) -> (Tensor, Tensor)");
+    m.def("sample_volume_backward_volumes(Tensor volumes, Tensor index, Tensor grad_samples, bool paired) -> Tensor");
+    m.def("sample_volume_backward_geometry(Tensor volumes, Tensor points, Tensor rot, Tensor center, float[] position, float[] sides, bool paired, "
+          "Tensor index, Tensor grad_samples, bool need_points, bool need_pose) -> (Tensor, Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(mvhmr_volsample, CUDA, m)
+{
+    m.impl("sample_volume", &sample_volume_native);
+    m.impl("sample_volume_backward_volumes", &sample_volume_backward_volumes_native);
+    m.impl("sample_volume_backward_geometry", &sample_volume_backward_geometry_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)
