@@ -40,7 +40,8 @@ extern "C" {
                                  *_weighted entry points and their *_weighted_workspace_bytes queries (per-view confidence weights), the
                                  *_visible entry points, their *_visible_workspace_bytes queries and mvhmr_unproject_visibility[_cuboid]
                                  (visibility-aware aggregation), the mvhmr_soft_argmax3d_* entry points (volumetric soft-argmax), the
-                                 mvhmr_sample_volume_* entry points (trilinear volume sampling at world points) */
+                                 mvhmr_sample_volume_* entry points (trilinear volume sampling at world points), the mvhmr_volume_peaks*
+                                 entry points (3-D non-maximum suppression and top-K proposals) */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -923,6 +924,50 @@ int mvhmr_sample_volume_backward_geometry(const void *volumes, int32_t dtype, co
                                           int32_t vol_y, int32_t vol_z, int32_t n_points, int32_t paired, const float *index,
                                           const float *grad_samples, float *grad_points, float *grad_rot, float *grad_center, void *workspace,
                                           size_t workspace_bytes, void *hip_stream);
+
+/*
+ * 3-D non-maximum suppression and top-K proposals from heat volumes (additive within ABI 4).  Per slice (b, j) of volumes
+ * (B,J,X,Y,Z), voxel n = (i*Y + j)*Z + k is a PEAK iff, with the box [i-r, i+r] x [j-r, j+r] x [k-r, k+r] clipped to the volume,
+ *     no value in the box is NaN (the centre included),      v_n >= every value in the box (equal neighbours do not suppress each other:
+ *     a plateau is all peaks; -0 and +0 are equal),          v_n > threshold, strictly (values widened to fp32, threshold an fp32).
+ * threshold = -inf keeps every peak but a -inf voxel, which is never one; +inf can be one.  radius r is 0 .. 3 (0: no suppression) and may
+ * exceed an extent.  The K outputs of a slice are its peaks by value descending, ties by ascending n; slots beyond the number of peaks
+ * hold scores = -inf, index = -1, positions = 0.  Every output is a function of the input bits alone (no float atomics; the integer
+ * counters inside a block only order work that is sorted afterwards by distinct keys).
+ *   volumes      (B,J,X,Y,Z) of `dtype` (MVHMR_F32 / MVHMR_F16 / MVHMR_BF16), device                                  [read]
+ *   scores       (B,J,K) fp32: the stored values, widened [write]         index (B,J,K) int32 [write]
+ *   positions    (B,J,K,3) fp32 or NULL.  Non-null needs rot (B,9), center (B,3) fp32 on the device and position / sides, 3 host doubles
+ *                each: the voxel's world coordinate by the cuboid recipe, bit-equal to mvhmr_build_coord_volumes' entry at that index.
+ *                With positions NULL the four cuboid pointers are not read and may be NULL                              [write]
+ *   workspace    mvhmr_volume_peaks_workspace_bytes(...) bytes, 16-byte aligned: blocks_per_slice * K 64-bit keys per slice, whatever the
+ *                volume holds (a constant volume, where every voxel is a peak, included)
+ * Checked in this order, before anything is launched: null pointers, batch / joints / extents >= 1, X*Y*Z and B*J below 2^31, 1 <= k <=
+ * mvhmr_volume_peaks_max_k(), 0 <= radius <= 3, a NaN threshold (MVHMR_ERR_INVALID_ARGUMENT); an unknown dtype, or more blocks than one
+ * launch holds (MVHMR_ERR_UNSUPPORTED); the workspace (MVHMR_ERR_WORKSPACE).
+ * mvhmr_volume_peaks_tile: the extents (X run, Y tile, Z tile) of the strip of a slice that one block owns; blocks_per_slice is the
+ * product of ceil(extent / tile) over the three axes.  Constants of the library, for tests that want shapes on both sides of a tile edge.
+ */
+void mvhmr_volume_peaks_tile(int32_t tile[3]);
+int32_t mvhmr_volume_peaks_max_k(void);
+size_t mvhmr_volume_peaks_workspace_bytes(int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t k);
+int mvhmr_volume_peaks(const void *volumes, int32_t dtype, int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t k,
+                       int32_t radius, float threshold, const float *rot, const float *center, const double position[3], const double sides[3],
+                       float *scores, int32_t *index, float *positions, void *workspace, size_t workspace_bytes, void *hip_stream);
+/*
+ * Its backward w.r.t. the volume: grad_volumes (B,J,X,Y,Z) in `dtype` is zero-filled by the call, then grad_volumes[b,j,index[b,j,s]] =
+ * grad_scores[b,j,s] (rounded once to `dtype`) for every slot with index >= 0.  The indices of a slice are distinct: plain stores.
+ */
+int mvhmr_volume_peaks_backward(int32_t dtype, const int32_t *index, const float *grad_scores, int32_t batch, int32_t joints, int32_t vol_x,
+                                int32_t vol_y, int32_t vol_z, int32_t k, void *grad_volumes, void *hip_stream);
+/*
+ * The backward of positions w.r.t. the pose.  x = rot d + center with d = grid - center (the recipe's un-rotated offset, recomputed from
+ * index), g = grad_positions (B,J,K,3):  grad_rot[b][r][c] = sum g_r d_c by acc = fma(g_r, d_c, acc),  grad_center[b][c] = sum (g_c -
+ * (rot^T g)_c) by acc = acc + (g_c - h_c), both over the slots of sample b with index >= 0 in (j, slot) order.  grad_rot (B,9) and
+ * grad_center (B,3) fp32 may each be NULL, not both.  Nothing is differentiated through index.
+ */
+int mvhmr_volume_peaks_backward_pose(const int32_t *index, const float *grad_positions, const float *rot, const float *center,
+                                     const double position[3], const double sides[3], int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y,
+                                     int32_t vol_z, int32_t k, float *grad_rot, float *grad_center, void *hip_stream);
 
 /* Which kernel AUTO would run for this problem (an mvhmr_variant_t), for logs and tests. */
 int mvhmr_unproject_selected_variant(const mvhmr_unproject_desc *desc);

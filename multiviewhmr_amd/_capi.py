@@ -40,7 +40,10 @@ EXPORTS = (
     "mvhmr_soft_argmax3d_backward_coords", "mvhmr_soft_argmax3d_backward_pose") + (
     # trilinear volume sampling at world points (volsample.py)
     "mvhmr_sample_volume_chunk_points", "mvhmr_sample_volume_workspace_bytes", "mvhmr_sample_volume_forward",
-    "mvhmr_sample_volume_backward_volumes", "mvhmr_sample_volume_backward_geometry")
+    "mvhmr_sample_volume_backward_volumes", "mvhmr_sample_volume_backward_geometry") + (
+    # 3-D non-maximum suppression and top-K proposals (peaks.py)
+    "mvhmr_volume_peaks_tile", "mvhmr_volume_peaks_max_k", "mvhmr_volume_peaks_workspace_bytes", "mvhmr_volume_peaks",
+    "mvhmr_volume_peaks_backward", "mvhmr_volume_peaks_backward_pose")
 
 
 class Desc(ctypes.Structure):
@@ -223,6 +226,19 @@ def lib():
     L.mvhmr_sample_volume_backward_volumes.argtypes = [i32, vp, vp] + [i32] * 7 + [vp, vp, sz, vp]
     L.mvhmr_sample_volume_backward_geometry.restype = ctypes.c_int
     L.mvhmr_sample_volume_backward_geometry.argtypes = [vp, i32, vp, vp, vp, d3, d3] + [i32] * 7 + [vp, vp, vp, vp, vp, vp, sz, vp]
+    # peaks: (volumes, dtype, B, J, X, Y, Z, K, radius, threshold, rot, center, position, sides, scores, index, positions, ws, bytes, stream)
+    L.mvhmr_volume_peaks_tile.restype = None
+    L.mvhmr_volume_peaks_tile.argtypes = [ctypes.POINTER(i32)]
+    L.mvhmr_volume_peaks_max_k.restype = i32
+    L.mvhmr_volume_peaks_max_k.argtypes = []
+    L.mvhmr_volume_peaks_workspace_bytes.restype = sz
+    L.mvhmr_volume_peaks_workspace_bytes.argtypes = [i32] * 6
+    L.mvhmr_volume_peaks.restype = ctypes.c_int
+    L.mvhmr_volume_peaks.argtypes = [vp, i32] + [i32] * 7 + [ctypes.c_float, vp, vp, d3, d3, vp, vp, vp, vp, sz, vp]
+    L.mvhmr_volume_peaks_backward.restype = ctypes.c_int
+    L.mvhmr_volume_peaks_backward.argtypes = [i32, vp, vp] + [i32] * 6 + [vp, vp]
+    L.mvhmr_volume_peaks_backward_pose.restype = ctypes.c_int
+    L.mvhmr_volume_peaks_backward_pose.argtypes = [vp, vp, vp, vp, d3, d3] + [i32] * 6 + [vp, vp, vp]
     L.mvhmr_internal_det_exponent_table.restype = ctypes.c_int
     L.mvhmr_internal_det_exponent_table.argtypes = [dp, cp, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     if L.mvhmr_abi_version() != ABI_VERSION:

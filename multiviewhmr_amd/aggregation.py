@@ -1104,6 +1104,14 @@ class VolumeGenerator(nn.Module):
         cub = self.cuboid()
         return volsample.sample_volume_cuboid(volumes, points, rotations, centers, cub.position, cub.sides, paired=paired, return_index=return_index)
 
+    def peaks(self, volumes, rotations, centers, k, radius=1, threshold=None):
+        """(scores, index, positions) of the k largest local maxima of every slice of heat volumes (B, J, S, S, S) that live on this module's
+        cuboid, placed by the rotations and centers forward_with_pose returned (peaks.volume_peaks_cuboid: 3-D non-maximum suppression of
+        half-width `radius`, strictly above `threshold`; peaks.peak_proposals turns the result into one fine volume per proposal)."""
+        from . import peaks
+        cub = self.cuboid()
+        return peaks.volume_peaks_cuboid(volumes, rotations, centers, cub.position, cub.sides, k, radius=radius, threshold=threshold)
+
     def _fused_path_applies(self, features, S):
         """The fused conv writes the quad-planar layout, which the un-projection consumes for every geometry (brick kernels as it
         is, gather kernels through one conversion; the device-side gate picks per call).  So only shapes, dtypes and devices

@@ -1746,4 +1746,97 @@ int mvhmr_sample_volume_backward_geometry(const void *volumes, int32_t dtype, co
                     "sample_volume geometry gradient");
 }
 
+// ---- 3-D non-maximum suppression and top-K proposals (volume_peaks.hip)
+namespace {
+int pk_sizes(int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t k)
+{
+    if (batch < 1 || joints < 1 || vol_x < 1 || vol_y < 1 || vol_z < 1)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks: every dimension must be >= 1 (B=%d J=%d vol=%dx%dx%d)", batch, joints, vol_x, vol_y, vol_z);
+    const long long lim = 0x7fffffffLL, xy = (long long)vol_x * vol_y;             // stepwise: three 31-bit extents overflow 64 bits
+    if (xy > lim || xy * vol_z > lim || (long long)batch * joints > lim)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks: X*Y*Z and B*J must stay below 2^31 (vol=%dx%dx%d, B=%d J=%d)", vol_x, vol_y, vol_z, batch, joints);
+    if (k < 1 || k > pk3d_max_k()) return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks: k must be 1 .. %d, got %d", pk3d_max_k(), k);
+    return MVHMR_OK;
+}
+
+int pk_dtype(int32_t dtype)
+{
+    if (dtype < MVHMR_F32 || dtype > MVHMR_BF16) return fail(MVHMR_ERR_UNSUPPORTED, "volume_peaks: no kernel for dtype %d", dtype);
+    return MVHMR_OK;
+}
+}  // namespace
+
+void mvhmr_volume_peaks_tile(int32_t tile[3])
+{
+    int t[3];
+    pk3d_tile(t);
+    if (tile) { tile[0] = t[0]; tile[1] = t[1]; tile[2] = t[2]; }
+}
+
+int32_t mvhmr_volume_peaks_max_k(void) { return pk3d_max_k(); }
+
+size_t mvhmr_volume_peaks_workspace_bytes(int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t k)
+{
+    if (batch < 1 || joints < 1 || vol_x < 1 || vol_y < 1 || vol_z < 1 || k < 1 || k > pk3d_max_k()) return 0;
+    return pk3d_workspace_bytes(batch, joints, vol_x, vol_y, vol_z, k);
+}
+
+int mvhmr_volume_peaks(const void *volumes, int32_t dtype, int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t k,
+                       int32_t radius, float threshold, const float *rot, const float *center, const double position[3], const double sides[3],
+                       float *scores, int32_t *index, float *positions, void *workspace, size_t workspace_bytes, void *hip_stream)
+{
+    if (!volumes || !scores || !index) return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks: volumes / scores / index must be non-null");
+    if (positions && (!rot || !center || !position || !sides))
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks: positions need rot / center / position / sides");
+    int rc = pk_sizes(batch, joints, vol_x, vol_y, vol_z, k);
+    if (rc != MVHMR_OK) return rc;
+    if (radius < 0 || radius > 3) return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks: radius must be 0 .. 3, got %d", radius);
+    if (threshold != threshold) return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks: threshold must not be NaN");
+    if ((rc = pk_dtype(dtype)) != MVHMR_OK) return rc;
+    // one launch holds fewer than 2^32 threads along x: 2^24 - 1 blocks of 256 (the launcher applies the same limit)
+    if ((long long)batch * joints * pk3d_blocks_per_slice(vol_x, vol_y, vol_z) > (1LL << 24) - 1)
+        return fail(MVHMR_ERR_UNSUPPORTED, "volume_peaks: B*J*blocks_per_slice must stay below 2^24 (B=%d J=%d vol=%dx%dx%d): split the batch", batch, joints,
+                    vol_x, vol_y, vol_z);
+    const size_t need = pk3d_workspace_bytes(batch, joints, vol_x, vol_y, vol_z, k);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u))
+        return fail(MVHMR_ERR_WORKSPACE, "volume_peaks: workspace of %zu bytes needed, 16-byte aligned (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    Coords cs{};
+    if (positions) {
+        Problem p{};
+        p.X = vol_x; p.Y = vol_y; p.Z = vol_z;
+        if ((rc = coords_from_cuboid(rot, center, position, sides, p, &cs)) != MVHMR_OK) return rc;
+    }
+    return launched(launch_pk3d_forward(volumes, dtype, cs, batch, joints, vol_x, vol_y, vol_z, k, radius, pk3d_key(threshold), scores, index, positions,
+                                        workspace, static_cast<hipStream_t>(hip_stream)), "volume_peaks forward");
+}
+
+int mvhmr_volume_peaks_backward(int32_t dtype, const int32_t *index, const float *grad_scores, int32_t batch, int32_t joints, int32_t vol_x,
+                                int32_t vol_y, int32_t vol_z, int32_t k, void *grad_volumes, void *hip_stream)
+{
+    if (!index || !grad_scores || !grad_volumes) return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks backward: index / grad_scores / grad_volumes must be non-null");
+    int rc = pk_sizes(batch, joints, vol_x, vol_y, vol_z, k);
+    if (rc != MVHMR_OK) return rc;
+    if ((rc = pk_dtype(dtype)) != MVHMR_OK) return rc;
+    return launched(launch_pk3d_backward(dtype, index, grad_scores, (long long)batch * joints, (long long)vol_x * vol_y * vol_z, k, grad_volumes,
+                                         static_cast<hipStream_t>(hip_stream)), "volume_peaks volume gradient");
+}
+
+int mvhmr_volume_peaks_backward_pose(const int32_t *index, const float *grad_positions, const float *rot, const float *center,
+                                     const double position[3], const double sides[3], int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y,
+                                     int32_t vol_z, int32_t k, float *grad_rot, float *grad_center, void *hip_stream)
+{
+    if (!index || !grad_positions || !rot || !center || !position || !sides)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks backward_pose: index / grad_positions / rot / center / position / sides must be non-null");
+    if (!grad_rot && !grad_center) return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks backward_pose: grad_rot and grad_center are both null: nothing to compute");
+    int rc = pk_sizes(batch, joints, vol_x, vol_y, vol_z, k);
+    if (rc != MVHMR_OK) return rc;
+    if ((long long)joints * k > 0x7fffffffLL) return fail(MVHMR_ERR_INVALID_ARGUMENT, "volume_peaks backward_pose: J*K must stay below 2^31 (J=%d K=%d)", joints, k);
+    Coords cs;
+    Problem p{};
+    p.X = vol_x; p.Y = vol_y; p.Z = vol_z;
+    if ((rc = coords_from_cuboid(rot, center, position, sides, p, &cs)) != MVHMR_OK) return rc;
+    return launched(launch_pk3d_backward_pose(index, grad_positions, cs, batch, joints, k, grad_rot, grad_center, static_cast<hipStream_t>(hip_stream)),
+                    "volume_peaks pose gradient");
+}
+
 }  // extern "C"

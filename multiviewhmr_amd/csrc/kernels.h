@@ -301,4 +301,19 @@ hipError_t launch_vs3d_backward_geometry(const void *vol, int dtype, const Coord
                                          int B, int C, int X, int N, int paired, float *grad_points, float *grad_rot, float *grad_center, float *ws,
                                          hipStream_t s);
 
+// 3-D non-maximum suppression and top-K (volume_peaks.hip).  `dtype` is an mvhmr_dtype_t of vol / grad_vol; cs is the cuboid
+// recipe and is read only when positions is non-null.  ws holds pk3d_workspace_bytes(...) bytes: pk3d_blocks_per_slice * K keys per slice.
+// tkey is the order-preserving key of the threshold (pk3d_key).
+void pk3d_tile(int tile[3]);
+int pk3d_max_k();
+unsigned pk3d_key(float v);
+long long pk3d_blocks_per_slice(int X, int Y, int Z);
+size_t pk3d_workspace_bytes(long long B, long long J, int X, int Y, int Z, int K);
+hipError_t launch_pk3d_forward(const void *vol, int dtype, const Coords &cs, int B, int J, int X, int Y, int Z, int K, int radius, unsigned tkey,
+                               float *scores, int *index, float *positions, void *ws, hipStream_t s);
+hipError_t launch_pk3d_backward(int dtype, const int *index, const float *grad_scores, long long slices, long long N, int K, void *grad_vol,
+                                hipStream_t s);
+hipError_t launch_pk3d_backward_pose(const int *index, const float *grad_pos, const Coords &cs, int B, int J, int K, float *grad_rot,
+                                     float *grad_center, hipStream_t s);
+
 }  // namespace mvhmr

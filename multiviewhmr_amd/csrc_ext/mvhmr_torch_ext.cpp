@@ -9,7 +9,8 @@
 // (B, X, Y, Z) int32 bitmask of the views that see each voxel; the tensor and the cuboid form of a call share one body, generic over what
 // places the volume.  Per call: tensor checks, descriptor, record, output and workspace from the caching allocator, the current HIP stream,
 // one C-ABI call.  mvhmr_softargmax::soft_argmax3d[_cuboid] and their backwards are the volumetric soft-argmax (softargmax.py),
-// mvhmr_volsample::sample_volume and its two backwards the trilinear read-back of a volume at world points (volsample.py).  Host code only: the
+// mvhmr_volsample::sample_volume and its two backwards the trilinear read-back of a volume at world points (volsample.py),
+// mvhmr_peaks::volume_peaks[_cuboid] and their two backwards the 3-D non-maximum suppression with top-K (peaks.py).  Host code only: the
 // kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
@@ -724,6 +725,109 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_volume_backward_geometry_n
     return {gp, gr, gc};
 }
 
+
+// 3-D non-maximum suppression and top-K proposals (mvhmr_volume_peaks*; multiviewhmr_amd/peaks.py): volumes (B,J,X,Y,Z) fp32 / fp16 / bf16 in,
+// scores (B,J,K) fp32 and index (B,J,K) int32 out, and with a cuboid (rot != null) positions (B,J,K,3) fp32.
+int32_t pk_dtype(at::ScalarType t)
+{
+    TORCH_CHECK(t == at::kFloat || t == at::kHalf || t == at::kBFloat16, "mvhmr_volume_peaks: volumes must be fp32, fp16 or bf16, got ", t);
+    return t == at::kHalf ? MVHMR_F16 : t == at::kBFloat16 ? MVHMR_BF16 : MVHMR_F32;
+}
+
+void pk_check_sizes(at::IntArrayRef shape, int64_t k)
+{
+    TORCH_CHECK(shape.size() == 5, "mvhmr_volume_peaks: volumes must be (B, J, X, Y, Z)");
+    for (int64_t e : shape) TORCH_CHECK(e >= 1, "mvhmr_volume_peaks: volumes must not be empty");
+    const int64_t lim = int64_t(1) << 31;
+    for (int64_t e : shape) TORCH_CHECK(e < lim, "mvhmr_volume_peaks: every extent must stay below 2^31");                 // so that no product below overflows
+    TORCH_CHECK(shape[2] * shape[3] < lim && shape[2] * shape[3] * shape[4] < lim && shape[0] * shape[1] < lim,
+                "mvhmr_volume_peaks: X*Y*Z and B*J must stay below 2^31");
+    TORCH_CHECK(k >= 1 && k <= mvhmr_volume_peaks_max_k(), "mvhmr_volume_peaks: k must be 1 .. ", mvhmr_volume_peaks_max_k(), ", got ", k);
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> pk_forward(const at::Tensor &volumes, const at::Tensor *rot, const at::Tensor *center,
+                                                          at::ArrayRef<double> position, at::ArrayRef<double> sides, int64_t k, int64_t radius,
+                                                          double threshold)
+{
+    TORCH_CHECK(volumes.is_cuda() && volumes.is_contiguous() && volumes.dim() == 5,
+                "mvhmr_volume_peaks: volumes must be a contiguous (B, J, X, Y, Z) tensor on a HIP device");
+    pk_check_sizes(volumes.sizes(), k);
+    TORCH_CHECK(radius >= 0 && radius <= 3, "mvhmr_volume_peaks: radius must be 0 .. 3, got ", radius);
+    TORCH_CHECK(threshold == threshold, "mvhmr_volume_peaks: threshold must not be NaN");
+    const int32_t dtype = pk_dtype(volumes.scalar_type());
+    const int64_t B = volumes.size(0), J = volumes.size(1), X = volumes.size(2), Y = volumes.size(3), Z = volumes.size(4);
+    if (rot) {
+        TORCH_CHECK(position.size() == 3 && sides.size() == 3, "mvhmr_volume_peaks: position and sides take 3 values each");
+        check_tensor(*rot, volumes, "rotations (B, 3, 3)", at::kFloat, B * 9);
+        check_tensor(*center, volumes, "centers (B, 3)", at::kFloat, B * 3);
+    }
+    c10::DeviceGuard guard(volumes.device());
+    const auto f32 = volumes.options().dtype(at::kFloat);
+    at::Tensor scores = at::empty({B, J, k}, f32), index = at::empty({B, J, k}, volumes.options().dtype(at::kInt));
+    at::Tensor positions = rot ? at::empty({B, J, k, 3}, f32) : at::Tensor();
+    const size_t need = mvhmr_volume_peaks_workspace_bytes((int32_t)B, (int32_t)J, (int32_t)X, (int32_t)Y, (int32_t)Z, (int32_t)k);
+    at::Tensor ws = at::empty({(int64_t)need}, volumes.options().dtype(at::kByte));
+    check_status(mvhmr_volume_peaks(volumes.data_ptr(), dtype, (int32_t)B, (int32_t)J, (int32_t)X, (int32_t)Y, (int32_t)Z, (int32_t)k, (int32_t)radius,
+                                    (float)threshold, rot ? rot->data_ptr<float>() : nullptr, rot ? center->data_ptr<float>() : nullptr,
+                                    rot ? position.data() : nullptr, rot ? sides.data() : nullptr, scores.data_ptr<float>(), index.data_ptr<int32_t>(),
+                                    rot ? positions.data_ptr<float>() : nullptr, ws.data_ptr(), need,
+                                    c10::hip::getCurrentHIPStream(volumes.device().index()).stream()));
+    return {scores, index, positions};
+}
+
+std::tuple<at::Tensor, at::Tensor> volume_peaks_native(const at::Tensor &volumes, int64_t k, int64_t radius, double threshold)
+{
+    auto out = pk_forward(volumes, nullptr, nullptr, {}, {}, k, radius, threshold);
+    return {std::get<0>(out), std::get<1>(out)};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> volume_peaks_cuboid_native(const at::Tensor &volumes, const at::Tensor &rot, const at::Tensor &center,
+                                                                          at::ArrayRef<double> position, at::ArrayRef<double> sides, int64_t k,
+                                                                          int64_t radius, double threshold)
+{
+    return pk_forward(volumes, &rot, &center, position, sides, k, radius, threshold);
+}
+
+// grad_volumes of `shape` and `dtype` from index and grad_scores (B, J, K): the volume itself is not needed
+at::Tensor volume_peaks_backward_native(const at::Tensor &index, const at::Tensor &grad_scores, at::IntArrayRef shape, at::ScalarType dtype)
+{
+    TORCH_CHECK(index.is_cuda() && index.is_contiguous() && index.dim() == 3 && index.scalar_type() == at::kInt,
+                "mvhmr_volume_peaks: index must be a contiguous (B, J, K) int32 tensor on a HIP device");
+    pk_check_sizes(shape, index.size(2));
+    TORCH_CHECK(index.size(0) == shape[0] && index.size(1) == shape[1], "mvhmr_volume_peaks: index must be (B, J, K) of the volumes' B and J");
+    check_tensor(grad_scores, index, "grad_scores (B, J, K)", at::kFloat, index.numel());
+    const int32_t dt = pk_dtype(dtype);
+    c10::DeviceGuard guard(index.device());
+    at::Tensor gv = at::empty(shape, index.options().dtype(dtype));
+    check_status(mvhmr_volume_peaks_backward(dt, index.data_ptr<int32_t>(), grad_scores.data_ptr<float>(), (int32_t)shape[0], (int32_t)shape[1],
+                                             (int32_t)shape[2], (int32_t)shape[3], (int32_t)shape[4], (int32_t)index.size(2), gv.data_ptr(),
+                                             c10::hip::getCurrentHIPStream(index.device().index()).stream()));
+    return gv;
+}
+
+// (grad_rot (B,3,3), grad_center (B,3)) from index and grad_positions (B, J, K, 3); vol is (X, Y, Z)
+std::tuple<at::Tensor, at::Tensor> volume_peaks_backward_pose_native(const at::Tensor &index, const at::Tensor &grad_positions, const at::Tensor &rot,
+                                                                     const at::Tensor &center, at::ArrayRef<double> position, at::ArrayRef<double> sides,
+                                                                     at::IntArrayRef vol)
+{
+    TORCH_CHECK(index.is_cuda() && index.is_contiguous() && index.dim() == 3 && index.scalar_type() == at::kInt,
+                "mvhmr_volume_peaks: index must be a contiguous (B, J, K) int32 tensor on a HIP device");
+    TORCH_CHECK(vol.size() == 3 && position.size() == 3 && sides.size() == 3, "mvhmr_volume_peaks: vol, position and sides take 3 values each");
+    const int64_t B = index.size(0), J = index.size(1), K = index.size(2);
+    pk_check_sizes({B, J, vol[0], vol[1], vol[2]}, K);
+    check_tensor(grad_positions, index, "grad_positions (B, J, K, 3)", at::kFloat, index.numel() * 3);
+    check_tensor(rot, index, "rotations (B, 3, 3)", at::kFloat, B * 9);
+    check_tensor(center, index, "centers (B, 3)", at::kFloat, B * 3);
+    c10::DeviceGuard guard(index.device());
+    const auto f32 = index.options().dtype(at::kFloat);
+    at::Tensor gr = at::empty({B, 3, 3}, f32), gc = at::empty({B, 3}, f32);
+    check_status(mvhmr_volume_peaks_backward_pose(index.data_ptr<int32_t>(), grad_positions.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(),
+                                                  position.data(), sides.data(), (int32_t)B, (int32_t)J, (int32_t)vol[0], (int32_t)vol[1], (int32_t)vol[2],
+                                                  (int32_t)K, gr.data_ptr<float>(), gc.data_ptr<float>(),
+                                                  c10::hip::getCurrentHIPStream(index.device().index()).stream()));
+    return {gr, gc};
+}
+
 }  // namespace
 
 // the descriptor's fields after an op's tensors, and the cuboid ops' arguments
@@ -814,6 +918,25 @@ TORCH_LIBRARY_IMPL(mvhmr_volsample, CUDA, m)
     m.impl("sample_volume", &sample_volume_native);
     m.impl("sample_volume_backward_volumes", &sample_volume_backward_volumes_native);
     m.impl("sample_volume_backward_geometry", &sample_volume_backward_geometry_native);
+}
+
+// peaks of a heat volume: a reader of volumes like the two above, with integer outputs
+TORCH_LIBRARY(mvhmr_peaks, m)
+{
+    m.def("volume_peaks(Tensor volumes, int k, int radius, float threshold) -> (Tensor, Tensor)");
+    m.def("volume_peaks_cuboid(Tensor volumes, Tensor rot, Tensor center, float[] position, float[] sides, int k, int radius, float threshold) -> "
+          "(Tensor, Tensor, Tensor)");
+    m.def("volume_peaks_backward(Tensor index, Tensor grad_scores, int[] shape, ScalarType dtype) -> Tensor");
+    m.def("volume_peaks_backward_pose(Tensor index, Tensor grad_positions, Tensor rot, Tensor center, float[] position, float[] sides, int[] vol) -> "
+          "(Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(mvhmr_peaks, CUDA, m)
+{
+    m.impl("volume_peaks", &volume_peaks_native);
+    m.impl("volume_peaks_cuboid", &volume_peaks_cuboid_native);
+    m.impl("volume_peaks_backward", &volume_peaks_backward_native);
+    m.impl("volume_peaks_backward_pose", &volume_peaks_backward_pose_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)
