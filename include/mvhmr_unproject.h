@@ -41,7 +41,8 @@ extern "C" {
                                  *_visible entry points, their *_visible_workspace_bytes queries and mvhmr_unproject_visibility[_cuboid]
                                  (visibility-aware aggregation), the mvhmr_soft_argmax3d_* entry points (volumetric soft-argmax), the
                                  mvhmr_sample_volume_* entry points (trilinear volume sampling at world points), the mvhmr_volume_peaks*
-                                 entry points (3-D non-maximum suppression and top-K proposals) */
+                                 entry points (3-D non-maximum suppression and top-K proposals), the mvhmr_project_volume_* entry points
+                                 (ray-marching volumes into camera-view maps) */
 
 typedef enum mvhmr_status_t {
     MVHMR_OK = 0,
@@ -968,6 +969,58 @@ int mvhmr_volume_peaks_backward(int32_t dtype, const int32_t *index, const float
 int mvhmr_volume_peaks_backward_pose(const int32_t *index, const float *grad_positions, const float *rot, const float *center,
                                      const double position[3], const double sides[3], int32_t batch, int32_t joints, int32_t vol_x, int32_t vol_y,
                                      int32_t vol_z, int32_t k, float *grad_rot, float *grad_center, void *hip_stream);
+
+/*
+ * Ray-marching volumes into camera-view maps (additive within ABI 4): renders (B,C,X,Y,Z) volumes that live on the cuboid
+ * recipe into maps (B,V,C,Hm,Wm), the direction opposite to un-projection.  rays (B,V,3,4) fp32 holds [D | o] per view: with the
+ * projection P = [M | p4], D = M^-1 and o = -M^-1 p4, so the world point of pixel (u, v) = (column, row) at parameter lambda is
+ * o + lambda D (u, v, 1)^T and projects back to (u, v) with homogeneous w = lambda.  Per ray, every line one rounded fp32 operation:
+ *     t_o = the index of o as mvhmr_sample_volume_forward computes it      d_i = fma(D[i][1], v, fma(D[i][0], u, D[i][2]))
+ *     r_a = fma(R[2][a], d_2, fma(R[1][a], d_1, R[0][a] * d_0))            e_a = r_a / step_a
+ *     slab clip against 0 <= t_a <= S_a - 1, axes in order: e_a == 0 misses unless t_o,a lies in the slab; else l0 = (0 - t_o,a) / e_a,
+ *     l1 = ((S_a - 1) - t_o,a) / e_a, lin = max(min_depth, the smaller of each pair), lout = min(max_depth, the larger); a NaN is a miss
+ *     hit iff lin < lout, both finite      h = (lout - lin) / K      lam_k = fma(k + 0.5, h, lin)      t_k,a = fma(lam_k, e_a, t_o,a)
+ *     s_k = the sample at index t_k by mvhmr_sample_volume_forward's tap rule
+ * method (mvhmr_project_t), over k ascending: MEAN  acc = acc + s_k, out = acc / K.   MAX  the maximum, the lowest k that attains it.
+ * SOFTMAX  sum_k p_k s_k, p = softmax_k(beta s_k), by the running-maximum recurrence at the top of volume_project.hip; beta finite, != 0.
+ * A miss gives 0 in every channel, ranges (0, 0), and takes part in no gradient.
+ *   volumes      (B,C,X,Y,Z) of `dtype` (MVHMR_F32 / MVHMR_F16 / MVHMR_BF16), device                                [read]
+ *   rays         (B,V,3,4) fp32; rot (B,9), center (B,3) fp32, device; position / sides 3 host doubles each
+ *   maps         (B,V,C,Hm,Wm) fp32 [write]       ranges (B,V,Hm,Wm,2) fp32: (lin, lout) per ray [write]
+ *   aux          (B,V,C,Hm,Wm) 4-byte words the backward reads: MAX the arg-k (int32), SOFTMAX the log-sum-exp of beta s_k (fp32); MEAN: may be NULL
+ * Sizes: batch, views, channels, map extents >= 1, every volume extent >= 2, 1 <= n_samples <= mvhmr_project_volume_max_samples(),
+ * X*Y*Z, B*C*V and V*Hm*Wm*n_samples below 2^31; min_depth finite, max_depth not NaN (MVHMR_ERR_INVALID_ARGUMENT otherwise).
+ */
+typedef enum {
+    MVHMR_PROJECT_MEAN = 0,
+    MVHMR_PROJECT_MAX = 1,
+    MVHMR_PROJECT_SOFTMAX = 2
+} mvhmr_project_t;
+int32_t mvhmr_project_volume_max_samples(void);
+/* (channels per block, channels per trip of a sample's channel loop): constants of the library, for tests that want channel counts on
+ * both sides of either boundary */
+void mvhmr_project_volume_channel_group(int32_t group_unroll[2]);
+size_t mvhmr_project_volume_workspace_bytes(int32_t batch, int32_t channels, int32_t vol_x, int32_t vol_y, int32_t vol_z);
+int mvhmr_project_volume_forward(const void *volumes, int32_t dtype, const float *rays, const float *rot, const float *center,
+                                 const double position[3], const double sides[3], int32_t batch, int32_t views, int32_t channels, int32_t vol_x,
+                                 int32_t vol_y, int32_t vol_z, int32_t map_h, int32_t map_w, int32_t n_samples, int32_t method, double beta,
+                                 double min_depth, double max_depth, float *maps, float *ranges, void *aux, void *hip_stream);
+/*
+ * Its backward w.r.t. the volume, from g = grad_maps (B,V,C,Hm,Wm) fp32 and the forward's maps and aux: the rays are marched again and every
+ * live tap adds w * ds_k -- ds_k = g / K (MEAN), g at the saved k (MAX), (g p_k) * fma(beta, s_k - out, 1) with p_k = exp(beta s_k - lse)
+ * (SOFTMAX) -- to an int64 fixed-point accumulator with 64-bit integer atomics; one exponent per (b, c), chosen before any add so that no
+ * sum can overflow.  Integer adds are associative: grad_volumes (B,C,X,Y,Z) in `dtype`, fully written by the call, is bitwise
+ * reproducible.  A (b, c) whose grad_maps rows (or, SOFTMAX, whose volume) hold a non-finite value comes back NaN.
+ *   workspace    mvhmr_project_volume_workspace_bytes(...) bytes, 16-byte aligned: three B*C tables and the accumulator of one pass of
+ *                channels, 8 bytes per voxel and channel, as many channels as keep it within 2^30 bytes (one at the least); a null,
+ *                short or misaligned one is MVHMR_ERR_WORKSPACE
+ */
+int mvhmr_project_volume_backward_volumes(const void *volumes, int32_t dtype, const float *rays, const float *rot, const float *center,
+                                          const double position[3], const double sides[3], int32_t batch, int32_t views, int32_t channels,
+                                          int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t map_h, int32_t map_w, int32_t n_samples,
+                                          int32_t method, double beta, double min_depth, double max_depth, const float *grad_maps,
+                                          const float *maps, const void *aux, void *grad_volumes, void *workspace, size_t workspace_bytes,
+                                          void *hip_stream);
 
 /* Which kernel AUTO would run for this problem (an mvhmr_variant_t), for logs and tests. */
 int mvhmr_unproject_selected_variant(const mvhmr_unproject_desc *desc);

@@ -41,6 +41,9 @@ EXPORTS = (
     # trilinear volume sampling at world points (volsample.py)
     "mvhmr_sample_volume_chunk_points", "mvhmr_sample_volume_workspace_bytes", "mvhmr_sample_volume_forward",
     "mvhmr_sample_volume_backward_volumes", "mvhmr_sample_volume_backward_geometry") + (
+    # ray-marching volumes into camera-view maps (volproject.py)
+    "mvhmr_project_volume_max_samples", "mvhmr_project_volume_channel_group", "mvhmr_project_volume_workspace_bytes", "mvhmr_project_volume_forward",
+    "mvhmr_project_volume_backward_volumes") + (
     # 3-D non-maximum suppression and top-K proposals (peaks.py)
     "mvhmr_volume_peaks_tile", "mvhmr_volume_peaks_max_k", "mvhmr_volume_peaks_workspace_bytes", "mvhmr_volume_peaks",
     "mvhmr_volume_peaks_backward", "mvhmr_volume_peaks_backward_pose")
@@ -239,6 +242,17 @@ def lib():
     L.mvhmr_volume_peaks_backward.argtypes = [i32, vp, vp] + [i32] * 6 + [vp, vp]
     L.mvhmr_volume_peaks_backward_pose.restype = ctypes.c_int
     L.mvhmr_volume_peaks_backward_pose.argtypes = [vp, vp, vp, vp, d3, d3] + [i32] * 6 + [vp, vp, vp]
+    # volume projection: (..., B, V, C, X, Y, Z, Hm, Wm, K, method, beta, min_depth, max_depth, ...)
+    L.mvhmr_project_volume_max_samples.restype = i32
+    L.mvhmr_project_volume_max_samples.argtypes = []
+    L.mvhmr_project_volume_channel_group.restype = None
+    L.mvhmr_project_volume_channel_group.argtypes = [ctypes.POINTER(i32)]
+    L.mvhmr_project_volume_workspace_bytes.restype = sz
+    L.mvhmr_project_volume_workspace_bytes.argtypes = [i32] * 5
+    L.mvhmr_project_volume_forward.restype = ctypes.c_int
+    L.mvhmr_project_volume_forward.argtypes = [vp, i32, vp, vp, vp, d3, d3] + [i32] * 10 + [dbl] * 3 + [vp, vp, vp, vp]
+    L.mvhmr_project_volume_backward_volumes.restype = ctypes.c_int
+    L.mvhmr_project_volume_backward_volumes.argtypes = [vp, i32, vp, vp, vp, d3, d3] + [i32] * 10 + [dbl] * 3 + [vp, vp, vp, vp, vp, sz, vp]
     L.mvhmr_internal_det_exponent_table.restype = ctypes.c_int
     L.mvhmr_internal_det_exponent_table.argtypes = [dp, cp, ctypes.POINTER(sz), ctypes.POINTER(sz)]
     if L.mvhmr_abi_version() != ABI_VERSION:

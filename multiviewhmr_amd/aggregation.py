@@ -1104,6 +1104,14 @@ class VolumeGenerator(nn.Module):
         cub = self.cuboid()
         return volsample.sample_volume_cuboid(volumes, points, rotations, centers, cub.position, cub.sides, paired=paired, return_index=return_index)
 
+    def project(self, volumes, rays, rotations, centers, map_shape, n_samples, method="mean", **kwargs):
+        """Volumes (B, C, S, S, S) that live on this module's cuboid, placed by the rotations and centers forward_with_pose returned, rendered
+        into camera-view maps (B, V, C, Hm, Wm) along rays (B, V, 3, 4) = volproject.camera_rays(proj_matricies)
+        (volproject.project_volume_cuboid, which takes the keywords beta, min_depth, max_depth, return_ranges; differentiable w.r.t. volumes)."""
+        from . import volproject
+        cub = self.cuboid()
+        return volproject.project_volume_cuboid(volumes, rays, rotations, centers, cub.position, cub.sides, map_shape, n_samples, method, **kwargs)
+
     def peaks(self, volumes, rotations, centers, k, radius=1, threshold=None):
         """(scores, index, positions) of the k largest local maxima of every slice of heat volumes (B, J, S, S, S) that live on this module's
         cuboid, placed by the rotations and centers forward_with_pose returned (peaks.volume_peaks_cuboid: 3-D non-maximum suppression of

@@ -9,7 +9,7 @@ LIB = os.path.join(PKG, "lib", "libmvhmr_unproject.so")
 
 
 def build(force=False, jobs=None, verbose=False):
-    # 27 translation units, about an hour of compile time between them (the longest alone takes several minutes): 8 jobs build a
+    # 28 translation units, about an hour of compile time between them (the longest alone takes several minutes): 8 jobs build a
     # clean checkout in ~12 minutes where 4 took ~18
     jobs = jobs or min(8, os.cpu_count() or 1)
     cmd = ["make", "-C", CSRC, "-j%d" % jobs]

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <cmath>
 #include <mutex>
 #include <unordered_map>
 
@@ -1744,6 +1745,86 @@ int mvhmr_sample_volume_backward_geometry(const void *volumes, int32_t dtype, co
     return launched(launch_vs3d_backward_geometry(volumes, dtype, cs, points, index, grad_samples, batch, channels, vol_x, n_points, paired, grad_points,
                                                   grad_rot, grad_center, static_cast<float *>(workspace), static_cast<hipStream_t>(hip_stream)),
                     "sample_volume geometry gradient");
+}
+
+// ---- ray-marching volumes into camera-view maps (volume_project.hip)
+namespace {
+int pv_sizes(int32_t dtype, int32_t batch, int32_t views, int32_t channels, int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t map_h, int32_t map_w,
+             int32_t n_samples, int32_t method, double beta, double min_depth, double max_depth)
+{
+    if (batch < 1 || views < 1 || channels < 1 || map_h < 1 || map_w < 1)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: batch, views, channels and the map extents must be >= 1 (B=%d V=%d C=%d map=%dx%d)", batch,
+                    views, channels, map_h, map_w);
+    if (vol_x < 2 || vol_y < 2 || vol_z < 2)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: every extent must be >= 2: a one-voxel axis has no step (vol=%dx%dx%d)", vol_x, vol_y, vol_z);
+    if (n_samples < 1 || n_samples > pv3d_max_samples())
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: n_samples must be 1 .. %d, got %d", pv3d_max_samples(), n_samples);
+    const long long lim = 0x7fffffffLL, hw = (long long)map_h * map_w, bc = (long long)batch * channels;
+    if ((long long)vol_x * vol_y * vol_z > lim || bc > lim || bc * views > lim || hw > lim || hw * views > lim || hw * views * n_samples > lim)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: X*Y*Z, B*C*V and V*Hm*Wm*K must stay below 2^31 (vol=%dx%dx%d, B=%d C=%d V=%d map=%dx%d K=%d)",
+                    vol_x, vol_y, vol_z, batch, channels, views, map_h, map_w, n_samples);
+    if (dtype < MVHMR_F32 || dtype > MVHMR_BF16) return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: unknown dtype %d", dtype);
+    if (method < MVHMR_PROJECT_MEAN || method > MVHMR_PROJECT_SOFTMAX) return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: unknown method %d", method);
+    if (method == MVHMR_PROJECT_SOFTMAX && !(std::isfinite(beta) && (float)beta != 0.f && std::isfinite((float)beta)))
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: beta must be finite and nonzero, got %g", beta);
+    if (!std::isfinite(min_depth) || max_depth != max_depth)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: min_depth must be finite and max_depth not NaN (got %g, %g)", min_depth, max_depth);
+    return MVHMR_OK;
+}
+}  // namespace
+
+int32_t mvhmr_project_volume_max_samples(void) { return pv3d_max_samples(); }
+
+void mvhmr_project_volume_channel_group(int32_t group_unroll[2])
+{
+    int g[2];
+    pv3d_channel_group(g);
+    if (group_unroll) { group_unroll[0] = g[0]; group_unroll[1] = g[1]; }
+}
+
+size_t mvhmr_project_volume_workspace_bytes(int32_t batch, int32_t channels, int32_t vol_x, int32_t vol_y, int32_t vol_z)
+{
+    if (batch < 1 || channels < 1 || vol_x < 2 || vol_y < 2 || vol_z < 2 || (long long)vol_x * vol_y * vol_z > 0x7fffffffLL) return 0;
+    return pv3d_workspace_bytes(batch, channels, (long long)vol_x * vol_y * vol_z);
+}
+
+int mvhmr_project_volume_forward(const void *volumes, int32_t dtype, const float *rays, const float *rot, const float *center,
+                                 const double position[3], const double sides[3], int32_t batch, int32_t views, int32_t channels, int32_t vol_x,
+                                 int32_t vol_y, int32_t vol_z, int32_t map_h, int32_t map_w, int32_t n_samples, int32_t method, double beta,
+                                 double min_depth, double max_depth, float *maps, float *ranges, void *aux, void *hip_stream)
+{
+    if (!volumes || !rays || !maps || !ranges) return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: volumes / rays / maps / ranges must be non-null");
+    int rc = pv_sizes(dtype, batch, views, channels, vol_x, vol_y, vol_z, map_h, map_w, n_samples, method, beta, min_depth, max_depth);
+    if (rc != MVHMR_OK) return rc;
+    if (method != MVHMR_PROJECT_MEAN && !aux) return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume: max and softmax need aux");
+    Coords cs;
+    if ((rc = vs_cuboid(rot, center, position, sides, vol_x, vol_y, vol_z, &cs)) != MVHMR_OK) return rc;
+    return launched(launch_pv3d_forward(volumes, dtype, cs, rays, batch, views, channels, vol_x, map_h, map_w, n_samples, method, (float)beta,
+                                        (float)min_depth, (float)max_depth, maps, ranges, aux, static_cast<hipStream_t>(hip_stream)),
+                    "project_volume forward");
+}
+
+int mvhmr_project_volume_backward_volumes(const void *volumes, int32_t dtype, const float *rays, const float *rot, const float *center,
+                                          const double position[3], const double sides[3], int32_t batch, int32_t views, int32_t channels,
+                                          int32_t vol_x, int32_t vol_y, int32_t vol_z, int32_t map_h, int32_t map_w, int32_t n_samples,
+                                          int32_t method, double beta, double min_depth, double max_depth, const float *grad_maps,
+                                          const float *maps, const void *aux, void *grad_volumes, void *workspace, size_t workspace_bytes,
+                                          void *hip_stream)
+{
+    if (!volumes || !rays || !grad_maps || !grad_volumes)
+        return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume backward_volumes: volumes / rays / grad_maps / grad_volumes must be non-null");
+    int rc = pv_sizes(dtype, batch, views, channels, vol_x, vol_y, vol_z, map_h, map_w, n_samples, method, beta, min_depth, max_depth);
+    if (rc != MVHMR_OK) return rc;
+    if (method != MVHMR_PROJECT_MEAN && !aux) return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume backward_volumes: max and softmax need the forward's aux");
+    if (method == MVHMR_PROJECT_SOFTMAX && !maps) return fail(MVHMR_ERR_INVALID_ARGUMENT, "project_volume backward_volumes: softmax needs the forward's maps");
+    Coords cs;
+    if ((rc = vs_cuboid(rot, center, position, sides, vol_x, vol_y, vol_z, &cs)) != MVHMR_OK) return rc;
+    const size_t need = pv3d_workspace_bytes(batch, channels, (long long)vol_x * vol_y * vol_z);
+    if (!workspace || workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 15u))
+        return fail(MVHMR_ERR_WORKSPACE, "project_volume: workspace of %zu bytes needed, 16-byte aligned (got %zu)", need, workspace ? workspace_bytes : (size_t)0);
+    return launched(launch_pv3d_backward_volumes(volumes, dtype, cs, rays, batch, views, channels, vol_x, map_h, map_w, n_samples, method, (float)beta,
+                                                 (float)min_depth, (float)max_depth, grad_maps, maps, aux, grad_volumes, workspace,
+                                                 static_cast<hipStream_t>(hip_stream)), "project_volume volume gradient");
 }
 
 // ---- 3-D non-maximum suppression and top-K proposals (volume_peaks.hip)

@@ -16,11 +16,15 @@ The volume-sampling kernels (k_vs3d_*) keep a point's eight tap offsets and weig
 gather loads are in flight: scratch traffic would queue behind those loads, so they are held to zero scratch as well.
 
 The peak kernels (k_pk3d_*) keep a ring of up to 7 planes of box maxima, 4 voxels each, and the next plane's loads in registers, all
-indexed statically: a ring that fell into scratch would turn one read of the volume into several, so they are held to zero scratch."""
+indexed statically: a ring that fell into scratch would turn one read of the volume into several, so they are held to zero scratch.
+
+The projection kernels (k_pv3d_*) carry up to three accumulators for each of a block's eight channels across the whole march of a ray,
+beside a sample's taps and 32 tap values in flight: an accumulator in scratch would be read and written once per sample and channel, so
+they are held to zero scratch."""
 import re
 import sys
 
-NO_SCRATCH = ("k_fwd_brick", "k_bwd_geom", "k_sa3d", "k_vs3d", "k_pk3d")
+NO_SCRATCH = ("k_fwd_brick", "k_bwd_geom", "k_sa3d", "k_vs3d", "k_pk3d", "k_pv3d")
 EXEMPT = re.compile(r"k_fwd_brick_groups")      # (k_fwd_ws: cold noinline slow path + prologue spills outside its loops; check_loops.py holds the loops)
 text = open(sys.argv[1]).read()
 bad = []

@@ -35,6 +35,13 @@ __device__ __forceinline__ unsigned long long det_fixed(float x, int k)
     return (unsigned long long)(long long)__builtin_rintf(__builtin_ldexpf(x, k));
 }
 
+// an accumulated sum back as fp32: the one rounding of the deterministic gradient (NaN for a poisoned (b, c))
+__device__ __forceinline__ float det_value(unsigned long long acc, int k)
+{
+    if (k == kDetPoison) return __builtin_nanf("");
+    return (float)ldexp((double)(long long)acc, -k);
+}
+
 // Maxima are taken with integer atomicMax on the bits of |x|: non-negative floats order as integers, and Inf / NaN sort above every finite
 // value, so the result does not depend on the order and a non-finite input is seen
 __device__ __forceinline__ unsigned abs_bits(float x) { return __builtin_bit_cast(unsigned, x) & 0x7fffffffu; }
@@ -87,6 +94,17 @@ struct DetRowsShared {
         src = x;
         dst = (long long)fb * C + (x - (long long)m * C);
         return (unsigned)fb < (unsigned)B;
+    }
+};
+
+// Camera-view maps: x = (b * V + v) * C + c over the (B, V, C, N) gradient of a projected volume, reduced over the views into slot b * C + c
+struct DetRowsViews {
+    int V, C;
+    __device__ __forceinline__ bool map(long long x, long long &src, long long &dst) const
+    {
+        src = x;
+        dst = x / ((long long)V * C) * C + x % C;
+        return true;
     }
 };
 

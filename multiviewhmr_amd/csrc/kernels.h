@@ -316,4 +316,17 @@ hipError_t launch_pk3d_backward(int dtype, const int *index, const float *grad_s
 hipError_t launch_pk3d_backward_pose(const int *index, const float *grad_pos, const Coords &cs, int B, int J, int K, float *grad_rot,
                                      float *grad_center, hipStream_t s);
 
+// ray-marching volumes into camera-view maps (volume_project.hip).  `dtype` is an mvhmr_dtype_t of vol / grad_vol, `method` an
+// mvhmr_project_t; cs is the cuboid recipe; rays (B,V,3,4).  aux: the arg-k (max) or the log-sum-exp (softmax) per map element.  ws holds
+// pv3d_workspace_bytes(B, C, X*Y*Z) bytes: the scale tables and the int64 accumulator of pv3d_pass_channels(...) channels.
+int pv3d_max_samples();
+void pv3d_channel_group(int group_unroll[2]);
+int pv3d_pass_channels(long long B, long long C, long long vox);
+size_t pv3d_workspace_bytes(long long B, long long C, long long vox);
+hipError_t launch_pv3d_forward(const void *vol, int dtype, const Coords &cs, const float *rays, int B, int V, int C, int X, int Hm, int Wm, int K,
+                               int method, float beta, float dmin, float dmax, float *maps, float *ranges, void *aux, hipStream_t s);
+hipError_t launch_pv3d_backward_volumes(const void *vol, int dtype, const Coords &cs, const float *rays, int B, int V, int C, int X, int Hm, int Wm,
+                                        int K, int method, float beta, float dmin, float dmax, const float *grad_maps, const float *maps,
+                                        const void *aux, void *grad_vol, void *ws, hipStream_t s);
+
 }  // namespace mvhmr

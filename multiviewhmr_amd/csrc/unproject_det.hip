@@ -167,12 +167,7 @@ __global__ void __launch_bounds__(256) k_det_exponent(const unsigned *__restrict
 }
 
 // ------------------------------------------------------------------------------------------ conversions
-__device__ __forceinline__ float det_value(unsigned long long acc, int k)
-{
-    if (k == kDetPoison) return __builtin_nanf("");
-    return (float)ldexp((double)(long long)acc, -k);
-}
-
+// (det_value: det_scale.h)
 // int64 channels-last accumulator (BV, HW, C4) -> planar (BV, C, HW) in the feature dtype, 64 x 64 tiles turned through LDS
 template <typename T>
 __global__ void __launch_bounds__(256)

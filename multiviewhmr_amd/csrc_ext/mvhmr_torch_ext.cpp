@@ -10,6 +10,7 @@
 // places the volume.  Per call: tensor checks, descriptor, record, output and workspace from the caching allocator, the current HIP stream,
 // one C-ABI call.  mvhmr_softargmax::soft_argmax3d[_cuboid] and their backwards are the volumetric soft-argmax (softargmax.py),
 // mvhmr_volsample::sample_volume and its two backwards the trilinear read-back of a volume at world points (volsample.py),
+// mvhmr_volproject::project_volume and its backward the ray-march of a volume into camera-view maps (volproject.py),
 // mvhmr_peaks::volume_peaks[_cuboid] and their two backwards the 3-D non-maximum suppression with top-K (peaks.py).  Host code only: the
 // kernels live in libmvhmr_unproject.so.
 #include <ATen/ATen.h>
@@ -726,6 +727,82 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> sample_volume_backward_geometry_n
 }
 
 
+// Ray-marching volumes into camera-view maps (mvhmr_project_volume_*; multiviewhmr_amd/volproject.py): volumes (B,C,X,Y,Z) fp32 / fp16 / bf16 on
+// the cuboid of rot (B,3,3), center (B,3), position, sides; rays (B,V,3,4) fp32.  maps (B,V,C,Hm,Wm) and ranges (B,V,Hm,Wm,2) fp32; aux is what
+// the backward reads besides: the arg-k (int32, max), the log-sum-exp (fp32, softmax), nothing (0 elements, mean).
+struct PvCall {
+    int64_t B, C, X, Y, Z, V, Hm, Wm, K;
+    int32_t dtype, method;
+    hipStream_t stream;
+};
+
+PvCall pv_open(const at::Tensor &volumes, const at::Tensor &rays, const at::Tensor &rot, const at::Tensor &center, at::ArrayRef<double> position,
+               at::ArrayRef<double> sides, int64_t map_h, int64_t map_w, int64_t n_samples, int64_t method)
+{
+    TORCH_CHECK(volumes.is_cuda() && volumes.is_contiguous() && volumes.dim() == 5 && volumes.numel() > 0,
+                "mvhmr_project_volume: volumes must be a contiguous, non-empty (B, C, X, Y, Z) tensor on a HIP device");
+    TORCH_CHECK(rays.dim() == 4 && rays.size(0) == volumes.size(0) && rays.size(1) >= 1 && rays.size(2) == 3 && rays.size(3) == 4,
+                "mvhmr_project_volume: rays must be (B, V, 3, 4)");
+    PvCall c{volumes.size(0), volumes.size(1), volumes.size(2), volumes.size(3), volumes.size(4), rays.size(1), map_h, map_w, n_samples, 0, (int32_t)method, nullptr};
+    TORCH_CHECK(c.X >= 2 && c.Y >= 2 && c.Z >= 2, "mvhmr_project_volume: every extent of the volume must be >= 2");
+    TORCH_CHECK(c.Hm >= 1 && c.Wm >= 1 && c.K >= 1 && c.K <= mvhmr_project_volume_max_samples(), "mvhmr_project_volume: map extents >= 1, 1 <= n_samples <= ",
+                mvhmr_project_volume_max_samples());
+    const int64_t lim = int64_t(1) << 31;
+    TORCH_CHECK(c.X * c.Y * c.Z < lim && c.B * c.C * c.V < lim && c.Hm * c.Wm < lim && c.V * c.Hm * c.Wm < lim && c.V * c.Hm * c.Wm * c.K < lim,
+                "mvhmr_project_volume: X*Y*Z, B*C*V and V*Hm*Wm*n_samples must stay below 2^31");
+    TORCH_CHECK(position.size() == 3 && sides.size() == 3, "mvhmr_project_volume: position and sides take 3 values each");
+    check_tensor(rays, volumes, "rays (B, V, 3, 4)", at::kFloat, c.B * c.V * 12);
+    check_tensor(rot, volumes, "rotations (B, 3, 3)", at::kFloat, c.B * 9);
+    check_tensor(center, volumes, "centers (B, 3)", at::kFloat, c.B * 3);
+    c.dtype = sa_dtype(volumes);
+    c.stream = c10::hip::getCurrentHIPStream(volumes.device().index()).stream();
+    return c;
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> project_volume_native(const at::Tensor &volumes, const at::Tensor &rays, const at::Tensor &rot,
+                                                                     const at::Tensor &center, at::ArrayRef<double> position, at::ArrayRef<double> sides,
+                                                                     int64_t map_h, int64_t map_w, int64_t n_samples, int64_t method, double beta,
+                                                                     double min_depth, double max_depth)
+{
+    const PvCall c = pv_open(volumes, rays, rot, center, position, sides, map_h, map_w, n_samples, method);
+    c10::DeviceGuard guard(volumes.device());
+    const auto f32 = volumes.options().dtype(at::kFloat);
+    at::Tensor maps = at::empty({c.B, c.V, c.C, c.Hm, c.Wm}, f32), ranges = at::empty({c.B, c.V, c.Hm, c.Wm, 2}, f32);
+    at::Tensor aux = method == MVHMR_PROJECT_MAX       ? at::empty({c.B, c.V, c.C, c.Hm, c.Wm}, f32.dtype(at::kInt))
+                     : method == MVHMR_PROJECT_SOFTMAX ? at::empty({c.B, c.V, c.C, c.Hm, c.Wm}, f32)
+                                                       : at::empty({0}, f32);
+    check_status(mvhmr_project_volume_forward(volumes.data_ptr(), c.dtype, rays.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(),
+                                              position.data(), sides.data(), (int32_t)c.B, (int32_t)c.V, (int32_t)c.C, (int32_t)c.X, (int32_t)c.Y, (int32_t)c.Z,
+                                              (int32_t)c.Hm, (int32_t)c.Wm, (int32_t)c.K, c.method, beta, min_depth, max_depth, maps.data_ptr<float>(),
+                                              ranges.data_ptr<float>(), aux.numel() ? aux.data_ptr() : nullptr, c.stream));
+    return {maps, ranges, aux};
+}
+
+// grad_volumes, shaped and typed like volumes; the workspace (the int64 accumulator of one pass of channels) comes from torch's allocator
+at::Tensor project_volume_backward_volumes_native(const at::Tensor &volumes, const at::Tensor &rays, const at::Tensor &rot, const at::Tensor &center,
+                                                  at::ArrayRef<double> position, at::ArrayRef<double> sides, int64_t map_h, int64_t map_w, int64_t n_samples,
+                                                  int64_t method, double beta, double min_depth, double max_depth, const at::Tensor &grad_maps,
+                                                  const at::Tensor &maps, const at::Tensor &aux)
+{
+    const PvCall c = pv_open(volumes, rays, rot, center, position, sides, map_h, map_w, n_samples, method);
+    const int64_t n = c.B * c.V * c.C * c.Hm * c.Wm;
+    check_tensor(grad_maps, volumes, "grad_maps (B, V, C, Hm, Wm)", at::kFloat, n);
+    check_tensor(maps, volumes, "maps (B, V, C, Hm, Wm)", at::kFloat, n);
+    if (method == MVHMR_PROJECT_MAX) check_tensor(aux, volumes, "aux (B, V, C, Hm, Wm)", at::kInt, n);
+    if (method == MVHMR_PROJECT_SOFTMAX) check_tensor(aux, volumes, "aux (B, V, C, Hm, Wm)", at::kFloat, n);
+    c10::DeviceGuard guard(volumes.device());
+    at::Tensor gv = at::empty_like(volumes);
+    const size_t need = mvhmr_project_volume_workspace_bytes((int32_t)c.B, (int32_t)c.C, (int32_t)c.X, (int32_t)c.Y, (int32_t)c.Z);
+    at::Tensor ws = at::empty({(int64_t)need}, volumes.options().dtype(at::kByte));
+    check_status(mvhmr_project_volume_backward_volumes(volumes.data_ptr(), c.dtype, rays.data_ptr<float>(), rot.data_ptr<float>(), center.data_ptr<float>(),
+                                                       position.data(), sides.data(), (int32_t)c.B, (int32_t)c.V, (int32_t)c.C, (int32_t)c.X, (int32_t)c.Y,
+                                                       (int32_t)c.Z, (int32_t)c.Hm, (int32_t)c.Wm, (int32_t)c.K, c.method, beta, min_depth, max_depth,
+                                                       grad_maps.data_ptr<float>(), maps.data_ptr<float>(), aux.numel() ? aux.data_ptr() : nullptr,
+                                                       gv.data_ptr(), ws.data_ptr(), need, c.stream));
+    return gv;
+}
+
+
 // 3-D non-maximum suppression and top-K proposals (mvhmr_volume_peaks*; multiviewhmr_amd/peaks.py): volumes (B,J,X,Y,Z) fp32 / fp16 / bf16 in,
 // scores (B,J,K) fp32 and index (B,J,K) int32 out, and with a cuboid (rot != null) positions (B,J,K,3) fp32.
 int32_t pk_dtype(at::ScalarType t)
@@ -937,6 +1014,21 @@ TORCH_LIBRARY_IMPL(mvhmr_peaks, CUDA, m)
     m.impl("volume_peaks_cuboid", &volume_peaks_cuboid_native);
     m.impl("volume_peaks_backward", &volume_peaks_backward_native);
     m.impl("volume_peaks_backward_pose", &volume_peaks_backward_pose_native);
+}
+
+// rendering a volume into the cameras: a reader of volumes and of rays, the fourth of its kind
+TORCH_LIBRARY(mvhmr_volproject, m)
+{
+    m.def("project_volume(Tensor volumes, Tensor rays, Tensor rot, Tensor center, float[] position, float[] sides, int map_h, int map_w, int n_samples, "
+          "int method, float beta, float min_depth, float max_depth) -> (Tensor, Tensor, Tensor)");
+    m.def("project_volume_backward_volumes(Tensor volumes, Tensor rays, Tensor rot, Tensor center, float[] position, float[] sides, int map_h, int map_w, "
+          "int n_samples, int method, float beta, float min_depth, float max_depth, Tensor grad_maps, Tensor maps, Tensor aux) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(mvhmr_volproject, CUDA, m)
+{
+    m.impl("project_volume", &project_volume_native);
+    m.impl("project_volume_backward_volumes", &project_volume_backward_volumes_native);
 }
 
 TORCH_LIBRARY_IMPL(mvhmr_native, CompositeExplicitAutograd, m)
